@@ -13,8 +13,14 @@ tracking is a sequential single-view optimisation and is replicated ("replicas o
 frame-equivalents of non-redundant work: (tracking views once + mapping views of all ranks) / 250 views per frame.
 
 One JSON line on rank 0, with `roofline` (dominant kernel = backward compositor; algorithmic bytes per SURVEY.md 8d with
-the measured N, duration from HIP events recorded on the launch stream inside the C-ABI library) and `cpu_baseline` (the
-PyTorch-CPU oracle timed on the host cores on a bounded sample).
+the measured N, duration from HIP events recorded on the launch stream inside the C-ABI library).  A plain run does only
+that: set-up, warm-up, the timed steps, the line.  `--full` adds the runs of their own that the line has carried before:
+`steady_state`, `full_seed`, `moving`, `mono_depth` (slam workload, 1 GPU) and `cpu_baseline` (the PyTorch-CPU oracle timed
+on the host cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step handed back (slam: the estimated poses of the timed frames and the map's
+parameters; c5: the rendered image and the gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB in all.  The inputs
+are seeded, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -33,8 +39,13 @@ sys.path.insert(0, ROOT)
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: slam on 1 GPU: --steady-frames, --full-seed-steps, --moving-frames, "
+                         "--mono-frames; slam / c3 / c4 on 1 GPU: the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--gaussians", type=int, default=150000)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
@@ -58,15 +69,15 @@ def parse():
                          "c5 = configs[4]: synthetic 1920x1080, 3 M Gaussians, SH degree 3, rasterizer forward+backward sweep (a step = one render + "
                          "backward of one view)")
     ap.add_argument("--steady-frames", type=int, default=100,
-                    help="slam, 1 GPU: after the timed region keep running this many more frames and report them as `steady_state` (0 = skip)")
+                    help="--full, slam, 1 GPU: after the timed region keep running this many more frames and report them as `steady_state` (0 = skip)")
     ap.add_argument("--full-seed-steps", type=int, default=10,
-                    help="slam, 1 GPU: a second run with the reference-faithful seeding (one Gaussian per valid frame-0 pixel, ~292 k), "
+                    help="--full, slam, 1 GPU: a second run with the reference-faithful seeding (one Gaussian per valid frame-0 pixel, ~292 k), "
                          "this many timed frames, reported as `full_seed` (0 = skip)")
     ap.add_argument("--moving-frames", type=int, default=60,
-                    help="slam, 1 GPU: a further run on a hand-held sweep at TUM fr1/desk's pace (up to 1.4 cm / 0.8 deg per frame: a keyframe every 5 frames, "
+                    help="--full, slam, 1 GPU: a further run on a hand-held sweep at TUM fr1/desk's pace (up to 1.4 cm / 0.8 deg per frame: a keyframe every 5 frames, "
                          "seeding, a growing map, a filling window), this many timed frames, reported as `moving` (0 = skip)")
     ap.add_argument("--mono-frames", type=int, default=20,
-                    help="slam, 1 GPU: a further run WITHOUT sensor depth (use_gt_depth: false, what configs/TUM.yml:8 ships): every frame renders the map once "
+                    help="--full, slam, 1 GPU: a further run WITHOUT sensor depth (use_gt_depth: false, what configs/TUM.yml:8 ships): every frame renders the map once "
                          "more and fits a synthetic monocular estimate to it by least squares (slam/SLAM.py:411-448), reported as `mono_depth` (0 = skip)")
     ap.add_argument("--window-batch", type=int, default=1, help="views per rank and optimiser step in the mapping window (SURVEY 8e)")
     ap.add_argument("--force-collectives", action="store_true",
@@ -85,7 +96,39 @@ def parse():
     ap.add_argument("--optimizer", choices=("auto", "allreduce", "reduce_scatter"), default="auto",
                     help="multi-GPU window: all-reduce + replicated Adam, or reduce-scatter -> Adam on 1 / N of the elements -> all-gather of the parameters "
                          "(auto: the latter from 500 k Gaussians on; window_parallel.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 48 << 20      # under the 64 MB bound on a dump, with room to spare for the .npy headers
+
+
+def dump_outputs(dirname, whole, per_gaussian):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 (integer arrays as float64: exact), at most DUMP_BYTES in all.
+    `whole` is written as it is.  `per_gaussian` (arrays with one row per Gaussian) is written whole when it fits into what is left,
+    else on a fixed, seeded sample of the rows (the same for the same row count), whose indices go to `gaussian_rows`."""
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    out = {name: host(t) for name, t in whole.items()}
+    n = {int(t.shape[0]) for t in per_gaussian.values()}
+    assert len(n) == 1, n
+    n = n.pop()
+    row_bytes = sum(host(t[:1]).nbytes for t in per_gaussian.values())
+    k = (DUMP_BYTES - sum(a.nbytes for a in out.values())) // (row_bytes + 8)
+    assert k > 0
+    if n > k:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+        out["gaussian_rows"] = rows.double().numpy()
+        per_gaussian = {name: t[rows.to(t.device)] for name, t in per_gaussian.items()}
+    out.update({name: host(t) for name, t in per_gaussian.items()})
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"wrote {len(out)} arrays ({sum(a.nbytes for a in out.values()) / 2 ** 20:.1f} MB) to {dirname}" +
+        (f", {k} of {n} Gaussians" if n > k else ""))
 
 
 def self_spawn(args):
@@ -256,7 +299,8 @@ def c5_workload(args, rank, world, dev):
     r = -(-(32 + (T - 1).bit_length()) // 8)
     alg_fwd = P * (44 + 12 * M) + Pv * (36 + 4 * Cn) + 8 * P + 12 * N + 24 * N * r + 8 * N + (8 * N + 8 * T) + N * (28 + 4 * Cn) + H * W * (4 * Cn + 8)
     alg_bwd = N * (28 + 4 * Cn) + H * W * (4 * Cn + 8) + N * (24 + 4 * Cn) + Pv * (96 + 12 * M + 4 * Cn) + Pv * (44 + 12 * M)
-    return step, dict(H=H, W=W, P=P, Pv=Pv, N=N, M=M, C=Cn, alg_fwd=alg_fwd, alg_bwd=alg_bwd,
+    return step, dict(H=H, W=W, P=P, Pv=Pv, N=N, M=M, C=Cn, alg_fwd=alg_fwd, alg_bwd=alg_bwd, image=out,
+                      per_gaussian=dict(radii=radii, **{"d_" + k: v for k, v in d.items()}),
                       workload=f"synthetic {W}x{H}, fov {fov:.0f} deg, {P} Gaussians seeded like the reference's first frame (anisotropic jitter), "
                                f"SH degree 3 (16 coefficients, sigma 0.1), rasterizer forward + backward with all input gradients through the "
                                f"C ABI (generic path), {N} (tile, splat) pairs, {Pv} visible")
@@ -371,6 +415,8 @@ def main():
         elapsed = time.perf_counter() - t0
         _lib.profile_enable(0)
         prof = _lib.profile_read()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"image": info["image"]}, info["per_gaussian"])
         if collective:
             t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -403,8 +449,11 @@ def main():
     # the reference seeds one Gaussian per valid frame-0 pixel (~292k at 640x480); BASELINE.json's configs[1] is quoted
     # at ~150k Gaussians, so the seeding is thinned to hit that count (stated in config.workload)
     frac = args.seed_fraction or min(1.0, args.gaussians / (0.95 * args.height * args.width))
-    extras = world == 1 and rank == 0 and not args.force_collectives
-    steady = args.steady_frames if extras else 0
+    single = world == 1 and rank == 0 and not args.force_collectives
+    extras = args.full and single
+    # the sequence holds the steady-state frames also when they are not run: the mapper makes frame n - 2 of an n-frame sequence a
+    # keyframe (mapper.need_new_keyframe), so the sequence's length is part of the timed workload
+    steady = args.steady_frames if single else 0
 
     strong = args.scaling == "strong"
     views_total = args.map_iters
@@ -478,6 +527,12 @@ def main():
     _lib.profile_enable(False)
     prof = _lib.profile_read()
     log(f"timed region done: {elapsed:.2f} s; mapping loops re-run after a binning overflow: {getattr(slam.mapper, 'loop_reruns', 0)}")
+    if args.dump_outputs and rank == 0:
+        g_ = slam.gaussians
+        params = {"xyz": g_._xyz, "features_dc": g_._features_dc, "features_rest": g_._features_rest, "opacity": g_._opacity,
+                  "scaling": g_._scaling, "rotation": g_._rotation}
+        dump_outputs(args.dump_outputs, {"poses": torch.stack(slam.estimate_pose_list[first_timed:first_timed + args.steps])},
+                     {k: v for k, v in params.items() if v.numel()})
     if phases:
         for k, v in phases.items():
             log(f"  phase {k:34s} {v / args.steps * 1e3:8.2f} ms/frame")
@@ -531,8 +586,9 @@ def main():
                                (f"map grown by keyframes from {P_seeded} (the reference's one Gaussian per valid frame-0 pixel) to the configuration's stated size over {grown} "
                                 f"untimed frames of a hand-held sweep (trajectory_desk, amplitudes x 1.6) that continues through the timed frames, " if grow_to else "") +
                                f"render_mode={args.render_mode}, "
-                               f"binning={args.policy}; also in this line: `steady_state` = the {steady} frames that follow the timed region of "
-                               f"the same run, `full_seed` = a second run seeded like the reference (one Gaussian per valid frame-0 pixel)",
+                               f"binning={args.policy}" + (f"; also in this line: `steady_state` = the {steady} frames that follow the timed region of "
+                                                           f"the same run, `full_seed` = a second run seeded like the reference (one Gaussian per valid "
+                                                           f"frame-0 pixel)" if extras and steady else ""),
                    "gaussians": P_now, "image": [H, W], "iterations_per_frame": views_per_frame, "grown": bool(grow_to),
                    **({"strong_scaling": f"{views_total} mapping views per frame in total = {args.map_iters} optimiser steps of {vps} view(s); value = frames per second"} if strong else {}),
                    "multi_gpu": ({"description": f"mapping window sharded: {world} rank(s) x {args.window_batch} view(s) per optimiser step, one all-reduce of the "
@@ -615,7 +671,7 @@ def main():
         # rocprofv3 --stats of this command averages over, up to the few launches of the process warm-up
         whole = {k: (prof[k][0] + prof_before.get(k, (0, 0.0))[0], prof[k][1] + prof_before.get(k, (0, 0.0))[1]) for k in prof}
         out["kernel_us_whole_run"] = {k: max(v[1] / v[0] * 1e3 - ev_overhead * 1e6, 0.0) for k, v in whole.items() if v[0]}
-    if steady:
+    if extras and steady:
         log(f"steady state: {steady} more frames of the same run")
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -713,7 +769,7 @@ def main():
                                      "the estimate to it by least squares (slam/SLAM.py:411-448, depth_utils.scale_depth_estimate), the mapper seeds from and regresses "
                                      "(Pearson term) on the rescaled estimate; the headline line runs with sensor depth, where that render + fit do not exist"}
         del slam4
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         log("cpu baseline (oracle on the host cores)")
         out["cpu_baseline"] = cpu_baseline(args)
         log("done")

@@ -2,7 +2,7 @@
 # Per-kernel durations of the headline bench under rocprofv3 (run on the GPU box from the repo root).
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf /tmp/p_ks
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_ks -o ks -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --profile 0 > /tmp/ks.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_ks -o ks -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --profile 0 > /tmp/ks.json 2>/dev/null
 python - <<'PY'
 import csv, glob
 f = glob.glob("/tmp/p_ks/**/*kernel_stats.csv", recursive=True)[0]

@@ -48,7 +48,7 @@ PY
 }
 pmc_pass slam kernel $SHORT
 # the bench line below replays these counters as roofline.traffic
-python bench.py 2>$OUT/bench.err | tee $OUT/bench.json | cut -c1-300
+python bench.py --full 2>$OUT/bench.err | tee $OUT/bench.json | cut -c1-300
 # same command as the bench line (minus the follow-up runs), so the per-kernel averages are over the same frames as roofline.avg_launch_us
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_bench -o bench -- python bench.py --no-cpu-baseline --full-seed-steps 0 --steady-frames 0 --moving-frames 0 --mono-frames 0 > $OUT/bench_under_rocprof.json 2>/dev/null
 cp $(find /tmp/p_bench -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
