@@ -346,6 +346,38 @@ int mm3dgs_seed_gaussians(int H, int W, const float* color /*[3,H,W]*/, const fl
                           const float* pose, float fx, float fy, float cx, float cy, uint32_t row0, const Mm3dgsSeedOutputs* out, int n_rest,
                           void* stream);
 
+/* Densification (slam/gaussian_model.py:490-592: densify_and_clone :560-583, densify_and_split :490-558, densify :585-590) on the
+ * device, in two calls around one 12-byte read-back.
+ * mm3dgs_densify_plan: grad = grad_accum[i] / denom[i] (NaN -> 0), s = max_k exp(log_scales[i,k]); row i is
+ *   split  if grad >= max_grad && s >  max_clone_scale (max_clone_scale = percent_dense * scene extent),
+ *   clone  if grad >= max_grad && s <= max_clone_scale (the row stays and a copy is appended),
+ *   kept   otherwise;
+ * `work` (mm3dgs_densify_work_bytes(P)) receives the class bytes and three order-preserving rank plans (no atomics decide a position),
+ * counts[3] (device memory) = { n_keep (rows that are not split), n_clone, n_split }. */
+size_t mm3dgs_densify_work_bytes(size_t P);
+int mm3dgs_densify_plan(size_t P, const float* grad_accum /*[P]*/, const float* denom /*[P]*/, const float* log_scales /*[P,3]*/, float max_grad,
+                        float max_clone_scale, void* work, uint32_t* counts /*[3]*/, void* stream);
+/* One per-Gaussian array of the scatter: rows of `width` floats (0 skips the group), its Adam moments (NULL: a group without state). */
+typedef struct Mm3dgsDensifyGroup {
+  const float* src; float* dst; const float* m_src; float* m_dst; const float* v_src; float* v_dst; int32_t width;
+} Mm3dgsDensifyGroup;
+/* group[] in the optimiser's order: xyz [P,3], f_dc, f_rest (any width, 0 at SH degree 0), opacity, scaling [P,3], rotation [P,4], rgb.
+ * The statistics arrays (n_keep + n_clone + N n_split rows) are zero-filled; parent[dst] = source row of dst. */
+typedef struct Mm3dgsDensifyState {
+  Mm3dgsDensifyGroup group[7];
+  float* grad_accum; float* denom; float* max_radii2D;
+  int32_t* parent; /* may be NULL */
+} Mm3dgsDensifyState;
+/* mm3dgs_densify_rows: the densified map, rows in the reference's order after its clone, split and prune-of-parents sequence:
+ *   [kept rows in order: parameters and both moments copied] [clones in order: parameters copied, moments 0]
+ *   [split child k = 0 of each split row, in order] ... [child k = N-1]: xyz = R(normalize(q)) (exp(s) * z) + xyz,
+ *   scaling = log(exp(s) / (0.8 N)), the rest copied, moments 0.
+ * z = the stateless normals of general_utils.densify_normals: key_j = fmix32(fmix32(fmix32(seed) ^ row) ^ (8 k + j)), j = 0..5,
+ * u_j = ((key_j >> 8) + 0.5) 2^-24, z_a = sqrt(-2 ln u_2a) cos(2 pi u_2a+1), row = index before densification.  The counts are the
+ * plan's (read back by the caller); src and dst must not overlap. */
+int mm3dgs_densify_rows(size_t P, const void* work, uint32_t n_keep, uint32_t n_clone, uint32_t n_split, int N, uint32_t seed,
+                        const Mm3dgsDensifyState* state, void* stream);
+
 /* Keyframe test (slam/mapper.py:141-216: need_new_keyframe -> get_depth_pointcloud + is_covisible): back-project the last keyframe's
  * rendered surface (depth where silhouette > 0.99, minus points that round to the world origin at 4 decimals) to the world and
  * project it into the current view.  counts[0] = points inside the image in front of the camera, counts[1] = points tested
@@ -409,8 +441,9 @@ const char* mm3dgs_last_error(void);
         records); the SLAM modes' block records are addressed by list position and the sorted bin (mask | per-tile record) overwrites the keys:
         binning_state / backward_scratch keep their sizes, their interior layout is the library's own; image_state must be zero-initialised
         to at least sizeof(Mm3dgsHeader) before its first use with MM3DGS_FWD_STATE_CLEAN
-   209: Mm3dgsSlamInputs.f_rest / sh_degree / n_rest, Mm3dgsSlamGrads.d_f_rest, Mm3dgsMapAdam.rest_* (all appended): native loops at an active SH degree > 0 */
-#define MM3DGS_ABI_VERSION 209
+   209: Mm3dgsSlamInputs.f_rest / sh_degree / n_rest, Mm3dgsSlamGrads.d_f_rest, Mm3dgsMapAdam.rest_* (all appended): native loops at an active SH degree > 0
+   210: mm3dgs_densify_work_bytes / mm3dgs_densify_plan / mm3dgs_densify_rows, Mm3dgsDensifyGroup / Mm3dgsDensifyState (densification) */
+#define MM3DGS_ABI_VERSION 210
 int mm3dgs_version(void);
 
 #ifdef __cplusplus

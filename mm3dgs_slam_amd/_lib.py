@@ -79,6 +79,16 @@ class Mm3dgsSeedOutputs(C.Structure):
                 ("rotation", C.c_void_p), ("rgb", C.c_void_p)]
 
 
+class Mm3dgsDensifyGroup(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("m_src", C.c_void_p), ("m_dst", C.c_void_p), ("v_src", C.c_void_p),
+                ("v_dst", C.c_void_p), ("width", C.c_int32)]
+
+
+class Mm3dgsDensifyState(C.Structure):
+    _fields_ = [("group", Mm3dgsDensifyGroup * 7), ("grad_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii2D", C.c_void_p),
+                ("parent", C.c_void_p)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mm3dgs_profile_event_overhead_ms": (C.c_double, [_P]),
@@ -90,6 +100,9 @@ _SIGS = {
     "mm3dgs_compact_rows": (C.c_int, [C.c_size_t, _P, _P, C.POINTER(Mm3dgsCompactArray), C.c_int, _P]),
     "mm3dgs_seed_gaussians": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32,
                                         C.POINTER(Mm3dgsSeedOutputs), C.c_int, _P]),
+    "mm3dgs_densify_work_bytes": (C.c_size_t, [C.c_size_t]),
+    "mm3dgs_densify_plan": (C.c_int, [C.c_size_t, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P]),
+    "mm3dgs_densify_rows": (C.c_int, [C.c_size_t, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(Mm3dgsDensifyState), _P]),
     "mm3dgs_geom_bytes": (C.c_size_t, [C.c_int]),
     "mm3dgs_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mm3dgs_binning_bytes": (C.c_size_t, [C.c_size_t]),

@@ -720,6 +720,41 @@ int mm3dgs_seed_gaussians(int H, int W, const float* color, const float* depth, 
   return check_launch("seed_gaussians");
 }
 
+// densification (slam/gaussian_model.py:490-592).  work = [class bytes, P rounded up to 256][3 x nb block counts]
+static size_t densify_cls_bytes(size_t P) { return align_up(P, 256); }
+size_t mm3dgs_densify_work_bytes(size_t P) { return densify_cls_bytes(P) + align_up((3 * ((P + 255) / 256) + 1) * 4, 256); }
+int mm3dgs_densify_plan(size_t P, const float* grad_accum, const float* denom, const float* log_scales, float max_grad, float max_clone_scale,
+                        void* work, uint32_t* counts, void* stream) {
+  if (P > 0x7fffffffull) return fail(-1, "P too large");
+  if (!work || !counts || (P > 0 && (!grad_accum || !denom || !log_scales))) return fail(-1, "NULL argument");
+  launch_densify_plan((int)P, grad_accum, denom, log_scales, max_grad, max_clone_scale, (uint8_t*)work,
+                      (uint32_t*)((char*)work + densify_cls_bytes(P)), counts, (hipStream_t)stream);
+  return check_launch("densify_plan");
+}
+int mm3dgs_densify_rows(size_t P, const void* work, uint32_t n_keep, uint32_t n_clone, uint32_t n_split, int N, uint32_t seed,
+                        const Mm3dgsDensifyState* st, void* stream) {
+  if (P > 0x7fffffffull) return fail(-1, "P too large");
+  if (N < 1 || N > 64) return fail(-1, "N out of range");
+  // (the destination rows are placed by these counts: they must be the plan's)
+  if ((uint64_t)n_keep + n_split != P || n_clone > n_keep) return fail(-1, "counts do not describe a plan of %zu rows", P);
+  if ((uint64_t)n_keep + n_clone + (uint64_t)N * n_split > 0x7fffffffull) return fail(-1, "densified map too large");
+  if (P == 0) return 0;
+  if (!work || !st || !st->grad_accum || !st->denom || !st->max_radii2D) return fail(-1, "NULL argument");
+  DensifyTable t = {};
+  for (int a = 0; a < 7; a++) {
+    const Mm3dgsDensifyGroup& g = st->group[a];
+    if (g.width < 0) return fail(-1, "group %d: negative width", a);
+    if (g.width > 0 && (!g.src || !g.dst)) return fail(-1, "group %d: NULL pointer", a);
+    if ((g.m_dst && !g.m_src) || (g.v_dst && !g.v_src)) return fail(-1, "group %d: moment destination without source", a);
+    t.src[a] = g.src; t.dst[a] = g.dst; t.m_src[a] = g.m_src; t.m_dst[a] = g.m_dst; t.v_src[a] = g.v_src; t.v_dst[a] = g.v_dst; t.width[a] = g.width;
+  }
+  if (n_split > 0 && (t.width[0] != 3 || t.width[4] != 3 || t.width[5] != 4)) return fail(-1, "split needs xyz[3], scaling[3], rotation[4]");
+  t.grad_accum = st->grad_accum; t.denom = st->denom; t.max_radii2D = st->max_radii2D; t.parent = st->parent;
+  launch_densify_rows((int)P, (const uint8_t*)work, (const uint32_t*)((const char*)work + densify_cls_bytes(P)), n_keep, n_clone, n_split, N, seed,
+                      (float)(0.8 * (double)N), t, (hipStream_t)stream);
+  return check_launch("densify_rows");
+}
+
 int mm3dgs_mark_visible(const Mm3dgsCamera* cam, int P, const float* means3D, uint8_t* visible, void* stream) {
   if (!cam || !cam->viewmatrix || (P > 0 && (!means3D || !visible))) return fail(-1, "NULL buffer");
   launch_mark_visible(cam_dev(cam), P, means3D, visible, (hipStream_t)stream);

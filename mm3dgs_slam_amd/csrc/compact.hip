@@ -7,7 +7,8 @@
 // log-scale log(z / ((fx + fy) / 2)) on all axes, opacity logit 0, identity quaternion, f_dc = (rgb - 0.5) / C0).
 //
 // Compaction = three small launches over `n` flagged elements (Gaussians or pixels): per-256 counts, one workgroup scanning the
-// counts, scatter by rank.  Order preserving and deterministic (no atomics decide a position).
+// counts, scatter by rank.  Order preserving and deterministic (no atomics decide a position).  Densification (clone + split,
+// slam/gaussian_model.py:490-592) is the same machinery with three classes: classify + count, three scans, one scatter.
 #include "mm3dgs_common.h"
 #include <algorithm>
 #include "fused_api.h"
@@ -40,8 +41,8 @@ __global__ void __launch_bounds__(CB) compact_count_kernel(int n, const uint8_t*
   if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// one workgroup: block_counts[0..nb) -> exclusive prefix in place, total to *n_keep
-__global__ void __launch_bounds__(1024) compact_scan_kernel(int nb, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ n_keep) {
+// one workgroup: block_counts[0..nb) -> exclusive prefix in place, total to *total
+__device__ __forceinline__ void scan_block_counts(int nb, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ total) {
   __shared__ uint32_t wtot[16];
   __shared__ uint32_t carry;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -60,20 +61,28 @@ __global__ void __launch_bounds__(1024) compact_scan_kernel(int nb, uint32_t* __
     if (tid == 1023) carry = pre + x;
     __syncthreads();
   }
-  if (tid == 0) *n_keep = carry;
+  if (tid == 0) *total = carry;
+}
+__global__ void __launch_bounds__(1024) compact_scan_kernel(int nb, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ n_keep) {
+  scan_block_counts(nb, block_counts, n_keep);
+}
+
+// position of this lane's element among the flagged ones of the workgroup, offset by the workgroup's exclusive prefix `base`
+__device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t base, uint32_t* wsum) {
+  const unsigned long long m = __ballot(flag);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) wsum[wv] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t pre = base;
+  for (int w = 0; w < wv; w++) pre += wsum[w];
+  return pre + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
 }
 
 // rank[i] = position of element i among the kept ones (only meaningful where keep[i])
 __device__ __forceinline__ uint32_t compact_rank(int i, int n, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ block_pre,
                                                  bool& kept, uint32_t* wsum) {
   kept = i < n && keep[i] != 0;
-  const unsigned long long m = __ballot(kept);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) wsum[wv] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t pre = block_pre[blockIdx.x];
-  for (int w = 0; w < wv; w++) pre += wsum[w];
-  return pre + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  return block_rank(kept, block_pre[blockIdx.x], wsum);
 }
 
 __global__ void __launch_bounds__(CB)
@@ -125,6 +134,111 @@ seed_gaussians_kernel(int H, int W, const float* __restrict__ color, const float
   for (int a = 0; a < o.n_rest * 3; a++) o.f_rest[(size_t)r * o.n_rest * 3 + a] = 0.f;
   o.opacity[r] = 0.f;
   o.rotation[(size_t)r * 4] = 1.f; o.rotation[(size_t)r * 4 + 1] = 0.f; o.rotation[(size_t)r * 4 + 2] = 0.f; o.rotation[(size_t)r * 4 + 3] = 0.f;
+}
+
+// ---- densification (slam/gaussian_model.py:490-592): clone + split as one classify-and-plan pass and one scatter ---------------------
+// Class per row: 0 kept, 1 cloned (kept + a copy appended), 2 split (replaced by N children).  Three order-preserving ranks per row --
+// among the rows that stay (class < 2), the clones, the split rows -- from per-workgroup counts and one scan per class; the scatter
+// recomputes them from the class bytes by ballot, like compact_rows_kernel.  Output order (the reference's after its clone, split and
+// prune-of-parents sequence): [kept rows][clones][child 0 of each split row]...[child N-1].
+#define DENSIFY_KEEP 0
+#define DENSIFY_CLONE 1
+#define DENSIFY_SPLIT 2
+
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || a > b) ? a : b; }      // torch.max: NaN wins
+
+__global__ void __launch_bounds__(CB)
+densify_classify_kernel(int P, int nb, const float* __restrict__ grad_accum, const float* __restrict__ denom, const float* __restrict__ scaling,
+                        float max_grad, float max_clone_scale, uint8_t* __restrict__ cls, uint32_t* __restrict__ block_counts) {
+  __shared__ uint32_t wsum[3][CB / 64];
+  const int i = blockIdx.x * CB + threadIdx.x;
+  int c = 3;
+  if (i < P) {
+    float g = grad_accum[i] / denom[i];
+    if (g != g) g = 0.f;                                   // rows never seen: 0 / 0
+    // (accurate exp, as the prune predicate: the decisions must match torch.exp)
+    const float s = max_nan(max_nan(expf(scaling[(size_t)i * 3]), expf(scaling[(size_t)i * 3 + 1])), expf(scaling[(size_t)i * 3 + 2]));
+    c = g >= max_grad ? (s > max_clone_scale ? DENSIFY_SPLIT : (s <= max_clone_scale ? DENSIFY_CLONE : DENSIFY_KEEP)) : DENSIFY_KEEP;
+    cls[i] = (uint8_t)c;
+  }
+  const unsigned long long m[3] = {__ballot(c < 2), __ballot(c == DENSIFY_CLONE), __ballot(c == DENSIFY_SPLIT)};
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 3; k++) wsum[k][threadIdx.x >> 6] = (uint32_t)__popcll(m[k]);
+  __syncthreads();
+  if (threadIdx.x < 3) block_counts[threadIdx.x * nb + blockIdx.x] = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
+}
+
+// workgroup k scans class k's block counts; counts[k] = its total
+__global__ void __launch_bounds__(1024) densify_scan_kernel(int nb, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ counts) {
+  scan_block_counts(nb, block_counts + (size_t)blockIdx.x * nb, counts + blockIdx.x);
+}
+
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+
+// parameters (and, with_moments, both moments -- else zeros) of source row i to destination row d, groups skipped by mask bit
+__device__ __forceinline__ void densify_copy_row(const DensifyTable& t, int i, uint32_t d, bool with_moments, unsigned skip) {
+  for (int a = 0; a < 7; a++) {
+    const int w = t.width[a];
+    if (w == 0) continue;
+    const size_t si = (size_t)i * w, di = (size_t)d * w;
+    if (!((skip >> a) & 1u))
+      for (int c = 0; c < w; c++) t.dst[a][di + c] = t.src[a][si + c];
+    if (t.m_dst[a])
+      for (int c = 0; c < w; c++) t.m_dst[a][di + c] = with_moments ? t.m_src[a][si + c] : 0.f;
+    if (t.v_dst[a])
+      for (int c = 0; c < w; c++) t.v_dst[a][di + c] = with_moments ? t.v_src[a][si + c] : 0.f;
+  }
+  t.grad_accum[d] = 0.f; t.denom[d] = 0.f; t.max_radii2D[d] = 0.f;
+  if (t.parent) t.parent[d] = i;
+}
+
+__global__ void __launch_bounds__(CB)
+densify_rows_kernel(int P, int nb, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ block_pre, uint32_t n_keep, uint32_t n_clone,
+                    uint32_t n_split, int N, uint32_t seed, float shrink, DensifyTable t) {
+  __shared__ uint32_t wsum[3][CB / 64];
+  const int i = blockIdx.x * CB + threadIdx.x;
+  const int c = i < P ? cls[i] : 3;
+  const uint32_t r_keep = block_rank(c < 2, block_pre[blockIdx.x], wsum[0]);
+  const uint32_t r_clone = block_rank(c == DENSIFY_CLONE, block_pre[nb + blockIdx.x], wsum[1]);
+  const uint32_t r_split = block_rank(c == DENSIFY_SPLIT, block_pre[2 * nb + blockIdx.x], wsum[2]);
+  if (i >= P) return;
+  if (c != DENSIFY_SPLIT) {
+    densify_copy_row(t, i, r_keep, true, 0u);
+    if (c == DENSIFY_CLONE) densify_copy_row(t, i, n_keep + r_clone, false, 0u);
+    return;
+  }
+  // split: N children with xyz = R(normalize(q)) (exp(s) * z) + xyz, scaling = log(exp(s) / (0.8 N)) (gaussian_model.py:490-515)
+  const float* q = t.src[5] + (size_t)i * 4;
+  float w = q[0], x = q[1], y = q[2], z = q[3];
+  const float qn = sqrtf(w * w + x * x + y * y + z * z);
+  w /= qn; x /= qn; y /= qn; z /= qn;
+  const float R[3][3] = {{1.f - 2.f * (y * y + z * z), 2.f * (x * y - w * z), 2.f * (x * z + w * y)},
+                         {2.f * (x * y + w * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - w * x)},
+                         {2.f * (x * z - w * y), 2.f * (y * z + w * x), 1.f - 2.f * (x * x + y * y)}};
+  const float* ls = t.src[4] + (size_t)i * 3;
+  const float* p = t.src[0] + (size_t)i * 3;
+  const float sc[3] = {expf(ls[0]), expf(ls[1]), expf(ls[2])};
+  const uint32_t base = fmix32(fmix32(seed) ^ (uint32_t)i);
+  for (int k = 0; k < N; k++) {
+    const uint32_t d = n_keep + n_clone + (uint32_t)k * n_split + r_split;
+    densify_copy_row(t, i, d, false, (1u << 0) | (1u << 4));
+    float v[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      // general_utils.densify_normals, operation for operation in float32
+      const uint32_t k0 = fmix32(base ^ (uint32_t)(8 * k + 2 * a)), k1 = fmix32(base ^ (uint32_t)(8 * k + 2 * a + 1));
+      const float u0 = ((float)(k0 >> 8) + 0.5f) * 0x1p-24f, u1 = ((float)(k1 >> 8) + 0.5f) * 0x1p-24f;
+      v[a] = sc[a] * (sqrtf(-2.f * logf(u0)) * cosf(u1 * 6.28318548f));
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      t.dst[0][(size_t)d * 3 + a] = R[a][0] * v[0] + R[a][1] * v[1] + R[a][2] * v[2] + p[a];
+      t.dst[4][(size_t)d * 3 + a] = logf(sc[a] / shrink);
+    }
+  }
 }
 
 // ---- keyframe test: covisibility ratio of two views (slam/mapper.py:141-173 need_new_keyframe -> get_depth_pointcloud :175-196 +
@@ -202,6 +316,20 @@ void launch_seed_gaussians(int H, int W, const float* color, const float* depth,
   if (n <= 0) return;
   hipLaunchKernelGGL(seed_gaussians_kernel, dim3((n + CB - 1) / CB), dim3(CB), 0, s, H, W, color, depth, keep, block_pre, pose, fx, fy, cx, cy,
                      row0, o);
+}
+void launch_densify_plan(int P, const float* grad_accum, const float* denom, const float* scaling, float max_grad, float max_clone_scale,
+                         uint8_t* cls, uint32_t* block_counts, uint32_t* counts, hipStream_t s) {
+  const int nb = (P + CB - 1) / CB;
+  if (P > 0)
+    hipLaunchKernelGGL(densify_classify_kernel, dim3(nb), dim3(CB), 0, s, P, nb, grad_accum, denom, scaling, max_grad, max_clone_scale, cls,
+                       block_counts);
+  hipLaunchKernelGGL(densify_scan_kernel, dim3(3), dim3(1024), 0, s, nb, block_counts, counts);
+}
+void launch_densify_rows(int P, const uint8_t* cls, const uint32_t* block_pre, uint32_t n_keep, uint32_t n_clone, uint32_t n_split, int N,
+                         uint32_t seed, float shrink, const DensifyTable& t, hipStream_t s) {
+  if (P <= 0) return;
+  const int nb = (P + CB - 1) / CB;
+  hipLaunchKernelGGL(densify_rows_kernel, dim3(nb), dim3(CB), 0, s, P, nb, cls, block_pre, n_keep, n_clone, n_split, N, seed, shrink, t);
 }
 __global__ void zero_words_kernel(uint32_t* __restrict__ p, int n) {
   if ((int)threadIdx.x < n) p[threadIdx.x] = 0u;

@@ -96,6 +96,16 @@ void launch_prune_mask(int P, const float* opacity, const float* scaling, const 
                        float max_screen_size, int use_screen, uint8_t* keep, uint32_t* n_pruned, hipStream_t s);
 void launch_compact_plan(int n, const uint8_t* keep, uint32_t* block_pre, uint32_t* n_keep, hipStream_t s);
 void launch_compact_rows(int n, const uint8_t* keep, const uint32_t* block_pre, const CompactTable& t, hipStream_t s);
+// densification: groups in the optimiser's order (0 xyz, 1 f_dc, 2 f_rest, 3 opacity, 4 scaling, 5 rotation, 6 rgb); width 0 skips a group,
+// NULL moment pointers mean a group without Adam state
+struct DensifyTable {
+  const float* src[7]; float* dst[7]; const float* m_src[7]; float* m_dst[7]; const float* v_src[7]; float* v_dst[7]; int width[7];
+  float* grad_accum; float* denom; float* max_radii2D; int32_t* parent;
+};
+void launch_densify_plan(int P, const float* grad_accum, const float* denom, const float* scaling, float max_grad, float max_clone_scale,
+                         uint8_t* cls, uint32_t* block_counts, uint32_t* counts, hipStream_t s);
+void launch_densify_rows(int P, const uint8_t* cls, const uint32_t* block_pre, uint32_t n_keep, uint32_t n_clone, uint32_t n_split, int N,
+                         uint32_t seed, float shrink, const DensifyTable& t, hipStream_t s);
 void launch_seed_gaussians(int H, int W, const float* color, const float* depth, const uint8_t* keep, const uint32_t* block_pre,
                            const float* pose, float fx, float fy, float cx, float cy, uint32_t row0, const SeedOut& o, hipStream_t s);
 

@@ -22,6 +22,7 @@ from random import randint
 import torch
 
 from . import _lib
+from .general_utils import densify_frame, densify_seed
 from .mapper import Mapper
 from .rasterizer import _camera, _stream
 from .tracker import Tracker
@@ -696,10 +697,13 @@ class FusedMapper(Mapper):
         # `unrecovered_overflows`, warned about, capacity raised for the next frame.
         eng._ensure(int(g._xyz.shape[0]), True)
         need_snap = self.always_snapshot or getattr(eng, "headroom", lambda: 0.0)() < 1.5 or (self.window is not None and self.window._collective)
+        # (densification can grow the map inside the loop -- by up to one row per split -- where pruning only shrinks it: a densifying
+        #  frame always keeps a snapshot to re-run from)
+        need_snap = need_snap or (not splatam and densify_frame(m, idx))
         snap, rng_state = (g.snapshot(), _random.getstate()) if need_snap else (None, None)
         self._late_overflow, self._piggybacked = False, False
         for attempt in range(4):
-            self._map_loop_once(eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback=snap is None)
+            self._map_loop_once(eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback=snap is None, frame=idx)
             if snap is None and self.lazy_checks and self._piggybacked and getattr(eng, "headroom", lambda: 0.0)() >= 1.5:
                 # no snapshot was needed (ample headroom) and the header was read at this loop's pruning steps, where the device is
                 # drained anyway: the end-of-loop read-back (one more synchronisation per frame) is left to the next drained point
@@ -742,7 +746,7 @@ class FusedMapper(Mapper):
             self.mapping_time_sum += time.perf_counter() - t_start
         self.mapping_iter_count += num_iter
 
-    def _map_loop_once(self, eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback=False):
+    def _map_loop_once(self, eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback=False, frame=0):
         splatam = self.cfg["method"].lower() == "splatam"       # prunes (prune_at), never collects densification statistics
 
         def dens(it):
@@ -755,7 +759,7 @@ class FusedMapper(Mapper):
             return n
 
         try:
-            self._map_loop_body(eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback, splatam, dens, run_length)
+            self._map_loop_body(eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback, splatam, dens, run_length, frame)
         except BaseException:
             #  an exception after sharded optimiser steps -- a failing check, a prune that raises, a collective error -- must not
             # leave every rank with fresh Adam moments for its own slice only: SLAM.run goes on to write the map.  Gather them if the
@@ -767,7 +771,7 @@ class FusedMapper(Mapper):
                     self.window_incoherent = True
             raise
 
-    def _map_loop_body(self, eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback, splatam, dens, run_length):
+    def _map_loop_body(self, eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback, splatam, dens, run_length, frame=0):
         with torch.no_grad():
             iteration = 0
             prepared = None      # (first iteration, views, table) of a run whose host side was built while the GPU was still busy
@@ -876,7 +880,14 @@ class FusedMapper(Mapper):
                     # The capacity header (sticky: every forward since the last read, the tracker's included) rides on the pruning
                     # step's read-back: its copy to pinned memory is enqueued before, parsed after -- no round trip of its own
                     token = eng.check_capacity_begin() if (piggyback and hasattr(eng, "check_capacity_begin")) else None
-                    pruned = g.prune(m["min_opacity"], self.camera_extent, None if splatam else m["size_threshold"], lazy_mask=True)
+                    if not splatam and densify_frame(m, frame):
+                        # densification (slam/mapper.py:913-927, commented out in the reference) at this pruning step: classify-and-plan,
+                        # a 12-byte read-back, one scatter (gaussian_model.densify_device), then the prune.  The seed is a function of
+                        # (mapping.densify_seed, frame, iteration): an overflow re-run of this loop draws the same samples
+                        pruned, parent = g.densify_and_prune(m["densify_grad_threshold"], m["min_opacity"], self.camera_extent, m["size_threshold"],
+                                                             seed=densify_seed(m.get("densify_seed", 0), frame, iteration), lazy_mask=True)
+                    else:
+                        pruned, parent = g.prune(m["min_opacity"], self.camera_extent, None if splatam else m["size_threshold"], lazy_mask=True), None
                     if token is not None:
                         if not eng.check_capacity_end(token):
                             self._late_overflow = True
@@ -885,8 +896,8 @@ class FusedMapper(Mapper):
                         if not eng.check_capacity():
                             self._late_overflow = True
                         self._piggybacked = True
-                    if self._opt_mask is not None and self._opt_mask.shape[0] != g._xyz.shape[0]:
-                        self._opt_mask = self._opt_mask[~pruned()].contiguous()
+                    if self._opt_mask is not None and (parent is not None or self._opt_mask.shape[0] != g._xyz.shape[0]):
+                        self._opt_mask = g.carry_rows(self._opt_mask, parent, pruned()).contiguous()      # (children take their parent's flag)
                 iteration += 1
             if multi:
                 self._sync_moments(eng)      # whoever touches the map next (seeding, snapshot, checkpoint) finds whole replicas

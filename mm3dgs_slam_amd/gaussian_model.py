@@ -8,6 +8,9 @@ same (file:line are into ``slam/gaussian_model.py``):
   surgery     densification_postfix -> cat_tensors_to_optimizer (:418-487), prune -> prune_points -> _prune_optimizer
               (:380-417, :574-588): parameters are REPLACED by fresh ``nn.Parameter`` objects, so a gradient computed
               before the prune never reaches ``optimizer.step()`` (SURVEY.md section 3.3 -- reproduced on purpose)
+  densify     densify_and_clone / densify_and_split / densify / densify_and_prune (:490-592), reset_opacity and
+              replace_tensor_to_optimizer (:259-264, :360-378); the split samples come from general_utils.densify_normals
+              (a stateless generator the device path reproduces) instead of torch.normal
   stats       max_radii2D, xyz_gradient_accum, denom; add_densification_stats (:594-598)
 PLY import/export keeps the reference's attribute order (:205-257) with a dependency-free binary writer.
 """
@@ -17,9 +20,16 @@ import numpy as np
 import torch
 from torch import nn
 
-from .general_utils import build_scaling_rotation, get_expon_lr_func, inverse_sigmoid, strip_symmetric
+from .general_utils import (build_rotation, build_scaling_rotation, densify_normals, get_expon_lr_func, inverse_sigmoid,
+                            strip_symmetric)
 
 _GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "rgb")
+
+
+def draw_densify_seed():
+    """The seed of a densification without one: 31 bits from torch's global CPU generator (the reference's dependence on the global
+    RNG, for direct callers; the mapping loops pass general_utils.densify_seed)."""
+    return int(torch.randint(0, 2 ** 31, (1,)).item())
 
 
 class GaussianModel:
@@ -281,6 +291,60 @@ class GaussianModel:
         self._surgery_keepalive = (keep, work, color, depth, pose)
         return n
 
+    def densify_device(self, max_grad, extent, seed, N=2):
+        """``densify`` (clone + split) with the kernels of csrc/compact.hip: one classify-and-plan pass (class byte per row and three
+        order-preserving ranks), ONE 12-byte read-back of {n_keep, n_clone, n_split} to size the new tensors, one scatter launch
+        that writes every destination row of every parameter, Adam moment and statistic.  Returns the parent row of every new row
+        (int32), or None when nothing was selected (tensors left in place, gradients dropped, statistics zeroed)."""
+        import ctypes as C
+        from . import _lib
+        from .rasterizer import _stream
+        lib = _lib.load()
+        P = int(self._xyz.shape[0])
+        dev = self._xyz.device
+        work = torch.empty(lib.mm3dgs_densify_work_bytes(P), dtype=torch.uint8, device=dev)
+        counts = torch.empty(3, dtype=torch.int32, device=dev)
+        _lib.check(lib.mm3dgs_densify_plan(P, C.c_void_p(self.xyz_gradient_accum.data_ptr()), C.c_void_p(self.denom.data_ptr()),
+                                           C.c_void_p(self._scaling.data_ptr()), float(max_grad), float(self.percent_dense * extent),
+                                           C.c_void_p(work.data_ptr()), C.c_void_p(counts.data_ptr()), _stream()))
+        n_keep, n_clone, n_split = (int(v) for v in counts.tolist())
+        if n_clone == 0 and n_split == 0:
+            self._drop_grads_and_stats()
+            return None
+        n = n_keep + n_clone + N * n_split
+        st = _lib.Mm3dgsDensifyState()
+        keep = []
+
+        def fresh(t):
+            new = torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+            keep.append(t)
+            return new
+        out = {}
+        self.generation += 1
+        for gi, group in enumerate(self.optimizer.param_groups):
+            assert group["name"] == _GROUPS[gi]       # (the kernel finds xyz / scaling / rotation by position)
+            old = group["params"][0].detach()
+            state = self.optimizer.state.pop(group["params"][0], None)
+            new = nn.Parameter(fresh(old).requires_grad_(True))
+            e = st.group[gi]
+            e.src, e.dst, e.width = old.data_ptr(), new.data_ptr(), int(old[0].numel()) if P else 0
+            if state is not None and "exp_avg" in state:
+                m, v = state["exp_avg"], state["exp_avg_sq"]
+                state["exp_avg"], state["exp_avg_sq"] = fresh(m), fresh(v)
+                e.m_src, e.m_dst, e.v_src, e.v_dst = m.data_ptr(), state["exp_avg"].data_ptr(), v.data_ptr(), state["exp_avg_sq"].data_ptr()
+                self.optimizer.state[new] = state
+            group["params"][0] = new
+            out[group["name"]] = new
+        self._assign(out)
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = fresh(self.xyz_gradient_accum), fresh(self.denom), fresh(self.max_radii2D)
+        st.grad_accum, st.denom, st.max_radii2D = self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self.max_radii2D.data_ptr()
+        parent = torch.empty(n, dtype=torch.int32, device=dev)
+        st.parent = parent.data_ptr()
+        _lib.check(lib.mm3dgs_densify_rows(P, C.c_void_p(work.data_ptr()), n_keep, n_clone, n_split, N, int(seed) & 0xFFFFFFFF, C.byref(st),
+                                           _stream()))
+        self._surgery_keepalive = (keep, work)      # the launch is asynchronous
+        return parent
+
     def prune_points(self, mask):
         # ONE nonzero (one host sync) shared by the ~24 tensors instead of a boolean-mask gather (= nonzero + sync) per
         # tensor; nothing to prune (the common case in SLAM: two pruning steps per frame) leaves every tensor, parameter
@@ -323,6 +387,112 @@ class GaussianModel:
         mask = torch.logical_or(mask, big)
         self.prune_points(mask)
         return (lambda: mask) if lazy_mask else mask
+
+    # ---- densification (slam/gaussian_model.py:490-592) ---------------------------------------------------------------------------
+    def _drop_grads_and_stats(self):
+        """densification_postfix with nothing to add: the tensors stay in place (same values as the rebuild), the gradients go (the
+        rebuild would hand the optimiser fresh parameters without them) and the statistics are zeroed, as the postfix always does."""
+        for group in self.optimizer.param_groups:
+            group["params"][0].grad = None
+        torch._foreach_zero_([self.xyz_gradient_accum, self.denom, self.max_radii2D])
+
+    @torch.no_grad()
+    def densify_and_clone(self, grads, grad_threshold, scene_extent):
+        """Appends a copy of every row with |grad| >= grad_threshold and max scale <= percent_dense * scene_extent (:560-583).
+        Returns the selection mask over the rows before the call."""
+        sel = torch.norm(grads, dim=-1) >= grad_threshold
+        sel = torch.logical_and(sel, self.get_scaling.max(dim=1).values <= self.percent_dense * scene_extent)
+        if not bool(sel.any()):
+            self._drop_grads_and_stats()
+            return sel
+        self.densification_postfix(self._xyz[sel], self._features_dc[sel], self._features_rest[sel], self._opacity[sel],
+                                   self._scaling[sel], self._rotation[sel], self._rgb[sel])
+        return sel
+
+    @torch.no_grad()
+    def densify_and_split(self, grads, grad_threshold, scene_extent, N=2, seed=None):
+        """Replaces every row with grad >= grad_threshold and max scale > percent_dense * scene_extent (rows appended since `grads`
+        was taken count as grad 0) by N children (:490-538): xyz = R(q) (exp(s) z) + xyz, scaling = log(exp(s) / (0.8 N)), the rest
+        copied; children appended k-major after the existing rows, parents removed.  z = densify_normals(seed, parent rows, N) where
+        the reference draws torch.normal; seed None takes one from torch's global generator.  Returns the selection mask."""
+        n_init = self._xyz.shape[0]
+        padded = torch.zeros((n_init,), device=self._xyz.device)
+        padded[: grads.shape[0]] = grads.reshape(-1)
+        sel = torch.logical_and(padded >= grad_threshold, self.get_scaling.max(dim=1).values > self.percent_dense * scene_extent)
+        rows = torch.nonzero(sel, as_tuple=False).squeeze(1)
+        if rows.numel() == 0:
+            self._drop_grads_and_stats()
+            return sel
+        if seed is None:
+            seed = draw_densify_seed()
+        stds = self.get_scaling[sel].repeat(N, 1)
+        samples = stds * densify_normals(seed, rows, N).to(stds.device)
+        rots = build_rotation(self._rotation[sel]).repeat(N, 1, 1)
+        new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + self._xyz[sel].repeat(N, 1)
+        new_scaling = torch.log(self.get_scaling[sel].repeat(N, 1) / (0.8 * N))
+        self.densification_postfix(new_xyz.detach(), self._features_dc[sel].repeat(N, 1, 1), self._features_rest[sel].repeat(N, 1, 1),
+                                   self._opacity[sel].repeat(N, 1), new_scaling.detach(), self._rotation[sel].repeat(N, 1),
+                                   self._rgb[sel].repeat(N, 1))
+        self.prune_points(torch.cat((sel, torch.zeros(N * rows.numel(), device=sel.device, dtype=torch.bool))))
+        return sel
+
+    def _densify_torch(self, max_grad, extent, seed, N=2):
+        P0 = int(self._xyz.shape[0])
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        clone = self.densify_and_clone(grads, max_grad, extent)
+        split = self.densify_and_split(grads, max_grad, extent, N=N, seed=seed)[:P0]
+        if not bool(clone.any()) and not bool(split.any()):
+            return None
+        ar = torch.arange(P0, device=clone.device)
+        return torch.cat((ar[~split], ar[clone], ar[split].repeat(N)))
+
+    def densify(self, max_grad, extent, seed=None):
+        """Clone, then split (:585-590), on the device for CUDA tensors.  Returns the parent row (index before the call) of every
+        row after it, or None when nothing was added (the rows are then unchanged)."""
+        if seed is None:
+            seed = draw_densify_seed()
+        if self._native():
+            return self.densify_device(max_grad, extent, seed)
+        return self._densify_torch(max_grad, extent, seed)
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, seed=None, lazy_mask=False):
+        """densify, then prune (:590-592).  Returns (prune mask over the densified rows, parent rows or None -- see densify): a per-row
+        mask m of the map before the call becomes ``carry_rows(m, parent, prune_mask)`` after it.  lazy_mask as in prune."""
+        parent = self.densify(max_grad, extent, seed)
+        # densification zeroed max_radii2D, so the screen-size clause of this prune cannot fire: the reference's behaviour, kept
+        return self.prune(min_opacity, extent, max_screen_size, lazy_mask=lazy_mask), parent
+
+    @staticmethod
+    def carry_rows(mask, parent, prune_mask):
+        """A per-row tensor of the map before densify_and_prune, on the rows after it: children inherit their parent's row."""
+        if parent is not None:
+            mask = mask.index_select(0, parent.to(torch.int64))
+        return mask[~prune_mask]
+
+    def replace_tensor_to_optimizer(self, tensor, name):
+        """The group `name` gets `tensor` as a fresh parameter with zeroed Adam moments (:360-378)."""
+        out = {}
+        self.generation += 1
+        for group in self.optimizer.param_groups:
+            if group["name"] != name:
+                continue
+            state = self.optimizer.state.pop(group["params"][0], None)
+            new = nn.Parameter(tensor.requires_grad_(True))
+            if state is not None:
+                state["exp_avg"] = torch.zeros_like(tensor)
+                state["exp_avg_sq"] = torch.zeros_like(tensor)
+                self.optimizer.state[new] = state
+            group["params"][0] = new
+            out[name] = new
+        return out
+
+    @torch.no_grad()
+    def reset_opacity(self):
+        """opacity = inverse_sigmoid(min(sigmoid(opacity), 0.01)), moments of the opacity group zeroed (:259-264).  No loop calls it
+        (the reference has no call site)."""
+        op = self.get_opacity.detach()
+        self._opacity = self.replace_tensor_to_optimizer(inverse_sigmoid(torch.min(op, torch.ones_like(op) * 0.01)), "opacity")["opacity"]
 
     def add_densification_stats(self, viewspace_point_tensor, update_filter):
         self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1,

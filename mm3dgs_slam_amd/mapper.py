@@ -22,6 +22,7 @@ from random import randint
 import numpy as np
 import torch
 
+from .general_utils import densify_frame, densify_seed
 from .loss_utils import l1_loss, pearson_loss, ssim
 from .pose_utils import apply_rigid, get_camera_from_tensor, rigid_inverse
 from .sh_utils import RGB2SH
@@ -329,9 +330,17 @@ class Mapper:
                         g.max_radii2D[vis] = torch.max(g.max_radii2D[vis], radii[vis].to(g.max_radii2D.dtype))
                         g.add_densification_stats(result["viewspace_points"], vis)
                     if iteration >= m["densify_from_iter"] and iteration % m["pruning_interval"] == 0:
-                        pruned = g.prune(m["min_opacity"], self.camera_extent, m["size_threshold"])
-                        if do_ba:
-                            opt_mask = opt_mask[~pruned]
+                        if densify_frame(m, idx):
+                            # slam/mapper.py:913-927 (commented out in the reference): densify, then prune, at the pruning step of every
+                            # densification_interval-th frame; the seed is a function of (mapping.densify_seed, frame, iteration)
+                            pruned, parent = g.densify_and_prune(m["densify_grad_threshold"], m["min_opacity"], self.camera_extent,
+                                                                 m["size_threshold"], seed=densify_seed(m.get("densify_seed", 0), idx, iteration))
+                            if do_ba:      # children take their parent's flag
+                                opt_mask = g.carry_rows(opt_mask, parent, pruned)
+                        else:
+                            pruned = g.prune(m["min_opacity"], self.camera_extent, m["size_threshold"])
+                            if do_ba:
+                                opt_mask = opt_mask[~pruned]
                 if do_ba:
                     for group in g.optimizer.param_groups:
                         for p in group["params"]:
