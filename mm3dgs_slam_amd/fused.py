@@ -16,8 +16,9 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import random
 import time
-from random import randint
+import warnings
 
 import torch
 
@@ -102,7 +103,6 @@ class FusedEngine:
                                              (f"active SH degree {gaussians.active_sh_degree} > 0 with convert_SHs_python / world-frame means", not sh_native)) if bad)
             if why not in FusedEngine._warned:
                 FusedEngine._warned.add(why)
-                import warnings
                 warnings.warn(f"mm3dgs: this configuration ({why}) is outside the native SLAM loops (covariances from scales + rotations; an active SH degree > 0 only in the shipped mode with the kernel's SH evaluation); "
                               "tracking and mapping run the torch-graph loops around the generic HIP rasterizer -- correct, but about 30x slower")
         return ok
@@ -302,7 +302,6 @@ class FusedEngine:
             # a tracking loop that skipped its own header read (lazy check, ample headroom) ran -- at least in part -- on an overflowed
             # forward: the kernels voided those pose steps (no optimiser step, no corruption), but the frame was tracked with fewer
             # iterations than configured.  By now the map has moved on, so the loop cannot be re-run; counted and said aloud.
-            import warnings
             self.unrecovered_tracking_overflows = getattr(self, "unrecovered_tracking_overflows", 0) + 1
             warnings.warn(f"mm3dgs: the tracking loop of frame {unchecked} ran without a capacity check and the binning capacity overflowed since "
                           "(its pose steps from the first overflowing forward on were skipped on the device); capacity raised")
@@ -443,9 +442,10 @@ class FusedTracker(Tracker):
 class FusedMapper(Mapper):
     fuse_adam_project = True     # multi-GPU window: the optimiser step and the next view's projection + binning in one launch (False: mm3dgs_adam, then the projection)
     lazy_checks = True       # False: read the capacity header back after every loop (debugging / tests)
-    _piggybacked = False
-    _late_overflow = False
     always_snapshot = False      # debugging / tests: snapshot the map before every mapping loop (the round-2 behaviour)
+    loop_reruns = 0              # mapping loops re-run after a binning overflow
+    unrecovered_overflows = 0    # ... and loops that overflowed without a snapshot to re-run from
+    _adam_cache = None           # _adam_step's group table and the pointers it was built for
 
     def _render_depth_sil(self, pose):
         # the keyframe test renders once per frame: one native forward instead of the ~40 torch launches of Renderer.render
@@ -581,8 +581,6 @@ class FusedMapper(Mapper):
 
     def optimize_map(self, idx, num_iter, keyframe_idx_list, new_gaussians_mask, curr_camera_tensor, curr_gt_color,
                      curr_gt_depth=None, curr_est_depth=None):
-        m = self.cfg["mapping"]
-        do_ba = bool(m["do_BA"]) and idx > 0
         sh_window = int(self.gaussians.active_sh_degree) > 0 and self.window is not None      # (the sharded window's flat gradient layout has no f_rest rows)
         if num_iter == 0 or sh_window or not FusedEngine.eligible(self.cfg, self.gaussians):
             return super().optimize_map(idx, num_iter, keyframe_idx_list, new_gaussians_mask, curr_camera_tensor, curr_gt_color,
@@ -590,99 +588,7 @@ class FusedMapper(Mapper):
         eng = _engine(self.renderer)
         t_start = time.perf_counter()
         g = self.gaussians
-        lam = float(m["lambda_dssim"])
-        w_p, pmask = 0.0, 0
-        if m["use_depth_estimate_loss"]:
-            w_p = float(m["pearson_weight"])
-            pmask = 0 if not self.cfg["use_gt_depth"] else 2
-        lcfg = _loss_cfg(eng.H, eng.W, 1.0 - lam, lam, w_p, 0, pmask, 0, 0.5)
-        splatam = self.cfg["method"].lower() == "splatam"
-        if splatam:
-            # slam/mapper.py:836-855: mean |gt_depth - depth| over { gt_depth > 0 } + 0.5 ((1-l) L1 + l (1 - SSIM)); no Pearson term
-            w_p = 0.0
-            lcfg = _loss_cfg(eng.H, eng.W, 0.5 * (1.0 - lam), 0.5 * lam, 0.0, 0, 0, 0, 0.5, w_depth_l1=1.0, depth_l1_mask=2)
-        stack = None
-
-        def pop():
-            nonlocal stack
-            if not stack:
-                stack = list(keyframe_idx_list)
-            return stack.pop(randint(0, len(stack) - 1))
-
-        view_cache = {}
-
-        def view_of(k):
-            # the window holds a handful of distinct views; the ~150 picks of a frame reuse their (pose, target, reference)
-            # tensors instead of re-deriving them with torch calls while the GPU waits for the next run to be enqueued
-            if k not in view_cache:
-                view_cache[k] = _view_of(k)
-            return view_cache[k]
-
-        ba_state = {}     # view id -> (pose buffer, m, v, step, Mm3dgsPoseAdam): bundle adjustment steps every window pose on the device
-
-        def _view_of(k):
-            if k == -1:
-                pose, gt_color, gt_depth, est_depth = curr_camera_tensor, curr_gt_color, curr_gt_depth, curr_est_depth
-            else:
-                kf = self.keyframes[k]
-                pose, gt_color, gt_depth, est_depth = kf.pose, kf.gt_color, kf.gt_depth, kf.est_depth
-            ref = None
-            if w_p:
-                ref = (est_depth if not self.cfg["use_gt_depth"] else gt_depth).contiguous()
-            if splatam:
-                ref = gt_depth.contiguous()
-            buf = pose.detach().float().contiguous()
-            # Reference quirk kept by default: slam/mapper.py:752-760 puts `keyframes[k].pose[:4].requires_grad_()` views into the pose
-            # optimiser, but the loop renders from FRESH views `keyframe.pose[:4]` (:817-819) that do not require grad -- so the
-            # reference's bundle adjustment only ever refines the CURRENT frame's pose.  mapping.ba_optimize_keyframes: true gives
-            # the intended behaviour (every window pose stepped when its view is rendered).
-            if not do_ba or (k != -1 and not m.get("ba_optimize_keyframes", False)):
-                return buf, gt_color.contiguous(), ref
-            if multi:
-                # sharded window (round 4): the view hands its pose gradient out; the gradients of a step's views are summed over the
-                # ranks and every replica takes the identical pose step (_ba_window_step below) -- the state was created up front
-                st = ba_state[k]
-                return st[0], gt_color.contiguous(), ref, None, st[6]
-            # pose Adam of slam/mapper.py:742-752: Adam(lr=0, eps=1e-15), groups cam_rot (cam_q_lr) / cam_pos (cam_t_lr); a pose is
-            # only stepped in the iterations that render its view (torch skips parameters without a gradient), hence per-view state
-            buf = buf.clone()
-            mom, var = torch.zeros(7, device=eng.dev), torch.zeros(7, device=eng.dev)
-            step = torch.zeros(1, dtype=torch.int32, device=eng.dev)
-            ad = _lib.Mm3dgsPoseAdam()
-            ad.pose, ad.m, ad.v, ad.step = buf.data_ptr(), mom.data_ptr(), var.data_ptr(), step.data_ptr()
-            ad.lr_q, ad.lr_t, ad.beta1, ad.beta2, ad.eps = float(m["cam_q_lr"]), float(m["cam_t_lr"]), 0.9, 0.999, 1e-15
-            ba_state[k] = (buf, mom, var, step, ad, pose)
-            return buf, gt_color.contiguous(), ref, ad
-
-        def prune_at(it):
-            if splatam:      # "Splatam does not densify -- only prunes" (slam/mapper.py:879-884): iterations 0 and 20, no size threshold
-                return it <= 20 and it % 20 == 0
-            return it <= m["densify_until_iter"] and it >= m["densify_from_iter"] and it % m["pruning_interval"] == 0
-
-        import random as _random
-        self._opt_mask = None
-        if do_ba:
-            with torch.no_grad():
-                om = self.get_covisible_gaussians(keyframe_idx_list, curr_camera_tensor, 2)
-                if new_gaussians_mask is not None:
-                    om = om | new_gaussians_mask
-                self._opt_mask = om.to(torch.uint8).contiguous()
-        multi = self.window is not None and self.window.sharded
-        self._ba_ids = []
-        if do_ba and multi:
-            # bundle adjustment with a sharded window, natively: pose, moments, step counter and a gradient slot for EVERY optimisable
-            # pose of the window, created on every rank in the same order (the views a rank renders differ, the state must not)
-            def ba_init():
-                ba_state.clear()
-                ids = sorted(set(k for k in keyframe_idx_list if k == -1 or m.get("ba_optimize_keyframes", False)))
-                self._ba_ids = ids
-                self._ba_grad = torch.zeros(max(len(ids), 1), 7, device=eng.dev)
-                for k in ids:
-                    pose = curr_camera_tensor if k == -1 else self.keyframes[k].pose
-                    buf = pose.detach().float().contiguous().clone()
-                    ba_state[k] = (buf, torch.zeros(7, device=eng.dev), torch.zeros(7, device=eng.dev), [0], None, pose, torch.zeros(7, device=eng.dev))
-            ba_init()
-            self._ba_state, self._ba_init = ba_state, ba_init
+        loop = _MapLoop(self, eng, idx, num_iter, keyframe_idx_list, new_gaussians_mask, (curr_camera_tensor, curr_gt_color, curr_gt_depth, curr_est_depth))
         # overflow recovery: a forward whose (tile, splat) pairs exceed the binning capacity renders clamped lists (flagged
         # sticky in the header).  The loop below is read back once, at its end; if any of its forwards overflowed, the map,
         # the optimiser, the statistics and the keyframe-pick RNG are put back and the loop is re-run (capacity raised).
@@ -696,394 +602,482 @@ class FusedMapper(Mapper):
         # so the map stays as the last complete iteration left it -- the rest of the loop is lost, not corrupted: counted in
         # `unrecovered_overflows`, warned about, capacity raised for the next frame.
         eng._ensure(int(g._xyz.shape[0]), True)
-        need_snap = self.always_snapshot or getattr(eng, "headroom", lambda: 0.0)() < 1.5 or (self.window is not None and self.window._collective)
+        collective = self.window is not None and self.window._collective
+        need_snap = self.always_snapshot or getattr(eng, "headroom", lambda: 0.0)() < 1.5 or collective
         # (densification can grow the map inside the loop -- by up to one row per split -- where pruning only shrinks it: a densifying
         #  frame always keeps a snapshot to re-run from)
-        need_snap = need_snap or (not splatam and densify_frame(m, idx))
-        snap, rng_state = (g.snapshot(), _random.getstate()) if need_snap else (None, None)
-        self._late_overflow, self._piggybacked = False, False
-        for attempt in range(4):
-            self._map_loop_once(eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback=snap is None, frame=idx)
-            if snap is None and self.lazy_checks and self._piggybacked and getattr(eng, "headroom", lambda: 0.0)() >= 1.5:
+        need_snap = need_snap or loop.densifies
+        snap = (g.snapshot(), random.getstate()) if need_snap else None
+        for _ in range(4):
+            loop.run(piggyback=snap is None)
+            if snap is None and self.lazy_checks and loop.piggybacked and getattr(eng, "headroom", lambda: 0.0)() >= 1.5:
                 # no snapshot was needed (ample headroom) and the header was read at this loop's pruning steps, where the device is
                 # drained anyway: the end-of-loop read-back (one more synchronisation per frame) is left to the next drained point
-                ok = not self._late_overflow
+                ok = not loop.late_overflow
             else:
-                ok = eng.check_capacity() and not self._late_overflow
-            if self.window is not None and self.window._collective:
+                ok = eng.check_capacity() and not loop.late_overflow
+            if collective:
                 ok = not self.window.any_flag(not ok, device=eng.dev)
             if ok:
                 break
             if snap is None:
-                import warnings
-                self.unrecovered_overflows = getattr(self, "unrecovered_overflows", 0) + 1
+                self.unrecovered_overflows += 1
                 warnings.warn("mm3dgs: a mapping loop overflowed its binning capacity without a snapshot to restore (its iterations from the "
                               "first overflowing forward on were skipped on the device: no optimiser step taken); capacity raised")
                 break
-            self.loop_reruns = getattr(self, "loop_reruns", 0) + 1
-            g.restore(snap)
-            self._moments_stale = False      # (the snapshot was taken with whole replicas: sharded optimiser steps of the failed attempt are gone with it)
-            _random.setstate(rng_state)
-            stack = None
-            view_cache.clear(); ba_state.clear()       # (pose buffers and their Adam state start over)
-            if do_ba and multi:
-                self._ba_init()
-            if do_ba:
-                with torch.no_grad():
-                    om = self.get_covisible_gaussians(keyframe_idx_list, curr_camera_tensor, 2)
-                    if new_gaussians_mask is not None:
-                        om = om | new_gaussians_mask
-                    self._opt_mask = om.to(torch.uint8).contiguous()
+            self.loop_reruns += 1
+            loop.reset(snap)
         else:
             raise RuntimeError("mm3dgs: mapping loop kept overflowing its binning capacity")
-        if do_ba:      # the optimised window poses go back where the reference's in-place Adam leaves them
+        self._opt_mask, self._ba_ids = loop.opt_mask, loop.ba_ids      # (what the loop ended with: bundle adjustment's mask and window poses)
+        if loop.do_ba:      # the optimised window poses go back where the reference's in-place Adam leaves them
             with torch.no_grad():
-                for k, st in ba_state.items():
-                    st[5].data.copy_(st[0])
+                for st in loop.ba.values():
+                    st.source.data.copy_(st.buf)
         if self.cfg["debug"]["get_runtime_stats"]:
             if eng.dev.type == "cuda":
                 torch.cuda.synchronize(eng.dev)
             self.mapping_time_sum += time.perf_counter() - t_start
         self.mapping_iter_count += num_iter
 
-    def _map_loop_once(self, eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback=False, frame=0):
-        splatam = self.cfg["method"].lower() == "splatam"       # prunes (prune_at), never collects densification statistics
-
-        def dens(it):
-            return (not splatam) and it <= m["densify_until_iter"]
-
-        def run_length(start):
-            n = 1
-            while start + n < num_iter and not prune_at(start + n) and dens(start + n) == dens(start):
-                n += 1
-            return n
-
-        try:
-            self._map_loop_body(eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback, splatam, dens, run_length, frame)
-        except BaseException:
-            #  an exception after sharded optimiser steps -- a failing check, a prune that raises, a collective error -- must not
-            # leave every rank with fresh Adam moments for its own slice only: SLAM.run goes on to write the map.  Gather them if the
-            # process group still answers; if it does not, say so in the state the writers look at.
-            if multi and getattr(self, "_moments_stale", False):
-                try:
-                    self._sync_moments(eng)
-                except Exception:      # noqa: BLE001 -- the original exception is the one to report
-                    self.window_incoherent = True
-            raise
-
-    def _map_loop_body(self, eng, g, m, lcfg, num_iter, multi, pop, view_of, prune_at, piggyback, splatam, dens, run_length, frame=0):
-        with torch.no_grad():
-            iteration = 0
-            prepared = None      # (first iteration, views, table) of a run whose host side was built while the GPU was still busy
-            pending, projected_next = None, False      # multi-GPU window: the next step's keyframe picks, drawn ahead by a fused Adam + projection launch
-            while iteration < num_iter:
-                densify = dens(iteration)
-                if not multi and not prune_at(iteration):
-                    # single GPU: the run of iterations up to the next pruning step (or the end of the densification phase)
-                    # is enqueued by ONE C call -- no Python between the ~9 launches of an iteration
-                    if prepared is not None and prepared[0] == iteration:
-                        views = prepared[1]
-                    else:
-                        views = _Views(view_of(pop()) for _ in range(run_length(iteration)))
-                        views.table = FusedEngine.view_table(views)
-                    prepared = None
-                    n = len(views)
-                    stats = (g.max_radii2D, g.xyz_gradient_accum, g.denom) if densify else None
-                    eng.map_loop(views, g, lcfg, stats, self._inline_adam(n))
-                    iteration += n
-                    continue
-                # one optimiser step over this rank's share of the window batch (a single view without a window)
-                if pending is not None:
-                    all_ids, ids = pending        # (popped ahead by the previous step, whose Adam launch already projected ids[0]'s view)
-                else:
-                    all_ids, ids = self.window.take_all(pop) if self.window is not None else (None, [pop()])
-                was_projected, pending, projected_next = projected_next, None, False
-                P = int(g._xyz.shape[0])
-                eng._ensure(P, True)
-                prune_now = prune_at(iteration)
-                if multi:
-                    # forward, loss and backward of each view in one C call (gradients written out, not stepped); more than
-                    # one local view (window-batch mode): summed in view order; then ONE flat all-reduce over the ranks carries
-                    # every parameter gradient and, while densifying, the statistics tail [14P, 16P) (+ a max-reduce of the radii)
-                    if densify:
-                        torch._foreach_zero_([eng.stat_delta[0], eng.flat[14 * P:]])        # (one launch)
-                    if self._ba_ids:
-                        self._ba_grad.zero_()
-                    for j, k in enumerate(ids):
-                        # (one iteration per C call here: the workgroup -> tile table is rebuilt by the first call of the loop only, the
-                        #  loss scalars are finished by the last one only -- 9 + 6 us of launches per step otherwise)
-                        eng.map_loop([view_of(k)], g, lcfg, eng.stat_delta if densify else None, None, grads=eng.grads,
-                                     keep_tile_order=iteration > 0 or j > 0, want_loss=iteration == num_iter - 1 and j == len(ids) - 1,
-                                     **({"projected": True} if (was_projected and j == 0) else {}))
-                        if k in self._ba_ids:      # this view's pose gradient (its slot is overwritten by the pose's next view)
-                            self._ba_grad[self._ba_ids.index(k)] += self._ba_state[k][6]
-                        if len(ids) > 1:
-                            if j == 0:
-                                eng.acc[:14 * P].copy_(eng.flat[:14 * P])
-                            else:
-                                eng.acc[:14 * P].add_(eng.flat[:14 * P])
-                    if len(ids) > 1:
-                        eng.flat[:14 * P].copy_(eng.acc[:14 * P])
-                    # how the summed gradients become stepped parameters everywhere: one flat all-reduce + the identical step on every replica, or
-                    # (WindowParallel.optimizer; default from 500 k Gaussians on) reduce-scatter -> Adam on this rank's 1 / world of the elements ->
-                    # all-gather of the parameters; the statistics tail and the radii always travel by all-reduce (every replica prunes)
-                    shard = (not prune_now) and self.window.shard_optimizer(P)
-                    if shard and self._opt_mask is not None:      # bundle adjustment: frozen Gaussians keep a zero gradient (masked before the sum: the mask is the same everywhere)
-                        keep = self._opt_mask.to(eng.flat.dtype)
-                        for t in eng.grads.values():
-                            t.mul_(keep.view(-1, *([1] * (t.dim() - 1))))
-                    if shard:
-                        self._shard_buffers(eng, P)
-                        self.window.reduce_scatter_flat(eng.flat, 14 * P, eng.shard_g, tail=2 * P if densify else 0, rmax=eng.stat_delta[0] if densify else None)
-                    elif densify:
-                        self.window.reduce_flat(eng.flat[:16 * P], eng.stat_delta[0])
-                    else:
-                        self.window.reduce_flat(eng.flat[:14 * P])
-                    if densify:
-                        torch.maximum(g.max_radii2D, eng.stat_delta[0], out=g.max_radii2D)
-                        torch._foreach_add_([g.xyz_gradient_accum, g.denom], [eng.stat_delta[1], eng.stat_delta[2]])      # (one launch)
-                    if self._ba_ids:
-                        self._ba_window_step(eng, m, all_ids, ids)
-                    if shard:
-                        self._sharded_step(eng, g, P)
-                    elif not prune_now:
-                        fuse = (self.fuse_adam_project and iteration + 1 < num_iter and hasattr(eng, "adam_project") and eng.can_adam_project(g))
-                        if fuse:
-                            # the step and the NEXT view's projection + binning in one launch: the next step's keyframe picks are drawn now
-                            # (same draws, same order as at the head of the next iteration), its first local view's pose goes with the step
-                            pending = self.window.take_all(pop)
-                            eng.adam_project(view_of(pending[1][0])[0], g, eng.grads, self._inline_adam(1))      # (opt_mask rides in the Adam struct)
-                            projected_next = True
-                        else:
-                            if self._opt_mask is not None:       # bundle adjustment: Gaussians outside the covisible set keep a zero gradient (slam/mapper.py:931-938)
-                                keep = self._opt_mask.to(eng.flat.dtype)
-                                for t in eng.grads.values():
-                                    t.mul_(keep.view(-1, *([1] * (t.dim() - 1))))
-                            self._adam_step(eng)
-                else:
-                    # a pruning iteration: gradients + statistics only (the reference prunes BEFORE optimizer.step(): the
-                    # parameters are replaced, so that step is a no-op)
-                    stats = (g.max_radii2D, g.xyz_gradient_accum, g.denom) if densify else None
-                    eng.map_loop([view_of(ids[0])], g, lcfg, stats, None, grads=eng.grads, keep_tile_order=iteration > 0,
-                                 want_loss=iteration == num_iter - 1)
-                if prune_now:
-                    if multi:
-                        self._sync_moments(eng)      # (sharded optimiser steps: the compaction moves rows across shard boundaries)
-                    # on the device: predicate kernel, compaction plan, a 4-byte read-back of the new size, and -- only if
-                    # something is pruned -- one scatter launch over parameters, moments and statistics (gaussian_model.py).
-                    # The read-back blocks until the GPU has drained: the views of the run that follows (same keyframe picks, in the
-                    # same order, whatever the pruning decides) are popped and tabulated first, while the GPU is still working.
-                    if not multi and iteration + 1 < num_iter and not prune_at(iteration + 1):
-                        nxt = _Views(view_of(pop()) for _ in range(run_length(iteration + 1)))
-                        nxt.table = FusedEngine.view_table(nxt)
-                        prepared = (iteration + 1, nxt)
-                    # The capacity header (sticky: every forward since the last read, the tracker's included) rides on the pruning
-                    # step's read-back: its copy to pinned memory is enqueued before, parsed after -- no round trip of its own
-                    token = eng.check_capacity_begin() if (piggyback and hasattr(eng, "check_capacity_begin")) else None
-                    if not splatam and densify_frame(m, frame):
-                        # densification (slam/mapper.py:913-927, commented out in the reference) at this pruning step: classify-and-plan,
-                        # a 12-byte read-back, one scatter (gaussian_model.densify_device), then the prune.  The seed is a function of
-                        # (mapping.densify_seed, frame, iteration): an overflow re-run of this loop draws the same samples
-                        pruned, parent = g.densify_and_prune(m["densify_grad_threshold"], m["min_opacity"], self.camera_extent, m["size_threshold"],
-                                                             seed=densify_seed(m.get("densify_seed", 0), frame, iteration), lazy_mask=True)
-                    else:
-                        pruned, parent = g.prune(m["min_opacity"], self.camera_extent, None if splatam else m["size_threshold"], lazy_mask=True), None
-                    if token is not None:
-                        if not eng.check_capacity_end(token):
-                            self._late_overflow = True
-                        self._piggybacked = True
-                    elif piggyback and hasattr(eng, "check_capacity"):
-                        if not eng.check_capacity():
-                            self._late_overflow = True
-                        self._piggybacked = True
-                    if self._opt_mask is not None and (parent is not None or self._opt_mask.shape[0] != g._xyz.shape[0]):
-                        self._opt_mask = g.carry_rows(self._opt_mask, parent, pruned()).contiguous()      # (children take their parent's flag)
-                iteration += 1
-            if multi:
-                self._sync_moments(eng)      # whoever touches the map next (seeding, snapshot, checkpoint) finds whole replicas
-
-    def _ba_window_step(self, eng, m, all_ids, my_ids):
-        """Bundle adjustment with a sharded window: this rank's views wrote their pose gradients out (Mm3dgsMapView.dpose_out_or_null)
-        and the loop summed them per pose (a pose rendered twice in a step gets both gradients, like autograd accumulates them);
-        here they are all-reduced over the ranks, then every replica steps -- with mm3dgs_adam: Adam(eps=1e-15), cam_q_lr / cam_t_lr,
-        slam/mapper.py:742-752 -- exactly the poses SOME rank rendered in this step (known on every rank from the shared keyframe
-        stack: no flags travel), so a pose nobody rendered keeps its moments and step counter, as torch skips parameters without a
-        gradient (the torch-graph window does the same through WindowParallel.reduce_pose_grads)."""
-        st_all, order = self._ba_state, self._ba_ids
-        gbuf = self._ba_grad           # (this rank's views added their gradients as they were rendered)
-        self.window.reduce_small(gbuf)
-        for k in sorted(set(i for i in all_ids if i in st_all)):
-            buf, mom, var, step, _ad, _pose, _slot = st_all[k]
-            step[0] += 1
-            gk = gbuf[order.index(k)]
-            table = (_lib.Mm3dgsAdamGroup * 8)()
-            for j, (lo, hi, lr) in enumerate(((0, 4, float(m["cam_q_lr"])), (4, 7, float(m["cam_t_lr"])))):
-                e = table[j]
-                e.param, e.grad = buf[lo:hi].data_ptr(), gk[lo:hi].data_ptr()
-                e.exp_avg, e.exp_avg_sq = mom[lo:hi].data_ptr(), var[lo:hi].data_ptr()
-                e.n, e.lr = hi - lo, lr
-            _lib.check(eng.lib.mm3dgs_adam(table, 2, step[0], 0.9, 0.999, 1e-15, _stream()))
-
-    def _inline_adam(self, n=1):
+    def _inline_adam(self, n=1, opt_mask=None):
         """Mm3dgsMapAdam over the optimiser's own state tensors (created like torch.optim.Adam would on its first step);
-        `step` = step number of the first of the n iterations it will serve (the optimiser's counters advance by n)."""
+        `step` = step number of the first of the n iterations it will serve (the optimiser's counters advance by n).
+        opt_mask: bundle adjustment's uint8 mask of the Gaussians that may move (None: all of them)."""
         opt = self.gaussians.optimizer
         ma = _lib.Mm3dgsMapAdam()
-        step_val = None
         for i, name in enumerate(("xyz", "f_dc", "opacity", "scaling", "rotation")):
-            group = next(gr for gr in opt.param_groups if gr["name"] == name)
-            p = group["params"][0]
-            st = opt.state[p]
-            if "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            first = int(st["step"].item()) + 1
+            group, p, st = _adam_state(opt, name)
+            if i == 0:
+                ma.step = int(st["step"].item()) + 1
             st["step"] += n
-            step_val = first if step_val is None else step_val
             ma.param[i], ma.exp_avg[i], ma.exp_avg_sq[i] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
             ma.lr[i] = float(group["lr"])
         if int(self.gaussians.active_sh_degree) > 0:      # (ABI 209) the sixth group: f_rest, stepped in the kernel at an active SH degree > 0
-            group = next(gr for gr in opt.param_groups if gr["name"] == "f_rest")
-            p = group["params"][0]
-            st = opt.state[p]
-            if "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            group, p, st = _adam_state(opt, "f_rest")
             st["step"] += n
             ma.rest_param, ma.rest_exp_avg, ma.rest_exp_avg_sq = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
             ma.rest_lr = float(group["lr"])
         b1, b2 = opt.param_groups[0]["betas"]
-        ma.beta1, ma.beta2, ma.eps, ma.step = float(b1), float(b2), float(opt.param_groups[0]["eps"]), step_val
-        if getattr(self, "_opt_mask", None) is not None:
-            ma.opt_mask = self._opt_mask.data_ptr()
+        ma.beta1, ma.beta2, ma.eps = float(b1), float(b2), float(opt.param_groups[0]["eps"])
+        if opt_mask is not None:
+            ma.opt_mask = opt_mask.data_ptr()
         return ma
+
+    def _adam_step(self, eng):
+        """mm3dgs_adam over the whole map from the gradient arrays eng.grads (the window's replicated optimiser step)."""
+        opt = self.gaussians.optimizer
+        g = self.gaussians
+        # the group table only changes when a tensor is replaced (prune / densify): cache it on the pointers
+        key = (g.generation, g._xyz.data_ptr(), eng.grads["xyz"].data_ptr(), int(g._xyz.shape[0]))
+        cache = self._adam_cache
+        if cache is None or cache[0] != key or any(float(group["lr"]) != lr for group, lr, _ in cache[2]):
+            table, used = (_lib.Mm3dgsAdamGroup * 8)(), []
+            for group in opt.param_groups:
+                if group["name"] not in eng.grads:
+                    continue                     # f_rest (empty at SH degree 0) and rgb never receive a gradient
+                _, p, st = _adam_state(opt, group["name"])
+                e = table[len(used)]
+                e.param, e.grad = p.data_ptr(), eng.grads[group["name"]].data_ptr()
+                e.exp_avg, e.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+                e.n, e.lr = p.numel(), float(group["lr"])
+                used.append((group, float(group["lr"]), st))
+            cache = self._adam_cache = (key, table, used)
+        _, table, used = cache
+        for _, _, st in used:
+            st["step"] += 1
+        b1, b2 = opt.param_groups[0]["betas"]
+        _lib.check(eng.lib.mm3dgs_adam(table, len(used), int(used[0][2]["step"].item()), float(b1), float(b2), float(opt.param_groups[0]["eps"]),
+                                       _stream()))
+
+
+def _adam_state(opt, name):
+    """(group, parameter, Adam state) of the optimiser group `name`; the state is created the way torch.optim.Adam creates it on its
+    first step (the step counter a CPU tensor, as in the optimiser's state dict and checkpoints)."""
+    group = next(gr for gr in opt.param_groups if gr["name"] == name)
+    p = group["params"][0]
+    st = opt.state[p]
+    if "exp_avg" not in st:
+        st["step"] = torch.tensor(0.0)
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+    return group, p, st
+
+
+class _PoseState:
+    """Bundle-adjustment state of one window pose: the buffer its views render from and Adam steps, the two moments, the step counter,
+    the pose it was copied from (written back after the loop) and either
+      - one GPU (lrs given): the Mm3dgsPoseAdam the pose's views carry -- the library steps the pose and counts `step`, a device int32;
+      - the sharded window: `grad`, the slot the view's pose gradient is written to (Mm3dgsMapView.dpose_out_or_null); the gradients
+        are summed over the ranks and every replica steps the pose with mm3dgs_adam, counting `step` on the host."""
+    __slots__ = ("source", "buf", "m", "v", "step", "adam", "grad")
+
+    def __init__(self, source, dev, lrs=None):
+        self.source = source
+        self.buf = source.detach().float().contiguous().clone()
+        self.m, self.v = torch.zeros(7, device=dev), torch.zeros(7, device=dev)
+        self.adam = self.grad = None
+        if lrs is None:
+            self.step, self.grad = 0, torch.zeros(7, device=dev)
+            return
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        ad = self.adam = _lib.Mm3dgsPoseAdam()
+        ad.pose, ad.m, ad.v, ad.step = self.buf.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr()
+        ad.lr_q, ad.lr_t, ad.beta1, ad.beta2, ad.eps = lrs[0], lrs[1], 0.9, 0.999, 1e-15
+
+
+class _MapLoop:
+    """One FusedMapper.optimize_map call on the native loops: its schedule, loss configuration and per-attempt state -- the keyframe stack,
+    the view cache, the bundle-adjustment pose states and the opt mask -- and, on the sharded window, the optimiser state only that window
+    has (shard buffers, whether other ranks' moment elements are stale, the summed pose gradients).  reset() is the one place the
+    per-attempt state is (re)built: for the first attempt and for every overflow re-run."""
+
+    def __init__(self, mapper, eng, frame, num_iter, keyframe_ids, new_mask, current):
+        m = mapper.cfg["mapping"]
+        self.mapper, self.eng, self.g, self.m, self.window = mapper, eng, mapper.gaussians, m, mapper.window
+        self.frame, self.num_iter, self.kf_ids, self.new_mask = frame, num_iter, keyframe_ids, new_mask
+        self.current = current       # (pose, gt_color, gt_depth, est_depth) of the frame being mapped: window entry -1
+        self.do_ba = bool(m["do_BA"]) and frame > 0
+        self.multi = self.window is not None and self.window.sharded
+        self.splatam = mapper.cfg["method"].lower() == "splatam"       # prunes (prune_at), never collects densification statistics
+        self.densifies = not self.splatam and densify_frame(m, frame)
+        lam = float(m["lambda_dssim"])
+        # ref_at: where a view's reference depth sits in (pose, gt_color, gt_depth, est_depth) -- None: the loss takes none
+        if self.splatam:
+            # slam/mapper.py:836-855: mean |gt_depth - depth| over { gt_depth > 0 } + 0.5 ((1-l) L1 + l (1 - SSIM)); no Pearson term
+            self.lcfg, self.ref_at = _loss_cfg(eng.H, eng.W, 0.5 * (1.0 - lam), 0.5 * lam, 0.0, 0, 0, 0, 0.5, w_depth_l1=1.0, depth_l1_mask=2), 2
+        else:
+            w_p, pmask, self.ref_at = 0.0, 0, None
+            if m["use_depth_estimate_loss"]:
+                gt = mapper.cfg["use_gt_depth"]
+                w_p, pmask = float(m["pearson_weight"]), 2 if gt else 0
+                self.ref_at = (2 if gt else 3) if w_p else None
+            self.lcfg = _loss_cfg(eng.H, eng.W, 1.0 - lam, lam, w_p, 0, pmask, 0, 0.5)
+        self.piggyback = self.piggybacked = self.late_overflow = False
+        self.shard_S = None          # the shard size the sharded window's buffers were made for
+        self.reset()
+
+    def reset(self, snap=None):
+        """The per-attempt state as an attempt starts from it.  An overflow re-run passes snap = (GaussianModel.snapshot(),
+        random.getstate()) of the first attempt: the map, optimiser and statistics and the keyframe-pick RNG go back too."""
+        if snap is not None:
+            self.g.restore(snap[0])
+            random.setstate(snap[1])
+        self.stack, self.views, self.ba, self.ba_ids = None, {}, {}, []
+        self.stale = False       # (a snapshot holds whole replicas: sharded optimiser steps of a failed attempt are gone with it)
+        if self.do_ba and self.multi:
+            # bundle adjustment with a sharded window, natively: pose, moments, step counter and a gradient slot for EVERY optimisable
+            # pose of the window, created on every rank in the same order (the views a rank renders differ, the state must not)
+            self.ba_ids = sorted(set(k for k in self.kf_ids if k == -1 or self.m.get("ba_optimize_keyframes", False)))
+            self.ba_grad = torch.zeros(max(len(self.ba_ids), 1), 7, device=self.eng.dev)
+            for k in self.ba_ids:
+                self.ba[k] = _PoseState(self._frame(k)[0], self.eng.dev)
+        self.opt_mask = None
+        if self.do_ba:
+            with torch.no_grad():
+                om = self.mapper.get_covisible_gaussians(self.kf_ids, self.current[0], 2)
+                if self.new_mask is not None:
+                    om = om | self.new_mask
+                self.opt_mask = om.to(torch.uint8).contiguous()
+
+    # ---- schedule and views ----------------------------------------------------------------------------------------------------------
+    def prune_at(self, it):
+        if self.splatam:      # "Splatam does not densify -- only prunes" (slam/mapper.py:879-884): iterations 0 and 20, no size threshold
+            return it <= 20 and it % 20 == 0
+        m = self.m
+        return it <= m["densify_until_iter"] and it >= m["densify_from_iter"] and it % m["pruning_interval"] == 0
+
+    def dens(self, it):
+        """Whether iteration `it` collects densification statistics."""
+        return (not self.splatam) and it <= self.m["densify_until_iter"]
+
+    def run_length(self, start):
+        n = 1
+        while start + n < self.num_iter and not self.prune_at(start + n) and self.dens(start + n) == self.dens(start):
+            n += 1
+        return n
+
+    def pop(self):
+        if not self.stack:
+            self.stack = list(self.kf_ids)
+        return self.stack.pop(random.randint(0, len(self.stack) - 1))
+
+    def _frame(self, k):
+        if k == -1:
+            return self.current
+        kf = self.mapper.keyframes[k]
+        return kf.pose, kf.gt_color, kf.gt_depth, kf.est_depth
+
+    def view_of(self, k):
+        # the window holds a handful of distinct views; the ~150 picks of a frame reuse their (pose, target, reference)
+        # tensors instead of re-deriving them with torch calls while the GPU waits for the next run to be enqueued
+        if k not in self.views:
+            self.views[k] = self._make_view(k)
+        return self.views[k]
+
+    def _make_view(self, k):
+        src = self._frame(k)
+        pose, gt_color = src[:2]
+        ref = None if self.ref_at is None else src[self.ref_at].contiguous()
+        # Reference quirk kept by default: slam/mapper.py:752-760 puts `keyframes[k].pose[:4].requires_grad_()` views into the pose
+        # optimiser, but the loop renders from FRESH views `keyframe.pose[:4]` (:817-819) that do not require grad -- so the
+        # reference's bundle adjustment only ever refines the CURRENT frame's pose.  mapping.ba_optimize_keyframes: true gives
+        # the intended behaviour (every window pose stepped when its view is rendered).
+        if not self.do_ba or (k != -1 and not self.m.get("ba_optimize_keyframes", False)):
+            return pose.detach().float().contiguous(), gt_color.contiguous(), ref
+        if self.multi:
+            # sharded window (round 4): the view hands its pose gradient out; the gradients of a step's views are summed over the
+            # ranks and every replica takes the identical pose step (_ba_step below) -- the state was created up front
+            st = self.ba[k]
+            return st.buf, gt_color.contiguous(), ref, None, st.grad
+        # pose Adam of slam/mapper.py:742-752: Adam(lr=0, eps=1e-15), groups cam_rot (cam_q_lr) / cam_pos (cam_t_lr); a pose is
+        # only stepped in the iterations that render its view (torch skips parameters without a gradient), hence per-view state
+        st = self.ba[k] = _PoseState(pose, self.eng.dev, (float(self.m["cam_q_lr"]), float(self.m["cam_t_lr"])))
+        return st.buf, gt_color.contiguous(), ref, st.adam
+
+    def _run_views(self, start):
+        """The views of the run that starts at iteration `start`, with their Mm3dgsMapView table."""
+        views = _Views(self.view_of(self.pop()) for _ in range(self.run_length(start)))
+        views.table = FusedEngine.view_table(views)
+        return views
+
+    # ---- the loop --------------------------------------------------------------------------------------------------------------------
+    def run(self, piggyback):
+        """One attempt at the whole loop.  piggyback (no snapshot to re-run from): read the capacity header back at the pruning steps."""
+        self.piggyback = piggyback
+        try:
+            with torch.no_grad():
+                it = 0
+                self.prepared = None      # the views of a single-GPU run, built while the GPU was still busy (_prune)
+                self.pending = None       # multi-GPU window: the next step's keyframe picks, drawn ahead by a fused Adam + projection launch
+                while it < self.num_iter:
+                    prune = self.prune_at(it)
+                    n = self._window_step(it, prune) if self.multi else self._single_run(it, prune)
+                    if prune:
+                        self._prune(it)
+                    it += n
+                if self.multi:
+                    self.sync_moments()      # whoever touches the map next (seeding, snapshot, checkpoint) finds whole replicas
+        except BaseException:
+            # (ADVICE round 5) an exception after sharded optimiser steps -- a failing check, a prune that raises, a collective error -- must not
+            # leave every rank with fresh Adam moments for its own slice only: SLAM.run goes on to write the map.  Gather them if the
+            # process group still answers; if it does not, say so.
+            if self.stale:
+                try:
+                    self.sync_moments()
+                except Exception:      # noqa: BLE001 -- the original exception is the one to report
+                    warnings.warn("mm3dgs: the mapping loop failed after sharded optimiser steps and its Adam moments could not be gathered: "
+                                  "this rank's moments are fresh only for its own shard of the elements")
+            raise
+
+    def _single_run(self, it, prune):
+        """One GPU: the run of iterations up to the next pruning step (or the end of the densification phase) enqueued by ONE C call -- no
+        Python between the ~9 launches of an iteration.  A pruning iteration renders one view for gradients + statistics only (the reference
+        prunes BEFORE optimizer.step(): the parameters are replaced, so that step is a no-op).  Returns the number of iterations run."""
+        g, eng = self.g, self.eng
+        stats = (g.max_radii2D, g.xyz_gradient_accum, g.denom) if self.dens(it) else None
+        if prune:
+            view = self.view_of(self.pop())      # (a window that is not sharded has one view per step)
+            eng._ensure(int(g._xyz.shape[0]), True)
+            eng.map_loop([view], g, self.lcfg, stats, None, grads=eng.grads, keep_tile_order=it > 0, want_loss=it == self.num_iter - 1)
+            return 1
+        views, self.prepared = self.prepared or self._run_views(it), None
+        eng.map_loop(views, g, self.lcfg, stats, self.mapper._inline_adam(len(views), self.opt_mask))
+        return len(views)
+
+    def _window_step(self, it, prune):
+        """One optimiser step over this rank's share of the window batch: the local views' gradients (_local_grads), their sum over the
+        ranks, the statistics, bundle adjustment's pose step, then the map's step -- sharded Adam, or on every replica the fused Adam +
+        next projection or mm3dgs_adam; none at a pruning iteration.  Returns 1 (iterations run)."""
+        g, eng, w = self.g, self.eng, self.window
+        projected = self.pending is not None      # (its ids were popped by the previous step, whose Adam launch already projected ids[0]'s view)
+        all_ids, ids = self.pending if projected else w.take_all(self.pop)
+        self.pending = None
+        P = int(g._xyz.shape[0])
+        eng._ensure(P, True)
+        densify = self.dens(it)
+        self._local_grads(it, ids, projected, densify, P)
+        # how the summed gradients become stepped parameters everywhere: one flat all-reduce + the identical step on every replica, or
+        # (WindowParallel.optimizer; default from 500 k Gaussians on) reduce-scatter -> Adam on this rank's 1 / world of the elements ->
+        # all-gather of the parameters; the statistics tail and the radii always travel by all-reduce (every replica prunes)
+        shard = (not prune) and w.shard_optimizer(P)
+        if shard:
+            self._mask_grads()      # (before the sum: the mask is the same everywhere)
+            self._shard_buffers(P)
+            w.reduce_scatter_flat(eng.flat, 14 * P, self.shard_g, tail=2 * P if densify else 0, rmax=eng.stat_delta[0] if densify else None)
+        elif densify:
+            w.reduce_flat(eng.flat[:16 * P], eng.stat_delta[0])
+        else:
+            w.reduce_flat(eng.flat[:14 * P])
+        if densify:
+            torch.maximum(g.max_radii2D, eng.stat_delta[0], out=g.max_radii2D)
+            torch._foreach_add_([g.xyz_gradient_accum, g.denom], [eng.stat_delta[1], eng.stat_delta[2]])      # (one launch)
+        if self.ba_ids:
+            self._ba_step(all_ids)
+        if shard:
+            self._sharded_adam(P)
+        elif not prune:
+            if self.mapper.fuse_adam_project and it + 1 < self.num_iter and hasattr(eng, "adam_project") and eng.can_adam_project(g):
+                # the step and the NEXT view's projection + binning in one launch: the next step's keyframe picks are drawn now
+                # (same draws, same order as at the head of the next iteration), its first local view's pose goes with the step
+                self.pending = w.take_all(self.pop)
+                eng.adam_project(self.view_of(self.pending[1][0])[0], g, eng.grads, self.mapper._inline_adam(1, self.opt_mask))      # (opt_mask rides in the Adam struct)
+            else:
+                self._mask_grads()
+                self.mapper._adam_step(eng)
+        return 1
+
+    def _local_grads(self, it, ids, projected, densify, P):
+        """Forward, loss and backward of each of this rank's views of a window step, gradients written out (not stepped) to eng.flat; more
+        than one local view (window-batch mode): summed there in view order.  ONE flat all-reduce over the ranks then carries every
+        parameter gradient and, while densifying, the statistics tail [14P, 16P) (+ a max-reduce of the radii)."""
+        g, eng = self.g, self.eng
+        if densify:
+            torch._foreach_zero_([eng.stat_delta[0], eng.flat[14 * P:]])        # (one launch)
+        if self.ba_ids:
+            self.ba_grad.zero_()
+        for j, k in enumerate(ids):
+            # (one iteration per C call here: the workgroup -> tile table is rebuilt by the first call of the loop only, the
+            #  loss scalars are finished by the last one only -- 9 + 6 us of launches per step otherwise)
+            eng.map_loop([self.view_of(k)], g, self.lcfg, eng.stat_delta if densify else None, None, grads=eng.grads,
+                         keep_tile_order=it > 0 or j > 0, want_loss=it == self.num_iter - 1 and j == len(ids) - 1,
+                         **({"projected": True} if (projected and j == 0) else {}))
+            if k in self.ba_ids:      # this view's pose gradient (its slot is overwritten by the pose's next view)
+                self.ba_grad[self.ba_ids.index(k)] += self.ba[k].grad
+            if len(ids) > 1:
+                if j == 0:
+                    eng.acc[:14 * P].copy_(eng.flat[:14 * P])
+                else:
+                    eng.acc[:14 * P].add_(eng.flat[:14 * P])
+        if len(ids) > 1:
+            eng.flat[:14 * P].copy_(eng.acc[:14 * P])
+
+    def _mask_grads(self):
+        """Bundle adjustment: Gaussians outside the covisible set keep a zero gradient (slam/mapper.py:931-938)."""
+        if self.opt_mask is None:
+            return
+        keep = self.opt_mask.to(self.eng.flat.dtype)
+        for t in self.eng.grads.values():
+            t.mul_(keep.view(-1, *([1] * (t.dim() - 1))))
+
+    def _prune(self, it):
+        """The pruning step, on the device: predicate kernel, compaction plan, a 4-byte read-back of the new size, and -- only if
+        something is pruned -- one scatter launch over parameters, moments and statistics (gaussian_model.py); the opt mask follows
+        the rows."""
+        g, eng, m = self.g, self.eng, self.m
+        if self.multi:
+            self.sync_moments()      # (sharded optimiser steps: the compaction moves rows across shard boundaries)
+        # The read-back blocks until the GPU has drained: the views of the run that follows (same keyframe picks, in the
+        # same order, whatever the pruning decides) are popped and tabulated first, while the GPU is still working.
+        if not self.multi and it + 1 < self.num_iter and not self.prune_at(it + 1):
+            self.prepared = self._run_views(it + 1)
+        # The capacity header (sticky: every forward since the last read, the tracker's included) rides on the pruning
+        # step's read-back: its copy to pinned memory is enqueued before, parsed after -- no round trip of its own
+        token = eng.check_capacity_begin() if (self.piggyback and hasattr(eng, "check_capacity_begin")) else None
+        if self.densifies:
+            # densification (slam/mapper.py:913-927, commented out in the reference) at this pruning step: classify-and-plan,
+            # a 12-byte read-back, one scatter (gaussian_model.densify_device), then the prune.  The seed is a function of
+            # (mapping.densify_seed, frame, iteration): an overflow re-run of this loop draws the same samples
+            pruned, parent = g.densify_and_prune(m["densify_grad_threshold"], m["min_opacity"], self.mapper.camera_extent, m["size_threshold"],
+                                                 seed=densify_seed(m.get("densify_seed", 0), self.frame, it), lazy_mask=True)
+        else:
+            pruned, parent = g.prune(m["min_opacity"], self.mapper.camera_extent, None if self.splatam else m["size_threshold"], lazy_mask=True), None
+        if token is not None or (self.piggyback and hasattr(eng, "check_capacity")):
+            ok = eng.check_capacity_end(token) if token is not None else eng.check_capacity()
+            self.late_overflow = self.late_overflow or not ok
+            self.piggybacked = True
+        if self.opt_mask is not None and (parent is not None or self.opt_mask.shape[0] != g._xyz.shape[0]):
+            self.opt_mask = g.carry_rows(self.opt_mask, parent, pruned()).contiguous()      # (children take their parent's flag)
+
+    # ---- the sharded window's own optimiser state ------------------------------------------------------------------------------------
+    def _ba_step(self, all_ids):
+        """Bundle adjustment with a sharded window: this rank's views wrote their pose gradients out (Mm3dgsMapView.dpose_out_or_null)
+        and _local_grads summed them per pose (a pose rendered twice in a step gets both gradients, like autograd accumulates them);
+        here they are all-reduced over the ranks, then every replica steps -- with mm3dgs_adam: Adam(eps=1e-15), cam_q_lr / cam_t_lr,
+        slam/mapper.py:742-752 -- exactly the poses SOME rank rendered in this step (known on every rank from the shared keyframe
+        stack: no flags travel), so a pose nobody rendered keeps its moments and step counter, as torch skips parameters without a
+        gradient (the torch-graph window does the same through WindowParallel.reduce_pose_grads)."""
+        self.window.reduce_small(self.ba_grad)
+        lrs = ((0, 4, float(self.m["cam_q_lr"])), (4, 7, float(self.m["cam_t_lr"])))
+        for k in sorted(set(i for i in all_ids if i in self.ba)):
+            st, gk = self.ba[k], self.ba_grad[self.ba_ids.index(k)]
+            st.step += 1
+            table = (_lib.Mm3dgsAdamGroup * 8)()
+            for j, (lo, hi, lr) in enumerate(lrs):
+                e = table[j]
+                e.param, e.grad = st.buf[lo:hi].data_ptr(), gk[lo:hi].data_ptr()
+                e.exp_avg, e.exp_avg_sq = st.m[lo:hi].data_ptr(), st.v[lo:hi].data_ptr()
+                e.n, e.lr = hi - lo, lr
+            _lib.check(self.eng.lib.mm3dgs_adam(table, 2, st.step, 0.9, 0.999, 1e-15, _stream()))
 
     _FLAT_GROUPS = (("xyz", 0, 3), ("f_dc", 3, 6), ("opacity", 6, 7), ("scaling", 7, 10), ("rotation", 10, 14))      # the engine's flat layout, in units of P
 
     def _flat_groups(self, P):
         """[(optimiser group, its parameter, its Adam state, a, b)]: the five stepped groups and their element ranges [a, b) in the
         engine's flat gradient layout."""
-        opt = self.gaussians.optimizer
-        out = []
-        for name, a, b in self._FLAT_GROUPS:
-            group = next(gr for gr in opt.param_groups if gr["name"] == name)
-            p = group["params"][0]
-            st = opt.state[p]
-            if "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            out.append((group, p, st, a * P, b * P))
-        return out
+        return [(*_adam_state(self.g.optimizer, name), a * P, b * P) for name, a, b in self._FLAT_GROUPS]
 
-    def _sharded_step(self, eng, g, P):
+    def _shard_buffers(self, P):
+        """shard_g / shard_p (this rank's S elements of the flat gradient / of the parameters or a moment) and pflat (world x S: what
+        the all-gather fills), made for the map's current size."""
+        w, dev = self.window, self.eng.dev
+        S = w.shard_bounds(14 * P)[0]
+        if self.shard_S != S:
+            self.shard_S = S
+            self.shard_g, self.shard_p = torch.zeros(S, device=dev), torch.zeros(S, device=dev)
+            self.pflat = torch.zeros(w.world * S, device=dev)
+
+    def _sharded_adam(self, P):
         """One optimiser step of the sharded window with the optimiser itself sharded over the ranks by ELEMENT (the
         reference's step is slam/mapper.py:931-948 on one view's gradients): the caller's reduce-scatter of the flat gradient [14 P] left
-        this rank's S = ceil(14 P / world) summed elements in eng.shard_g; mm3dgs_adam on exactly those elements of the parameters and of both moments (the slice cuts
-        through the five groups: one table entry per group it touches); all-gather of the stepped PARAMETERS.  The moments of elements
-        another rank owns go stale here and are gathered when somebody needs them (_sync_moments: before map surgery and at the end of
-        the loop).  Same arithmetic per element as the all-reduce path's mm3dgs_adam: bit-identical parameters (tested over gloo)."""
-        w = self.window
-        n = 14 * P
-        S, lo, hi = w.shard_bounds(n)
+        this rank's S = ceil(14 P / world) summed elements in shard_g; mm3dgs_adam on exactly those elements of the parameters and of both
+        moments (the slice cuts through the five groups: one table entry per group it touches); all-gather of the stepped PARAMETERS.  The
+        moments of elements another rank owns go stale here and are gathered when somebody needs them (sync_moments: before map surgery
+        and at the end of the loop).  Same arithmetic per element as the all-reduce path's mm3dgs_adam: bit-identical parameters (tested
+        over gloo)."""
+        opt = self.g.optimizer
+        lo, hi = self.window.shard_bounds(14 * P)[1:]
         groups = self._flat_groups(P)
-        table = (_lib.Mm3dgsAdamGroup * 8)()
-        k, cuts = 0, []
-        step_val = None
+        table, k = (_lib.Mm3dgsAdamGroup * 8)(), 0
         for group, p, st, a, b in groups:
             st["step"] += 1                                     # (every replica counts every step of every group, as the replicated path does)
-            step_val = int(st["step"].item()) if step_val is None else step_val
             i0, i1 = max(lo, a), min(hi, b)
             if i0 >= i1:
                 continue
             e = table[k]; k += 1
             e.param = p.data_ptr() + 4 * (i0 - a)
-            e.grad = eng.shard_g.data_ptr() + 4 * (i0 - lo)
+            e.grad = self.shard_g.data_ptr() + 4 * (i0 - lo)
             e.exp_avg, e.exp_avg_sq = st["exp_avg"].data_ptr() + 4 * (i0 - a), st["exp_avg_sq"].data_ptr() + 4 * (i0 - a)
             e.n, e.lr = i1 - i0, float(group["lr"])
-            cuts.append((p, a, i0, i1))
-        opt = g.optimizer
         b1, b2 = opt.param_groups[0]["betas"]
         if k:
-            _lib.check(eng.lib.mm3dgs_adam(table, k, step_val, float(b1), float(b2), float(opt.param_groups[0]["eps"]), _stream()))
-        for p, a, i0, i1 in cuts:
-            eng.shard_p[i0 - lo:i1 - lo].copy_(p.detach().view(-1)[i0 - a:i1 - a])
-        w.all_gather_flat(eng.pflat, eng.shard_p, n)
-        for group, p, st, a, b in groups:
-            p.detach().view(-1).copy_(eng.pflat[a:b])
-        self._moments_stale = True
-        w.sharded_steps += 1
+            _lib.check(self.eng.lib.mm3dgs_adam(table, k, int(groups[0][2]["step"].item()), float(b1), float(b2),
+                                                float(opt.param_groups[0]["eps"]), _stream()))
+        self._all_gather(groups, P, lambda p, st: p.detach())
+        self.stale = True
+        self.window.sharded_steps += 1
 
-    def _shard_buffers(self, eng, P):
-        w = self.window
-        S = w.shard_bounds(14 * P)[0]
-        if getattr(eng, "_shard_S", None) != (S, w.world):
-            eng._shard_S = (S, w.world)
-            eng.shard_g = torch.zeros(S, device=eng.dev)
-            eng.shard_p = torch.zeros(S, device=eng.dev)
-            eng.pflat = torch.zeros(w.world * S, device=eng.dev)
-
-    def _sync_moments(self, eng):
+    def sync_moments(self):
         """After sharded steps every rank holds fresh Adam moments for ITS elements only: gather both moment arrays so that the replicas
         are whole again (before a pruning step compacts rows across shard boundaries, before a snapshot / checkpoint, at the end of the
         loop).  Two all-gathers of 14 P floats, a few times per frame."""
-        if not getattr(self, "_moments_stale", False):
+        if not self.stale:
             return
-        self._moments_stale = False
-        g, w = self.gaussians, self.window
-        P = int(g._xyz.shape[0])
-        n = 14 * P
-        S, lo, hi = w.shard_bounds(n)
-        self._shard_buffers(eng, P)      # (sized at the last sharded step: the map may have changed size since -- ADVICE round 5)
-        assert eng._shard_S == (S, w.world) and eng.pflat.numel() >= w.world * S
+        self.stale = False
+        P = int(self.g._xyz.shape[0])
+        self._shard_buffers(P)      # (made at the last sharded step: the map may have changed size since -- ADVICE round 5)
         groups = self._flat_groups(P)
         for key in ("exp_avg", "exp_avg_sq"):
-            for group, p, st, a, b in groups:
-                i0, i1 = max(lo, a), min(hi, b)
-                if i0 < i1:
-                    eng.shard_p[i0 - lo:i1 - lo].copy_(st[key].view(-1)[i0 - a:i1 - a])
-            w.all_gather_flat(eng.pflat, eng.shard_p, n)
-            for group, p, st, a, b in groups:
-                st[key].view(-1).copy_(eng.pflat[a:b])
+            self._all_gather(groups, P, lambda p, st: st[key])
 
-    def _adam_step(self, eng):
-        g = self.gaussians
-        opt = g.optimizer
-        # the group table only changes when a tensor is replaced (prune / densify): cache it on the pointers
-        key = (g.generation, g._xyz.data_ptr(), eng.grads["xyz"].data_ptr(), int(g._xyz.shape[0]))
-        cache = getattr(self, "_adam_cache", None)
-        if cache is not None and cache[0] == key and all(float(gr["lr"]) == lr for gr, lr in zip(cache[3], cache[4])):
-            _, table, n, groups, _, states = cache
-            for st in states:
-                st["step"] += 1
-            step_val = int(states[0]["step"].item())
-            b1, b2 = opt.param_groups[0]["betas"]
-            _lib.check(eng.lib.mm3dgs_adam(table, n, step_val, float(b1), float(b2), float(opt.param_groups[0]["eps"]), _stream()))
-            return
-        table = (_lib.Mm3dgsAdamGroup * 8)()
-        n = 0
-        step_val = None
-        used_groups, used_states = [], []
-        for group in opt.param_groups:
-            name = group["name"]
-            if name not in eng.grads:
-                continue                     # f_rest (empty at SH degree 0) and rgb never receive a gradient
-            p = group["params"][0]
-            st = opt.state[p]
-            if "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["step"] += 1
-            step_val = int(st["step"].item()) if step_val is None else step_val
-            e = table[n]
-            e.param, e.grad = p.data_ptr(), eng.grads[name].data_ptr()
-            e.exp_avg, e.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-            e.n, e.lr = p.numel(), float(group["lr"])
-            used_groups.append(group); used_states.append(st)
-            n += 1
-        self._adam_cache = (key, table, n, used_groups, [float(gr["lr"]) for gr in used_groups], used_states)
-        b1, b2 = opt.param_groups[0]["betas"]
-        _lib.check(eng.lib.mm3dgs_adam(table, n, step_val, float(b1), float(b2), float(opt.param_groups[0]["eps"]), _stream()))
+    def _all_gather(self, groups, P, part):
+        """Every replica's `part(parameter, Adam state)` of each flat group made whole from the ranks' shards: this rank's elements go
+        into shard_p, the all-gather fills pflat, and each group's range is copied back."""
+        lo, hi = self.window.shard_bounds(14 * P)[1:]
+        for group, p, st, a, b in groups:
+            i0, i1 = max(lo, a), min(hi, b)
+            if i0 < i1:
+                self.shard_p[i0 - lo:i1 - lo].copy_(part(p, st).view(-1)[i0 - a:i1 - a])
+        self.window.all_gather_flat(self.pflat, self.shard_p, 14 * P)
+        for group, p, st, a, b in groups:
+            part(p, st).view(-1).copy_(self.pflat[a:b])
