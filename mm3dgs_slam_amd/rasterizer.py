@@ -21,6 +21,7 @@ There is no CPU path here: tensors must live on a HIP device and the shared libr
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import NamedTuple, Optional
 
 import torch
@@ -68,6 +69,17 @@ def last_header():
     h = img[:32].view(torch.int32).cpu()
     return dict(num_rendered=int(h[0]), overflow=int(h[1]), max_tile_len=int(h[2]), fwd_wave_iters=int(h[4]),
                 bwd_wave_iters=int(h[5]), bwd_wave_visits=int(h[6]))
+
+
+def last_state():
+    """The state buffers of the most recent forward (geom, image, binning state, P, H, W, binning capacity, radii) -- what
+    tests/list_ref.py reads the tile lists back from; None once the forward's autograd graph (which holds the binning state) is gone.
+    Diagnostics / tests."""
+    binning = _last["binning"]() if "binning" in _last else None
+    if binning is None:
+        return None
+    H, W = _last["HW"]
+    return dict(geom=_last["geom"], img=_last["img"], binning=binning, P=_last["P"], H=H, W=W, N=_last["n_cap"], radii=_last["radii"])
 
 
 def last_depths():
@@ -204,6 +216,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 ev.record()
                 _pending.append((ev, hdr, n_cap, (key, max(P, 1))))
         _last["img"], _last["geom"], _last["P"] = img, geom, P
+        # (the binning state by weak reference: it lives as long as the autograd graph that saved it, and no longer)
+        _last["binning"], _last["n_cap"], _last["radii"], _last["HW"] = weakref.ref(binning), n_cap, radii, (H, W)
         ctx.rs = rs
         ctx.dims = (P, M, Cn, n_cap)
         ctx.save_for_backward(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, view, proj, cpos,

@@ -149,7 +149,9 @@ def loss_weights(shape, seed):
     return torch.randn(*shape, generator=g, dtype=torch.float64)
 
 
-def run_hip(case, weights=None, need_grad=True, device="cuda", gaussian_grads=True, camera_grads=True):
+def run_hip(case, weights=None, need_grad=True, device="cuda", gaussian_grads=True, camera_grads=True, on_forward=None):
+    """on_forward: called right after the forward, while its autograd graph (and with it the binning state that
+    mm3dgs_slam_amd.rasterizer.last_state() hands out) is alive."""
     from mm3dgs_slam_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
     L = leaves(case, torch.float32, device)
     if not gaussian_grads:
@@ -166,6 +168,8 @@ def run_hip(case, weights=None, need_grad=True, device="cuda", gaussian_grads=Tr
     img, radii = rast(means3D=L["means3D"], means2D=L["means2D"], opacities=L["opacities"], shs=L["shs"],
                       colors_precomp=L["colors"], scales=L["scales"], rotations=L["rotations"],
                       cov3D_precomp=L["cov3D"], extra_channels=L["extras"])
+    if on_forward is not None:
+        on_forward()
     grads = {}
     if need_grad:
         if weights is None:

@@ -12,9 +12,11 @@ configs[4] 1920x1080 / 3 M / SH degree 3 (generic path, packed bins, lists of up
 And through size-independent properties over the WHOLE image: determinism, equivalence of the fused 6-channel pass with two
 3-channel passes, linearity of the backward pass in dL/dimage, consistency of the depth bundle, agreement of the native SLAM
 engine with the generic C-ABI path, direct bins == packed bins bit for bit."""
+import numpy as np
 import pytest
 import torch
 
+from tests import list_ref as lr
 from tests import parity_util as pu
 
 pytestmark = pytest.mark.gpu
@@ -235,7 +237,14 @@ def test_generic_path_matches_the_tile_sampled_float64_oracle_at_full_size(name)
     tiles = pu.pick_tiles(counts, N_TILES, seed=3)
     mask = pu.tile_mask(H, W, tiles)
     from mm3dgs_slam_amd import rasterizer as rz
-    img_h, radii_h, _ = pu.run_hip(case, need_grad=False)
+    lists = {}
+
+    def check_lists():      # the exact list check on every sampled tile (non-clean ones included) and the kernels' heaviest tile
+        s = rz.last_state()
+        st = lr.ListState(s["geom"], s["img"], s["binning"], s["P"], s["H"], s["W"], s["N"], s["radii"])
+        heaviest = int(np.argmax(np.diff(st.ranges)))
+        lists["stats"] = lr.check_tiles(st, list(dict.fromkeys(list(tiles) + [heaviest])), direct=False)
+    img_h, radii_h, _ = pu.run_hip(case, need_grad=False, on_forward=check_lists)
     img_h, key = img_h.cpu(), rz.last_depths().cpu()
     # step 0: the oracle under its OWN float64 order (how many sampled tiles carry a near-tie that float32 breaks differently)
     img_own, _, aux, _ = pu.run_oracle(case, need_grad=False, tiles=tiles)
@@ -252,7 +261,12 @@ def test_generic_path_matches_the_tile_sampled_float64_oracle_at_full_size(name)
          "radii_mismatch": int((radii_h.cpu() != radii_o).sum()), "max_list": int(counts.max()), "touched": int(vis.numel())}
     w = pu.loss_weights((3, H, W), 123) * pu.tile_mask(H, W, clean)
     _, _, _, g_o = pu.run_oracle(case, weights=w, tiles=clean, depth_key=key)
-    _, _, _, g_32 = pu.run_oracle(case, torch.float32, weights=w, tiles=clean, depth_key=key)
+    # (the float32 oracle over ALL sampled tiles: the weights are zero outside the clean ones, so its gradients are those of the clean
+    #  tiles alone, and its image counts the tiles on which float32 arithmetic itself flips a decision)
+    img_32, _, _, g_32 = pu.run_oracle(case, torch.float32, weights=w, tiles=tiles, depth_key=key)
+    clean_32 = pu.clean_tiles(pu.tile_errors(img_32, img_o, tiles))
+    m["non_clean_tiles"], m["f32_oracle_non_clean_tiles"] = len(tiles) - len(clean), len(tiles) - len(clean_32)
+    m["lists"], m["list_tiers"] = str(lists["stats"]), lr.tier_counts(lists["stats"].lens)
     _, _, g_h = pu.run_hip(case, weights=w)
     floor = {}
     for k, go in g_o.items():
@@ -266,6 +280,9 @@ def test_generic_path_matches_the_tile_sampled_float64_oracle_at_full_size(name)
     assert m["depth_key_rel_err"] <= 1e-6, m
     assert m["img"] <= pu.IMG_TOL and m["img_worst_tile"] <= pu.FLIP_TILE_TOL and len(clean) >= N_TILES // 2, (m, errs)
     assert m["img_under_the_oracles_own_order"] <= 2e-3, m       # (near-tie swaps: what two float32 programs differ by as well)
+    # the lists of every sampled tile are exact (check_lists), so a non-clean tile carries a float32 decision flip and nothing else: the
+    # kernels have no more of them than the float32 oracle evaluated on the same tiles under the same order, up to a few
+    assert m["non_clean_tiles"] <= m["f32_oracle_non_clean_tiles"] + 4, m
     for k in ("d_view", "d_proj", "d_campos"):
         if k in m:
             assert m[k] <= max(pu.POSE_TOL, 1.5 * floor[k]), (k, m, floor)
@@ -312,6 +329,8 @@ def test_native_path_matches_the_tile_sampled_float64_oracle_at_full_size(name):
     m = native_vs_oracle(seed=7, direct=True, slam_like=True, iso=iso, floor=True, setup=_bench_map(name), n_tiles=N_TILES)
     _report(name, f"native {name}: " + str({k: (f"{v:.2e}" if isinstance(v, float) else v) for k, v in m.items() if k not in ("tiles", "tile_errors")}))
     assert len(m["tiles"]) == N_TILES and m["max_list"] > 200
+    assert m["lists_checked"] >= N_TILES       # (native_vs_oracle ran the exact list check on every sampled tile and the heaviest one)
+    assert N_TILES - m["clean_tiles"] <= N_TILES - m["f32:clean_tiles"] + 4, m
     # (the oracle took its depth ORDER from the kernels' float32 depths, checked to float32 rounding; the gradients ran on the tiles
     #  without a 1/255 / T < 1e-4 flip -- see the generic test's docstring)
     assert m["depth_key_rel_err"] <= 1e-6, m

@@ -304,6 +304,16 @@ def native_vs_oracle(seed=0, direct=False, P=3000, H=120, W=160, floor=False, sl
         return ref_.detach(), p_.grad, {k: leaf[k].grad for k in keys}
 
     ref, dp, lg = oracle(torch.float64)
+    if n_tiles:      # the exact list check (tests/list_ref.py) on every sampled tile and the kernels' heaviest one, before the backward
+        from tests import list_ref as lr
+        st = lr.ListState(eng.geom, eng.img_state, eng.binning, eng.P, eng.H, eng.W, eng.n_cap, eng.radii)
+        direct_bins = st.hdr["bin_cap"] != 0
+        lens = [st.span(t)[1] for t in range(st.T)]
+        heaviest = int(np.argmax(lens))
+        nb = max((eng.P + 255) // 256, 1)
+        stats = lr.check_tiles(st, list(dict.fromkeys(list(sample["tiles"]) + [heaviest])), direct_bins,
+                               min(eng.n_cap // nb, 0xffffffff // nb) if direct_bins else 0)
+        list_stats = (stats.tiles, str(stats), lr.tier_counts(stats.lens))
     eng.dL.copy_(W6["w"].float().to(DEV))
     eng.backward(si, grads=eng.grads, dpose=eng.dpose)
     assert eng.check_capacity()
@@ -319,6 +329,7 @@ def native_vs_oracle(seed=0, direct=False, P=3000, H=120, W=160, floor=False, sl
         z64 = g._xyz.detach().double().cpu() @ P_.quad2rotation(q64[None, :4])[0][2] + q64[6]
         vis = (eng.radii > 0).cpu()
         m["depth_key_rel_err"] = float(((depth_key[vis].double() - z64[vis]).abs() / z64[vis].abs()).max())
+        m["lists_checked"], m["lists"], m["list_tiers"] = list_stats
     for name, key in names:
         m["d_" + name] = pu.rel_l2(eng.grads[name], lg[key])
     if raw:      # (diagnostics: the gradient arrays themselves)
@@ -329,6 +340,8 @@ def native_vs_oracle(seed=0, direct=False, P=3000, H=120, W=160, floor=False, sl
         if raw:
             m["raw"]["f32"] = {name: lg32[key] for name, key in names}
         m["f32:img"], m["f32:d_pose"] = pu.rel_l2(ref32[:, sel], ref[:, sel]), pu.rel_l2(dp32, dp)
+        if n_tiles:      # tiles on which float32 arithmetic itself flips a decision (same order, same CLEAN_PIXEL_TOL as the kernels' count)
+            m["f32:clean_tiles"] = len(pu.clean_tiles(pu.tile_errors(ref32, ref, sample["tiles"])))
         for name, key in names:
             m["f32:d_" + name] = pu.rel_l2(lg32[key], lg[key])
     return m
