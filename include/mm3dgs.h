@@ -142,7 +142,7 @@ int mm3dgs_mark_visible(const Mm3dgsCamera* cam, int P, const float* means3D, ui
  * One projection kernel folds in the pose transform of `transform_means_python` mode (slam/renderer.py:142-153),
  * the [z,1,z^2] depth bundle (:26-43), the GaussianModel activations (slam/gaussian_model.py:108-137) and, in the
  * backward, their chain rules, the pose gradient (P -> 12 float reduction -> (dq,dt)), the densification statistics
- * (slam/mapper.py:887-899) and the pose Adam step (slam/tracker.py:233-246).  SH degree 0 only (both shipped configs).
+ * (slam/mapper.py:887-899) and the pose Adam step (slam/tracker.py:233-246).  SH degrees 0-3 (Mm3dgsSlamInputs.sh_degree / sh_dir).
  * Output image has 6 channels: RGB, alpha-weighted z, silhouette, alpha-weighted z^2.
  * ===================================================================================================== */
 typedef struct Mm3dgsSlamInputs {
@@ -162,10 +162,18 @@ typedef struct Mm3dgsSlamInputs {
   /* ABI 209 (appended): an ACTIVE spherical-harmonics degree above 0 -- a map resumed from a checkpoint starts at its maximal degree
    * (slam/gaussian_model.py:363), and slam/renderer.py:179-193 then hands the rasterizer shs = cat(f_dc, f_rest) with sh_degree = the active
    * degree and campos = 0 in the shipped mode (means pre-transformed: the viewing direction is the camera-space mean, normalised).  NULL / 0:
-   * degree 0 (colour = SH_C0 f_dc + 0.5, no direction).  world_means = 1 with sh_degree > 0 is not supported (error -2).        */
+   * degree 0 (colour = SH_C0 f_dc + 0.5, no direction).  The direction the basis is evaluated at is chosen by sh_dir (ABI 211).     */
   const float* f_rest;    /* [P, n_rest, 3] GaussianModel._features_rest (n_rest = (max_sh_degree + 1)^2 - 1) or NULL    */
   int32_t sh_degree;      /* active degree 0..3; its (sh_degree + 1)^2 - 1 first rows of f_rest are used            */
   int32_t n_rest;         /* rows of f_rest per Gaussian                                                            */
+  /* ABI 211 (appended): the source of the SH viewing direction d at sh_degree > 0 (p = R x + t the camera-space mean, c = -R^T t the camera centre):
+   *   0  p / |p|              world_means = 0, the rasterizer's own SH evaluation (convert_SHs_python: false); a zero-initialised struct gets this
+   *   1  x / |x|              world_means = 0 with convert_SHs_python: true -- the world mean about the ORIGIN: slam/renderer.py:179-193 takes
+   *                           pc.get_xyz - camera_pos with camera_pos = 0 (the view matrix is the identity in that mode); d does not depend on the pose
+   *   2  (x - c) / |x - c|    world_means = 1 (either SH flag): the world mean seen from the camera centre; the pose gradient gains the centre's terms
+   * At sh_degree > 0, world_means = 1 needs sh_dir = 2 and sh_dir = 2 needs world_means = 1 (error -2 otherwise); at degree 0 the direction
+   * does not enter and any value 0..2 renders the same.                                                                                           */
+  int32_t sh_dir;
 } Mm3dgsSlamInputs;
 
 typedef struct Mm3dgsSlamGrads {
@@ -442,8 +450,10 @@ const char* mm3dgs_last_error(void);
         binning_state / backward_scratch keep their sizes, their interior layout is the library's own; image_state must be zero-initialised
         to at least sizeof(Mm3dgsHeader) before its first use with MM3DGS_FWD_STATE_CLEAN
    209: Mm3dgsSlamInputs.f_rest / sh_degree / n_rest, Mm3dgsSlamGrads.d_f_rest, Mm3dgsMapAdam.rest_* (all appended): native loops at an active SH degree > 0
-   210: mm3dgs_densify_work_bytes / mm3dgs_densify_plan / mm3dgs_densify_rows, Mm3dgsDensifyGroup / Mm3dgsDensifyState (densification) */
-#define MM3DGS_ABI_VERSION 210
+   210: mm3dgs_densify_work_bytes / mm3dgs_densify_plan / mm3dgs_densify_rows, Mm3dgsDensifyGroup / Mm3dgsDensifyState (densification)
+   211: Mm3dgsSlamInputs.sh_dir (appended): native loops at an active SH degree > 0 with the world-origin (convert_SHs_python) and camera-centre
+        (world_means = 1) viewing directions */
+#define MM3DGS_ABI_VERSION 211
 int mm3dgs_version(void);
 
 #ifdef __cplusplus

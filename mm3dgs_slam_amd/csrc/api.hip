@@ -226,6 +226,7 @@ static SlamIn slam_in(const Mm3dgsSlamInputs* in) {
   s.rotation = in->rotation; s.isotropic = in->isotropic; s.world = in->world_means;
   s.sh_deg = (in->f_rest && in->sh_degree > 0) ? in->sh_degree : 0;
   s.f_rest = s.sh_deg ? in->f_rest : nullptr; s.n_rest = s.sh_deg ? in->n_rest : 0;
+  s.sh_dir = s.sh_deg ? in->sh_dir : 0;
   return s;
 }
 static int check_slam(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in) {
@@ -237,10 +238,13 @@ static int check_slam(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in
   if (!in->pose) return fail(-1, "pose is NULL");
   if (P > 0 && (!in->xyz || !in->f_dc || !in->opacity || !in->scaling || !in->rotation)) return fail(-1, "NULL Gaussian parameter");
   if (in->sh_degree < 0 || in->sh_degree > 3) return fail(-2, "sh_degree %d outside 0..3", in->sh_degree);
+  if (in->sh_dir < 0 || in->sh_dir > 2) return fail(-2, "sh_dir %d outside 0..2", in->sh_dir);
   if (in->sh_degree > 0) {
     if (P > 0 && !in->f_rest) return fail(-2, "sh_degree %d needs the f_rest rows", in->sh_degree);
     if (in->n_rest < (in->sh_degree + 1) * (in->sh_degree + 1) - 1 || in->n_rest > 15) return fail(-2, "n_rest = %d does not hold sh_degree %d (or exceeds 15)", in->n_rest, in->sh_degree);
-    if (in->world_means) return fail(-2, "an active SH degree > 0 is native in the transform_means_python mode only");
+    // (ABI 211) the direction source must match the means' frame: world-frame means see the Gaussians from the camera centre
+    if (in->world_means && in->sh_dir != 2) return fail(-2, "world_means = 1 needs sh_dir = 2 (direction from the camera centre), got sh_dir = %d", in->sh_dir);
+    if (in->sh_dir == 2 && !in->world_means) return fail(-2, "sh_dir = 2 (direction from the camera centre) needs world_means = 1");
   }
   return 0;
 }

@@ -155,9 +155,24 @@ __device__ __forceinline__ void pose_chain_record(const CamDev& cam, const float
   o[4] = make_float4(x[1], x[2], 0.f, 0.f);
 }
 
-// SH (ABI 209): an active degree above 0 -- colour = sum_k basis_k(dir) sh_k + 0.5, clamped at 0, with dir = the normalised CAMERA-space mean: the
-// shipped mode hands the rasterizer pre-transformed means and campos = 0 (slam/renderer.py:117-124,142-153,179-193); rest = this Gaussian's f_rest rows
-template <bool SH = false>
+// The (unnormalised) SH viewing direction v of the three sources, Mm3dgsSlamInputs.sh_dir (ABI 211; slam/renderer.py:117-124,179-193):
+//   0  p = R x + t, the camera-space mean: the shipped mode hands the rasterizer pre-transformed means and campos = 0
+//   1  x, the world mean about the ORIGIN: convert_SHs_python evaluates SH on pc.get_xyz - camera_pos with the shipped mode's camera_pos = 0
+//   2  x - c = x + R^T t, the world mean seen from the camera centre c = -R^T t (world-frame means, campos = w2c^-1[3, :3])
+template <int SHDIR>
+__device__ __forceinline__ void sh_dir_vec(const PoseDev& ps, const float x[3], const float p[3], float v[3]) {
+  static_assert(SHDIR >= 0 && SHDIR <= 2, "sh_dir is 0, 1 or 2");
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    if constexpr (SHDIR == 0) v[j] = p[j];
+    else if constexpr (SHDIR == 1) v[j] = x[j];
+    else v[j] = x[j] + ps.R[0][j] * ps.t[0] + ps.R[1][j] * ps.t[1] + ps.R[2][j] * ps.t[2];
+  }
+}
+
+// SH (ABI 209): an active degree above 0 -- colour = sum_k basis_k(dir) sh_k + 0.5, clamped at 0, with dir = v / |v| of sh_dir_vec<SHDIR> (ABI 211:
+// SHDIR 1 and 2; SHDIR 0 is the instance of ABI 209); rest = this Gaussian's f_rest rows
+template <bool SH = false, int SHDIR = 0>
 __device__ __forceinline__ Projected slam_project_vals(const CamDev& cam, bool live, int idx, const float* __restrict__ pose, bool isotropic,
                                                        const RawGaussian& rg, int32_t* __restrict__ radii, const GeomView& g, bool world = false,
                                                        bool want_poserec = false, const float* __restrict__ rest = nullptr, int sh_deg = 0) {
@@ -210,9 +225,11 @@ __device__ __forceinline__ Projected slam_project_vals(const CamDev& cam, bool l
         const float* fd = fd_raw;
         float c0 = SH_C0F * fd[0] + 0.5f, c1 = SH_C0F * fd[1] + 0.5f, c2 = SH_C0F * fd[2] + 0.5f;
         if constexpr (SH) {
-          const float inv = 1.f / sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+          float v[3];
+          sh_dir_vec<SHDIR>(ps, rg.x, p, v);
+          const float inv = 1.f / sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
           float bb[16];
-          sh_basis(sh_deg, p[0] * inv, p[1] * inv, p[2] * inv, bb);
+          sh_basis(sh_deg, v[0] * inv, v[1] * inv, v[2] * inv, bb);
           const int nb = (sh_deg + 1) * (sh_deg + 1);
           c0 = bb[0] * fd[0]; c1 = bb[0] * fd[1]; c2 = bb[0] * fd[2];
 #pragma unroll
@@ -247,7 +264,7 @@ __device__ __forceinline__ Projected slam_project_vals(const CamDev& cam, bool l
   return o;
 }
 
-template <bool SH = false>
+template <bool SH = false, int SHDIR = 0>
 __device__ __forceinline__ Projected slam_project_one(const CamDev& cam, int P, int idx, const SlamIn& in, int32_t* __restrict__ radii,
                                                       const GeomView& g, bool want_poserec = false) {
   const bool live = idx < P;
@@ -263,11 +280,11 @@ __device__ __forceinline__ Projected slam_project_one(const CamDev& cam, int P, 
     for (int k = 0; k < 3; k++) { rg.ls[k] = in.scaling[(size_t)idx * 3 + k]; rg.fd[k] = in.f_dc[(size_t)idx * 3 + k]; }
     rg.op = in.opacity[idx];
   }
-  return slam_project_vals<SH>(cam, live, idx, in.pose, in.isotropic != 0, rg, radii, g, in.world != 0, want_poserec,
+  return slam_project_vals<SH, SHDIR>(cam, live, idx, in.pose, in.isotropic != 0, rg, radii, g, in.world != 0, want_poserec,
                                SH ? in.f_rest + (size_t)(live ? idx : 0) * (size_t)in.n_rest * 3 : nullptr, in.sh_deg);
 }
 
-template <bool SH>
+template <bool SH, int SHDIR = 0>
 __global__ void __launch_bounds__(FB)
 slam_preprocess_fwd_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radii, GeomView g, ImageView iv, int lds_tiles,
                            int vis_only, uint32_t* __restrict__ seen, int want_poserec) {
@@ -277,7 +294,7 @@ slam_preprocess_fwd_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ r
   if (lds_tiles) __syncthreads();
   const int idx = blockIdx.x * FB + threadIdx.x;
   const bool live = idx < P;
-  const Projected pr = slam_project_one<SH>(cam, P, idx, in, radii, g, want_poserec != 0);
+  const Projected pr = slam_project_one<SH, SHDIR>(cam, P, idx, in, radii, g, want_poserec != 0);
   const uint32_t r0 = pr.r0, r1 = pr.r1;
   const int32_t rad = pr.rad;
   if (vis_only) {      // mm3dgs_slam_visibility: the projection stage alone (workgroup-uniform): no tile counting, no scans
@@ -328,10 +345,10 @@ void launch_slam_preprocess_fwd(const CamDev& cam, int P, const SlamIn& in, int3
   if (P <= 0) return;
   const int T = cam.gx * cam.gy;
   const int lds_tiles = (T <= MAX_LDS_TILES && !visibility_only) ? T : 0;
-  if (in.sh_deg > 0)
-    hipLaunchKernelGGL(slam_preprocess_fwd_kernel<true>, dim3((P + FB - 1) / FB), dim3(FB), (size_t)lds_tiles * 4, s, cam, P, in, radii, g,
-                       iv, lds_tiles, visibility_only ? 1 : 0, seen, 0);
-  else
+  if (in.sh_deg > 0) {
+    auto k = in.sh_dir == 2 ? slam_preprocess_fwd_kernel<true, 2> : in.sh_dir == 1 ? slam_preprocess_fwd_kernel<true, 1> : slam_preprocess_fwd_kernel<true>;
+    hipLaunchKernelGGL(k, dim3((P + FB - 1) / FB), dim3(FB), (size_t)lds_tiles * 4, s, cam, P, in, radii, g, iv, lds_tiles, visibility_only ? 1 : 0, seen, 0);
+  } else
     hipLaunchKernelGGL(slam_preprocess_fwd_kernel<false>, dim3((P + FB - 1) / FB), dim3(FB), (size_t)lds_tiles * 4, s, cam, P, in, radii, g,
                        iv, lds_tiles, visibility_only ? 1 : 0, seen, want_poserec ? 1 : 0);
 }
@@ -477,7 +494,7 @@ __device__ __forceinline__ void slam_bin_pairs(const CamDev& cam, int P, int idx
   }
 }
 
-template <bool SH>
+template <bool SH, int SHDIR = 0>
 __global__ void __launch_bounds__(FB)
 slam_project_bin_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radii, GeomView g, ImageView iv, BinView b, uint32_t cap,
                         uint32_t rec_cap, int slot_bits, int want_poserec) {
@@ -487,7 +504,7 @@ slam_project_bin_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radi
   for (int t = tid; t < T; t += FB) hist[t] = 0;
   if (blockIdx.x == 0 && tid == 0) iv.hdr->bin_cap = cap;
   const int idx = blockIdx.x * FB + tid;
-  const Projected pr = slam_project_one<SH>(cam, P, idx, in, radii, g, want_poserec != 0);
+  const Projected pr = slam_project_one<SH, SHDIR>(cam, P, idx, in, radii, g, want_poserec != 0);
   slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
 }
 
@@ -495,9 +512,10 @@ void launch_slam_project_bin(const CamDev& cam, int P, const SlamIn& in, int32_t
                              uint32_t rec_cap, int slot_bits, hipStream_t s, bool want_poserec) {
   if (P <= 0) return;
   const int T = cam.gx * cam.gy;
-  if (in.sh_deg > 0)
-    hipLaunchKernelGGL(slam_project_bin_kernel<true>, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, bin_cap, rec_cap, slot_bits, 0);
-  else
+  if (in.sh_deg > 0) {
+    auto k = in.sh_dir == 2 ? slam_project_bin_kernel<true, 2> : in.sh_dir == 1 ? slam_project_bin_kernel<true, 1> : slam_project_bin_kernel<true>;
+    hipLaunchKernelGGL(k, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, bin_cap, rec_cap, slot_bits, 0);
+  } else
     hipLaunchKernelGGL(slam_project_bin_kernel<false>, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, bin_cap, rec_cap, slot_bits,
                        want_poserec ? 1 : 0);
 }
@@ -558,8 +576,10 @@ __device__ __forceinline__ void gather_tile_records(int area, uint32_t first, co
 #define NPOSE 12  // dR (9, row-major) | dt (3)
 // stepped: (the map's in-kernel Adam, ma.on) the lane's parameters AFTER the step -- what the next iteration's projection reads
 // SH (ABI 209, active degree > 0; mapping-layout records -- the colour sums -- also when only the pose gradient is wanted): d/d(f_rest), the
-// direction's share of d/d(mean) (into dm: the means and the pose), the sixth Adam group
-template <bool TRACK, bool DIRECT, bool WORLD = false, bool SH = false>
+// direction's share of d/d(mean), the sixth Adam group.  SHDIR (ABI 211) = the direction's source, sh_dir_vec: 0 -- its share goes into dm (the
+// camera-space mean: the means and the pose); 1 and 2 -- straight into d/d(xyz), and for 2 (world-frame means only) the camera centre's terms into
+// the pose rows: v = x + R^T t, so dL/dR_ij += t_i g_j and dL/dt += R g (g = dL/dv)
+template <bool TRACK, bool DIRECT, bool WORLD = false, bool SH = false, int SHDIR = 0>
 __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const SlamIn& in, const int32_t* __restrict__ radii, const GeomView& g,
                                               uint32_t N_cap, const float* __restrict__ dsub, float* __restrict__ posepartial, const SlamGrads& out,
                                               const MapAdam& ma, RawGaussian* stepped, const uint32_t* __restrict__ ovf) {
@@ -624,6 +644,7 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
     constexpr int AG_OFF[5] = {0, 3, 6, 7, 10}, AG_N[5] = {3, 3, 1, 3, 4};
     float ap[14], am[14], av[14];
     float shb[16], shg[3] = {0.f, 0.f, 0.f};      // (SH) basis values at this Gaussian's direction, clamp-masked colour gradient: zero for an invisible Gaussian
+    float shw[3] = {0.f, 0.f, 0.f};               // (SH, SHDIR 1 / 2) dL/dv of the world-frame direction vector: the direction's share of d/d(xyz)
     if constexpr (SH) {
 #pragma unroll
       for (int k = 0; k < 16; k++) shb[k] = 0.f;
@@ -734,9 +755,15 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
       if constexpr (SH) {
         // colour = clamp(sum_k b_k(dir) sh_k + 0.5), dir = p / |p|: the basis values weight the coefficient gradients, the basis' direction
         // derivative runs through the normalisation into dm (and from there into the means and the pose)
-        static_assert(!TRACK && !WORLD, "the SH path runs on mapping-layout records, pre-transformed means");
-        const float pinv = 1.f / sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-        const float ux = p[0] * pinv, uy = p[1] * pinv, uz = p[2] * pinv;
+        static_assert(!TRACK, "the SH path runs on mapping-layout records");
+        static_assert(WORLD == (SHDIR == 2), "world-frame means take the direction from the camera centre, pre-transformed ones from the mean or the origin");
+        float v[3];
+        {
+          const float xw[3] = {x0, x1, x2};
+          sh_dir_vec<SHDIR>(ps, xw, p, v);
+        }
+        const float pinv = 1.f / sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        const float ux = v[0] * pinv, uy = v[1] * pinv, uz = v[2] * pinv;
         sh_basis(in.sh_deg, ux, uy, uz, shb);
         float gbx[16], gby[16], gbz[16];
         sh_basis_grad(in.sh_deg, ux, uy, uz, gbx, gby, gbz);
@@ -751,7 +778,11 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
             ddx += gbx[k] * tk; ddy += gby[k] * tk; ddz += gbz[k] * tk;
           }
         const float dot = ux * ddx + uy * ddy + uz * ddz;
-        dm[0] += (ddx - ux * dot) * pinv; dm[1] += (ddy - uy * dot) * pinv; dm[2] += (ddz - uz * dot) * pinv;
+        if constexpr (SHDIR == 0) {
+          dm[0] += (ddx - ux * dot) * pinv; dm[1] += (ddy - uy * dot) * pinv; dm[2] += (ddz - uz * dot) * pinv;
+        } else {
+          shw[0] = (ddx - ux * dot) * pinv; shw[1] = (ddy - uy * dot) * pinv; shw[2] = (ddz - uz * dot) * pinv;
+        }
       }
       // pose: means_cam = R x + t
       cg[0] = dm[0] * x0; cg[1] = dm[0] * x1; cg[2] = dm[0] * x2;
@@ -766,9 +797,22 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
           for (int i = 0; i < 3; i++) cg[k * 3 + i] += dRc[k][i];
         cg[2] += dz_tot * x0; cg[5] += dz_tot * x1; cg[8] += dz_tot * x2;
       }
+      if constexpr (SH && SHDIR == 2) {
+        // the camera centre: v = x + R^T t  ->  dL/dR_ij += t_i shw_j,  dL/dt_i += (R shw)_i
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+          for (int j = 0; j < 3; j++) cg[i * 3 + j] += ps.t[i] * shw[j];
+          cg[9 + i] += ps.R[i][0] * shw[0] + ps.R[i][1] * shw[1] + ps.R[i][2] * shw[2];
+        }
+      }
       if (out.d_xyz || ma.on) {
 #pragma unroll
         for (int j = 0; j < 3; j++) dxyz[j] = ps.R[0][j] * dm[0] + ps.R[1][j] * dm[1] + ps.R[2][j] * dm[2] + (world ? dz_tot * ps.R[j][2] : 0.f);
+        if constexpr (SH && SHDIR != 0) {
+#pragma unroll
+          for (int j = 0; j < 3; j++) dxyz[j] += shw[j];
+        }
         const uint32_t cl = cl_bits;
         dfd[0] = (cl & 1) ? 0.f : SH_C0F * dc0;      // (SH_C0 = the degree-0 basis value)
         dfd[1] = (cl & 2) ? 0.f : SH_C0F * dc1;
@@ -1195,12 +1239,12 @@ __global__ void __launch_bounds__(1024) slam_pose_finish_kernel(const float* __r
 // The backward projection of an iteration that needs the pose gradient (every tracking iteration; mapping views under bundle adjustment).
 // (The pose finish in the LAST workgroup of this launch -- a ticket counter -- was measured and rejected: 25 .. 32 us against 9.1 + 6.8 for the two
 // launches; the finish stays a one-workgroup launch of its own, slam_pose_finish_kernel.)
-template <bool TRACK, bool DIRECT, bool WORLD, bool SH = false>
+template <bool TRACK, bool DIRECT, bool WORLD, bool SH = false, int SHDIR = 0>
 __global__ void __launch_bounds__(SLAM_BWD_FB)
 slam_preprocess_bwd_kernel(CamDev cam, int P, SlamIn in, const int32_t* __restrict__ radii, GeomView g, BinView bn, uint32_t N_cap,
                            const float* __restrict__ dsub, float* __restrict__ posepartial, SlamGrads out, MapAdam ma,
                            const uint32_t* __restrict__ ovf) {
-  slam_bwd_body<TRACK, DIRECT, WORLD, SH>(cam, P, in, radii, g, N_cap, dsub, posepartial, out, ma, nullptr, ovf);
+  slam_bwd_body<TRACK, DIRECT, WORLD, SH, SHDIR>(cam, P, in, radii, g, N_cap, dsub, posepartial, out, ma, nullptr, ovf);
 }
 
 // The pose finish alone, over the per-TILE rows the tracking compositor's pose chain wrote (composite.hip): rows[nrows][32] floats.
@@ -1220,7 +1264,10 @@ void launch_slam_preprocess_bwd(const CamDev& cam, int P, const SlamIn& in, cons
   if (P > 0) {
     const bool map = out.d_xyz || ma.on || in.sh_deg > 0;      // (an active SH degree > 0 runs on mapping-layout records even when only the pose gradient is wanted)
     if (in.sh_deg > 0) {
-      auto ksh = direct ? slam_preprocess_bwd_kernel<false, true, false, true> : slam_preprocess_bwd_kernel<false, false, false, true>;
+      // (sh_dir: 0 -- the instances of ABI 209; 1 -- world mean about the origin; 2 -- world-frame means, direction from the camera centre)
+      auto ksh = in.sh_dir == 2 ? (direct ? slam_preprocess_bwd_kernel<false, true, true, true, 2> : slam_preprocess_bwd_kernel<false, false, true, true, 2>)
+               : in.sh_dir == 1 ? (direct ? slam_preprocess_bwd_kernel<false, true, false, true, 1> : slam_preprocess_bwd_kernel<false, false, false, true, 1>)
+                                : (direct ? slam_preprocess_bwd_kernel<false, true, false, true> : slam_preprocess_bwd_kernel<false, false, false, true>);
       hipLaunchKernelGGL(ksh, dim3((P + SLAM_BWD_FB - 1) / SLAM_BWD_FB), dim3(SLAM_BWD_FB), 0, s, cam, P, in, radii, g, b, ncap, bw.dsub, partial, out, ma, ovf);
     } else {
     auto kern = in.world ? (map ? (direct ? slam_preprocess_bwd_kernel<false, true, true> : slam_preprocess_bwd_kernel<false, false, true>)

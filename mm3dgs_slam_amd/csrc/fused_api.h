@@ -7,6 +7,7 @@ struct SlamIn {
   int isotropic;
   int world;     // Mm3dgsSlamInputs.world_means
   const float* f_rest; int sh_deg; int n_rest;      // active SH degree > 0 (ABI 209): rows [P][n_rest][3]; sh_deg == 0: unused
+  int sh_dir;    // Mm3dgsSlamInputs.sh_dir (ABI 211): the SH viewing direction's source; 0 whenever sh_deg == 0
 };
 struct SlamGrads {
   float* d_xyz; float* d_f_dc; float* d_opacity; float* d_scaling; float* d_rotation;

@@ -5,11 +5,12 @@ collapsed into a handful of C-ABI calls with no host synchronisation inside the 
     mm3dgs_slam_forward  ->  mm3dgs_loss  ->  mm3dgs_slam_backward ( -> pose Adam on device | mm3dgs_adam )
 
 ``FusedTracker`` / ``FusedMapper`` subclass the torch-graph ``Tracker`` / ``Mapper`` and take over ``optimize_cam`` /
-``optimize_map`` whenever the covariances come from scales + rotations and the ACTIVE SH degree is 0 (the reference never
-raises it): both branches of ``transform_means_python`` (round 4: world-frame means natively), models that carry SH rows,
-``convert_SHs_python``, the IMU residual, bundle adjustment -- also with a sharded mapping window (round 4) -- and the
+``optimize_map`` whenever the covariances come from scales + rotations: both branches of ``transform_means_python`` (round 4:
+world-frame means natively), models that carry SH rows, ``convert_SHs_python``, an ACTIVE SH degree 1-3 (a map resumed from a
+checkpoint) with each of the three viewing-direction sources (Mm3dgsSlamInputs.sh_dir, ABI 211), the IMU residual, bundle adjustment
+-- also with a sharded mapping window (round 4; at an active SH degree > 0 the window stays on the torch-graph loop) -- and the
 ``method: splatam`` losses and pruning schedule, and (round 5) ``keep_best_candidate`` (the arg-min over the iterations' losses is
-kept on the device).  What is left (``compute_cov3D_python``, a resumed checkpoint with an active SH degree > 0) falls back to the
+kept on the device).  What is left (``compute_cov3D_python``, the torch-graph renderer's own ``fix_depth_transpose``) falls back to the
 torch-graph loop with a warning; that loop stays the parity reference for these kernels (tests/test_gpu_fused.py).
 """
 from __future__ import annotations
@@ -90,20 +91,20 @@ class FusedEngine:
         # (with the reference's literal depth bundle; this repository's optional `fix_depth_transpose` only exists in the torch-graph renderer)
         fixed_depth = (not pipe["transform_means_python"]) and pipe.get("fix_depth_transpose", False)
         # round 6 (ABI 209): an ACTIVE degree above 0 (a map resumed from a checkpoint, slam/gaussian_model.py:363) runs natively too -- the kernels evaluate
-        # the SH colour at the normalised camera-space mean (what slam/renderer.py:179-193 hands the rasterizer in the shipped mode: means pre-transformed,
-        # campos = 0), step f_rest as a sixth Adam group and carry the direction's share of the pose / mean gradients -- in the shipped mode with the
-        # kernel's own SH evaluation; `convert_SHs_python` (directions taken from the WORLD means in Python) and the world-frame mode stay on the torch-graph loops
-        sh_native = gaussians.active_sh_degree == 0 or (pipe["transform_means_python"] and not pipe["convert_SHs_python"] and gaussians.active_sh_degree <= 3
-                                                        and int(gaussians._features_rest.shape[1]) <= 15)
+        # the SH colour, step f_rest as a sixth Adam group and carry the direction's share of the pose / mean gradients.  ABI 211: in every mode, with the
+        # direction slam/renderer.py:117-124,179-193 produces there (inputs(): sh_dir) -- the normalised camera-space mean (shipped mode, SH in the
+        # rasterizer), the world mean about the origin (convert_SHs_python with pre-transformed means: camera_pos = 0), the world mean seen from the
+        # camera centre (world-frame means, either SH flag)
+        sh_native = gaussians.active_sh_degree == 0 or (gaussians.active_sh_degree <= 3 and int(gaussians._features_rest.shape[1]) <= 15)
         ok = (not pipe["compute_cov3D_python"] and not fixed_depth and sh_native and str(cfg["device"]).startswith("cuda"))
         if not ok and str(cfg["device"]).startswith("cuda"):
             # (the fallback is ~30x slower and used to be silent)
             why = ", ".join(w for w, bad in (("pipeline.compute_cov3D_python: true", pipe["compute_cov3D_python"]),
                                              ("pipeline.fix_depth_transpose", fixed_depth),
-                                             (f"active SH degree {gaussians.active_sh_degree} > 0 with convert_SHs_python / world-frame means", not sh_native)) if bad)
+                                             (f"active SH degree {gaussians.active_sh_degree} with {int(gaussians._features_rest.shape[1])} f_rest rows", not sh_native)) if bad)
             if why not in FusedEngine._warned:
                 FusedEngine._warned.add(why)
-                warnings.warn(f"mm3dgs: this configuration ({why}) is outside the native SLAM loops (covariances from scales + rotations; an active SH degree > 0 only in the shipped mode with the kernel's SH evaluation); "
+                warnings.warn(f"mm3dgs: this configuration ({why}) is outside the native SLAM loops (covariances from scales + rotations, the reference's depth bundle, SH degree <= 3); "
                               "tracking and mapping run the torch-graph loops around the generic HIP rasterizer -- correct, but about 30x slower")
         return ok
 
@@ -172,7 +173,11 @@ class FusedEngine:
         si.xyz, si.f_dc, si.opacity = g._xyz.data_ptr(), g._features_dc.data_ptr(), g._opacity.data_ptr()
         si.scaling, si.rotation = g._scaling.data_ptr(), g._rotation.data_ptr()
         si.isotropic = self.isotropic
-        si.world_means = 0 if self.r.cfg["pipeline"]["transform_means_python"] else 1
+        pipe = self.r.cfg["pipeline"]
+        si.world_means = 0 if pipe["transform_means_python"] else 1
+        # (ABI 211) the SH viewing direction of slam/renderer.py:117-124,179-193: world-frame means -- from the camera centre; pre-transformed means --
+        # the camera-space mean (SH in the rasterizer) or, with convert_SHs_python, the world mean about the origin (camera_pos = 0 in that mode)
+        si.sh_dir = 2 if si.world_means else (1 if pipe["convert_SHs_python"] else 0)
         deg = int(getattr(g, "active_sh_degree", 0))
         if deg > 0:      # (ABI 209) the rows the kernels evaluate / step natively
             si.f_rest, si.sh_degree, si.n_rest = g._features_rest.data_ptr(), deg, int(g._features_rest.shape[1])
