@@ -321,7 +321,10 @@ int mm3dgs_adam(const Mm3dgsAdamGroup* groups, int n_groups, int step, double be
  * still in registers, what the head of the next mm3dgs_slam_map / mm3dgs_slam_forward call would launch for the view at in->pose.
  * That call must carry MM3DGS_FWD_PROJECTED (and the same cam, P, buffers, capacity and flags).  Replaces mm3dgs_adam + the next
  * call's projection launch; same arithmetic as both.  Needs direct bins (MM3DGS_FWD_DIRECT_BINS in fwd_flags and honoured for this
- * P / capacity): returns -3 otherwise, nothing done. */
+ * P / capacity): returns -3 otherwise, nothing done.
+ * ABI 212: in->sh_degree 1-3 is accepted.  It needs grads->d_f_rest and the rest_* group of `adam` (-2 otherwise, nothing done); every
+ * one of the n_rest rows steps with rest_lr (rows beyond the active degree take a zero gradient, their moments decay), and the next
+ * view's SH colour is evaluated from the stepped rows, with the direction of in->sh_dir. */
 /* 1 if the SLAM entry points run with direct bins for this camera, map size, capacity and flags, 0 otherwise (pure host arithmetic:
  * what a caller of mm3dgs_slam_adam_project asks first). */
 int mm3dgs_slam_direct_bins(const Mm3dgsCamera* cam, int P, size_t N_capacity, int fwd_flags);
@@ -452,8 +455,10 @@ const char* mm3dgs_last_error(void);
    209: Mm3dgsSlamInputs.f_rest / sh_degree / n_rest, Mm3dgsSlamGrads.d_f_rest, Mm3dgsMapAdam.rest_* (all appended): native loops at an active SH degree > 0
    210: mm3dgs_densify_work_bytes / mm3dgs_densify_plan / mm3dgs_densify_rows, Mm3dgsDensifyGroup / Mm3dgsDensifyState (densification)
    211: Mm3dgsSlamInputs.sh_dir (appended): native loops at an active SH degree > 0 with the world-origin (convert_SHs_python) and camera-centre
-        (world_means = 1) viewing directions */
-#define MM3DGS_ABI_VERSION 211
+        (world_means = 1) viewing directions
+   212: mm3dgs_slam_adam_project accepts an active SH degree 1-3 (needs Mm3dgsSlamGrads.d_f_rest and Mm3dgsMapAdam.rest_*; no struct changes):
+        the multi-GPU mapping window runs natively at an active SH degree */
+#define MM3DGS_ABI_VERSION 212
 int mm3dgs_version(void);
 
 #ifdef __cplusplus

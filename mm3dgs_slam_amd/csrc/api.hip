@@ -648,9 +648,12 @@ int mm3dgs_slam_adam_project(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInp
                              int32_t* radii, void* geom_state, void* image_state, void* binning_state, size_t N_capacity, int fwd_flags, void* stream) {
   int rc = check_slam(cam, P, in);
   if (rc) return rc;
-  if (in->sh_degree > 0) return fail(-2, "mm3dgs_slam_adam_project has no SH form: step with mm3dgs_adam, the next mm3dgs_slam_map call projects");
   if (!grads || !adam || !geom_state || !image_state || !binning_state || (P > 0 && !radii)) return fail(-1, "NULL argument");
   if (!grads->d_xyz || !grads->d_f_dc || !grads->d_opacity || !grads->d_scaling || !grads->d_rotation) return fail(-2, "all five gradient arrays are needed");
+  // (ABI 212) an active SH degree: the sixth group -- its gradient array and its Adam state -- or nothing is launched
+  if (in->sh_degree > 0 && !grads->d_f_rest) return fail(-2, "sh_degree %d needs grads->d_f_rest", in->sh_degree);
+  if (in->sh_degree > 0 && (!adam->rest_param || !adam->rest_exp_avg || !adam->rest_exp_avg_sq))
+    return fail(-2, "sh_degree %d needs the f_rest group of the map Adam (rest_param / rest_exp_avg / rest_exp_avg_sq)", in->sh_degree);
   hipStream_t s = (hipStream_t)stream;
   CamDev cd = cam_dev(cam);
   cd.bg_extras = 1;
@@ -663,6 +666,7 @@ int mm3dgs_slam_adam_project(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInp
   if ((rc = map_adam_dev(adam, ma))) return rc;
   SlamGrads sg = {};
   sg.d_xyz = grads->d_xyz; sg.d_f_dc = grads->d_f_dc; sg.d_opacity = grads->d_opacity; sg.d_scaling = grads->d_scaling; sg.d_rotation = grads->d_rotation;
+  sg.d_f_rest = in->sh_degree > 0 ? grads->d_f_rest : nullptr;
   { ProfScope ps(MM3DGS_PROF_ADAM, s);
     launch_slam_adam_project(cd, P, slam_in(in), radii, geom_view(geom_state, P > 0 ? P : 1), image_view(image_state, cd.H, cd.W), bin_view(binning_state, N_capacity),
                              sg, ma, in->pose, db.bin_cap, db.rec_cap, db.slot_bits, s); }

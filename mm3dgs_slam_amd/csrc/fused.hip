@@ -989,10 +989,14 @@ void launch_slam_bwd_project(const CamDev& cam, int P, const SlamIn& in, int32_t
 // fused_adam_kernel + slam_project_bin_kernel do in two, with the stepped parameters going from the optimiser to the projection in
 // registers (the second half of slam_bwd_project_kernel, fed by gradient arrays instead of the record gather).  Same update arithmetic as
 // slam_bwd_body's in-kernel Adam; opt_mask as there.
-template <bool WORLD>
+// SH (ABI 212): an active degree above 0 -- the sixth group (f_rest from gr.d_f_rest, every one of the n_rest rows stepped: zero gradient beyond
+// the active degree, the moments decay) and the projection's SH colour from the STEPPED rows, handed over in registers like the other
+// parameters (the kernel never reads f_rest through `in`: in.f_rest and ma.rp are the same memory).  SHDIR as slam_project_bin_kernel's.
+template <bool WORLD, bool SH = false, int SHDIR = 0>
 __global__ void __launch_bounds__(FB)
 slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radii, GeomView g, ImageView iv, BinView b, SlamGrads gr, MapAdam ma,
                          const float* __restrict__ next_pose, uint32_t cap, uint32_t rec_cap, int slot_bits) {
+  static_assert(!SH || WORLD == (SHDIR == 2), "world-frame means take the direction from the camera centre, pre-transformed ones from the mean or the origin");
   extern __shared__ uint32_t hist[];
   const int T = cam.gx * cam.gy;
   const int tid = threadIdx.x;
@@ -1000,6 +1004,7 @@ slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ rad
   if (blockIdx.x == 0 && tid == 0) iv.hdr->bin_cap = cap;
   const int idx = blockIdx.x * FB + tid;
   RawGaussian rg = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f};
+  float rs[SH ? 45 : 1];      // (SH) the stepped f_rest rows the colour reads: [k - 1][3] for k < (sh_deg + 1)^2, compile-time indices only
   if (idx < P) {
     constexpr int AG_OFF[5] = {0, 3, 6, 7, 10}, AG_N[5] = {3, 3, 1, 3, 4};     // xyz | f_dc | opacity | scaling | rotation
     const float* gsrc[5] = {gr.d_xyz, gr.d_f_dc, gr.d_opacity, gr.d_scaling, gr.d_rotation};
@@ -1026,21 +1031,50 @@ slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ rad
         ap[q] = ap[q] - ma.step_size[gq] * (mi / (sqrtf(vi) / ma.bc2s + ma.eps));
         ma.p[gq][off] = ap[q];
       }
+    if constexpr (SH) {
+      // the sixth group, row by row (slam_bwd_body's arithmetic): rows the active degree does not reach take a zero gradient
+      const int nb = (in.sh_deg + 1) * (in.sh_deg + 1);
+      const size_t base = (size_t)idx * (size_t)in.n_rest * 3;
+#pragma unroll
+      for (int k = 1; k < 16; k++)
+        if (k - 1 < in.n_rest) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ch++) {
+            const size_t off = base + (size_t)(k - 1) * 3 + ch;
+            const float grd = k < nb ? keepg * gr.d_f_rest[off] : 0.f;
+            const float m0 = ma.rm[off], v0 = ma.rv[off];
+            const float mi = m0 + (grd - m0) * ma.omb1;
+            const float vi = v0 * ma.beta2 + grd * grd * ma.omb2;
+            ma.rm[off] = mi; ma.rv[off] = vi;
+            const float pn = ma.rp[off] - ma.rest_step_size * (mi / (sqrtf(vi) / ma.bc2s + ma.eps));
+            ma.rp[off] = pn;
+            rs[(k - 1) * 3 + ch] = pn;
+          }
+        }
+    }
 #pragma unroll
     for (int k = 0; k < 3; k++) { rg.x[k] = ap[k]; rg.fd[k] = ap[3 + k]; rg.ls[k] = ap[7 + k]; }
     rg.op = ap[6];
 #pragma unroll
     for (int k = 0; k < 4; k++) rg.q[k] = ap[10 + k];
   }
-  const Projected pr = slam_project_vals(cam, idx < P, idx, next_pose, in.isotropic != 0, rg, radii, g, WORLD);
-  slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
+  if constexpr (SH) {
+    const Projected pr = slam_project_vals<true, SHDIR>(cam, idx < P, idx, next_pose, in.isotropic != 0, rg, radii, g, WORLD, false, rs, in.sh_deg);
+    slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
+  } else {
+    const Projected pr = slam_project_vals(cam, idx < P, idx, next_pose, in.isotropic != 0, rg, radii, g, WORLD);
+    slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
+  }
 }
 
 void launch_slam_adam_project(const CamDev& cam, int P, const SlamIn& in, int32_t* radii, GeomView g, ImageView iv, BinView b, const SlamGrads& gr,
                               const MapAdam& ma, const float* next_pose, uint32_t bin_cap, uint32_t rec_cap, int slot_bits, hipStream_t s) {
   if (P <= 0) return;
   const int T = cam.gx * cam.gy;
-  if (in.world)
+  if (in.sh_deg > 0) {      // (ABI 212; api.hip admits world_means = 1 with sh_dir = 2 only, and sh_dir = 2 with world_means = 1 only)
+    auto k = in.sh_dir == 2 ? slam_adam_project_kernel<true, true, 2> : in.sh_dir == 1 ? slam_adam_project_kernel<false, true, 1> : slam_adam_project_kernel<false, true, 0>;
+    hipLaunchKernelGGL(k, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, gr, ma, next_pose, bin_cap, rec_cap, slot_bits);
+  } else if (in.world)
     hipLaunchKernelGGL(slam_adam_project_kernel<true>, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, gr, ma, next_pose,
                        bin_cap, rec_cap, slot_bits);
   else

@@ -8,7 +8,7 @@ collapsed into a handful of C-ABI calls with no host synchronisation inside the 
 ``optimize_map`` whenever the covariances come from scales + rotations: both branches of ``transform_means_python`` (round 4:
 world-frame means natively), models that carry SH rows, ``convert_SHs_python``, an ACTIVE SH degree 1-3 (a map resumed from a
 checkpoint) with each of the three viewing-direction sources (Mm3dgsSlamInputs.sh_dir, ABI 211), the IMU residual, bundle adjustment
--- also with a sharded mapping window (round 4; at an active SH degree > 0 the window stays on the torch-graph loop) -- and the
+-- also with a sharded mapping window (round 4; ABI 212: at an active SH degree too, the f_rest rows in its flat gradient buffer) -- and the
 ``method: splatam`` losses and pruning schedule, and (round 5) ``keep_best_candidate`` (the arg-min over the iterations' losses is
 kept on the device).  What is left (``compute_cov3D_python``, the torch-graph renderer's own ``fix_depth_transpose``) falls back to the
 torch-graph loop with a warning; that loop stays the parity reference for these kernels (tests/test_gpu_fused.py).
@@ -139,24 +139,44 @@ class FusedEngine:
             self.n_cap = int(want * 1.25) if self.ratio is not None else want
             self.binning = torch.empty(self.lib.mm3dgs_binning_bytes(self.n_cap), **u8)
             self.scratch = torch.empty(self.lib.mm3dgs_backward_scratch_bytes(self._cap_P, self.n_cap), **u8)
-        if need_grads and self.grads is None:
-            # one flat buffer [xyz 3P | f_dc 3P | opacity P | scaling 3P | rotation 4P | accum P | denom P]: the multi-GPU
-            # window all-reduces it in a single collective (window_parallel.py)
-            # (+ 64: a sharded optimiser step reduce-scatters world x S >= 14 P elements of it, S = the 4-aligned shard size)
-            self.flat = torch.zeros(16 * P + 64, device=self.dev)
-            self.acc = torch.zeros(14 * P, device=self.dev)      # window-batch mode: sum of the local views' gradients
-            o = [0, 3 * P, 6 * P, 7 * P, 10 * P, 14 * P, 15 * P, 16 * P]
+        if need_grads and (self.grads is None or self._flat_rest != self.rest_rows):
+            # one flat buffer [xyz 3P | f_dc 3P | opacity P | scaling 3P | rotation 4P | f_rest 3 n P | accum P | denom P] (n = rest_rows, 0 at
+            # SH degree 0): the multi-GPU window all-reduces it in a single collective (window_parallel.py).  W = 14 + 3 n parameter columns.
+            # (+ 64: a sharded optimiser step reduce-scatters world x S >= W P elements of it, S = the 4-aligned shard size)
+            n, W = self.rest_rows, self.flat_width
+            self.flat = torch.zeros((W + 2) * P + 64, device=self.dev)
+            self.acc = torch.zeros(W * P, device=self.dev)      # window-batch mode: sum of the local views' gradients
+            o = [0, 3 * P, 6 * P, 7 * P, 10 * P, 14 * P, W * P, (W + 1) * P, (W + 2) * P]
             v = lambda i, shape: self.flat[o[i]:o[i + 1]].view(shape)
             self.grads = dict(xyz=v(0, (P, 3)), f_dc=v(1, (P, 1, 3)), opacity=v(2, (P, 1)), scaling=v(3, (P, 3)), rotation=v(4, (P, 4)))
-            self.stat_delta = (torch.zeros(P, device=self.dev), v(5, (P, 1)), v(6, (P, 1)))   # max radii | accum | denom
+            if n:
+                self.grads["f_rest"] = v(5, (P, n, 3))
+            self.stat_delta = (torch.zeros(P, device=self.dev), v(6, (P, 1)), v(7, (P, 1)))   # max radii | accum | denom
+            self._flat_rest = n
             self._rest_rows = None
+
+    # f_rest rows per Gaussian that the flat gradient buffer carries (bind_rest_rows): the model's n_rest at an active SH degree > 0, else 0
+    rest_rows = 0
+    _flat_rest = 0
+
+    @property
+    def flat_width(self):
+        """W: parameter columns of the flat gradient buffer, 14 + 3 rest_rows (the window's collectives and optimiser steps cover W P)."""
+        return 14 + 3 * self.rest_rows
+
+    def bind_rest_rows(self, g):
+        """Size the flat buffer's f_rest block for model g (the next _ensure with gradients re-lays the buffer out if it changed)."""
+        self.rest_rows = int(g._features_rest.shape[1]) if int(getattr(g, "active_sh_degree", 0)) > 0 else 0
 
     def rest_grad(self, g):
         """Gradient buffer of the f_rest rows [P, n_rest, 3] for a model at an active SH degree > 0 (None at degree 0): what
-        Mm3dgsSlamGrads.d_f_rest points at whenever the other gradient outputs are set."""
+        Mm3dgsSlamGrads.d_f_rest points at whenever the other gradient outputs are set -- the flat buffer's f_rest block while the
+        gradient buffers are live."""
         if int(getattr(g, "active_sh_degree", 0)) <= 0:
             return None
         shape = tuple(g._features_rest.shape)
+        if self.grads is not None and "f_rest" in self.grads and tuple(self.grads["f_rest"].shape) == shape:
+            return self.grads["f_rest"]
         if getattr(self, "_rest_rows", None) is None or tuple(self._rest_rows.shape) != shape:
             self._rest_rows = torch.zeros(shape, device=self.dev)
             if self.grads is not None:
@@ -185,6 +205,7 @@ class FusedEngine:
 
     def forward(self, pose, g, need_grads=False):
         P = int(g._xyz.shape[0])
+        self.bind_rest_rows(g)
         self._ensure(P, need_grads)
         si = self.inputs(pose, g)
         self._last_g = g
@@ -213,6 +234,8 @@ class FusedEngine:
         sg = _lib.Mm3dgsSlamGrads()
         sg.d_xyz, sg.d_f_dc, sg.d_opacity = grads["xyz"].data_ptr(), grads["f_dc"].data_ptr(), grads["opacity"].data_ptr()
         sg.d_scaling, sg.d_rotation = grads["scaling"].data_ptr(), grads["rotation"].data_ptr()
+        if si.sh_degree > 0:      # (ABI 212) the sixth group: f_rest stepped from the flat buffer's f_rest block
+            sg.d_f_rest = grads["f_rest"].data_ptr()
         self._pose_keepalive = next_pose
         _lib.check(self.lib.mm3dgs_slam_adam_project(C.byref(self.cam), P, C.byref(si), C.byref(sg), C.byref(map_adam), _p(self.radii), _p(self.geom),
                                                      _p(self.img_state), _p(self.binning), self.n_cap, self._flags(), _stream()))
@@ -230,6 +253,7 @@ class FusedEngine:
         call stays in force (MM3DGS_FWD_KEEP_TILE_ORDER) and the loss scalars' finishing launch is left out (`loss` then keeps the values
         of the last call that asked for them).  projected: adam_project already launched the projection + binning of views[0]."""
         P = int(g._xyz.shape[0])
+        self.bind_rest_rows(g)
         self._ensure(P, True)
         arr = getattr(views, "table", None)      # built ahead of time by FusedMapper (a _Views list)
         if arr is None:
@@ -446,6 +470,9 @@ class FusedTracker(Tracker):
 
 class FusedMapper(Mapper):
     fuse_adam_project = True     # multi-GPU window: the optimiser step and the next view's projection + binning in one launch (False: mm3dgs_adam, then the projection)
+    # ... at an active SH degree too (ABI 212).  Off by default: at 157 k Gaussians, SH 2, the fused SH launch measured 312 us against 28 + 19 us for
+    # mm3dgs_adam + the projection (profiles/r08_sh_window_kernel_stats_*.csv)
+    fuse_adam_project_sh = False
     lazy_checks = True       # False: read the capacity header back after every loop (debugging / tests)
     always_snapshot = False      # debugging / tests: snapshot the map before every mapping loop (the round-2 behaviour)
     loop_reruns = 0              # mapping loops re-run after a binning overflow
@@ -586,13 +613,14 @@ class FusedMapper(Mapper):
 
     def optimize_map(self, idx, num_iter, keyframe_idx_list, new_gaussians_mask, curr_camera_tensor, curr_gt_color,
                      curr_gt_depth=None, curr_est_depth=None):
-        sh_window = int(self.gaussians.active_sh_degree) > 0 and self.window is not None      # (the sharded window's flat gradient layout has no f_rest rows)
-        if num_iter == 0 or sh_window or not FusedEngine.eligible(self.cfg, self.gaussians):
+        if num_iter == 0 or not FusedEngine.eligible(self.cfg, self.gaussians):
             return super().optimize_map(idx, num_iter, keyframe_idx_list, new_gaussians_mask, curr_camera_tensor, curr_gt_color,
                                         curr_gt_depth, curr_est_depth)
         eng = _engine(self.renderer)
         t_start = time.perf_counter()
         g = self.gaussians
+        if hasattr(eng, "bind_rest_rows"):      # (ABI 212) at an active SH degree the flat gradient buffer carries the f_rest rows too
+            eng.bind_rest_rows(g)
         loop = _MapLoop(self, eng, idx, num_iter, keyframe_idx_list, new_gaussians_mask, (curr_camera_tensor, curr_gt_color, curr_gt_depth, curr_est_depth))
         # overflow recovery: a forward whose (tile, splat) pairs exceed the binning capacity renders clamped lists (flagged
         # sticky in the header).  The loop below is read back once, at its end; if any of its forwards overflowed, the map,
@@ -900,6 +928,7 @@ class _MapLoop:
         self.pending = None
         P = int(g._xyz.shape[0])
         eng._ensure(P, True)
+        W = self.width()
         densify = self.dens(it)
         self._local_grads(it, ids, projected, densify, P)
         # how the summed gradients become stepped parameters everywhere: one flat all-reduce + the identical step on every replica, or
@@ -909,11 +938,11 @@ class _MapLoop:
         if shard:
             self._mask_grads()      # (before the sum: the mask is the same everywhere)
             self._shard_buffers(P)
-            w.reduce_scatter_flat(eng.flat, 14 * P, self.shard_g, tail=2 * P if densify else 0, rmax=eng.stat_delta[0] if densify else None)
+            w.reduce_scatter_flat(eng.flat, W * P, self.shard_g, tail=2 * P if densify else 0, rmax=eng.stat_delta[0] if densify else None)
         elif densify:
-            w.reduce_flat(eng.flat[:16 * P], eng.stat_delta[0])
+            w.reduce_flat(eng.flat[:(W + 2) * P], eng.stat_delta[0])
         else:
-            w.reduce_flat(eng.flat[:14 * P])
+            w.reduce_flat(eng.flat[:W * P])
         if densify:
             torch.maximum(g.max_radii2D, eng.stat_delta[0], out=g.max_radii2D)
             torch._foreach_add_([g.xyz_gradient_accum, g.denom], [eng.stat_delta[1], eng.stat_delta[2]])      # (one launch)
@@ -922,7 +951,8 @@ class _MapLoop:
         if shard:
             self._sharded_adam(P)
         elif not prune:
-            if self.mapper.fuse_adam_project and it + 1 < self.num_iter and hasattr(eng, "adam_project") and eng.can_adam_project(g):
+            fuse = self.mapper.fuse_adam_project and (self.mapper.fuse_adam_project_sh or int(g.active_sh_degree) == 0)
+            if fuse and it + 1 < self.num_iter and hasattr(eng, "adam_project") and eng.can_adam_project(g):
                 # the step and the NEXT view's projection + binning in one launch: the next step's keyframe picks are drawn now
                 # (same draws, same order as at the head of the next iteration), its first local view's pose goes with the step
                 self.pending = w.take_all(self.pop)
@@ -935,10 +965,11 @@ class _MapLoop:
     def _local_grads(self, it, ids, projected, densify, P):
         """Forward, loss and backward of each of this rank's views of a window step, gradients written out (not stepped) to eng.flat; more
         than one local view (window-batch mode): summed there in view order.  ONE flat all-reduce over the ranks then carries every
-        parameter gradient and, while densifying, the statistics tail [14P, 16P) (+ a max-reduce of the radii)."""
+        parameter gradient and, while densifying, the statistics tail [WP, (W+2)P) (+ a max-reduce of the radii)."""
         g, eng = self.g, self.eng
+        W = self.width()
         if densify:
-            torch._foreach_zero_([eng.stat_delta[0], eng.flat[14 * P:]])        # (one launch)
+            torch._foreach_zero_([eng.stat_delta[0], eng.flat[W * P:]])        # (one launch)
         if self.ba_ids:
             self.ba_grad.zero_()
         for j, k in enumerate(ids):
@@ -951,11 +982,11 @@ class _MapLoop:
                 self.ba_grad[self.ba_ids.index(k)] += self.ba[k].grad
             if len(ids) > 1:
                 if j == 0:
-                    eng.acc[:14 * P].copy_(eng.flat[:14 * P])
+                    eng.acc[:W * P].copy_(eng.flat[:W * P])
                 else:
-                    eng.acc[:14 * P].add_(eng.flat[:14 * P])
+                    eng.acc[:W * P].add_(eng.flat[:W * P])
         if len(ids) > 1:
-            eng.flat[:14 * P].copy_(eng.acc[:14 * P])
+            eng.flat[:W * P].copy_(eng.acc[:W * P])
 
     def _mask_grads(self):
         """Bundle adjustment: Gaussians outside the covisible set keep a zero gradient (slam/mapper.py:931-938)."""
@@ -1017,16 +1048,23 @@ class _MapLoop:
 
     _FLAT_GROUPS = (("xyz", 0, 3), ("f_dc", 3, 6), ("opacity", 6, 7), ("scaling", 7, 10), ("rotation", 10, 14))      # the engine's flat layout, in units of P
 
+    def width(self):
+        """W, the parameter columns of the engine's flat gradient buffer: 14, + 3 n_rest at an active SH degree (an engine without
+        FusedEngine.flat_width has the 14 of degree 0)."""
+        return getattr(self.eng, "flat_width", 14)
+
     def _flat_groups(self, P):
-        """[(optimiser group, its parameter, its Adam state, a, b)]: the five stepped groups and their element ranges [a, b) in the
-        engine's flat gradient layout."""
-        return [(*_adam_state(self.g.optimizer, name), a * P, b * P) for name, a, b in self._FLAT_GROUPS]
+        """[(optimiser group, its parameter, its Adam state, a, b)]: the stepped groups -- five, and f_rest at an active SH degree -- and
+        their element ranges [a, b) in the engine's flat gradient layout."""
+        W = self.width()
+        groups = self._FLAT_GROUPS + ((("f_rest", 14, W),) if W > 14 else ())
+        return [(*_adam_state(self.g.optimizer, name), a * P, b * P) for name, a, b in groups]
 
     def _shard_buffers(self, P):
         """shard_g / shard_p (this rank's S elements of the flat gradient / of the parameters or a moment) and pflat (world x S: what
         the all-gather fills), made for the map's current size."""
         w, dev = self.window, self.eng.dev
-        S = w.shard_bounds(14 * P)[0]
+        S = w.shard_bounds(self.width() * P)[0]
         if self.shard_S != S:
             self.shard_S = S
             self.shard_g, self.shard_p = torch.zeros(S, device=dev), torch.zeros(S, device=dev)
@@ -1034,14 +1072,14 @@ class _MapLoop:
 
     def _sharded_adam(self, P):
         """One optimiser step of the sharded window with the optimiser itself sharded over the ranks by ELEMENT (the
-        reference's step is slam/mapper.py:931-948 on one view's gradients): the caller's reduce-scatter of the flat gradient [14 P] left
-        this rank's S = ceil(14 P / world) summed elements in shard_g; mm3dgs_adam on exactly those elements of the parameters and of both
-        moments (the slice cuts through the five groups: one table entry per group it touches); all-gather of the stepped PARAMETERS.  The
+        reference's step is slam/mapper.py:931-948 on one view's gradients): the caller's reduce-scatter of the flat gradient [W P] left
+        this rank's S = ceil(W P / world) summed elements in shard_g; mm3dgs_adam on exactly those elements of the parameters and of both
+        moments (the slice cuts through the groups: one table entry per group it touches); all-gather of the stepped PARAMETERS.  The
         moments of elements another rank owns go stale here and are gathered when somebody needs them (sync_moments: before map surgery
         and at the end of the loop).  Same arithmetic per element as the all-reduce path's mm3dgs_adam: bit-identical parameters (tested
         over gloo)."""
         opt = self.g.optimizer
-        lo, hi = self.window.shard_bounds(14 * P)[1:]
+        lo, hi = self.window.shard_bounds(self.width() * P)[1:]
         groups = self._flat_groups(P)
         table, k = (_lib.Mm3dgsAdamGroup * 8)(), 0
         for group, p, st, a, b in groups:
@@ -1065,7 +1103,7 @@ class _MapLoop:
     def sync_moments(self):
         """After sharded steps every rank holds fresh Adam moments for ITS elements only: gather both moment arrays so that the replicas
         are whole again (before a pruning step compacts rows across shard boundaries, before a snapshot / checkpoint, at the end of the
-        loop).  Two all-gathers of 14 P floats, a few times per frame."""
+        loop).  Two all-gathers of W P floats, a few times per frame."""
         if not self.stale:
             return
         self.stale = False
@@ -1078,11 +1116,12 @@ class _MapLoop:
     def _all_gather(self, groups, P, part):
         """Every replica's `part(parameter, Adam state)` of each flat group made whole from the ranks' shards: this rank's elements go
         into shard_p, the all-gather fills pflat, and each group's range is copied back."""
-        lo, hi = self.window.shard_bounds(14 * P)[1:]
+        n = self.width() * P
+        lo, hi = self.window.shard_bounds(n)[1:]
         for group, p, st, a, b in groups:
             i0, i1 = max(lo, a), min(hi, b)
             if i0 < i1:
                 self.shard_p[i0 - lo:i1 - lo].copy_(part(p, st).view(-1)[i0 - a:i1 - a])
-        self.window.all_gather_flat(self.pflat, self.shard_p, 14 * P)
+        self.window.all_gather_flat(self.pflat, self.shard_p, n)
         for group, p, st, a, b in groups:
             part(p, st).view(-1).copy_(self.pflat[a:b])
