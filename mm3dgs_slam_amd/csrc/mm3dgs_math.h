@@ -1,5 +1,10 @@
 // Device-side maths shared by the per-Gaussian kernels (preprocess.hip, fused.hip): SH basis, quaternion -> rotation,
-// 3D covariance, EWA projection to a 2D conic.  Conventions: see preprocess.hip's header.
+// 3D covariance, EWA projection to a 2D conic, and the pieces of its chain rule and of the Adam update that several kernels must evaluate
+// bit-identically.  Conventions: see preprocess.hip's header.
+// Floating-point contraction: every helper here is inlined into its caller and INHERITS THE INCLUDING FILE'S CONTRACTION MODE (fused.hip sets
+// `#pragma clang fp contract(on)` before this include: a product and a sum inside one source expression fuse, nothing else does;
+// preprocess.hip compiles under hipcc's default).  Each expression below is therefore one rounding recipe: do not split or merge them, and
+// keep the temporaries where they are.
 #pragma once
 #include "mm3dgs_common.h"
 
@@ -139,3 +144,98 @@ __device__ __forceinline__ void ewa_project(const CamDev& cam, const float* V, c
   e.c = AS[1][0] * e.A[1][0] + AS[1][1] * e.A[1][1] + AS[1][2] * e.A[1][2] + 0.3f;
 }
 
+
+// preprocess.hip (hipcc's default contraction) keeps its own copies of the conic -> cov2D step and of dR -> dq: routed through the helpers
+// below its kernels kept their registers but not their instruction stream, and bit-identity of the generic kernels was not established.
+
+// Homogeneous projection of a point p under the row-vector matrix PV: clip x, y, w and pw = 1 / (w + 1e-7).
+struct HomPoint { float hx, hy, hw, pw; };
+__device__ __forceinline__ HomPoint hom_project(const float* PV, const float p[3]) {
+  HomPoint h;
+  h.hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
+  h.hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
+  h.hw = p[0] * PV[3] + p[1] * PV[7] + p[2] * PV[11] + PV[15];
+  h.pw = 1.f / (h.hw + 1e-7f);
+  return h;
+}
+
+// d/d(conic) (gA, gB, gC) -> d/d(2D covariance) (da, db, dcc) of Sigma2 = [[a, b], [b, c]], conic = (c, -b, a) / det.
+// G2 = dL/dSigma2 is formed as 1/det [[gC, -gB/2], [-gB/2, gA]] + kappa adj(Sigma2), kappa = -(c gA - b gB + a gC) / det^2 -- NOT the expanded
+// closed form (-c^2 gA + b c gB - b^2 gC) / det^2 etc.: for a thin rotated ellipse (a c / det ~ 50) each expanded entry cancels ~75-fold on its
+// own, and the log-scale gradient of the long axis is v^T G2 v along the axis where G2 cancels ~50-fold again: independent 2e-6 errors of the
+// entries came out as 2e-4 (measured with a float32 numpy probe: tools/cov_chain_probe.py).  In this form the cancelling part is ONE scalar
+// times adj(Sigma2), whose quadratic form along the long axis is small by construction: 2e-4 -> 1.5e-5 on the same splat.
+struct Cov2dGrad { float da, db, dcc; };
+__device__ __forceinline__ Cov2dGrad conic_grad_to_cov2d(float a, float b, float c, float gA, float gB, float gC) {
+  const float det = a * c - b * b, idet = 1.f / det;
+  const float kappa = -(c * gA - b * gB + a * gC) * idet * idet;
+  Cov2dGrad g;
+  g.da = gC * idet + kappa * c;
+  g.db = -gB * idet - 2.f * (kappa * b);
+  g.dcc = gA * idet + kappa * a;
+  return g;
+}
+
+// d/d(2D covariance) -> GA = G2 A (2x3) and dA = 2 G2 A Sigma3, with A = J Wr of ewa_project (Sigma2 = A Sigma3 A^T)
+__device__ __forceinline__ void cov2d_grad_to_dA(const Ewa& e, const float S3[3][3], const Cov2dGrad& g, float GA[2][3], float dA[2][3]) {
+  const float G2[2][2] = {{g.da, 0.5f * g.db}, {0.5f * g.db, g.dcc}};
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    GA[0][i] = G2[0][0] * e.A[0][i] + G2[0][1] * e.A[1][i];
+    GA[1][i] = G2[1][0] * e.A[0][i] + G2[1][1] * e.A[1][i];
+  }
+#pragma unroll
+  for (int j = 0; j < 3; j++)
+#pragma unroll
+    for (int r = 0; r < 2; r++) dA[r][j] = 2.f * (GA[r][0] * S3[0][j] + GA[r][1] * S3[1][j] + GA[r][2] * S3[2][j]);
+}
+
+// d/dJ (the four non-zero entries of the perspective Jacobian) -> d/d(view-space mean), the +-1.3 tan-fov clamp of ewa_project included
+__device__ __forceinline__ void dJ_to_dmean(const CamDev& cam, const Ewa& e, float dJ00, float dJ02, float dJ11, float dJ12, float dm[3]) {
+  const float tz = e.t[2], itz = 1.f / tz, itz2 = itz * itz, itz3 = itz2 * itz;
+  dm[0] = e.in_x ? -cam.focal_x * itz2 * dJ02 : 0.f;
+  dm[1] = e.in_y ? -cam.focal_y * itz2 * dJ12 : 0.f;
+  dm[2] = -cam.focal_x * itz2 * dJ00 - cam.focal_y * itz2 * dJ11 + 2.f * cam.focal_x * e.txc * itz3 * dJ02 +
+          2.f * cam.focal_y * e.tyc * itz3 * dJ12;
+}
+
+// dL/dR -> dL/dq through quat_to_R at the quaternion q = (r, x, y, z)
+__device__ __forceinline__ void dR_to_dq(const float q[4], const float dR[3][3], float dq[4]) {
+  const float r = q[0], x = q[1], y = q[2], z = q[3];
+  dq[0] = 2.f * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
+  dq[1] = 2.f * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - 2.f * x * dR[1][1] - r * dR[1][2] + z * dR[2][0] +
+                 r * dR[2][1] - 2.f * x * dR[2][2]);
+  dq[2] = 2.f * (-2.f * y * dR[0][0] + x * dR[0][1] + r * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r * dR[2][0] +
+                 z * dR[2][1] - 2.f * y * dR[2][2]);
+  dq[3] = 2.f * (-2.f * z * dR[0][0] - r * dR[0][1] + x * dR[0][2] + r * dR[1][0] - 2.f * z * dR[1][1] +
+                 y * dR[1][2] + x * dR[2][0] + y * dR[2][1]);
+}
+// the same for R(q / |q|): qn = q / |q|, inv = 1 / |q|; the normalisation projects the gradient onto qn's tangent space
+__device__ __forceinline__ void dR_to_dq_raw(const float qn[4], float inv, const float dR[3][3], float dq_raw[4]) {
+  float dq[4];
+  dR_to_dq(qn, dR, dq);
+  const float dot = qn[0] * dq[0] + qn[1] * dq[1] + qn[2] * dq[2] + qn[3] * dq[3];
+#pragma unroll
+  for (int k = 0; k < 4; k++) dq_raw[k] = (dq[k] - qn[k] * dot) * inv;
+}
+
+// One element of torch.optim.Adam's update (slam/gaussian_model.py:143-195, slam/tracker.py:233-246): omb1 = 1 - beta1, omb2 = 1 - beta2,
+// bc2s = sqrt(1 - beta2^t), step = lr / (1 - beta1^t).  With eps = 1e-15 a one-ulp disagreement between two evaluations of this is a full
+// +-lr step: every kernel that steps a parameter calls this.
+struct AdamElem { float p, m, v; };
+__device__ __forceinline__ void adam_moments(float m, float v, float g, float omb1, float beta2, float omb2, AdamElem& r) {
+  r.m = m + (g - m) * omb1;                 // exp_avg.lerp_(grad, 1 - beta1)
+  r.v = v * beta2 + g * g * omb2;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+}
+// (the two halves are separate for the kernels that load p only after the moments are stored: requesting it earlier cost
+//  slam_adam_project_kernel<true, true, 2> four VGPRs and a wave of occupancy)
+__device__ __forceinline__ float adam_param(float p, const AdamElem& r, float bc2s, float eps, float step) {
+  return p - step * (r.m / (sqrtf(r.v) / bc2s + eps));
+}
+__device__ __forceinline__ AdamElem adam_elem(float p, float m, float v, float g, float omb1, float beta2, float omb2, float bc2s, float eps,
+                                              float step) {
+  AdamElem r;
+  adam_moments(m, v, g, omb1, beta2, omb2, r);
+  r.p = adam_param(p, r, bc2s, eps, step);
+  return r;
+}

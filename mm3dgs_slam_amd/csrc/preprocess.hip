@@ -301,7 +301,7 @@ preprocess_bwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
       float det = a * c - b * b;
       float idet = 1.f / det;
       // conic = (c, -b, a)/det  ->  d/d(a,b,c)
-      // (G2 as 1/det [[gC, -gB/2], [-gB/2, gA]] + kappa adj(Sigma2), not the expanded closed form: fused.hip slam_bwd_body says why)
+      // (G2 as 1/det [[gC, -gB/2], [-gB/2, gA]] + kappa adj(Sigma2), not the expanded closed form: mm3dgs_math.h conic_grad_to_cov2d says why)
       float kappa = -(c * gA - b * gB + a * gC) * idet * idet;
       float da = gC * idet + kappa * c;
       float db = -gB * idet - 2.f * (kappa * b);
