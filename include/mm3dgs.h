@@ -403,6 +403,19 @@ int mm3dgs_covisibility_ratio(int H, int W, const float* depth /*[H,W]*/, const 
 int mm3dgs_propagate_const_vel(const float* pose_m1 /*[7], frame idx-1*/, const float* pose_m2 /*[7], frame idx-2*/, float* out_pose /*[7]*/,
                                void* stream);
 
+/* IMU dead-reckoning of the tracker's start pose (utils/pose_utils.py:148-200 propagate_imu, called at slam/tracker.py:200-206): the IMU pose
+ * i2w = W1^-1 c2i^-1 of frame idx-1 stepped through the n samples of the interval (frame idx-1, frame idx] -- velocity
+ * (i2w2^-1 i2w1)[:3,3] / dt_cam held constant over the samples, acc = a - R(i2w)^T g, delta = [euler 'sxyz' (omega dt_imu) |
+ * v dt_imu + acc dt_imu^2 / 2], i2w <- i2w delta -- and out = pose of (i2w c2i)^-1.  Poses are world->camera (qw,qx,qy,qz,tx,ty,tz); every
+ * pointer is device memory; imu6 is read only (the reference subtracts gravity from the caller's rows in place) and may be NULL when
+ * n == 0, which returns pose_m1 with a unit quaternion.  c2i must be rigid (the inverses are closed-form).  Computed in double precision
+ * by one lane, rounded to float32 at the store; no host synchronisation.  -1: a NULL pointer; -2: n < 0, dt_cam == 0 or a non-finite
+ * dt / gravity (nothing is launched). */
+int mm3dgs_propagate_imu(const float* pose_m1 /*[7], frame idx-1*/, const float* pose_m2 /*[7], frame idx-2*/,
+                         const float* imu6 /*[n,6]: angular velocity xyz (rad/s), linear acceleration xyz incl. gravity (m/s^2)*/, int n,
+                         const float* c2i /*16 floats, row-major camera->IMU*/, double dt_cam, double dt_imu, double gx, double gy, double gz,
+                         float* out_pose /*[7]*/, void* stream);
+
 /* ---- optional per-kernel timing (HIP events recorded on the caller's stream around each launch) ------------
  * Used by bench.py's roofline leg.  mm3dgs_profile_read() waits for the recorded events, returns the number of
  * (timed) launches and their summed duration since the previous read, and resets the counters. */
@@ -457,8 +470,9 @@ const char* mm3dgs_last_error(void);
    211: Mm3dgsSlamInputs.sh_dir (appended): native loops at an active SH degree > 0 with the world-origin (convert_SHs_python) and camera-centre
         (world_means = 1) viewing directions
    212: mm3dgs_slam_adam_project accepts an active SH degree 1-3 (needs Mm3dgsSlamGrads.d_f_rest and Mm3dgsMapAdam.rest_*; no struct changes):
-        the multi-GPU mapping window runs natively at an active SH degree */
-#define MM3DGS_ABI_VERSION 212
+        the multi-GPU mapping window runs natively at an active SH degree
+   213: mm3dgs_propagate_imu (the tracker's IMU pose prediction on the device; no struct changes) */
+#define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 
 #ifdef __cplusplus

@@ -18,7 +18,10 @@ _TUM = {
                  "force_isotropic": False, "use_rgb": False},
     "tracking": {"iters": 100, "use_gt_pose": False, "dynamics_model": "const_velocity", "use_imu_loss": False,
                  "imu_T_weight": 0.0, "imu_q_weight": 0.0, "use_depth_estimate_loss": False, "pearson_weight": 0.05,
-                 "position_lr": 0.001, "rotation_lr": 0.003},
+                 "position_lr": 0.001, "rotation_lr": 0.003,
+                 # dynamics_model imu: the start pose from mm3dgs_propagate_imu (one double-precision lane, no pose read-back) instead of
+                 # the float32 torch chain on the host; opt-in, the two differ in the last bits
+                 "imu_on_device": False},
     "mapping": {"iters": 150, "kf_every": 5, "niqe_kf": False, "niqe_window_size": 5, "kf_window_size": 25,
                 "covisibility_level": 1, "min_covisibility": 0.95, "kf_covisibility": 0.1, "do_BA": False,
                 "use_depth_estimate_loss": True, "pearson_weight": 0.05, "sh_degree": 0, "cam_t_lr": 0.001,

@@ -687,6 +687,17 @@ int mm3dgs_propagate_const_vel(const float* pose_m1, const float* pose_m2, float
   return check_launch("propagate_const_vel");
 }
 
+int mm3dgs_propagate_imu(const float* pose_m1, const float* pose_m2, const float* imu6, int n, const float* c2i, double dt_cam, double dt_imu,
+                         double gx, double gy, double gz, float* out_pose, void* stream) {
+  if (!pose_m1 || !pose_m2 || !c2i || !out_pose) return fail(-1, "propagate_imu: NULL argument");
+  if (n < 0) return fail(-2, "propagate_imu: n = %d < 0", n);
+  if (n > 0 && !imu6) return fail(-1, "propagate_imu: imu6 is NULL with n = %d samples", n);
+  if (!isfinite(dt_cam) || !isfinite(dt_imu) || dt_cam == 0.0) return fail(-2, "propagate_imu: dt_cam = %g (finite, not 0) / dt_imu = %g (finite)", dt_cam, dt_imu);
+  if (!isfinite(gx) || !isfinite(gy) || !isfinite(gz)) return fail(-2, "propagate_imu: gravity (%g, %g, %g) is not finite", gx, gy, gz);
+  launch_propagate_imu(pose_m1, pose_m2, imu6, n, c2i, dt_cam, dt_imu, gx, gy, gz, out_pose, (hipStream_t)stream);
+  return check_launch("propagate_imu");
+}
+
 int mm3dgs_prune_mask(int P, const float* opacity, const float* log_scales, const float* max_radii2D, float min_opacity, float max_scale,
                       float max_screen_size, uint8_t* keep, uint32_t* n_pruned_accum, void* stream) {
   if (P < 0) return fail(-1, "P < 0");

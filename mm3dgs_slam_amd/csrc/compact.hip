@@ -343,34 +343,41 @@ void launch_covisibility_ratio(int H, int W, const float* depth, const float* si
   hipLaunchKernelGGL(covisibility_ratio_kernel, dim3(nb), dim3(CB), 0, s, H, W, depth, sil, kf_pose, cur_pose, fx, fy, cx, cy, counts);
 }
 
-// ---- constant-velocity pose prediction (utils/pose_utils.py:203-216 propagate_const_vel; :352-383 get_camera_from_tensor /
-// get_tensor_from_camera): W' = (W1 W2^-1) W1 for the last two world->camera poses, back to (q, t).  One lane, double precision (the
-// tracker used to read the two poses back and do this on the host: a device drain at the head of every frame).  Same algebra as
-// pose_utils.propagate_const_vel_np: normalised quaternion -> R, closed-form rigid inverse, best-conditioned matrix -> quaternion branch.
-__global__ void propagate_const_vel_kernel(const float* __restrict__ pm1, const float* __restrict__ pm2, float* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double R1[3][3], R2[3][3], t1[3], t2[3];
-  const float* src[2] = {pm1, pm2};
-  for (int v = 0; v < 2; v++) {
-    double (*R)[3] = v == 0 ? R1 : R2;
-    double* t = v == 0 ? t1 : t2;
-    double w = src[v][0], x = src[v][1], y = src[v][2], z = src[v][3];
-    const double n = sqrt(w * w + x * x + y * y + z * z);
-    w /= n; x /= n; y /= n; z /= n;
-    R[0][0] = 1.0 - 2.0 * (y * y + z * z); R[0][1] = 2.0 * (x * y - w * z); R[0][2] = 2.0 * (x * z + w * y);
-    R[1][0] = 2.0 * (x * y + w * z); R[1][1] = 1.0 - 2.0 * (x * x + z * z); R[1][2] = 2.0 * (y * z - w * x);
-    R[2][0] = 2.0 * (x * z - w * y); R[2][1] = 2.0 * (y * z + w * x); R[2][2] = 1.0 - 2.0 * (x * x + y * y);
-    t[0] = src[v][4]; t[1] = src[v][5]; t[2] = src[v][6];
-  }
-  // step = W1 W2^-1: rotation A = R1 R2^T, translation a = t1 - A t2;  W' = step W1: rotation A R1, translation A t1 + a
-  double A[3][3], a[3], m[3][3], tn[3];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) A[i][j] = R1[i][0] * R2[j][0] + R1[i][1] * R2[j][1] + R1[i][2] * R2[j][2];
-  for (int i = 0; i < 3; i++) a[i] = t1[i] - (A[i][0] * t2[0] + A[i][1] * t2[1] + A[i][2] * t2[2]);
+// ---- rigid 4x4 algebra of the one-lane pose kernels below, in double: [R | t; 0 1] as (R, t) --------------------------------------------
+struct Rigid { double R[3][3], t[3]; };
+// world->camera 7-vector (qw,qx,qy,qz,tx,ty,tz): normalised quaternion -> R (utils/pose_utils.py:240-271,352-368)
+__device__ inline Rigid rigid_from_pose(const float* __restrict__ p) {
+  Rigid o;
+  double w = p[0], x = p[1], y = p[2], z = p[3];
+  const double n = sqrt(w * w + x * x + y * y + z * z);
+  w /= n; x /= n; y /= n; z /= n;
+  o.R[0][0] = 1.0 - 2.0 * (y * y + z * z); o.R[0][1] = 2.0 * (x * y - w * z); o.R[0][2] = 2.0 * (x * z + w * y);
+  o.R[1][0] = 2.0 * (x * y + w * z); o.R[1][1] = 1.0 - 2.0 * (x * x + z * z); o.R[1][2] = 2.0 * (y * z - w * x);
+  o.R[2][0] = 2.0 * (x * z - w * y); o.R[2][1] = 2.0 * (y * z + w * x); o.R[2][2] = 1.0 - 2.0 * (x * x + y * y);
+  o.t[0] = p[4]; o.t[1] = p[5]; o.t[2] = p[6];
+  return o;
+}
+// closed-form inverse [R^T | -R^T t]
+__device__ inline Rigid rigid_inverse(const Rigid& a) {
+  Rigid o;
   for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) m[i][j] = A[i][0] * R1[0][j] + A[i][1] * R1[1][j] + A[i][2] * R1[2][j];
-    tn[i] = A[i][0] * t1[0] + A[i][1] * t1[1] + A[i][2] * t1[2] + a[i];
+    for (int j = 0; j < 3; j++) o.R[i][j] = a.R[j][i];
+    o.t[i] = -(a.R[0][i] * a.t[0] + a.R[1][i] * a.t[1] + a.R[2][i] * a.t[2]);
   }
+  return o;
+}
+// a b = [Ra Rb | Ra tb + ta]
+__device__ inline Rigid rigid_mul(const Rigid& a, const Rigid& b) {
+  Rigid o;
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) o.R[i][j] = a.R[i][0] * b.R[0][j] + a.R[i][1] * b.R[1][j] + a.R[i][2] * b.R[2][j];
+    o.t[i] = a.R[i][0] * b.t[0] + a.R[i][1] * b.t[1] + a.R[i][2] * b.t[2] + a.t[i];
+  }
+  return o;
+}
+// (m, t) -> 7-vector, rounded to float32 at the store: the best-conditioned of the four matrix -> quaternion formulas (the largest of
+// |w|, |x|, |y|, |z|; utils/pose_utils.py:285-349,371-383), first maximum like argmax
+__device__ inline void store_pose(const double (*m)[3], const double* t, float* __restrict__ out) {
   const double four_sq[4] = {1.0 + m[0][0] + m[1][1] + m[2][2], 1.0 + m[0][0] - m[1][1] - m[2][2], 1.0 - m[0][0] + m[1][1] - m[2][2],
                              1.0 - m[0][0] - m[1][1] + m[2][2]};
   const double cand[4][4] = {{four_sq[0], m[2][1] - m[1][2], m[0][2] - m[2][0], m[1][0] - m[0][1]},
@@ -385,8 +392,72 @@ __global__ void propagate_const_vel_kernel(const float* __restrict__ pm1, const 
   }
   const double den = 2.0 * fmax(mag, 0.1);
   for (int k = 0; k < 4; k++) out[k] = (float)(cand[best][k] / den);
-  for (int k = 0; k < 3; k++) out[4 + k] = (float)tn[k];
+  for (int k = 0; k < 3; k++) out[4 + k] = (float)t[k];
+}
+
+// ---- constant-velocity pose prediction (utils/pose_utils.py:203-216 propagate_const_vel; :352-383 get_camera_from_tensor /
+// get_tensor_from_camera): W' = (W1 W2^-1) W1 for the last two world->camera poses, back to (q, t).  One lane, double precision (the
+// tracker used to read the two poses back and do this on the host: a device drain at the head of every frame).  Same algebra as
+// pose_utils.propagate_const_vel_np: normalised quaternion -> R, closed-form rigid inverse, best-conditioned matrix -> quaternion branch.
+__global__ void propagate_const_vel_kernel(const float* __restrict__ pm1, const float* __restrict__ pm2, float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const Rigid W1 = rigid_from_pose(pm1), W2 = rigid_from_pose(pm2);
+  const double (*R1)[3] = W1.R, (*R2)[3] = W2.R;
+  const double *t1 = W1.t, *t2 = W2.t;
+  // step = W1 W2^-1: rotation A = R1 R2^T, translation a = t1 - A t2;  W' = step W1: rotation A R1, translation A t1 + a
+  double A[3][3], a[3], m[3][3], tn[3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) A[i][j] = R1[i][0] * R2[j][0] + R1[i][1] * R2[j][1] + R1[i][2] * R2[j][2];
+  for (int i = 0; i < 3; i++) a[i] = t1[i] - (A[i][0] * t2[0] + A[i][1] * t2[1] + A[i][2] * t2[2]);
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) m[i][j] = A[i][0] * R1[0][j] + A[i][1] * R1[1][j] + A[i][2] * R1[2][j];
+    tn[i] = A[i][0] * t1[0] + A[i][1] * t1[1] + A[i][2] * t1[2] + a[i];
+  }
+  store_pose(m, tn, out);
 }
 void launch_propagate_const_vel(const float* pm1, const float* pm2, float* out, hipStream_t s) {
   hipLaunchKernelGGL(propagate_const_vel_kernel, dim3(1), dim3(64), 0, s, pm1, pm2, out);
+}
+
+// ---- IMU dead-reckoning of the tracker's start pose (utils/pose_utils.py:148-200 propagate_imu, :43-99 euler_matrix 'sxyz'): the IMU pose
+// i2w = W1^-1 c2i^-1 of frame idx-1 is stepped through the n samples of the interval -- velocity from the last two poses (constant over the
+// samples, as in the reference), gravity removed in the IMU frame, delta = [Rz Ry Rx (omega dt) | v dt + a dt^2 / 2] -- and W' = (i2w c2i)^-1
+// goes back to (q, t).  One lane, double precision, same algebra and operation order as pose_utils.propagate_imu_np; the tracker's host path
+// read the pose back (a device drain at the head of every frame) and ran this as ~100 one-element float32 torch operators.  The sample
+// rows are read only (the reference subtracts gravity from the caller's rows in place; every row is used once, so the pose is the same).
+__global__ void propagate_imu_kernel(const float* __restrict__ pm1, const float* __restrict__ pm2, const float* __restrict__ imu6, int n,
+                                     const float* __restrict__ c2i, double dt_cam, double dt_imu, double gx, double gy, double gz,
+                                     float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  Rigid C;
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) C.R[i][j] = c2i[4 * i + j];
+    C.t[i] = c2i[4 * i + 3];
+  }
+  const Rigid Ci = rigid_inverse(C);
+  const Rigid i2w1 = rigid_mul(rigid_inverse(rigid_from_pose(pm1)), Ci);
+  const Rigid i2w2 = rigid_mul(rigid_inverse(rigid_from_pose(pm2)), Ci);
+  const Rigid rel = rigid_mul(rigid_inverse(i2w2), i2w1);      // i(idx-1) -> i(idx-2)
+  const double vel[3] = {rel.t[0] / dt_cam, rel.t[1] / dt_cam, rel.t[2] / dt_cam};
+  Rigid X = i2w1;
+  for (int s = 0; s < n; s++) {
+    const float* __restrict__ row = imu6 + (size_t)s * 6;      // angular velocity xyz, linear acceleration xyz (gravity included)
+    Rigid D;
+    for (int k = 0; k < 3; k++) {
+      const double acc = (double)row[3 + k] - (X.R[0][k] * gx + X.R[1][k] * gy + X.R[2][k] * gz);      // a - R(i2w)^T g
+      D.t[k] = vel[k] * dt_imu + 0.5 * acc * dt_imu * dt_imu;
+    }
+    const double ai = (double)row[0] * dt_imu, aj = (double)row[1] * dt_imu, ak = (double)row[2] * dt_imu;
+    const double si = sin(ai), sj = sin(aj), sk = sin(ak), ci = cos(ai), cj = cos(aj), ck = cos(ak);
+    D.R[0][0] = cj * ck; D.R[0][1] = sj * si * ck - ci * sk; D.R[0][2] = sj * ci * ck + si * sk;
+    D.R[1][0] = cj * sk; D.R[1][1] = sj * si * sk + ci * ck; D.R[1][2] = sj * ci * sk - si * ck;
+    D.R[2][0] = -sj;     D.R[2][1] = cj * si;                D.R[2][2] = cj * ci;
+    X = rigid_mul(X, D);
+  }
+  const Rigid W = rigid_inverse(rigid_mul(X, C));
+  store_pose(W.R, W.t, out);
+}
+void launch_propagate_imu(const float* pm1, const float* pm2, const float* imu6, int n, const float* c2i, double dt_cam, double dt_imu,
+                          double gx, double gy, double gz, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(propagate_imu_kernel, dim3(1), dim3(64), 0, s, pm1, pm2, imu6, n, c2i, dt_cam, dt_imu, gx, gy, gz, out);
 }

@@ -113,3 +113,6 @@ void launch_seed_gaussians(int H, int W, const float* color, const float* depth,
 void launch_covisibility_ratio(int H, int W, const float* depth, const float* sil, const float* kf_pose, const float* cur_pose, float fx, float fy,
                                float cx, float cy, uint32_t* counts, hipStream_t s);
 void launch_propagate_const_vel(const float* pm1, const float* pm2, float* out, hipStream_t s);
+// imu6: [n,6] rows (angular velocity xyz, linear acceleration xyz incl. gravity), read only; c2i: 16 floats, row-major camera->IMU
+void launch_propagate_imu(const float* pm1, const float* pm2, const float* imu6, int n, const float* c2i, double dt_cam, double dt_imu,
+                          double gx, double gy, double gz, float* out, hipStream_t s);

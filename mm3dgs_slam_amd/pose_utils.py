@@ -4,7 +4,8 @@ Behavioural mirror of the reference's ``utils/pose_utils.py`` (names and argumen
 same): ``quad2rotation`` (:240-271), ``rotation2quad`` (:285-349), ``get_camera_from_tensor`` (:352-368),
 ``get_tensor_from_camera`` (:371-383), ``quadmultiply`` (:219-237), ``propagate_const_vel`` (:203-216),
 ``euler_matrix`` (:43-103, static 'sxyz'-family axes) and ``propagate_imu`` (:148-200).  Unlike the reference nothing
-here hard-codes ``.cuda()``: tensors stay on the device of their inputs.
+here hard-codes ``.cuda()``: tensors stay on the device of their inputs.  ``propagate_const_vel_np`` / ``propagate_imu_np`` restate
+the two pose predictions in float64 numpy: the algebra of the library's one-lane kernels, and what those are held to.
 """
 from __future__ import annotations
 
@@ -133,6 +134,20 @@ def apply_rigid(pts: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
     return pts[:, 0:1] * R[:, 0] + pts[:, 1:2] * R[:, 1] + pts[:, 2:3] * R[:, 2] + t
 
 
+def _rotation2quad_np(m):
+    """3x3 -> (w,x,y,z) in float64 numpy: ``rotation2quad``'s best-conditioned branch, first maximum like argmax."""
+    import numpy as np
+    four_sq = np.array([1 + m[0, 0] + m[1, 1] + m[2, 2], 1 + m[0, 0] - m[1, 1] - m[2, 2], 1 - m[0, 0] + m[1, 1] - m[2, 2],
+                        1 - m[0, 0] - m[1, 1] + m[2, 2]])
+    mag = np.sqrt(np.clip(four_sq, 0.0, None))
+    cand = np.array([[four_sq[0], m[2, 1] - m[1, 2], m[0, 2] - m[2, 0], m[1, 0] - m[0, 1]],
+                     [m[2, 1] - m[1, 2], four_sq[1], m[1, 0] + m[0, 1], m[0, 2] + m[2, 0]],
+                     [m[0, 2] - m[2, 0], m[1, 0] + m[0, 1], four_sq[2], m[1, 2] + m[2, 1]],
+                     [m[1, 0] - m[0, 1], m[2, 0] + m[0, 2], m[2, 1] + m[1, 2], four_sq[3]]])
+    best = int(np.argmax(mag))
+    return cand[best] / (2.0 * max(mag[best], 0.1))
+
+
 def propagate_const_vel_np(camm1, camm2):
     """``propagate_const_vel`` on the host in float64 numpy (7 floats in, 7 out): the per-frame pose prediction costs ~1 ms as
     a chain of ~100 tiny torch operators, ~30 us this way.  Same algebra (normalised quaternion -> R, step = W1 W2^-1 with
@@ -155,15 +170,51 @@ def propagate_const_vel_np(camm1, camm2):
     W2i[:3, :3] = W2[:3, :3].T
     W2i[:3, 3] = -W2[:3, :3].T @ W2[:3, 3]
     Wn = (W1 @ W2i) @ W1
-    m = Wn[:3, :3]
-    four_sq = np.array([1 + m[0, 0] + m[1, 1] + m[2, 2], 1 + m[0, 0] - m[1, 1] - m[2, 2], 1 - m[0, 0] + m[1, 1] - m[2, 2],
-                        1 - m[0, 0] - m[1, 1] + m[2, 2]])
-    mag = np.sqrt(np.clip(four_sq, 0.0, None))
-    cand = np.array([[four_sq[0], m[2, 1] - m[1, 2], m[0, 2] - m[2, 0], m[1, 0] - m[0, 1]],
-                     [m[2, 1] - m[1, 2], four_sq[1], m[1, 0] + m[0, 1], m[0, 2] + m[2, 0]],
-                     [m[0, 2] - m[2, 0], m[1, 0] + m[0, 1], four_sq[2], m[1, 2] + m[2, 1]],
-                     [m[1, 0] - m[0, 1], m[2, 0] + m[0, 2], m[2, 1] + m[1, 2], four_sq[3]]])
-    best = int(np.argmax(mag))
-    q = cand[best] / (2.0 * max(mag[best], 0.1))
-    return np.concatenate([q, Wn[:3, 3]])
+    return np.concatenate([_rotation2quad_np(Wn[:3, :3]), Wn[:3, 3]])
 
+
+def propagate_imu_np(camm1, camm2, imu6, c2i, dt_cam, dt_imu, gravity=GRAVITY):
+    """``propagate_imu`` on the host in float64 numpy: 7-vectors of frames idx-1 and idx-2, ``imu6`` = [n,6] rows (angular velocity
+    xyz, linear acceleration xyz with gravity: columns 13:16 and 25:28 of the reference's sample rows), ``c2i`` a rigid 4x4; 7 floats
+    out.  The algebra of ``mm3dgs_propagate_imu``, in its order: normalised quaternion -> R, closed-form rigid inverses,
+    i2w = W^-1 c2i^-1, velocity (i2w2^-1 i2w1)[:3,3] / dt_cam held constant over the samples, per sample acc = a - R(i2w)^T g,
+    delta = [Rz Ry Rx (omega dt) | v dt + acc dt^2 / 2], i2w <- i2w delta; W' = (i2w c2i)^-1 through the best-conditioned
+    matrix -> quaternion branch.  ``imu6`` is not modified (the reference subtracts gravity from its rows in place)."""
+    import numpy as np
+
+    def to_mat(p):
+        p = np.asarray(p, dtype=np.float64)
+        w, x, y, z = p[:4] / np.sqrt((p[:4] * p[:4]).sum())
+        M = np.eye(4)
+        M[:3, :3] = [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+        M[:3, 3] = p[4:7]
+        return M
+
+    def inv(M):
+        out = np.eye(4)
+        out[:3, :3] = M[:3, :3].T
+        out[:3, 3] = -(M[:3, :3].T @ M[:3, 3])
+        return out
+
+    C = np.eye(4)
+    C[:3, :] = np.asarray(c2i, dtype=np.float64).reshape(4, 4)[:3, :]
+    Ci = inv(C)
+    i2w1, i2w2 = inv(to_mat(camm1)) @ Ci, inv(to_mat(camm2)) @ Ci
+    vel = (inv(i2w2) @ i2w1)[:3, 3] / float(dt_cam)
+    g = np.asarray(gravity, dtype=np.float64)
+    dt = float(dt_imu)
+    X = i2w1
+    for row in np.asarray(imu6, dtype=np.float64).reshape(-1, 6):
+        acc = row[3:6] - X[:3, :3].T @ g
+        ai, aj, ak = row[0:3] * dt
+        si, sj, sk, ci, cj, ck = math.sin(ai), math.sin(aj), math.sin(ak), math.cos(ai), math.cos(aj), math.cos(ak)
+        D = np.eye(4)
+        D[:3, :3] = [[cj * ck, sj * si * ck - ci * sk, sj * ci * ck + si * sk],
+                     [cj * sk, sj * si * sk + ci * ck, sj * ci * sk - si * ck],
+                     [-sj, cj * si, cj * ci]]
+        D[:3, 3] = vel * dt + 0.5 * acc * dt * dt
+        X = X @ D
+    Wn = inv(X @ C)
+    return np.concatenate([_rotation2quad_np(Wn[:3, :3]), Wn[:3, 3]])

@@ -1,7 +1,8 @@
 """Per-frame camera pose optimisation (reference ``slam/tracker.py:12-266``).
 
 ``Tracker.run_frame(idx, gt_color, gt_depth, est_depth, imu_meas)`` keeps the reference's behaviour: pose initialised
-from the previous estimate, the constant-velocity model (``tracker.py:203-206``) or IMU propagation (``:208-228``);
+from the previous estimate, the constant-velocity model (``tracker.py:203-206``) or IMU propagation (``:208-228``; with
+``tracking.imu_on_device`` in one device launch from poses that stay on the device, like the constant-velocity model);
 Adam on translation (``tracking.position_lr``) and quaternion (``tracking.rotation_lr``) (``:233-246``);
 ``tracking.iters`` x {render -> loss -> backward -> step}; loss = masked mean-L1 over ``silhouette > 0.99`` plus the
 optional Pearson depth term and IMU relative-pose term (``:104-155``), or the "splatam" sum-L1 variant (``:110-126``).
@@ -18,7 +19,7 @@ import time
 import torch
 
 from .loss_utils import pearson_loss, rel_pose_loss
-from .pose_utils import propagate_const_vel, propagate_const_vel_np, propagate_imu
+from .pose_utils import GRAVITY, propagate_const_vel, propagate_const_vel_np, propagate_imu
 
 
 class _FrozenMap:
@@ -56,6 +57,7 @@ class Tracker:
         self.keep_best_candidate = keep_best_candidate
         self.tracking_time_sum = 0.0
         self.tracking_iter_count = 0
+        self._c2i_dev = None      # tracking.imu_on_device: the camera->IMU extrinsic, uploaded once
 
     def _loss(self, result, q, T, initial_pose, gt_color, gt_depth, est_depth):
         cfg, trk = self.cfg, self.cfg["tracking"]
@@ -127,10 +129,13 @@ class Tracker:
                     cam = torch.from_numpy(propagate_const_vel_np(both[0], both[1])).float()
         elif model == "imu":
             assert imu_meas is not None, "IMU measurements must be provided"
+            dt_cam = (self.tstamps[idx - 1] - self.tstamps[idx - 2]) if idx - 2 >= 0 else 1.0      # (zero velocity at the start)
+            if self.cfg["tracking"].get("imu_on_device", False) and poses[idx - 1].is_cuda:
+                # one single-lane launch (double precision) from poses that never leave the device, like the constant-velocity model
+                return self._predict_imu_device(poses[idx - 1], poses[idx - 2] if idx - 2 >= 0 else poses[idx - 1], imu_meas, dt_cam, 1 / 100.0)
             # 4x4 algebra over a handful of samples: on the host (one 7-float copy; ~100 one-element device kernels otherwise)
             p1 = poses[idx - 1].detach().cpu()
             p2 = poses[idx - 2].detach().cpu() if idx - 2 >= 0 else p1
-            dt_cam = (self.tstamps[idx - 1] - self.tstamps[idx - 2]) if idx - 2 >= 0 else 1.0      # (zero velocity at the start)
             cam = propagate_imu(p1, p2, imu_meas.cpu(), self.tf["c2i"].cpu(), dt_cam, 1 / 100.0)
         elif model:
             raise ValueError(f"Unknown dynamics model {self.dyn_model}")
@@ -147,6 +152,18 @@ class Tracker:
         _lib.check(_lib.load().mm3dgs_propagate_const_vel(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr()), _stream()))
         return out
 
+    def _predict_imu_device(self, pm1, pm2, imu_meas, dt_cam, dt_imu):
+        """The samples' six used columns go up through a fresh pinned block (torch's caching host allocator: the copy neither waits for the
+        device nor reuses memory an earlier copy may still be reading); the extrinsic is uploaded once.  ``imu_meas`` is not modified."""
+        dev = pm1.device
+        imu6 = torch.cat([imu_meas[:, 13:16], imu_meas[:, 25:28]], 1).float().contiguous()
+        if not imu6.is_cuda and imu6.shape[0] > 0:
+            imu6 = imu6.pin_memory().to(dev, non_blocking=True)
+        c2i = getattr(self, "_c2i_dev", None)
+        if c2i is None or c2i.device != dev:
+            c2i = self._c2i_dev = self.tf["c2i"].detach().float().contiguous().to(dev)
+        return propagate_imu_device(pm1, pm2, imu6, c2i, dt_cam, dt_imu)
+
     def run_frame(self, idx, gt_color, gt_depth=None, est_depth=None, imu_meas=None):
         cam = self.predict_pose(idx, imu_meas).to(self.cfg["device"])
         camera_tensor_T = cam[-3:].clone().requires_grad_()
@@ -159,3 +176,24 @@ class Tracker:
         with torch.no_grad():
             self.estimate_pose_list[idx] = torch.cat([camera_tensor_q, camera_tensor_T]).clone().detach()
         return image
+
+
+def propagate_imu_device(pm1, pm2, imu6, c2i, dt_cam, dt_imu, gravity=GRAVITY):
+    """mm3dgs_propagate_imu: utils/pose_utils.py:148-200 on the device (same algebra as pose_utils.propagate_imu_np, float64).  All four
+    tensors on the device: two 7-vectors, the [n,6] float32 sample block (angular velocity, linear acceleration; read only) and the 4x4
+    camera->IMU extrinsic.  One launch on the current stream, no synchronisation; returns the device 7-vector."""
+    import ctypes as C
+    from . import _lib
+    from .rasterizer import _stream
+    a, b = pm1.detach().float().contiguous(), pm2.detach().float().contiguous()
+    imu6, c2i = imu6.float().contiguous(), c2i.float().contiguous()
+    n = int(imu6.shape[0])
+    if a.numel() != 7 or b.numel() != 7 or c2i.numel() != 16 or imu6.dim() != 2 or imu6.shape[1] != 6:
+        raise ValueError(f"propagate_imu_device: poses [7], imu6 [n,6], c2i [4,4]; got {tuple(a.shape)}, {tuple(b.shape)}, {tuple(imu6.shape)}, {tuple(c2i.shape)}")
+    if not (a.is_cuda and b.is_cuda and c2i.is_cuda and (n == 0 or imu6.is_cuda)):
+        raise RuntimeError("propagate_imu_device needs device tensors (the host path is pose_utils.propagate_imu)")
+    out = torch.empty(7, dtype=torch.float32, device=a.device)
+    gx, gy, gz = (float(v) for v in gravity)
+    _lib.check(_lib.load().mm3dgs_propagate_imu(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(imu6.data_ptr() if n > 0 else None), n,
+                                                C.c_void_p(c2i.data_ptr()), float(dt_cam), float(dt_imu), gx, gy, gz, C.c_void_p(out.data_ptr()), _stream()))
+    return out
