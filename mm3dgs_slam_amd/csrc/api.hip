@@ -521,7 +521,7 @@ int mm3dgs_slam_track(int n_iter, const Mm3dgsCamera* cam, int P, const Mm3dgsSl
   // pose row per tile: no gradient records, no per-tile combine, no backward-projection launch (three launches per iteration).  The shipped mode only
   // (means pre-transformed: the world-frame mode's pose gradient also runs through the covariance rotation); MM3DGS_NO_POSE_CHAIN keeps the record path
   // (read per call: tests compare both in one process)
-  const bool pose_chain = composite_has_pose_chain() && !in->world_means && !sh && backward_scratch && !env_flag("MM3DGS_NO_POSE_CHAIN", 0) &&
+  const bool pose_chain = !in->world_means && !sh && backward_scratch && !env_flag("MM3DGS_NO_POSE_CHAIN", 0) &&
                           bwd_bytes_impl(P, N_capacity) >= (size_t)tiles_x(cam->image_width) * tiles_y(cam->image_height) * 32 * sizeof(float);
   if (n_iter > 0) slam_refresh_tile_order(cam, image_state, fwd_flags, stream);
   for (int it = 0; it < n_iter; it++) {

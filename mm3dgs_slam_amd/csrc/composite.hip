@@ -14,10 +14,11 @@
 // prefetched into registers while the current one is evaluated).  In the SLAM path the same workgroup first sorts its
 // tile (sort_composite_fwd_kernel).
 //
-// Backward: the per-lane gradient terms of one splat are reduced over the 16-lane row with DPP butterflies (generic:
-// 6 + C values, halving; SLAM modes: separable moments, 10 / 7 floats) and the row -- the only writer of that (block, splat)
-// record -- stores it with one plain store.  preprocess_bwd later sums a Gaussian's records (dense, contiguous) in a
-// fixed order, which makes the whole backward deterministic.
+// Backward: a row is the only writer of its (block, splat) records.  The SLAM modes (10 / 7 floats per record) and the generic
+// three-channel instance build them in two phases per sub-chunk of list entries (below); the other generic channel counts reduce
+// the 6 + C per-lane gradient terms of one splat over the 16-lane row with halving DPP butterflies and one plain store.  The
+// workgroup then sums a (tile, splat) pair's block records and preprocess_bwd a Gaussian's pair records (dense, contiguous), both
+// in a fixed order, which makes the whole backward deterministic.
 #include <type_traits>
 #include "mm3dgs_common.h"
 #include "sort_tile.h"
@@ -268,173 +269,6 @@ struct WaveReduce {
   }
 };
 
-#define ROW_ROR12 0x12C
-
-// Separable reduction of the SLAM modes over ONE 16-lane row = one 4x4 pixel block (lane bits 0,1 = x, bits 2,3 = y).
-// The geometric moments factor: sum u dx^a dy^b = sum_y dy^b (sum_x u dx^a).  The x direction is reduced first on 8 values
-//   a[] = { u, u dx, u dx^2, c0, c1, c2, c3, u }      (c* = colour / depth terms, plain sums; u twice on purpose)
-// with a halving butterfly (8 -> 4 -> 2 registers); register i of lane (b0, b1) then holds row-sum idx = i + 2 b1 + 4 b0.
-// The y direction works on those two registers and their dy-weighted copies Y_i = X_i * {dy, dy, dy^2} on the lanes
-// holding {R0, R1, R0'} (-> My, Mxy, Myy), halved on lane bits 2 and 3.  Result: lanes with b3 = 0 hold the X totals
-// (M0 Mx Mxx c0 c1 c2 c3), lanes with b3 = 1 the Y totals, value index idx = b2 + 2 b1 + 4 b0.
-template <bool RGB>
-struct SepReduce {
-  // record position of the value lane q (0..15 within its row) ends up with (-1: nothing to store)
-  //   mapping (RGB): [M0 Mx Mxx c0 | c1 c2 c3 My | Mxy Myy];   tracking (!RGB): [M0 Mx Mxx c3 | My Mxy Myy]
-  __device__ static __forceinline__ int slot(int q) {
-    const int b0 = q & 1, b1 = (q >> 1) & 1, b2 = (q >> 2) & 1, b3 = (q >> 3) & 1;
-    const int idx = b2 + 2 * b1 + 4 * b0;
-    if (!b3) {
-      if (idx <= 2) return idx;
-      if (RGB) return idx <= 6 ? idx : -1;
-      return idx == 6 ? 3 : -1;
-    }
-    const int base = RGB ? 7 : 4;
-    if (idx == 0) return base;       // My  = sum dy R0
-    if (idx == 1) return base + 1;   // Mxy = sum dy R1
-    if (idx == 7) return base + 2;   // Myy = sum dy^2 R0'
-    return -1;
-  }
-  // per-lane selectors of the dy weights: Y0 = X0 * dy * m0,  Y1 = X1 * dy * (m1a + m1b * dy)
-  __device__ static __forceinline__ void ymult(int q, float& m0, float& m1a, float& m1b) {
-    const int b0 = q & 1, b1 = (q >> 1) & 1;
-    m0 = (!b0 && !b1) ? 1.f : 0.f;    // register 0 holds idx 0 (R0) there
-    m1a = (!b0 && !b1) ? 1.f : 0.f;   // register 1 holds idx 1 (R1) there
-    m1b = (b0 && b1) ? 1.f : 0.f;     // register 1 holds idx 7 (R0') there
-  }
-  __device__ static __forceinline__ float run(float u, float dx, float dy, float c0, float c1, float c2, float c3, int lane, float m0,
-                                              float m1a, float m1b) {
-#pragma clang fp contract(off)
-    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-    const float udx = u * dx, udxx = udx * dx;
-    // bit 0: pairs (i, i + 4)
-    float l1[4];
-    {
-      const float s0 = u + dpp_all<QP_XOR1>(u), s1 = udx + dpp_all<QP_XOR1>(udx), s2 = udxx + dpp_all<QP_XOR1>(udxx);
-      const float s6 = c3 + dpp_all<QP_XOR1>(c3);
-      if (RGB) {
-        const float s3 = c0 + dpp_all<QP_XOR1>(c0), s4 = c1 + dpp_all<QP_XOR1>(c1), s5 = c2 + dpp_all<QP_XOR1>(c2);
-        l1[0] = b0 ? s4 : s0; l1[1] = b0 ? s5 : s1;
-        l1[3] = b0 ? s0 : s3;     // value 7 is u again (s0), value 3 is c0
-      } else {
-        l1[0] = s0; l1[1] = s1;   // odd lanes carry junk there: never stored (slot() = -1)
-        l1[3] = s0;               // no c0: keep u on both parities (even lanes: junk value 3, never stored)
-      }
-      l1[2] = b0 ? s6 : s2;
-    }
-    // bit 1: pairs (i, i + 2)
-    float X0, X1;
-    {
-      const float t0 = l1[0] + dpp_all<QP_XOR2>(l1[0]), t1 = l1[1] + dpp_all<QP_XOR2>(l1[1]);
-      const float t2 = l1[2] + dpp_all<QP_XOR2>(l1[2]), t3 = l1[3] + dpp_all<QP_XOR2>(l1[3]);
-      X0 = b1 ? t2 : t0;
-      X1 = b1 ? t3 : t1;
-    }
-    // y direction: dy-weighted copies, then bit 2 (partner 4 lanes away: row_ror:n hands lane i the value of lane i - n,
-    // measured with tools/ubench/dpp_dir.hip) and bit 3 (partner 8 lanes away)
-    const float Y0 = X0 * (dy * m0), Y1 = X1 * (dy * (m1a + m1b * dy));
-    const float xa = X0 + dpp_all<ROW_ROR12>(X0), xb = X1 + dpp_all<ROW_ROR4>(X1);
-    const float ya = Y0 + dpp_all<ROW_ROR12>(Y0), yb = Y1 + dpp_all<ROW_ROR4>(Y1);
-    const float X = b2 ? xb : xa, Y = b2 ? yb : ya;
-    const float tX = X + dpp_all<ROW_ROR8>(X), tY = Y + dpp_all<ROW_ROR8>(Y);
-    return b3 ? tY : tX;
-  }
-};
-
-// Round 3: the same separable reduction with the Y direction FIRST and its halving steps done by bank-masked DPP adds.  A DPP bank =
-// four consecutive lanes = one pixel row of the block (lane bits 2, 3 = y): `v_add_f32_dpp ... bank_mask` writes only the lanes of the
-// selected pixel rows, so "lanes with y even keep value i, lanes with y odd keep value i + 4" is two masked adds into one register
-// instead of two full adds and a select (the halving on lane bits 0, 1 needs the selects: a mask cannot tell the lanes of a bank apart).
-//   Y stage on 8 (mapping) / 4 (tracking) values  { u, u dy, u dy^2, c0, c1, c2, cz, u }  /  { u, u dy, u dy^2, cz }:
-//     partner row y ^ 1 (row_ror:12 = lane + 4 for the even rows, row_ror:4 = lane - 4 for the odd ones), then y ^ 2 (row_ror:8);
-//     afterwards pixel row y holds the column sums (over y) of two (one) of the values.
-//   X stage: up to three x-weighted copies per row ( 1 | dx | dx^2 ), full butterfly over the four lanes of the bank (quad_perm).
-// 27 (mapping) / 18 (tracking) instructions per (row, splat) step instead of 33 / 27.  The masked adds are inline assembly (the compiler's
-// DPP combiner does not form them); `s_nop 1` covers the VALU-write -> DPP-read hazard at the head of the block (2 wait states = TWO
-// instructions between the write and the DPP read); inside the mapping block every register is DPP-read at least three instructions
-// after its last write, the shorter tracking block needs one `s_nop 0` (r0 / r1 had only one instruction between).
-// Summation order differs from SepReduce in the last bit only.
-template <bool RGB>
-struct SepReduce2 {
-  // record position of the value lane q ends up with (-1: nothing to store); layouts as SepReduce
-  __device__ static __forceinline__ int slot(int q) {
-    const int x = q & 3, y = q >> 2;
-    if (RGB) {
-      // row 0: Mx My Mxy | row 1: c1 c2 - | row 2: Myy c0 - | row 3: cz M0 Mxx      ([M0 Mx Mxx c0 | c1 c2 cz My | Mxy Myy])
-      const int t[4][4] = {{1, 7, 8, -1}, {4, 5, -1, -1}, {9, 3, -1, -1}, {6, 0, 2, -1}};
-      return t[y][x];
-    }
-    // row 0: M0 Mx Mxx | row 1: Myy | row 2: My Mxy | row 3: cz                     ([M0 Mx Mxx cz | My Mxy Myy])
-    const int t[4][4] = {{0, 1, 2, -1}, {6, -1, -1, -1}, {4, 5, -1, -1}, {3, -1, -1, -1}};
-    return t[y][x];
-  }
-  __device__ static __forceinline__ float run(float u, float dx, float dy, float c0, float c1, float c2, float cz, int lane) {
-#pragma clang fp contract(off)
-    const int x = lane & 3, y = (lane >> 2) & 3;
-    const float udy = u * dy, udyy = udy * dy;
-    float t0, t1, t2;
-    if (RGB) {
-      float r0, r1, r2, r3, s0, s1;
-      asm volatile(
-          "s_nop 1\n\t"
-          "v_add_f32_dpp %0, %6, %6 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"     // rows 0, 2: u
-          "v_add_f32_dpp %1, %7, %7 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"     //            u dy
-          "v_add_f32_dpp %2, %8, %8 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"     //            u dy^2
-          "v_add_f32_dpp %3, %9, %9 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"     //            c0
-          "v_add_f32_dpp %0, %10, %10 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"    // rows 1, 3: c1
-          "v_add_f32_dpp %1, %11, %11 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"    //            c2
-          "v_add_f32_dpp %2, %12, %12 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"    //            cz
-          "v_add_f32_dpp %3, %6, %6 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"      //            u (again)
-          "v_add_f32_dpp %4, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"      // rows 0, 1 keep r0, r1
-          "v_add_f32_dpp %5, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
-          "v_add_f32_dpp %4, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"      // rows 2, 3 keep r2, r3
-          "v_add_f32_dpp %5, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-          : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(s0), "=&v"(s1)
-          : "v"(u), "v"(udy), "v"(udyy), "v"(c0), "v"(c1), "v"(c2), "v"(cz));
-      // row 0: s0 = U, s1 = U1 | row 1: c1, c2 | row 2: U2, c0 | row 3: cz, U
-      const float w0 = y == 0 ? dx : 1.f;
-      const float w2 = dx * (y == 0 ? 1.f : dx);
-      t0 = s0 * w0;       // U dx | c1 | U2 | cz
-      t1 = s1;            // U1   | c2 | c0 | U
-      t2 = s1 * w2;       // U1 dx | -  | -  | U dx^2
-    } else {
-      float r0, r1, sy;
-      asm volatile(
-          "s_nop 1\n\t"
-          "v_add_f32_dpp %0, %3, %3 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"     // rows 0, 2: u
-          "v_add_f32_dpp %1, %4, %4 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"     //            u dy
-          "v_add_f32_dpp %0, %5, %5 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"      // rows 1, 3: u dy^2
-          "v_add_f32_dpp %1, %6, %6 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"      //            cz
-          "s_nop 0\n\t"       // r0's second write is TWO instructions back only with this (a DPP read needs 2 wait states = 2 intervening instructions after a VALU write; the hazard recognizer does not see inside inline asm)
-          "v_add_f32_dpp %2, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"      // rows 0, 1 keep r0: U | U2
-          "v_add_f32_dpp %2, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"      // rows 2, 3 keep r1: U1 | cz
-          : "=&v"(r0), "=&v"(r1), "=&v"(sy)
-          : "v"(u), "v"(udy), "v"(udyy), "v"(cz));
-      t0 = sy;            // U | U2 | U1 | cz
-      t1 = sy * dx;       // U dx | - | U1 dx | -
-      t2 = t1 * dx;       // U dx^2 | - | - | -
-    }
-    // X stage: full butterfly over the four lanes of every pixel row (six fused DPP adds: left to the compiler, the second level came out
-    // as v_mov_b32_dpp + v_add_f32 inside exec-masked branches), then the lane picks the total it stores
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        : "+v"(t0), "+v"(t1), "+v"(t2));
-    const float t01 = x == 0 ? t0 : t1;
-    return x >= 2 ? t2 : t01;
-  }
-};
-#ifdef MM3DGS_OLD_REDUCE
-#define SEP_REDUCE2 0
-#else
-#define SEP_REDUCE2 1
-#endif
-
 // Record written per (4x4 block, splat); the moments m = sum_p u_p (1, dx, dy, dx^2, dx dy, dy^2) of u = dL/dG * G over the
 // block's pixels give d/dxy and d/dconic with the splat's conic (preprocess_bwd).
 // MODE 0: generic, record = [m_x m_y m_xx m_xy m_yy | dopacity | dcolour(C)].
@@ -444,33 +278,16 @@ struct SepReduce2 {
 // (a device function: the tracking loop runs it in the same launch as the sort and the forward compositor, see below)
 #define BWD_STG_BYTES (sizeof(float4) * 2 * 4 * 3 * STG_N + sizeof(uint32_t) * 2 * 4 * 64)   // staged splat records + record indices: 26 KB
 
-// ---- round 6: the SLAM modes' backward in TWO PHASES per sub-chunk of list entries ---------------------------------------------------------------
-// The one-phase loop (kept as the generic mode's, and under -DMM3DGS_BWD_ONE_PHASE as the SLAM modes' A/B baseline) reduces the ten / seven record
-// values over the 16 lanes of a row after EVERY (row, splat) step: 18 / 12 DPP adds, the products that feed them and a 10-lane scatter store -- 33 of
-// the step's 64 vector instructions (profiles/r05_isa_budget.txt), although per (pixel, splat) only TWO numbers are new: u = dL/dG G and w = alpha T.
-// Here phase 1 (lane = pixel, as before) writes (u, w) of SUB consecutive steps to a wave-private LDS tile, and phase 2 turns the tile around:
+// ---- the backward in TWO PHASES per sub-chunk of list entries: the SLAM modes and the generic three-channel instance -----------------------------
+// Per (pixel, splat) only TWO numbers are new: u = dL/dG G and w = alpha T.  Reducing a record's ten / seven values over the 16 lanes of a row after
+// EVERY (row, splat) step (the one-phase loop below, which the other generic channel counts keep) costs 18 / 12 DPP adds, the products that feed them
+// and a 10-lane scatter store -- 33 of such a step's 64 vector instructions (profiles/r05_isa_budget.txt).
+// Here phase 1 (lane = pixel) writes (u, w) of SUB consecutive steps to a wave-private LDS tile, and phase 2 turns the tile around:
 // lane = (list entry, part of the 4x4 block), 16 / SUB lanes per entry, each walking its SUB pixels with the entry's centre in registers and the pixels'
 // dL from a wave-private LDS table -- plain fmas into ten accumulators, one DPP add per value and part to merge them, and the record leaves as two wide
-// stores from the lanes that hold it.  Deterministic (fixed order: x inside a pixel row, rows ascending, parts ascending).  The summation order differs
-// from the one-phase reduction's in the last bits.
-#ifdef MM3DGS_BWD_ONE_PHASE
-#define BWD_TWO_PHASE 0
-#else
-#define BWD_TWO_PHASE 1
-#endif
-// (developer timing probes of the two-phase loop, variant builds only -- results INVALID: -DMM3DGS_BWD2_PROBE=<bits>  1: no phase 2 | 2: phase 2 without its
-//  record stores | 4: phase 1 without the (u, w) tile writes | 8: phase 2 on constants instead of its tile / table reads)
-#ifndef MM3DGS_BWD2_PROBE
-#define MM3DGS_BWD2_PROBE 0
-#endif
-// generic mode, three channels (the RGB pass of the reference's rasterizer: configs[4]): the two-phase loop too (round 6); -DMM3DGS_GEN3_ONE_PHASE keeps its
-// one-phase loop (A/B baseline).  Other channel counts of the generic mode stay on the one-phase loop.
-#ifdef MM3DGS_GEN3_ONE_PHASE
-#define GEN3_TWO_PHASE 0
-#else
-#define GEN3_TWO_PHASE BWD_TWO_PHASE
-#endif
-#define BWD_IS_TWO_PHASE(MODE, C) (((MODE) != 0 && BWD_TWO_PHASE) || ((MODE) == 0 && (C) == 3 && GEN3_TWO_PHASE))
+// stores from the lanes that hold it.  Deterministic (fixed order: x inside a pixel row, rows ascending, parts ascending).
+// Generic mode: three channels (the RGB pass of the reference's rasterizer: configs[4]) take this loop, the other channel counts the one-phase loop.
+constexpr bool bwd_is_two_phase(int MODE, int C) { return MODE != 0 || C == 3; }
 #define TP_STRIDE 65      // float2 per step row of the (u, w) tile: 64 lanes + 1 (the SUB lanes of a phase-2 group read SUB different rows at one column: the odd stride spreads them over the banks)
 template <int MODE>
 struct Bwd2Lds {      // wave-private slice of the workgroup's LDS block (bytes)
@@ -482,7 +299,15 @@ struct Bwd2Lds {      // wave-private slice of the workgroup's LDS block (bytes)
   static constexpr int OFF_T = OFF_TP + 8 * TP_STRIDE * 8;         // mapping: float4[64] (dL0 dL1 dL2 dL3) per pixel; tracking: float[64] (dL3)
   static constexpr int SLICE = OFF_T + (MODE == 1 ? 64 * 16 : 64 * 4);
 };
-#define BWD2_BYTES(MODE) (4 * Bwd2Lds<MODE>::SLICE)      // mapping 31616 B, tracking 28544 B: five workgroups per CU (160 KB in 1280-byte granules: at most 32000)
+// The layout an instance of the two-phase loop runs on: the generic three-channel instance takes the mapping layout (a float4 of dL per pixel).
+template <int MODE>
+using BwdLds = Bwd2Lds<(MODE == 0 ? 1 : MODE)>;
+// a wave's private piece of the backward's staging memory, and the four of them
+// (two-phase: mapping 31616 B, tracking 28544 B: five workgroups per CU -- 160 KB in 1280-byte granules: at most 32000)
+template <int C, int MODE>
+constexpr size_t BWD_WAVE_SLICE = bwd_is_two_phase(MODE, C) ? (size_t)BwdLds<MODE>::SLICE : sizeof(float4) * 3 * STG_N;
+template <int C, int MODE>
+constexpr size_t BWD_LDS_BYTES = bwd_is_two_phase(MODE, C) ? 4 * (size_t)BwdLds<MODE>::SLICE : (size_t)BWD_STG_BYTES;
 // POSE (tracking, two-phase loop only): the pose chain of fused.hip's pose_chain_record -- phase 2 applies the splat's { Kp, Kq, x } (GeomView.poserec) to
 // the block's moments and adds dm (x) [x; 1] to per-lane accumulators; at the end the workgroup writes ONE row of twelve floats, dsub[tile][32], for the
 // pose finish.  No gradient record is written, none zeroed, no per-tile combine, and no backward-projection launch follows.
@@ -490,7 +315,7 @@ template <int C, int MODE, bool POSE = false>
 __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, const GeomView& g, const ImageView& iv, const BinView& b,
                                                    uint32_t N_cap, const float* __restrict__ dL_dout, float* __restrict__ dsub, int has_tl,
                                                    const TrackLoss& tl, int dl_planes, unsigned char* smem_raw, const SortShared* span = nullptr) {
-  static_assert(!POSE || (MODE == 2 && BWD_TWO_PHASE), "the pose chain lives in the tracking mode's two-phase loop");
+  static_assert(!POSE || MODE == 2, "the pose chain lives in the tracking mode's loop");
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   // wave = 8x8 sub-tile wv of the tile; 16-lane row = 4x4 block `row` of the sub-tile, walking its own list
   const int row = lane >> 4, q = lane & 15;
@@ -592,9 +417,9 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
     zero_record<NV>(dsub + (rbase + e) * RECF);
   }
   float pacc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // POSE: this lane's share of the tile's pose row (lanes 0-7 of a row: dR rows 0, 1; lanes 8-15: dR row 2, dt)
-  if constexpr (BWD_IS_TWO_PHASE(MODE, C)) {
+  if constexpr (bwd_is_two_phase(MODE, C)) {
   if (maxtodo != 0) {   // wave-uniform (a wave without work still takes part in the workgroup's per-tile combine below)
-    using LY = Bwd2Lds<(MODE == 0 ? 1 : MODE)>;      // (generic three-channel instance: the mapping layout -- a float4 of dL per pixel)
+    using LY = BwdLds<MODE>;
     unsigned char* const wbase = smem_raw + (size_t)wv * LY::SLICE;
     float4* const sA = (float4*)(wbase + LY::OFF_A);
     float4* const sB = (float4*)(wbase + LY::OFF_B);
@@ -607,7 +432,11 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
     else {
       if constexpr (MODE == 1) ((float4*)(wbase + LY::OFF_T))[lane] = make_float4(dL[0], dL[1], dL[C > 3 ? 2 : 0], dL[C > 3 ? 3 : 0]);
       else ((float*)(wbase + LY::OFF_T))[lane] = dL[C > 3 ? 3 : 0];
-      z45_wave = __ballot(dL[C > 4 ? 4 : 0] != 0.f || dL[C > 5 ? 5 : 0] != 0.f || Tf_bg != 0.f) == 0ull;      // see the one-phase loop below
+      // The SLAM losses leave the silhouette and depth^2 channels without gradient (dL[4] = dL[5] = 0): a wave that sees only
+      // zeros there runs a loop instance with those terms removed (exact: they would multiply by zero).
+      // Likewise the background term of dL/dalpha, -T_final (bg . dL) / (1 - alpha): over a black background (the shipped configurations) it is
+      // zero for every pixel, and the same instance drops it (exact: x - 0 * r = x for the finite r = 1 / (1 - alpha), alpha <= 0.99).
+      z45_wave = __ballot(dL[C > 4 ? 4 : 0] != 0.f || dL[C > 5 ? 5 : 0] != 0.f || Tf_bg != 0.f) == 0ull;
       if (!z45_wave) t5[lane] = dL[C > 5 ? 5 : 0];
     }
     const uint32_t first_step = todo - min(todo, last_contributor);
@@ -668,7 +497,7 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
             const float dLa = (Z45 && MODE != 0) ? diff * Tr : diff * Tr - Tf_bg * r;
             // (generic: u WITHOUT the opacity -- the record wants sum G dL/dalpha beside the moments of o G dL/dalpha; phase 2 scales the moments)
             const float u = MODE == 0 ? dLa * G_eff : B.y * dLa * G_eff;
-            if (!(MM3DGS_BWD2_PROBE & 4)) *tpw = make_float2(u, w);
+            *tpw = make_float2(u, w);
             tpw += TP_STRIDE;
           };
           {
@@ -688,7 +517,7 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
           }
           __builtin_amdgcn_wave_barrier();
           // ---- phase 2: lane = (entry sub + e of the row's chunk, part of the block): the entry's record from the (u, w) tile
-          if (!(MM3DGS_BWD2_PROBE & 1)) {
+          {
 #pragma clang fp contract(off)
             const int ent = sub + e;
             const bool on2 = base + (uint32_t)ent < todo;
@@ -710,12 +539,12 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
               float s0 = 0.f, s1 = 0.f, s2 = 0.f;
 #pragma unroll
               for (int x = 0; x < 4; x++) {
-                const float2 uw = (MM3DGS_BWD2_PROBE & 8) ? make_float2(cxy.x, cxy.y) : tpr[yy * 4 + x];
+                const float2 uw = tpr[yy * 4 + x];
                 s0 = s0 + uw.x;
                 s1 = __builtin_fmaf(uw.x, dxv[x], s1);
                 s2 = __builtin_fmaf(uw.x, dxx[x], s2);
                 if constexpr (MODE != 2) {
-                  const float4 d4 = (MM3DGS_BWD2_PROBE & 8) ? make_float4(X0, Y0, X0, Y0) : ((const float4*)(wbase + LY::OFF_T))[pcol + yy * 4 + x];
+                  const float4 d4 = ((const float4*)(wbase + LY::OFF_T))[pcol + yy * 4 + x];
                   c0 = __builtin_fmaf(uw.y, d4.x, c0);
                   c1 = __builtin_fmaf(uw.y, d4.y, c1);
                   c2 = __builtin_fmaf(uw.y, d4.z, c2);
@@ -754,18 +583,17 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
               pacc[0] = __builtin_fmaf(ma, x0, pacc[0]); pacc[1] = __builtin_fmaf(ma, x1, pacc[1]); pacc[2] = __builtin_fmaf(ma, x2, pacc[2]);
               pacc[3] = __builtin_fmaf(mb, hi ? dm0 : x0, pacc[3]); pacc[4] = __builtin_fmaf(mb, hi ? dm1 : x1, pacc[4]); pacc[5] = __builtin_fmaf(mb, hi ? dm2 : x2, pacc[5]);
             } else
-            if (on2 && !(MM3DGS_BWD2_PROBE & 2)) {
-              float* const o = dsub + ((MM3DGS_BWD2_PROBE & 32) ? (size_t)lane : rbase + (size_t)(todo - 1u - (base + (uint32_t)ent))) * RECF;
+            if (on2) {
+              float* const o = dsub + (rbase + (size_t)(todo - 1u - (base + (uint32_t)ent))) * RECF;
               if constexpr (MODE == 0) {      // [Mx My Mxx Mxy | Myy sum(G dL/dalpha) c0 c1 | c2], the moments scaled by the splat's opacity (preprocess_bwd's layout)
                 const float op = sB[r17 + ent].y;
                 if (part == 0) { const f4u v0 = {op * Mx, op * My, op * Mxx, op * Mxy}; *(f4u*)o = v0; o[8] = c2; }
                 if (part == 1) { const f4u v1 = {op * Myy, M0, c0, c1}; *(f4u*)(o + 4) = v1; }
               } else
               if constexpr (MODE == 1) {      // [M0 Mx Mxx c0 | c1 c2 cz My | Mxy Myy]
-                if (MM3DGS_BWD2_PROBE & 16) { if (part == 0) { const f4u v0 = {M0 + Mx + Mxx + c0, c1 + c2 + cz + My, Mxy, Myy}; *(f4u*)o = v0; } } else {
                 if (part == 0) { const f4u v0 = {M0, Mx, Mxx, c0}; *(f4u*)o = v0; }
                 if (part == 1) { const f4u v1 = {c1, c2, cz, My}; *(f4u*)(o + 4) = v1; }
-                if (part == (NL == 2 ? 0 : 2)) { const f2u v2 = {Mxy, Myy}; *(f2u*)(o + 8) = v2; } }
+                if (part == (NL == 2 ? 0 : 2)) { const f2u v2 = {Mxy, Myy}; *(f2u*)(o + 8) = v2; }
               } else {                        // [M0 Mx Mxx cz | My Mxy Myy]
                 if (part == 0) { const f4u v0 = {M0, Mx, Mxx, cz}; *(f4u*)o = v0; }
                 if (part == 1) { const f2u v1 = {My, Mxy}; *(f2u*)(o + 4) = v1; o[6] = Myy; }
@@ -789,9 +617,7 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
   } else
   if (maxtodo != 0 && !PROBE(cam, 9)) {   // wave-uniform; (probe builds, bit 9: timing without the main loop) (a wave without work still takes part in the workgroup's per-tile combine below)
 
-  const int my_slot = MODE == 0 ? WaveReduce<NV>::slot(q) : (SEP_REDUCE2 ? SepReduce2<MODE == 1>::slot(q) : SepReduce<MODE == 1>::slot(q));
-  float ym_0 = 0.f, ym_1a = 0.f, ym_1b = 0.f;
-  if (MODE != 0 && !SEP_REDUCE2) SepReduce<MODE == 1>::ymult(q, ym_0, ym_1a, ym_1b);
+  const int my_slot = WaveReduce<NV>::slot(q);
   // this lane's component of record 0; the list entries carry the record index of their (splat, block)
   float* const my_rec = dsub + (my_slot >= 0 ? my_slot : 0);
   uint32_t n_visit = 0, n_red = 0;
@@ -799,10 +625,7 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
   // chunk c of a row holds its list entries todo-1-(16c+q): entry order == traversal order (back to front)
   {
     const uint2 e0 = (uint32_t)q < todo ? list[todo - 1u - q] : make_uint2(0u, 0u);
-    SplatRec r0 = load_rec<C>(g.splat, e0.x, (uint32_t)q < todo);
-    // SLAM modes: the entry's gradient-record index rides in the staged record's constant field (C.z = the "1" of [z, 1, z^2]): one LDS
-    // read and its address less per (row, splat) step than a separate index array
-    if constexpr (MODE != 0) r0.C.z = __uint_as_float(e0.y);
+    const SplatRec r0 = load_rec<C>(g.splat, e0.x, (uint32_t)q < todo);
     stg[0][wv][0][slane] = r0.A;
     stg[0][wv][1][slane] = r0.B;
     if (C > 2) stg[0][wv][2][slane] = r0.C;
@@ -810,21 +633,14 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
   uint2 ent_nxt = CH + q < todo ? list[todo - 1u - (CH + q)] : make_uint2(0u, 0u);
   int cur = 0;
 
-  // The SLAM losses leave the silhouette and depth^2 channels without gradient (dL[4] = dL[5] = 0): a wave that sees only
-  // zeros there runs a loop instance with those terms removed (exact: they would multiply by zero).
-  // Likewise the background term of dL/dalpha, -T_final (bg . dL) / (1 - alpha): over a black background (the shipped configurations) it is
-  // zero for every pixel, and the same instance drops it (exact: x - 0 * r = x for the finite r = 1 / (1 - alpha), alpha <= 0.99).
-  const bool z45_wave = MODE != 0 && __ballot(dL[C > 4 ? 4 : 0] != 0.f || dL[C > 5 ? 5 : 0] != 0.f || Tf_bg != 0.f) == 0ull;
   // A splat counts for this lane's pixel while  pos = todo - 1 - step < last_contributor,  step = base + j the wave-uniform position in the
   // traversal:  step >= first_step  with the per-lane constant below -- one compare against a scalar instead of a subtraction and a compare per
   // step.  (todo >= last_contributor unless the list was clamped to `count`; then first_step = 0: every listed splat counts.)
   const uint32_t first_step = todo - min(todo, last_contributor);
   const uint32_t mean_steps_b = wave_mean_steps(cam, iv);
-  auto run_chunks = [&](auto z45_tag) {
-  constexpr bool Z45 = decltype(z45_tag)::value && MODE != 0;   // (SLAM modes have C == 6)
+  auto run_chunks = [&]() {
   for (uint32_t base = 0; base < maxtodo; base += CH, cur ^= 1) {
-    SplatRec rec_n = load_rec<C>(g.splat, ent_nxt.x, base + CH + q < todo);
-    if constexpr (MODE != 0) rec_n.C.z = __uint_as_float(ent_nxt.y);
+    const SplatRec rec_n = load_rec<C>(g.splat, ent_nxt.x, base + CH + q < todo);
     const uint2 ent_nn = base + 2 * CH + q < todo ? list[todo - 1u - (base + 2 * CH + q)] : make_uint2(0u, 0u);
     const float4 (*wS)[STG_N] = stg[cur][wv];
     const int r16 = row * STG_ROW;
@@ -832,7 +648,7 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
     const int cnt = __builtin_amdgcn_readfirstlane((int)min(CH, maxtodo - base));
     auto splat_bwd = [&](const float4& A, const float4& B, const float4& Cc, const int j) {
       const uint32_t step = base + (uint32_t)j;               // wave-uniform
-      const size_t ti = rbase + (size_t)(todo - 1u - step);      // list-major records (every mode since round 6)
+      const size_t ti = rbase + (size_t)(todo - 1u - step);      // list-major records
       const bool row_on = step < todo;                        // this row still has an entry at this step
       const float dx = A.x - pxf, dy = A.y - pyf;
       const float power = splat_power(dx, dy, A.z, A.w, B.x);
@@ -842,23 +658,18 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
       const bool valid = row_on && (step >= first_step) && !(power > 0.f) && !(alpha < ALPHA_MIN);
       float tot = 0.f;
       n_visit++;
-      if (MODE != 0 || __ballot(valid) != 0ull) {   // SLAM modes: four rows with different splats -- a whole-wave miss is rare, the vote is not worth its cost
+      if (__ballot(valid) != 0ull) {
         n_red++;
         // two selects (a_eff, G_eff).  ONE select of the un-clamped o G with alpha = min(0.99, .) of it is two instructions and six registers
         // less and measured 1.3 us SLOWER: the select moves into the dependent chain alpha -> 1 - alpha -> rcp -> T
         const float a_eff = valid ? alpha : 0.f;
         const float G_eff = valid ? G : 0.f;
-        // generic mode: the reciprocal to within an ulp -- T is rebuilt by ~50 successive divisions per pixel and the raw 1-ulp v_rcp_f32 showed up as
+        // the reciprocal to within an ulp -- T is rebuilt by ~50 successive divisions per pixel and the raw 1-ulp v_rcp_f32 showed up as
         // 5e-6 of noise on every gradient (camera gradients are held to 1e-5).  v_rcp_f32 + one Newton step holds the same bars as the IEEE
         // division sequence (tests/test_gpu_parity.py) at 3 instead of ~10 instructions: 1080p / 3 M backward compositor 1327 -> 1291 us.
-        // The SLAM modes keep the raw v_rcp_f32 (an exact division changes none of their parity figures: measured, round 3).
-        float r;
-        if constexpr (MODE == 0) {
-          const float d = 1.f - a_eff, r0 = __builtin_amdgcn_rcpf(d);
-          r = fmaf(fmaf(-d, r0, 1.f), r0, r0);
-        } else {
-          r = __builtin_amdgcn_rcpf(1.f - a_eff);
-        }
+        // The SLAM modes' two-phase loop keeps the raw v_rcp_f32 (an exact division changes none of their parity figures: measured, round 3).
+        const float d = 1.f - a_eff, r0 = __builtin_amdgcn_rcpf(d);
+        const float r = fmaf(fmaf(-d, r0, 1.f), r0, r0);
         Tr *= r;  // transmittance in front of this splat
         const float w = a_eff * Tr;
         float col[C];
@@ -866,37 +677,30 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
         if constexpr (C > 1) col[1] = B.w;
         if constexpr (C > 2) col[2] = Cc.x;
         if constexpr (C > 3) col[3] = Cc.y;
-        if constexpr (C > 4) col[4] = MODE == 0 ? Cc.z : 1.f;      // (SLAM modes: that field carries the record index; the channel is the constant 1)
+        if constexpr (C > 4) col[4] = Cc.z;
         if constexpr (C > 5) col[5] = Cc.w;
         // dL/dalpha needs sum_ch (c_ch - behind_ch) dL_ch: track the dL-weighted colour behind as ONE scalar
         // (behind_dot) instead of C running colours: qd = c . dL;  dLa = qd - behind_dot;  behind_dot += a (qd - behind_dot)
         float qd = 0.f;
 #pragma unroll
-        for (int ch = 0; ch < (Z45 ? 4 : C); ch++) qd = fmaf(col[ch], dL[ch], qd);
+        for (int ch = 0; ch < C; ch++) qd = fmaf(col[ch], dL[ch], qd);
         const float diff = qd - behind_dot;
         behind_dot = fmaf(a_eff, diff, behind_dot);
-        const float dLa = Z45 ? diff * Tr : diff * Tr - Tf_bg * r;
+        const float dLa = diff * Tr - Tf_bg * r;
         // screen-space geometry: only the moments of u = dL/dG * G are reduced; the consumer (preprocess_bwd) turns them
         // into d/dxy and d/dconic with the splat's own conic:  dxy = -(Q m1),  dconic = -(1/2 m_xx, m_xy, 1/2 m_yy)
         const float u = B.y * dLa * G_eff;
-        if constexpr (MODE == 0) {
-          float vals[NV];
+        float vals[NV];
 #pragma unroll
-          for (int ch = 0; ch < C; ch++) vals[6 + ch] = w * dL[ch];
-          const float mx = u * dx, my = u * dy;
-          vals[0] = mx;
-          vals[1] = my;
-          vals[2] = mx * dx;
-          vals[3] = mx * dy;
-          vals[4] = my * dy;
-          vals[5] = G_eff * dLa;
-          tot = WaveReduce<NV>::run(vals, lane);
-        } else {
-          // SLAM records: the zeroth moment M0 = sum u also carries the opacity gradient (sum G dL/dalpha = M0 / opacity)
-          const float cz = Z45 ? w * dL[3] : w * fmaf(2.f * col[3], dL[5], dL[3]);   // d/dz of the [z, 1, z^2] bundle, chained here
-          if constexpr (SEP_REDUCE2) tot = SepReduce2<MODE == 1>::run(u, dx, dy, w * dL[0], w * dL[1], w * dL[2], cz, lane);
-          else tot = SepReduce<MODE == 1>::run(u, dx, dy, w * dL[0], w * dL[1], w * dL[2], cz, lane, ym_0, ym_1a, ym_1b);
-        }
+        for (int ch = 0; ch < C; ch++) vals[6 + ch] = w * dL[ch];
+        const float mx = u * dx, my = u * dy;
+        vals[0] = mx;
+        vals[1] = my;
+        vals[2] = mx * dx;
+        vals[3] = mx * dy;
+        vals[4] = my * dy;
+        vals[5] = G_eff * dLa;
+        tot = WaveReduce<NV>::run(vals, lane);
       }
       // this row is the only writer of the (block, splat) record: up to 12 of its lanes store 48 contiguous bytes
       if (my_slot >= 0 && row_on && !PROBE(cam, 0)) my_rec[ti * RECF] = tot;
@@ -921,8 +725,7 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
   }
   };
   wave_prio_by_steps(maxtodo, mean_steps_b);
-  if (z45_wave) run_chunks(std::true_type{});
-  else run_chunks(std::false_type{});
+  run_chunks();
   wave_prio_reset();      // (the combine at top priority instead: no gain, 56.8 -> 57.0 us)
   if (cam.stats && lane == 0) {
     atomicAdd(&iv.hdr->bwd_wave_visits, n_visit);
@@ -982,7 +785,7 @@ __device__ __forceinline__ void composite_bwd_body(int tile, const CamDev& cam, 
     constexpr int WPRE = (MODE == 0 && C > 4) ? 4 : 8;      // (the 11 / 12-float generic records leave registers for four)
     constexpr uint32_t COMB_OWN_MAX = 16;                    // own chunks whose counts fit the wave's scratch: tiles of up to 4096 pairs
     constexpr uint32_t COMB_DIST_CHUNKS = 4 * COMB_OWN_MAX;
-    constexpr size_t WSLICE = BWD_IS_TWO_PHASE(MODE, C) ? (size_t)Bwd2Lds<(MODE == 0 ? 1 : MODE)>::SLICE : sizeof(float4) * 3 * STG_N;   // a wave's private piece of the staging memory
+    constexpr size_t WSLICE = BWD_WAVE_SLICE<C, MODE>;      // a wave's private piece of the staging memory
     static_assert(WSLICE >= COMB_OWN_MAX * NLIST + 64 * (NLIST / 2) * 4, "a wave's slice holds its chunk counts and its list positions");
     const uint32_t nchunks = (len + 63u) >> 6;
     const bool dist = nchunks <= COMB_DIST_CHUNKS;          // workgroup-uniform
@@ -1165,7 +968,7 @@ composite_bwd_kernel(CamDev cam, GeomView g, ImageView iv, BinView b, uint32_t N
   // (generic mode: 32 KB on purpose -- five workgroups per CU; with the 26 KB the staging buffers need, six fit and the 1080p /
   //  3 M-Gaussian pass ran 14 % slower: every workgroup gathers ~1000 splat records by id, and six of them overflow the L1)
   constexpr size_t MIN_BYTES = MODE == 0 ? 32768 : 0;
-  constexpr size_t STG_BYTES = BWD_IS_TWO_PHASE(MODE, C) ? (size_t)BWD2_BYTES(MODE == 0 ? 1 : MODE) : (size_t)BWD_STG_BYTES;
+  constexpr size_t STG_BYTES = BWD_LDS_BYTES<C, MODE>;
   constexpr size_t NEED = STG_BYTES > LOSS_BYTES ? STG_BYTES : LOSS_BYTES;
   __shared__ __align__(16) unsigned char smem_raw[NEED > MIN_BYTES ? NEED : MIN_BYTES];
   const int T = cam.gx * cam.gy;
@@ -1185,7 +988,7 @@ template <bool POSE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5)))
 sort_composite_fwd_bwd_track_kernel(CamDev cam, GeomView g, ImageView iv, BinView b, uint32_t N_cap, float* __restrict__ out, int clean,
                                     TrackLoss tl, int direct_blocks, float* __restrict__ dsub, uint32_t direct_cap, int slot_bits) {
-  constexpr size_t TRACK_BWD_BYTES = BWD_TWO_PHASE ? (size_t)BWD2_BYTES(2) : (size_t)BWD_STG_BYTES;
+  constexpr size_t TRACK_BWD_BYTES = BWD_LDS_BYTES<6, 2>;
   __shared__ __align__(16) unsigned char smem[TRACK_BWD_BYTES];     // >= forward staging (25.5 KB) >= sort keys + runs + payloads (24 KB)
   __shared__ SortShared sh;
   __shared__ double red[4][12];
@@ -1227,12 +1030,9 @@ void launch_composite_bwd_slam(const CamDev& cam, bool tracking, GeomView g, Ima
   int T = cam.gx * cam.gy;
   int grid = slam_grid(cam, T);
   TrackLoss none = {};
-#if BWD_TWO_PHASE
   if (tracking && pose_chain)
     hipLaunchKernelGGL((composite_bwd_kernel<6, 2, true>), dim3(grid), dim3(256), slam_lds_pad(), s, cam, g, iv, b, ncap, dL, dsub, tl ? 1 : 0, tl ? *tl : none, dl_planes);
-  else
-#endif
-  if (tracking)
+  else if (tracking)
     hipLaunchKernelGGL((composite_bwd_kernel<6, 2>), dim3(grid), dim3(256), slam_lds_pad(), s, cam, g, iv, b, ncap, dL, dsub, tl ? 1 : 0, tl ? *tl : none, dl_planes);
   else
     hipLaunchKernelGGL((composite_bwd_kernel<6, 1>), dim3(grid), dim3(256), slam_lds_pad(), s, cam, g, iv, b, ncap, dL, dsub, tl ? 1 : 0, tl ? *tl : none, dl_planes);
@@ -1252,15 +1052,11 @@ void launch_sort_composite_fwd_bwd_track(const CamDev& cam, GeomView g, ImageVie
   uint32_t ncap = (uint32_t)(N_cap > 0xffffffffull ? 0xffffffffull : N_cap);
   int T = cam.gx * cam.gy;
   int grid = slam_grid(cam, T);
-#if BWD_TWO_PHASE
   if (pose_chain)
     hipLaunchKernelGGL(sort_composite_fwd_bwd_track_kernel<true>, dim3(grid), dim3(256), slam_lds_pad(), s, cam, g, iv, b, ncap, out, clean, tl, direct_blocks, dsub, direct_cap, slot_bits);
   else
-#endif
-  hipLaunchKernelGGL(sort_composite_fwd_bwd_track_kernel<false>, dim3(grid), dim3(256), slam_lds_pad(), s, cam, g, iv, b, ncap, out, clean, tl, direct_blocks, dsub, direct_cap, slot_bits);
+    hipLaunchKernelGGL(sort_composite_fwd_bwd_track_kernel<false>, dim3(grid), dim3(256), slam_lds_pad(), s, cam, g, iv, b, ncap, out, clean, tl, direct_blocks, dsub, direct_cap, slot_bits);
 }
-// whether this build's tracking compositors carry the pose chain (the one-phase A/B build does not)
-bool composite_has_pose_chain() { return BWD_TWO_PHASE != 0; }
 
 void launch_composite_fwd(const CamDev& cam, int C, GeomView g, ImageView iv, BinView b, size_t N_cap, float* out,
                           hipStream_t s) {

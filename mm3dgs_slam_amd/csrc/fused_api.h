@@ -54,7 +54,6 @@ void launch_loss_finish(const LossCfg& cfg, double* sums, const double* partial,
 
 void launch_slam_preprocess_fwd(const CamDev& cam, int P, const SlamIn& in, int32_t* radii, GeomView g, ImageView iv, hipStream_t s,
                                 uint32_t* seen_only = nullptr, bool visibility_only = false, bool want_poserec = false);
-bool composite_has_pose_chain();
 // the pose finish alone over per-tile pose rows (the tracking compositor's pose chain: composite.hip, GeomView.poserec)
 void launch_slam_pose_finish(const float* rows, int nrows, const float* pose_in, float* dpose, const PoseAdam& ad, hipStream_t s,
                              const PoseLossScale* pls, float* loss4, const uint32_t* ovf);

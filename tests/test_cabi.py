@@ -102,3 +102,17 @@ def test_product_sources_carry_no_timing_probe():
     if os.path.exists(_lib.LIB_PATH):
         out = subprocess.run(["strings", _lib.LIB_PATH], stdout=subprocess.PIPE, text=True).stdout
         assert "MM3DGS_EXP" not in out
+
+
+def test_product_sources_carry_no_retired_baseline_switch():
+    """The A/B baselines of the backward compositor (one-phase SLAM loops, the separable row reductions, the two-phase loop's compile-time
+    probes) were measured and then removed: no source or header names their switches any more."""
+    import glob
+    retired = ("MM3DGS_OLD_REDUCE", "MM3DGS_BWD_ONE_PHASE", "MM3DGS_GEN3_ONE_PHASE", "MM3DGS_BWD2_PROBE")
+    files = glob.glob(os.path.join(ROOT, "mm3dgs_slam_amd", "csrc", "**", "*"), recursive=True) + glob.glob(os.path.join(ROOT, "include", "**", "*"), recursive=True)
+    files = [f for f in files if os.path.isfile(f) and not f.endswith((".o", ".so"))]
+    assert files
+    for f in files:
+        text = open(f, errors="replace").read()
+        for name in retired:
+            assert name not in text, (f, name)
