@@ -79,6 +79,7 @@ def test_fused_forward_and_backward_match_torch_graph(white):
 
 @pytest.mark.parametrize("kind", ["track", "track_pearson", "map", "map_estdepth", "splatam_track", "splatam_map"])
 def test_fused_loss_matches_torch_losses(kind):
+    # (the precision check of these kernels, against float64 at edge shapes, is tests/test_gpu_loss.py; this one ties them to the torch-graph losses)
     from mm3dgs_slam_amd.fused import FusedEngine, _loss_cfg
     from mm3dgs_slam_amd.loss_utils import l1_loss, pearson_loss, ssim
     cfg, g, R, pose, color, depth = _setup(P=15000, H=200, W=272)
