@@ -416,6 +416,25 @@ int mm3dgs_propagate_imu(const float* pose_m1 /*[7], frame idx-1*/, const float*
                          const float* c2i /*16 floats, row-major camera->IMU*/, double dt_cam, double dt_imu, double gx, double gy, double gz,
                          float* out_pose /*[7]*/, void* stream);
 
+/* Least-squares alignment of a monocular depth estimate to a depth image (slam/SLAM.py:411-448 with utils/depth_utils.py:44-99):
+ * fits scale * est + shift ~ 1 / depth over the valid pixels and, with out_or_null, writes out = 1 / (scale * est + shift) for EVERY
+ * pixel in float32 (unfused multiply and add, correctly rounded division, the float32-rounded scale and shift).
+ *   considered: with a silhouette  silhouette > sil_min && est > est_min  (strict, float32; the SLAM frame path passes 0.99f and 1e-6f);
+ *               with silhouette_or_null = NULL  depth > 0  (sil_min and est_min are not read)
+ *   valid:      considered && 0 < z < +inf, z = the correctly rounded float32 1.0f / depth.  NaN, zero, negative and +inf depth are invalid,
+ *               and so is a depth so small that 1 / depth overflows (the host path of the Python package sums that pixel and returns NaN,
+ *               as the reference does).  A NaN / inf of est at a pixel that is not considered does not reach the sums.
+ * Sums in double over the valid pixels, h = est: a00 = sum h^2, a01 = sum h, n = sum 1, b0 = sum h z, b1 = sum z; det = a00 n - a01^2;
+ * ok = n >= 2 && |det| > 1e-9 max(|a00 n|, 1e-300) && isfinite(det); scale = (n b0 - a01 b1) / det, shift = (a00 b1 - a01 b0) / det, each
+ * rounded once to float32; not ok: scale 1, shift 0.  fit[16] (device, 8-byte aligned): scale, shift (the float32 values, widened), ok (0 / 1),
+ * n, a00, a01, b0, b1, then eight zeros.  work: mm3dgs_align_depth_work_bytes(H, W) bytes of device memory, 8-byte aligned, contents irrelevant
+ * before and after.  The images need no more than a float's alignment (planes of a [6,H,W] render qualify).  Two launches on `stream`, no
+ * atomics, no host synchronisation; the same inputs give the same bits on every call.  -1 (nothing is launched): H <= 0, W <= 0, a NULL est,
+ * depth, work or fit, or a misaligned work / fit. */
+size_t mm3dgs_align_depth_work_bytes(int H, int W);
+int mm3dgs_align_depth(int H, int W, const float* est /*[H,W]*/, const float* depth /*[H,W]*/, const float* silhouette_or_null /*[H,W]*/,
+                       float sil_min, float est_min, void* work, double* fit /*[16], device*/, float* out_or_null /*[H,W]*/, void* stream);
+
 /* ---- optional per-kernel timing (HIP events recorded on the caller's stream around each launch) ------------
  * Used by bench.py's roofline leg.  mm3dgs_profile_read() waits for the recorded events, returns the number of
  * (timed) launches and their summed duration since the previous read, and resets the counters. */
@@ -471,7 +490,10 @@ const char* mm3dgs_last_error(void);
         (world_means = 1) viewing directions
    212: mm3dgs_slam_adam_project accepts an active SH degree 1-3 (needs Mm3dgsSlamGrads.d_f_rest and Mm3dgsMapAdam.rest_*; no struct changes):
         the multi-GPU mapping window runs natively at an active SH degree
-   213: mm3dgs_propagate_imu (the tracker's IMU pose prediction on the device; no struct changes) */
+   213: mm3dgs_propagate_imu (the tracker's IMU pose prediction on the device; no struct changes)
+        later, without a new number (purely additive: no struct, signature or size of 213 changes, and tests/test_imu_predict.py holds the
+        library at exactly 213): mm3dgs_align_depth_work_bytes / mm3dgs_align_depth (the monocular depth estimate's least-squares fit to
+        the map, its fit record and its application on the device); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

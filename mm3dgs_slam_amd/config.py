@@ -11,7 +11,10 @@ def load_config(path):
 
 
 _TUM = {
-    "dataset": "synthetic", "device": "cuda:0", "method": "vigs", "use_gt_depth": True, "white_background": False,
+    "dataset": "synthetic", "device": "cuda:0", "method": "vigs", "use_gt_depth": True,
+    # use_gt_depth false: the per-frame least-squares fit of the monocular estimate to the map from mm3dgs_align_depth (two launches,
+    # sums and solve in double) instead of the torch operator graph; opt-in, it also records every frame's fit (results.npz: depth_align)
+    "depth_align_on_device": False, "white_background": False,
     "scene_radius_depth_ratio": 2, "desired_height": 480, "desired_width": 640,
     "debug": {"get_runtime_stats": False, "create_video": False, "save_keyframes": False},
     "pipeline": {"convert_SHs_python": False, "compute_cov3D_python": False, "transform_means_python": True,

@@ -698,6 +698,17 @@ int mm3dgs_propagate_imu(const float* pose_m1, const float* pose_m2, const float
   return check_launch("propagate_imu");
 }
 
+size_t mm3dgs_align_depth_work_bytes(int H, int W) { return (H > 0 && W > 0) ? align_depth_work_bytes(H, W) : 0; }
+
+int mm3dgs_align_depth(int H, int W, const float* est, const float* depth, const float* silhouette_or_null, float sil_min, float est_min,
+                       void* work, double* fit, float* out_or_null, void* stream) {
+  if (H <= 0 || W <= 0) return fail(-1, "align_depth: H = %d, W = %d (both must be positive)", H, W);
+  if (!est || !depth || !work || !fit) return fail(-1, "align_depth: NULL argument (est, depth, work and fit are required)");
+  if (((uintptr_t)work | (uintptr_t)fit) & 7) return fail(-1, "align_depth: work and fit must be 8-byte aligned");
+  launch_align_depth(H, W, est, depth, silhouette_or_null, sil_min, est_min, (double*)work, fit, out_or_null, (hipStream_t)stream);
+  return check_launch("align_depth");
+}
+
 int mm3dgs_prune_mask(int P, const float* opacity, const float* log_scales, const float* max_radii2D, float min_opacity, float max_scale,
                       float max_screen_size, uint8_t* keep, uint32_t* n_pruned_accum, void* stream) {
   if (P < 0) return fail(-1, "P < 0");

@@ -115,3 +115,7 @@ void launch_propagate_const_vel(const float* pm1, const float* pm2, float* out, 
 // imu6: [n,6] rows (angular velocity xyz, linear acceleration xyz incl. gravity), read only; c2i: 16 floats, row-major camera->IMU
 void launch_propagate_imu(const float* pm1, const float* pm2, const float* imu6, int n, const float* c2i, double dt_cam, double dt_imu,
                           double gx, double gy, double gz, float* out, hipStream_t s);
+// depth alignment (align.hip): rows = the work buffer of align_depth_work_bytes(H, W); sil and out may be NULL
+size_t align_depth_work_bytes(int H, int W);
+void launch_align_depth(int H, int W, const float* est, const float* depth, const float* sil, float sil_min, float est_min, double* rows,
+                        double* fit, float* out, hipStream_t s);

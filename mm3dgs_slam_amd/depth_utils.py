@@ -6,7 +6,11 @@ target of its Pearson term.  The monocular network itself (MiDaS, a download) is
 
 The reference gathers the valid pixels (``torch.where`` -> a host synchronisation) and solves the 2 x 2 normal equations with
 ``torch.inverse``; here the masked-out pixels stay in place as zero rows of ``H`` (the normal equations are the same sums), the 2 x 2
-inverse is written out, and nothing leaves the device."""
+inverse is written out, and nothing leaves the device.
+
+``align_depth_device`` is the same fit and its application as two HIP launches (``mm3dgs_align_depth``, csrc/align.hip) with the fit
+record -- scale, shift, whether the system had a fit, the pixel count and the four sums -- as a device tensor; the opt-in key
+``depth_align_on_device`` routes ``scale_depth_estimate`` through it."""
 from __future__ import annotations
 
 import torch
@@ -42,9 +46,59 @@ def get_scale_shift_LS(est_depth, render_depth, mask=None, return_ok=False):
     return (scale, shift, ok) if return_ok else (scale, shift)
 
 
-def scale_depth_estimate(cfg, idx, est_depth, gt_depth, render_depth_sil, resumed=False):
+_WORK = {}      # (H, W, device) -> the kernels' row buffer (contents irrelevant between calls; calls on one stream are ordered)
+
+
+def align_depth_device(est, depth, sil=None, sil_min=0.99, est_min=1e-6):
+    """``(1 / (scale * est + shift), fit)`` with the least-squares fit of ``scale * est + shift`` to ``1 / depth`` over
+    { sil > sil_min, est > est_min, 0 < 1 / depth < inf } -- without ``sil`` over { depth > 0, 1 / depth < inf } -- by mm3dgs_align_depth:
+    two launches on the current stream, nothing read back.  ``fit``: 16 float64 on the device = scale, shift (the float32 values), ok
+    (0 / 1), the number of valid pixels, a00, a01, b0, b1, zeros; not ok (fewer than two valid pixels, an estimate constant over them) is
+    the identity fit.  One difference from ``get_scale_shift_LS``: a pixel whose depth is so small that ``1 / depth`` overflows is left
+    out here and makes the host path return NaN.  The scaled estimate is a fresh tensor on every call (keyframes keep it)."""
+    import ctypes as C
+    from . import _lib
+    from .rasterizer import _stream
+    if not (est.is_cuda and depth.is_cuda and (sil is None or sil.is_cuda)):
+        raise RuntimeError("align_depth_device needs device tensors (the host path is get_scale_shift_LS)")
+    H, W = int(est.shape[-2]), int(est.shape[-1])
+    if est.numel() != H * W or depth.numel() != H * W or (sil is not None and sil.numel() != H * W):
+        raise ValueError(f"align_depth_device: est, depth and sil are [H,W] images of one size; got {tuple(est.shape)}, {tuple(depth.shape)}"
+                         + (f", {tuple(sil.shape)}" if sil is not None else ""))
+    est_c, depth_c = est.detach().float().contiguous(), depth.detach().float().contiguous()
+    sil_c = None if sil is None else sil.detach().float().contiguous()
+    lib = _lib.load()
+    key = (H, W, est_c.device)
+    work = _WORK.get(key)
+    if work is None:
+        work = _WORK[key] = torch.empty(int(lib.mm3dgs_align_depth_work_bytes(H, W)) // 8, dtype=torch.float64, device=est_c.device)
+    fit = torch.empty(16, dtype=torch.float64, device=est_c.device)
+    out = torch.empty_like(est_c)
+    _lib.check(lib.mm3dgs_align_depth(H, W, C.c_void_p(est_c.data_ptr()), C.c_void_p(depth_c.data_ptr()),
+                                      C.c_void_p(sil_c.data_ptr() if sil_c is not None else None), float(sil_min), float(est_min),
+                                      C.c_void_p(work.data_ptr()), C.c_void_p(fit.data_ptr()), C.c_void_p(out.data_ptr()), _stream()))
+    return out, fit
+
+
+def scale_depth_estimate(cfg, idx, est_depth, gt_depth, render_depth_sil, resumed=False, on_device=False, return_fit=False):
     """``est_depth_scaled`` of slam/SLAM.py:411-448.  render_depth_sil: a callable returning (depth, silhouette) of the map at the
-    frame's estimated pose (only called for idx > 0, or on a resumed run)."""
+    frame's estimated pose (only called for idx > 0, or on a resumed run).  ``on_device`` (the key ``depth_align_on_device``): the two
+    fits run through ``align_depth_device`` when the tensors are on the GPU.  ``return_fit``: also the fit record of that path (None
+    where no fit ran on the device)."""
+    if on_device and est_depth.is_cuda:
+        fit = None
+        with torch.no_grad():
+            if idx == 0 and not resumed:
+                if str(cfg.get("dataset", "")).lower() == "utmm":
+                    out, fit = align_depth_device(est_depth, gt_depth)
+                else:
+                    out = 1.0 / (est_depth + 0.001) * float(cfg["cam"]["png_depth_scale"]) / 10.0
+            else:
+                depth, sil = render_depth_sil()
+                out, fit = align_depth_device(est_depth, depth, sil)
+        return (out, fit) if return_fit else out
+    if return_fit:
+        return scale_depth_estimate(cfg, idx, est_depth, gt_depth, render_depth_sil, resumed), None
     with torch.no_grad():
         if idx == 0 and not resumed:
             if str(cfg.get("dataset", "")).lower() == "utmm":

@@ -219,6 +219,7 @@ class SLAM:
                                   tstamps=getattr(sequence, "tstamps", None))
         self.mapper = MapperCls(cfg, self.gaussians, self.renderer, self.estimate_pose_list, n_img=n, window=window)
         self.gt_pose_list = [None] * n
+        self.depth_fits, self.depth_fit_frames = [], []      # depth_align_on_device: the fit record (on the device) of every fitted frame, and its index
         if resume is not None:
             dev = cfg["device"]
             for i, p in enumerate(resume["pose_est"][:n]):
@@ -248,8 +249,15 @@ class SLAM:
         est_scaled = depth
         if mono:
             from .depth_utils import scale_depth_estimate
-            est_scaled = scale_depth_estimate(self.cfg, idx, est, depth, lambda: self.mapper._render_depth_sil(self.estimate_pose_list[idx]),
-                                              resumed="iteration" in self.cfg)
+            render = lambda: self.mapper._render_depth_sil(self.estimate_pose_list[idx])
+            if self.cfg.get("depth_align_on_device", False):
+                est_scaled, fit = scale_depth_estimate(self.cfg, idx, est, depth, render, resumed="iteration" in self.cfg, on_device=True,
+                                                       return_fit=True)
+                if fit is not None:
+                    self.depth_fits.append(fit)      # stays on the device: read back once, by save_results
+                    self.depth_fit_frames.append(idx)
+            else:
+                est_scaled = scale_depth_estimate(self.cfg, idx, est, depth, render, resumed="iteration" in self.cfg)
         if idx == 0:
             self.mapper.camera_extent = float((est_scaled if mono else depth).max()) / self.cfg["scene_radius_depth_ratio"]
         self.mapper.run_frame(idx, color, depth, est_scaled)
@@ -328,9 +336,27 @@ class SLAM:
         if self.cfg["debug"]["get_runtime_stats"]:
             results["avg_tracking_it_time"] = self.tracker.tracking_time_sum / max(self.tracker.tracking_iter_count, 1) * 1000
             results["avg_mapping_it_time"] = self.mapper.mapping_time_sum / max(self.mapper.mapping_iter_count, 1) * 1000
+        if self.cfg.get("depth_align_on_device", False):
+            results["depth_align"] = self.depth_align_table(last_idx)
         os.makedirs(self.cfg["outputdir"], exist_ok=True)
         np.savez(os.path.join(self.cfg["outputdir"], "results"), **results)
         return results
+
+    def depth_align_table(self, last_idx):
+        """[frames, 4] float64 = scale, shift, ok, valid pixels of every frame's depth alignment (depth_align_on_device); a frame without
+        a fit on the device (the arbitrarily scaled first frame, a host-side frame) is a row of NaN.  One read-back; warns about the
+        frames whose system had no fit and fell back to the identity."""
+        table = np.full((last_idx, 4), np.nan)
+        fits = [(i, f) for i, f in zip(self.depth_fit_frames, self.depth_fits) if i < last_idx]
+        if fits:
+            rows = torch.stack([f for _, f in fits])[:, :4].cpu().numpy()
+            for (i, _), r in zip(fits, rows):
+                table[i] = r
+            bad = [i for (i, _), r in zip(fits, rows) if r[2] != 1.0]
+            if bad:
+                print(f"Warning: the depth estimate of frame(s) {bad} had no least-squares fit to the map (fewer than two valid pixels or a "
+                      f"constant estimate); the identity (scale 1, shift 0) was used there.")
+        return table
 
     def pose_errors(self):
         """Translation error (m) of every estimated pose against the sequence's ground truth."""
