@@ -41,6 +41,21 @@ __device__ __forceinline__ PoseDev load_pose(const float* __restrict__ pose) {
   return p;
 }
 
+// A launch's uniform inputs -- a pose (7 floats) and the 16 floats of cam.proj -- read ONCE, as the kernel's first instructions, into
+// registers: before the first store of the kernel they are scalar loads that share the round trip of the kernel arguments.  Dereferenced
+// where they are used, behind stores the pointers may alias, each is a memory round trip of its own that every wave of the one-round grid
+// waits for alone (the next view's pose behind the Adam stores, cam.proj -- as vector loads -- behind the splat record).  The helpers below
+// take `pose` and `PV` as pointers and never go back to cam.proj or SlamIn::pose: the kernels built on slam_bwd_body hand them these arrays.
+struct PoseProj { float pose[7]; float PV[16]; };
+__device__ __forceinline__ PoseProj load_pose_proj(const float* __restrict__ pose, const float* __restrict__ proj) {
+  PoseProj u;
+#pragma unroll
+  for (int k = 0; k < 7; k++) u.pose[k] = pose[k];
+#pragma unroll
+  for (int k = 0; k < 16; k++) u.PV[k] = proj[k];
+  return u;
+}
+
 // raw rotation quaternion q[4] and log-scales ls[3] -> normalised quaternion, R, scales, Sigma = (R S)(R S)^T
 __device__ __forceinline__ void slam_cov3d_vals(const float q[4], const float ls[3], bool isotropic, float mod, float S3[3][3],
                                                 float R[3][3], float sm[3], float qn[4], float& qinv) {
@@ -99,7 +114,7 @@ __device__ __forceinline__ void pose_view_matrix(const PoseDev& ps, float V[16])
 // (conic <- 2D covariance <- J(p) S3 J(p)^T, the +-1.3 tanfov clamp included), both the helpers slam_bwd_body calls, evaluated on unit
 // inputs.  The projection stage writes { Kp, Kq, x } per visible Gaussian; the compositor applies it per (block, splat) and sums dm (x) [x; 1]
 // straight into the tile's pose-gradient row: no gradient record leaves the compositor, no per-tile combine, no backward projection launch.
-__device__ __forceinline__ void pose_chain_record(const CamDev& cam, const float* __restrict__ PV, const float p[3], const float x[3], const Ewa& e,
+__device__ __forceinline__ void pose_chain_record(const CamDev& cam, const float PV[16], const float p[3], const float x[3], const Ewa& e,
                                                   const float S3[3][3], float qa, float qb, float qc, float pw, float hx, float hy,
                                                   float* __restrict__ rec) {
   // covariance chain: (gA, gB, gC) = d/d(conic) -> dm, column by column
@@ -154,10 +169,9 @@ __device__ __forceinline__ void sh_dir_vec(const PoseDev& ps, const float x[3], 
 // SH (ABI 209): an active degree above 0 -- colour = sum_k basis_k(dir) sh_k + 0.5, clamped at 0, with dir = v / |v| of sh_dir_vec<SHDIR> (ABI 211:
 // SHDIR 1 and 2; SHDIR 0 is the instance of ABI 209); rest = this Gaussian's f_rest rows
 template <bool SH = false, int SHDIR = 0>
-__device__ __forceinline__ Projected slam_project_vals(const CamDev& cam, bool live, int idx, const float* __restrict__ pose, bool isotropic,
+__device__ __forceinline__ Projected slam_project_vals(const CamDev& cam, bool live, int idx, const float* __restrict__ pose, const float* PV, bool isotropic,
                                                        const RawGaussian& rg, int32_t* __restrict__ radii, const GeomView& g, bool world = false,
                                                        bool want_poserec = false, const float* __restrict__ rest = nullptr, int sh_deg = 0) {
-  const float* PV = cam.proj;
   const float Vi[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
   const PoseDev ps = load_pose(pose);
   float p[3] = {0.f, 0.f, 0.f};
@@ -258,7 +272,9 @@ __device__ __forceinline__ Projected slam_project_one(const CamDev& cam, int P, 
     for (int k = 0; k < 3; k++) { rg.ls[k] = in.scaling[(size_t)idx * 3 + k]; rg.fd[k] = in.f_dc[(size_t)idx * 3 + k]; }
     rg.op = in.opacity[idx];
   }
-  return slam_project_vals<SH, SHDIR>(cam, live, idx, in.pose, in.isotropic != 0, rg, radii, g, in.world != 0, want_poserec,
+  // (the pose and cam.proj are read from memory where they are used here: hoisting them to the kernel's entry, as slam_bwd_project_kernel does,
+  //  gained slam_project_bin_kernel 0.1 .. 0.15 us of 20 -- inside its run-to-run spread, profiles/r11_ab_per_gaussian_loads.txt)
+  return slam_project_vals<SH, SHDIR>(cam, live, idx, in.pose, cam.proj, in.isotropic != 0, rg, radii, g, in.world != 0, want_poserec,
                                SH ? in.f_rest + (size_t)(live ? idx : 0) * (size_t)in.n_rest * 3 : nullptr, in.sh_deg);
 }
 
@@ -551,6 +567,21 @@ __device__ __forceinline__ void gather_tile_records(int area, uint32_t first, co
   }
 }
 
+// One Gaussian's row of N (1, 3 or 4) floats of an Adam group, stepped: ONE store per array -- parameters, first and second moments -- of the
+// row's width (dword / dwordx3 / dwordx4; rows are 4-byte aligned, which is all a global store needs).  A [P, 3] array's last row ends
+// the allocation: its store is 12 bytes, never 16.  Element by element with the three arrays interleaved -- the arrays may alias as far as
+// the compiler knows -- the 14 parameters left as 42 single-dword stores, each strided by 12 or 16 bytes across the wave.
+// (n: a constant of the unrolled loop over the groups)
+__device__ __forceinline__ void store_row(float* dst, const float* v, int n) {
+  if (n == 4) { const f4u w = {v[0], v[1], v[2], v[3]}; *(f4u*)dst = w; }
+  else if (n == 3) { const float w[3] = {v[0], v[1], v[2]}; __builtin_memcpy(dst, w, 12); }
+  else dst[0] = v[0];
+}
+__device__ __forceinline__ void store_adam_rows(int n, float* p, float* m, float* v, int idx, const float* rp, const float* rm, const float* rv) {
+  const size_t off = (size_t)idx * n;
+  store_row(p + off, rp, n); store_row(m + off, rm, n); store_row(v + off, rv, n);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 #define NPOSE 12  // dR (9, row-major) | dt (3)
 // stepped: (the map's in-kernel Adam, ma.on) the lane's parameters AFTER the step -- what the next iteration's projection reads
@@ -558,8 +589,10 @@ __device__ __forceinline__ void gather_tile_records(int area, uint32_t first, co
 // direction's share of d/d(mean), the sixth Adam group.  SHDIR (ABI 211) = the direction's source, sh_dir_vec: 0 -- its share goes into dm (the
 // camera-space mean: the means and the pose); 1 and 2 -- straight into d/d(xyz), and for 2 (world-frame means only) the camera centre's terms into
 // the pose rows: v = x + R^T t, so dL/dR_ij += t_i g_j and dL/dt += R g (g = dL/dv)
-template <bool TRACK, bool DIRECT, bool WORLD = false, bool SH = false, int SHDIR = 0>
-__device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const SlamIn& in, const int32_t* __restrict__ radii, const GeomView& g,
+// FUSED: the instance of slam_bwd_project_kernel -- api.hip launches it only with the in-kernel Adam on and without gradient output, and as
+// constants the two leave the first round of loads one straight path (a wait behind a join of paths is sized for the path with the fewest loads)
+template <bool TRACK, bool DIRECT, bool WORLD = false, bool SH = false, int SHDIR = 0, bool FUSED = false>
+__device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const SlamIn& in, const PoseProj& u, const int32_t* __restrict__ radii, const GeomView& g,
                                               uint32_t N_cap, const float* __restrict__ dsub, float* __restrict__ posepartial, const SlamGrads& out,
                                               const MapAdam& ma, RawGaussian* stepped, const uint32_t* __restrict__ ovf) {
   const int idx = blockIdx.x * SLAM_BWD_FB + threadIdx.x;
@@ -569,9 +602,14 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
   // header is only read at a later drained point (fused.py: lazy checks) leaves the map exactly as the last complete iteration left it.
   // (requested here, consumed only after the gather below: nothing waits for it)
   const uint32_t ovf_word = ovf != nullptr ? __builtin_nontemporal_load(ovf) : 0u;
-  const float* PV = cam.proj;
+  const float* PV = u.PV;
   const float Vi[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
-  const PoseDev ps = load_pose(in.pose);
+  const PoseDev ps = load_pose(u.pose);
+  // (kernel arguments the late phases used to fetch -- and wait for -- where they are used: read here, with the rest)
+  const uint8_t* const opt_mask = ma.opt_mask;
+  const bool adam_on = FUSED || ma.on != 0;
+  const bool grads_out = !FUSED && out.d_xyz != nullptr;
+  float* const st_radii = out.max_radii2D; float* const st_grad = out.grad_accum; float* const st_denom = out.denom;
   float cg[NPOSE];
 #pragma unroll
   for (int k = 0; k < NPOSE; k++) cg[k] = 0.f;
@@ -580,28 +618,55 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
   uint32_t cl_bits = 0;     // clamped[idx]: SH clamp bits 0-2 | (direct bins) empty-pair bits 4-7
   float4 sA = make_float4(0.f, 0.f, 0.f, 0.f), sB = sA;   // first 32 bytes of this Gaussian's splat record (xy, conic, opacity)
   float px3[3] = {0.f, 0.f, 0.f}, q_raw[4] = {1.f, 0.f, 0.f, 0.f}, ls_raw[3] = {0.f, 0.f, 0.f}, op_raw = 0.f;
+  // Adam state of this Gaussian's 14 parameters, its three densification statistics and its opt_mask byte: they depend on idx and on
+  // kernel arguments only, so they belong to the FIRST round of loads (below) and are held in registers across the gather -- ~45 VGPRs,
+  // DESIGN.md section 4.  Requested behind the gather, as they were, the state was a round trip of its own (9 of its 15 loads had to land
+  // before the chain rule started), each statistic a load - wait - store of its own, the mask byte one more.
+  constexpr int AG_OFF[5] = {0, 3, 6, 7, 10}, AG_N[5] = {3, 3, 1, 3, 4};
+  float ap[14], am[14], av[14];
+  float st_r, st_g, st_d;      // (like the state: set and read under the same uniform conditions, no value on the other path to merge with)
+  uint32_t maskb;
   {
     uint32_t first = 0;
     int area = 0;
-    // one round of independent loads for everything the gather needs (this kernel is a chain of memory latencies: every
-    // dependent step costs ~2 us).  A culled Gaussian has rect = 0 (and an unwritten splat record, read but never used).
+    // one round of independent loads for everything this lane reads but the gradient records (this kernel is a chain of memory
+    // latencies: every dependent step costs ~2 us).  A culled Gaussian has rect = 0 (and an unwritten splat record, read but never used).
+    // The lanes past the map's end (the last workgroup's) read Gaussian P - 1 and use nothing of it (their rectangle is emptied below): loads
+    // under a divergent branch come out of it through a merge of registers, whose copies of the wide loads' results were waits for the
+    // state in front of the gather.
     uint32_t r0 = 0, r1 = 0, toff = 0, btile = 0, clb = 0;
-    if (idx < P) {
-      clb = g.clamped[idx];
-      // the Gaussian's own parameters depend on nothing but idx: requested with the first round, they land while the records are
+    {
+      const int li = idx < P ? idx : P - 1;
+      // (what the gather's addresses are formed from comes first: the loads return in order, so the gather starts when these four have
+      //  landed and everything requested behind them lands while the records are summed)
+      clb = g.clamped[li];
+      r0 = g.rect[(size_t)li * 2]; r1 = g.rect[(size_t)li * 2 + 1];
+      toff = g.tileoff[li];
+      if (!DIRECT) btile = g.block_tiles[li >> 8];
+      __builtin_amdgcn_sched_barrier(0);      // (the scheduler orders independent loads by register pressure: without this, tileoff is the 13th)
+      rad = radii[li];
+      // the Gaussian's own parameters depend on nothing but li: requested with the first round, they land while the records are
       // gathered (the chain rule below used to start with a memory round trip of its own)
 #pragma unroll
-      for (int k = 0; k < 3; k++) { px3[k] = in.xyz[(size_t)idx * 3 + k]; ls_raw[k] = in.scaling[(size_t)idx * 3 + k]; }
+      for (int k = 0; k < 3; k++) { px3[k] = in.xyz[(size_t)li * 3 + k]; ls_raw[k] = in.scaling[(size_t)li * 3 + k]; }
 #pragma unroll
-      for (int k = 0; k < 4; k++) q_raw[k] = in.rotation[(size_t)idx * 4 + k];
-      op_raw = in.opacity[idx];
-      rad = radii[idx];
-      r0 = g.rect[(size_t)idx * 2]; r1 = g.rect[(size_t)idx * 2 + 1];
-      toff = g.tileoff[idx];
-      if (!DIRECT) btile = g.block_tiles[idx >> 8];
-      const float4* spl = (const float4*)(g.splat + (size_t)idx * SPLAT_F);
+      for (int k = 0; k < 4; k++) q_raw[k] = in.rotation[(size_t)li * 4 + k];
+      op_raw = in.opacity[li];
+      const float4* spl = (const float4*)(g.splat + (size_t)li * SPLAT_F);
       sA = spl[0]; sB = spl[1];
+      if (adam_on) {
+#pragma unroll
+        for (int gq = 0; gq < 5; gq++)
+#pragma unroll
+          for (int c = 0; c < AG_N[gq]; c++) {
+            const size_t off = (size_t)li * AG_N[gq] + c;
+            ap[AG_OFF[gq] + c] = ma.p[gq][off]; am[AG_OFF[gq] + c] = ma.m[gq][off]; av[AG_OFF[gq] + c] = ma.v[gq][off];
+          }
+        if (opt_mask) maskb = opt_mask[li];
+      }
+      if (st_radii) { st_r = st_radii[li]; st_g = st_grad[li]; st_d = st_denom[li]; }
     }
+    if (idx >= P) { r0 = 0; r1 = 0; }
     if (r1 != r0) {   // <=> radii > 0
       area = ((int)(r1 & 0xffff) - (int)(r0 & 0xffff)) * ((int)(r1 >> 16) - (int)(r0 >> 16));
       // first per-tile record of this Gaussian's pairs (contiguous, row-major over its tile rectangle): direct bins -- inside its
@@ -618,24 +683,11 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
   if (idx < P) {
     float dxyz[3] = {0.f, 0.f, 0.f}, dfd[3] = {0.f, 0.f, 0.f}, dls[3] = {0.f, 0.f, 0.f}, dqr[4] = {0.f, 0.f, 0.f, 0.f};
     float dlogit = 0.f, gnorm = 0.f;
-    // Adam state of this Gaussian's 14 parameters: independent of the gradient, so the 42 loads are issued here and land
-    // while the chain rule below is evaluated
-    constexpr int AG_OFF[5] = {0, 3, 6, 7, 10}, AG_N[5] = {3, 3, 1, 3, 4};
-    float ap[14], am[14], av[14];
     float shb[16], shg[3] = {0.f, 0.f, 0.f};      // (SH) basis values at this Gaussian's direction, clamp-masked colour gradient: zero for an invisible Gaussian
     float shw[3] = {0.f, 0.f, 0.f};               // (SH, SHDIR 1 / 2) dL/dv of the world-frame direction vector: the direction's share of d/d(xyz)
     if constexpr (SH) {
 #pragma unroll
       for (int k = 0; k < 16; k++) shb[k] = 0.f;
-    }
-    if (ma.on) {
-#pragma unroll
-      for (int gq = 0; gq < 5; gq++)
-#pragma unroll
-        for (int c = 0; c < AG_N[gq]; c++) {
-          const size_t off = (size_t)idx * AG_N[gq] + c;
-          ap[AG_OFF[gq] + c] = ma.p[gq][off]; am[AG_OFF[gq] + c] = ma.m[gq][off]; av[AG_OFF[gq] + c] = ma.v[gq][off];
-        }
     }
     if (rad > 0) {
       // moments -> d/dxy (pixel units) and d/dconic, with this splat's conic (composite.hip record layout)
@@ -759,7 +811,7 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
           cg[9 + i] += ps.R[i][0] * shw[0] + ps.R[i][1] * shw[1] + ps.R[i][2] * shw[2];
         }
       }
-      if (out.d_xyz || ma.on) {
+      if (grads_out || adam_on) {
 #pragma unroll
         for (int j = 0; j < 3; j++) dxyz[j] = ps.R[0][j] * dm[0] + ps.R[1][j] * dm[1] + ps.R[2][j] * dm[2] + (world ? dz_tot * ps.R[j][2] : 0.f);
         if constexpr (SH && SHDIR != 0) {
@@ -792,13 +844,15 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
         }
         dR_to_dq_raw(qn, qinv, dR, dqr);
       }
-      if (out.max_radii2D) {
-        out.max_radii2D[idx] = fmaxf(out.max_radii2D[idx], (float)rad);
-        out.grad_accum[idx] += gnorm;
-        out.denom[idx] += 1.f;
+      if (st_radii) {      // (the old values came with the first round; a Gaussian with rad == 0 keeps its three words untouched)
+        // (opaque up to here: the compiler would otherwise do the first arithmetic on each right behind its load -- and wait for it there)
+        asm volatile("" : "+v"(st_r), "+v"(st_g), "+v"(st_d));
+        st_radii[idx] = fmaxf(st_r, (float)rad);
+        st_grad[idx] = st_g + gnorm;
+        st_denom[idx] = st_d + 1.f;
       }
     }
-    if (out.d_xyz) {
+    if (grads_out) {
       out.d_xyz[(size_t)idx * 3] = dxyz[0]; out.d_xyz[(size_t)idx * 3 + 1] = dxyz[1]; out.d_xyz[(size_t)idx * 3 + 2] = dxyz[2];
       out.d_f_dc[(size_t)idx * 3] = dfd[0]; out.d_f_dc[(size_t)idx * 3 + 1] = dfd[1]; out.d_f_dc[(size_t)idx * 3 + 2] = dfd[2];
       out.d_opacity[idx] = dlogit;
@@ -818,23 +872,23 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
         }
       }
     }
-    if (ma.on) {
+    if (adam_on) {
       // the map's Adam step for this Gaussian (every Gaussian, visible or not: zero gradients still decay the moments)
-      const float keepg = (ma.opt_mask && ma.opt_mask[idx] == 0) ? 0.f : 1.f;     // bundle adjustment: masked-out Gaussians get a zero gradient
+      if (opt_mask) asm volatile("" : "+v"(maskb));      // (as the statistics: the compare stays here, not behind the byte's load)
+      const float keepg = (opt_mask && maskb == 0u) ? 0.f : 1.f;     // bundle adjustment: masked-out Gaussians get a zero gradient
       const float gr14[14] = {keepg * dxyz[0], keepg * dxyz[1], keepg * dxyz[2], keepg * dfd[0], keepg * dfd[1], keepg * dfd[2], keepg * dlogit,
                               keepg * dls[0], keepg * dls[1], keepg * dls[2], keepg * dqr[0], keepg * dqr[1], keepg * dqr[2], keepg * dqr[3]};
       if (!skip) {
 #pragma unroll
-      for (int gq = 0; gq < 5; gq++)
+      for (int gq = 0; gq < 5; gq++) {
 #pragma unroll
         for (int c = 0; c < AG_N[gq]; c++) {
           const int q = AG_OFF[gq] + c;
-          const size_t off = (size_t)idx * AG_N[gq] + c;
           const AdamElem r = adam_elem(ap[q], am[q], av[q], gr14[q], ma.omb1, ma.beta2, ma.omb2, ma.bc2s, ma.eps, ma.step_size[gq]);
-          ma.m[gq][off] = r.m; ma.v[gq][off] = r.v;
-          ap[q] = r.p;
-          ma.p[gq][off] = ap[q];
+          am[q] = r.m; av[q] = r.v; ap[q] = r.p;
         }
+        store_adam_rows(AG_N[gq], ma.p[gq], ma.m[gq], ma.v[gq], idx, ap + AG_OFF[gq], am + AG_OFF[gq], av + AG_OFF[gq]);
+      }
       if constexpr (SH) {
         if (ma.rp) {      // the sixth group: every f_rest row steps (zero gradient beyond the active degree / for an invisible Gaussian: the moments decay)
           const int nb = (in.sh_deg + 1) * (in.sh_deg + 1);
@@ -898,12 +952,14 @@ slam_bwd_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radi
                         const float* __restrict__ dsub, SlamGrads out, MapAdam ma, const float* __restrict__ next_pose, uint32_t cap,
                         uint32_t rec_cap, int slot_bits) {
   extern __shared__ uint32_t hist[];
+  // both views' uniforms before the first store of the kernel: the projection half used to fetch next_pose behind the Adam stores
+  const PoseProj u = load_pose_proj(in.pose, cam.proj), un = load_pose_proj(next_pose, cam.proj);
   const int idx = slam_bin_prologue(cam, iv, cap, hist);
   RawGaussian rg = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f};
   // (the overflow word as the backward compositor of this iteration found it: the binning half below may set the live word while
   //  workgroups of this half are still starting, and a partially stepped map is worse than either outcome)
-  slam_bwd_body<false, true, WORLD>(cam, P, in, radii, g, N_cap, dsub, nullptr, out, ma, &rg, &iv.hdr->overflow_seen);
-  const Projected pr = slam_project_vals(cam, idx < P, idx, next_pose, in.isotropic != 0, rg, radii, g, WORLD);
+  slam_bwd_body<false, true, WORLD, false, 0, true>(cam, P, in, u, radii, g, N_cap, dsub, nullptr, out, ma, &rg, &iv.hdr->overflow_seen);
+  const Projected pr = slam_project_vals(cam, idx < P, idx, un.pose, un.PV, in.isotropic != 0, rg, radii, g, WORLD);
   slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
 }
 
@@ -930,6 +986,7 @@ slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ rad
                          const float* __restrict__ next_pose, uint32_t cap, uint32_t rec_cap, int slot_bits) {
   static_assert(!SH || WORLD == (SHDIR == 2), "world-frame means take the direction from the camera centre, pre-transformed ones from the mean or the origin");
   extern __shared__ uint32_t hist[];
+  const PoseProj un = load_pose_proj(next_pose, cam.proj);      // (before the first store of the kernel)
   const int idx = slam_bin_prologue(cam, iv, cap, hist);
   RawGaussian rg = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f};
   float rs[SH ? 45 : 1];      // (SH) the stepped f_rest rows the colour reads: [k - 1][3] for k < (sh_deg + 1)^2, compile-time indices only
@@ -951,14 +1008,15 @@ slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ rad
 #pragma unroll
       for (int c = 0; c < AG_N[gq]; c++) {
         const int q = AG_OFF[gq] + c;
-        const size_t off = (size_t)idx * AG_N[gq] + c;
         const float grd = keepg * g14[q];
         AdamElem r;
         adam_moments(am[q], av[q], grd, ma.omb1, ma.beta2, ma.omb2, r);
-        ma.m[gq][off] = r.m; ma.v[gq][off] = r.v;
+        am[q] = r.m; av[q] = r.v;
         ap[q] = adam_param(ap[q], r, ma.bc2s, ma.eps, ma.step_size[gq]);
-        ma.p[gq][off] = ap[q];
       }
+#pragma unroll
+    for (int gq = 0; gq < 5; gq++)
+      store_adam_rows(AG_N[gq], ma.p[gq], ma.m[gq], ma.v[gq], idx, ap + AG_OFF[gq], am + AG_OFF[gq], av + AG_OFF[gq]);
     if constexpr (SH) {
       // the sixth group, row by row (slam_bwd_body's arithmetic): rows the active degree does not reach take a zero gradient
       const int nb = (in.sh_deg + 1) * (in.sh_deg + 1);
@@ -987,10 +1045,10 @@ slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ rad
     for (int k = 0; k < 4; k++) rg.q[k] = ap[10 + k];
   }
   if constexpr (SH) {
-    const Projected pr = slam_project_vals<true, SHDIR>(cam, idx < P, idx, next_pose, in.isotropic != 0, rg, radii, g, WORLD, false, rs, in.sh_deg);
+    const Projected pr = slam_project_vals<true, SHDIR>(cam, idx < P, idx, un.pose, un.PV, in.isotropic != 0, rg, radii, g, WORLD, false, rs, in.sh_deg);
     slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
   } else {
-    const Projected pr = slam_project_vals(cam, idx < P, idx, next_pose, in.isotropic != 0, rg, radii, g, WORLD);
+    const Projected pr = slam_project_vals(cam, idx < P, idx, un.pose, un.PV, in.isotropic != 0, rg, radii, g, WORLD);
     slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
   }
 }
@@ -1188,7 +1246,8 @@ __global__ void __launch_bounds__(SLAM_BWD_FB)
 slam_preprocess_bwd_kernel(CamDev cam, int P, SlamIn in, const int32_t* __restrict__ radii, GeomView g, BinView bn, uint32_t N_cap,
                            const float* __restrict__ dsub, float* __restrict__ posepartial, SlamGrads out, MapAdam ma,
                            const uint32_t* __restrict__ ovf) {
-  slam_bwd_body<TRACK, DIRECT, WORLD, SH, SHDIR>(cam, P, in, radii, g, N_cap, dsub, posepartial, out, ma, nullptr, ovf);
+  const PoseProj u = load_pose_proj(in.pose, cam.proj);
+  slam_bwd_body<TRACK, DIRECT, WORLD, SH, SHDIR>(cam, P, in, u, radii, g, N_cap, dsub, posepartial, out, ma, nullptr, ovf);
 }
 
 // The pose finish alone, over the per-TILE rows the tracking compositor's pose chain wrote (composite.hip): rows[nrows][32] floats.

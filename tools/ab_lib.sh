@@ -6,7 +6,9 @@ A="--steps 10 --warmup 2 --no-cpu-baseline --full-seed-steps 0 --steady-frames 0
 for rep in 1 2; do
   for t in product "$@"; do
     if [ $t = product ]; then L=""; else L="$GRAFT_REPO_ROOT/mm3dgs_slam_amd/csrc/variants/libmm3dgs_hip_$t.so"; fi
-    rm -rf /tmp/p_ab; MM3DGS_LIB=$L rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_ab -o ks -- python bench.py $A > /tmp/ks_ab.out 2>&1
+    # (a run that fails or outlives its limit ends the comparison: nothing more is started on the device)
+    rm -rf /tmp/p_ab; MM3DGS_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_ab -o ks -- python bench.py $A > /tmp/ks_ab.out 2>&1 \
+      || { echo "$t: the profiled run failed (exit $?)"; tail -5 /tmp/ks_ab.out; exit 1; }
     python - "$t" <<'PY'
 import csv, glob, sys, re
 f = glob.glob("/tmp/p_ab/**/*kernel_stats.csv", recursive=True)[0]

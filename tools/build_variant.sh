@@ -8,7 +8,7 @@ TAG=$1; shift
 SRC=$(cd "$(dirname "$0")/../mm3dgs_slam_amd/csrc" && pwd)
 OBJ=/tmp/mm3dgs_variant_$TAG; mkdir -p $OBJ $SRC/variants
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -fno-slp-vectorize -Wall -Wno-unused-function $*"
-for f in api preprocess binning composite fused loss compact; do
+for f in api preprocess binning composite fused loss compact align; do
   /opt/rocm/bin/hipcc $FLAGS -c $SRC/$f.hip -o $OBJ/$f.o &
 done
 wait
