@@ -435,6 +435,24 @@ size_t mm3dgs_align_depth_work_bytes(int H, int W);
 int mm3dgs_align_depth(int H, int W, const float* est /*[H,W]*/, const float* depth /*[H,W]*/, const float* silhouette_or_null /*[H,W]*/,
                        float sil_min, float est_min, void* work, double* fit /*[16], device*/, float* out_or_null /*[H,W]*/, void* stream);
 
+/* ---- frame ingest: raw sensor bytes -> the two images the SLAM loops consume, in one launch ------------------------------------------
+ * rgb: uint8 interleaved [Hs,Ws,3] on the device, any byte alignment; depth_or_null: uint16 [Hs,Ws], 2-byte aligned.  out_color [3,H,W]
+ * float32 in [0,1]; out_depth_or_null [H,W] float32 in metres, required iff depth is given (a colour-only call passes NULL for both).
+ * With sx = (double)Ws / W, sy = (double)Hs / H:
+ *   colour, per output pixel (y, x) and channel: fx = (x + 0.5) sx - 0.5 in double, x0 = floor(fx), a = fx - x0; x0 < 0: x0 = 0, a = 0;
+ *     x0 >= Ws - 1: x0 = Ws - 1, a = 0; x1 = min(x0 + 1, Ws - 1); the same rule gives y0, y1, b; v = the bilinear blend of the four bytes
+ *     with the weights a, b; out = (float)v / 255.0f, the correctly rounded float32 division.
+ *   depth: xs = min((int)floor(x sx), Ws - 1), ys likewise, products in double; out = (float)((double)d / png_depth_scale), the double
+ *     quotient rounded once to float32.  Zero stays zero.
+ * This is meant to be the reference's cv2.resize on float64 input (INTER_LINEAR / INTER_NEAREST) followed by its casts; the match to cv2
+ * itself is unchecked (cv2 was not available).  Against the host path of the Python package (dataset.ingest_host): depth bit-exact at
+ * every shape; colour bit-exact whenever Ws / W and Hs / H are integers (a, b are 0 or 0.5: v is exact), within 1e-6 otherwise.
+ * Every source index is clamped: nothing outside [Hs,Ws] is read at any ratio.  One launch on `stream`, no atomics, no host
+ * synchronisation.  -1 (nothing is launched): a non-positive size or more than 2^30 pixels on either side, a NULL rgb or out_color, depth
+ * without out_depth or the reverse, a png_depth_scale that is not finite and positive, a misaligned depth (2) or output (4). */
+int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb /*[Hs,Ws,3]*/, const uint16_t* depth_or_null /*[Hs,Ws]*/, double png_depth_scale,
+                        int H, int W, float* out_color /*[3,H,W]*/, float* out_depth_or_null /*[H,W]*/, void* stream);
+
 /* ---- optional per-kernel timing (HIP events recorded on the caller's stream around each launch) ------------
  * Used by bench.py's roofline leg.  mm3dgs_profile_read() waits for the recorded events, returns the number of
  * (timed) launches and their summed duration since the previous read, and resets the counters. */
@@ -493,7 +511,8 @@ const char* mm3dgs_last_error(void);
    213: mm3dgs_propagate_imu (the tracker's IMU pose prediction on the device; no struct changes)
         later, without a new number (purely additive: no struct, signature or size of 213 changes, and tests/test_imu_predict.py holds the
         library at exactly 213): mm3dgs_align_depth_work_bytes / mm3dgs_align_depth (the monocular depth estimate's least-squares fit to
-        the map, its fit record and its application on the device); a caller that needs them looks the symbols up */
+        the map, its fit record and its application on the device); mm3dgs_ingest_frame (raw uint8 RGB + uint16 depth -> the float32 frame,
+        one launch); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

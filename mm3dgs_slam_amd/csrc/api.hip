@@ -709,6 +709,21 @@ int mm3dgs_align_depth(int H, int W, const float* est, const float* depth, const
   return check_launch("align_depth");
 }
 
+int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
+                        float* out_color, float* out_depth_or_null, void* stream) {
+  if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);
+  if ((size_t)Hs * (size_t)Ws > ((size_t)1 << 30) || (size_t)H * (size_t)W > ((size_t)1 << 30))
+    return fail(-1, "ingest_frame: source %d x %d or output %d x %d has more than 2^30 pixels", Hs, Ws, H, W);
+  if (!rgb || !out_color) return fail(-1, "ingest_frame: NULL argument (rgb and out_color are required)");
+  if ((depth_or_null != nullptr) != (out_depth_or_null != nullptr))
+    return fail(-1, "ingest_frame: depth and out_depth must both be given or both be NULL");
+  if (!(png_depth_scale > 0.0) || !isfinite(png_depth_scale)) return fail(-1, "ingest_frame: png_depth_scale = %g (must be finite and positive)", png_depth_scale);
+  if (((uintptr_t)depth_or_null & 1) || (((uintptr_t)out_color | (uintptr_t)out_depth_or_null) & 3))
+    return fail(-1, "ingest_frame: depth must be 2-byte aligned, out_color and out_depth 4-byte aligned");
+  launch_ingest_frame(Hs, Ws, rgb, depth_or_null, png_depth_scale, H, W, out_color, out_depth_or_null, (hipStream_t)stream);
+  return check_launch("ingest_frame");
+}
+
 int mm3dgs_prune_mask(int P, const float* opacity, const float* log_scales, const float* max_radii2D, float min_opacity, float max_scale,
                       float max_screen_size, uint8_t* keep, uint32_t* n_pruned_accum, void* stream) {
   if (P < 0) return fail(-1, "P < 0");

@@ -6,9 +6,9 @@ Harness outputs in the reference's formats: ``save_map`` = ``out
 (``SLAM.py:286-292``), ``save_iterations`` checkpoints inside ``run`` (``:488-492``) and the final map (``:497-500``),
 ``save_results`` = ``outputdir/results.npz`` with the reference's key set (``:294-373``: pose_est, pose_gt, keyframes, ate_rmse,
 psnr_list, ssim_list, lpips_list, avg_tracking_it_time, avg_mapping_it_time), and resuming from a checkpoint when the
-configuration carries ``iteration`` (``:90-104`` map + poses, ``slam/mapper.py:65-71`` keyframes + covisibility graph).  Dataset
-loaders, MiDaS depth alignment, debug videos and LPIPS (a downloaded network; its list stays empty) are out of scope
-(SURVEY.md section 2)."""
+configuration carries ``iteration`` (``:90-104`` map + poses, ``slam/mapper.py:65-71`` keyframes + covisibility graph).  Frame
+sources: ``SyntheticSequence`` here, recorded TUM / UT-MM directories in ``dataset.RecordedSequence``.  The Replica and other loaders, the
+monocular depth network, debug videos and LPIPS (a downloaded network; its list stays empty) are out of scope."""
 from __future__ import annotations
 
 import math

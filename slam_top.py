@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """Entry point with the reference's command line (`python slam_top.py --config X.yml`, reference slam_top.py:30-42).
 
-The YAML schema is the reference's (configs/TUM.yml, configs/UTMM.yml).  No dataset loader is in scope of this build
-(SURVEY.md section 2), so the frames come from the in-memory synthetic RGB-D sequence (`dataset: synthetic`, the
-default of `mm3dgs_slam_amd.config.default_config`); a reference config whose `dataset` is tum / utmm / replica is
-accepted for its hot-path settings (iteration budgets, learning rates, pipeline flags, intrinsics) and run on the
-synthetic sequence as well.  `use_gt_depth: false` (what configs/TUM.yml ships) and `tracking.dynamics_model: imu` are honoured: the
+The YAML schema is the reference's (configs/TUM.yml, configs/UTMM.yml).  A config with a non-empty `inputdir` and `dataset: tum` or
+`utmm` is read from disk (`mm3dgs_slam_amd.dataset.RecordedSequence`: TUM-format / UT-MM-format directory `inputdir/scene`, all
+frames or `--frames N` of them; `ingest_on_device` and `prefetch` choose how a frame gets to the device).  Every other config -- the
+default `dataset: synthetic`, and the two configs the reference ships, whose `inputdir:` is empty -- runs on the in-memory synthetic
+RGB-D sequence (10 frames unless `--frames` says otherwise) with the config's hot-path settings (iteration budgets, learning rates,
+pipeline flags, intrinsics); Replica, EXR depth, colour undistortion and the monocular depth network stay out of scope.  On the synthetic
+sequence `use_gt_depth: false` (what configs/TUM.yml ships) and `tracking.dynamics_model: imu` are honoured: the
 sequence provides a stand-in for the monocular estimate (`SyntheticSequence.est`, aligned per frame like slam/SLAM.py:411-448) and
-synthetic IMU rows (`SyntheticSequence.imu`); only `niqe_kf` is forced off (it needs a downloaded network).
+synthetic IMU rows (`SyntheticSequence.imu`); a recorded sequence has no estimate, so the sensor depth is used.  Only `niqe_kf` is forced
+off (it needs a downloaded network).
 
 Outputs in `outputdir`, in the reference's formats (slam/SLAM.py:286-373,488-500): `point_cloud/iteration_<n>/point_cloud.ply` for
 every frame index in `save_iterations` and for the final map (attribute layout of slam/gaussian_model.py:205-257), `results.npz`
@@ -35,14 +38,30 @@ def seed_everything(seed=0):
         torch.cuda.manual_seed_all(seed)
 
 
+def sequence_source(cfg):
+    """"recorded" when the merged config names a sequence on disk (non-empty `inputdir`, `dataset` tum / utmm), else "synthetic"."""
+    from mm3dgs_slam_amd.dataset import is_recorded
+    return "recorded" if is_recorded(cfg) else "synthetic"
+
+
+def build_sequence(cfg, frames=None, gaussians=150000):
+    """The frame source of a run: the directory `inputdir/scene` (all frames, or the first `frames`), or `frames` (default 10) synthetic
+    frames.  A recorded sequence writes its scaled intrinsics into `cfg["cam"]`: build it before the SLAM object."""
+    if sequence_source(cfg) == "recorded":
+        from mm3dgs_slam_amd.dataset import RecordedSequence
+        return RecordedSequence(cfg, frames=frames)
+    from mm3dgs_slam_amd.slam import SyntheticSequence
+    return SyntheticSequence(cfg, 10 if frames is None else frames, gaussians, seed=0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=None, help="YAML config in the reference's schema")
-    ap.add_argument("--frames", type=int, default=10)
+    ap.add_argument("--frames", type=int, default=None, help="frames to run (default: 10 synthetic frames, or the whole recorded sequence)")
     ap.add_argument("--gaussians", type=int, default=150000, help="size of the synthetic ground-truth scene")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
-    from mm3dgs_slam_amd.slam import SLAM, SyntheticSequence
+    from mm3dgs_slam_amd.slam import SLAM
     seed_everything(0)
     cfg = default_config()
     if args.config:
@@ -55,10 +74,10 @@ def main():
     cfg["mapping"]["niqe_kf"] = False
     dbg = dict(cfg.get("debug") or {})
     cfg["debug"] = {"get_runtime_stats": bool(dbg.get("get_runtime_stats", False)), "create_video": False, "save_keyframes": False}
-    cfg.setdefault("outputdir", "output/synthetic")
+    cfg.setdefault("outputdir", "output/" + (str(cfg.get("scene") or "recorded") if sequence_source(cfg) == "recorded" else "synthetic"))
     outdir = cfg["outputdir"]
     os.makedirs(outdir, exist_ok=True)
-    seq = SyntheticSequence(cfg, args.frames, args.gaussians, seed=0)
+    seq = build_sequence(cfg, args.frames, args.gaussians)
     slam = SLAM(cfg, seq)
     times, t_last = [], [time.perf_counter()]
 
