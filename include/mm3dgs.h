@@ -453,6 +453,24 @@ int mm3dgs_align_depth(int H, int W, const float* est /*[H,W]*/, const float* de
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb /*[Hs,Ws,3]*/, const uint16_t* depth_or_null /*[Hs,Ws]*/, double png_depth_scale,
                         int H, int W, float* out_color /*[3,H,W]*/, float* out_depth_or_null /*[H,W]*/, void* stream);
 
+/* ---- monocular depth estimate: the depth network's raw output -> the float32 estimate at frame size, in one launch -------------------
+ * est: [Hs,Ws] on the device, row-major, dtype 0 float32, 1 float16 (IEEE binary16), 2 uint16; aligned to its element size.  out: [H,W]
+ * float32, 4-byte aligned.  This is the last step of the reference's MiDaS.estimate_depth (utils/depth_utils.py): F.interpolate(prediction,
+ * size = (H, W), mode = "bilinear", align_corners = False); the network itself is not part of this library.  Per output pixel (y, x), every
+ * operation in double, each source value widened exactly:
+ *   Hs == H and Ws == W: out = (float)(p[y][x] * scale) -- the value itself, no blend: a non-finite neighbour does not spread.
+ *   otherwise: (x0, x1, a) and (y0, y1, b) by the colour rule of mm3dgs_ingest_frame (sx = (double)Ws / W, fx = (x + 0.5) sx - 0.5, ...);
+ *     v = (1 - b) ((1 - a) p00 + a p01) + b ((1 - a) p10 + a p11), evaluated as written, no fused multiply-add; out = (float)(v * scale):
+ *     one rounding to float32.
+ * Non-finite source values are not special-cased: they go through these operators (0 * inf is NaN).  Against the host path of the Python
+ * package (dataset.ingest_est_host), which restates the same operators in float64: bit-exact at equal sizes, within one float32 ulp of the
+ * largest tap elsewhere, the same set of non-finite outputs.  Every source index is clamped: nothing outside [Hs,Ws] is read at any ratio.
+ * One launch on `stream`, no atomics, no host synchronisation.  -1 (nothing is launched): a non-positive size or more than 2^30 pixels on
+ * either side, a NULL est or out, a dtype outside 0..2, an est that is not aligned to its element size or an out that is not 4-byte
+ * aligned, a scale that is not finite and positive. */
+int mm3dgs_ingest_est(int Hs, int Ws, const void* est /*[Hs,Ws]*/, int dtype /*0 float32, 1 float16, 2 uint16*/, double scale, int H, int W,
+                      float* out /*[H,W]*/, void* stream);
+
 /* ---- optional per-kernel timing (HIP events recorded on the caller's stream around each launch) ------------
  * Used by bench.py's roofline leg.  mm3dgs_profile_read() waits for the recorded events, returns the number of
  * (timed) launches and their summed duration since the previous read, and resets the counters. */
@@ -512,7 +530,8 @@ const char* mm3dgs_last_error(void);
         later, without a new number (purely additive: no struct, signature or size of 213 changes, and tests/test_imu_predict.py holds the
         library at exactly 213): mm3dgs_align_depth_work_bytes / mm3dgs_align_depth (the monocular depth estimate's least-squares fit to
         the map, its fit record and its application on the device); mm3dgs_ingest_frame (raw uint8 RGB + uint16 depth -> the float32 frame,
-        one launch); a caller that needs them looks the symbols up */
+        one launch); mm3dgs_ingest_est (the monocular depth network's raw output, float32 / float16 / uint16 at any size -> the float32
+        estimate at frame size, one launch); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

@@ -724,6 +724,19 @@ int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* dept
   return check_launch("ingest_frame");
 }
 
+int mm3dgs_ingest_est(int Hs, int Ws, const void* est, int dtype, double scale, int H, int W, float* out, void* stream) {
+  if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_est: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);
+  if ((size_t)Hs * (size_t)Ws > ((size_t)1 << 30) || (size_t)H * (size_t)W > ((size_t)1 << 30))
+    return fail(-1, "ingest_est: source %d x %d or output %d x %d has more than 2^30 pixels", Hs, Ws, H, W);
+  if (!est || !out) return fail(-1, "ingest_est: NULL argument (est and out are required)");
+  if (dtype < 0 || dtype > 2) return fail(-1, "ingest_est: dtype = %d (0 float32, 1 float16, 2 uint16)", dtype);
+  if (!(scale > 0.0) || !isfinite(scale)) return fail(-1, "ingest_est: scale = %g (must be finite and positive)", scale);
+  if (((uintptr_t)est & (dtype == 0 ? 3 : 1)) || ((uintptr_t)out & 3))
+    return fail(-1, "ingest_est: est must be aligned to its element size (%d bytes), out to 4 bytes", dtype == 0 ? 4 : 2);
+  launch_ingest_est(Hs, Ws, est, dtype, scale, H, W, out, (hipStream_t)stream);
+  return check_launch("ingest_est");
+}
+
 int mm3dgs_prune_mask(int P, const float* opacity, const float* log_scales, const float* max_radii2D, float min_opacity, float max_scale,
                       float max_screen_size, uint8_t* keep, uint32_t* n_pruned_accum, void* stream) {
   if (P < 0) return fail(-1, "P < 0");

@@ -123,3 +123,6 @@ void launch_align_depth(int H, int W, const float* est, const float* depth, cons
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,
                          float* out_depth, hipStream_t s);
+// the monocular depth estimate (ingest.hip): raw [Hs,Ws] float32 (dtype 0) / float16 (1) / uint16 (2) -> float32 [H,W], bilinear, times
+// scale, one launch; arguments as the entry point has checked them
+void launch_ingest_est(int Hs, int Ws, const void* est, int dtype, double scale, int H, int W, float* out, hipStream_t s);

@@ -20,7 +20,19 @@
 //   ingest_scalar_kernel   everything else (any ratio, any width, any byte alignment of rgb): one lane per output pixel, byte loads
 //                          at clamped indices -- no lane reads outside [Hs,Ws] whatever the ratio.  Always correct; the native kernel
 //                          gives the same bits where both apply (a = b = 0: v is the byte itself).
+//
+// Monocular depth estimate (mm3dgs_ingest_est; host path: dataset.py ingest_est_host): the depth network's raw output [Hs,Ws] as float32,
+// float16 or uint16 becomes the float32 [H,W] estimate, the reference's last step (utils/depth_utils.py MiDaS.estimate_depth: F.interpolate,
+// bilinear, align_corners=False) in ONE launch.  The colour rule above on one channel, then v * scale, the double product rounded once:
+//   Hs == H and Ws == W   out = (float)((double)p * scale): the value itself, no blend, so a non-finite neighbour does not spread;
+//   otherwise             out = (float)(((1 - b) ((1 - a) p00 + a p01) + b ((1 - a) p10 + a p11)) * scale), all in double.
+//   ingest_est_packed_kernel   equal sizes, W % 4 == 0, source 16-byte (float32) / 8-byte (16-bit types) and output 16-byte aligned: one lane
+//                              per four pixels, one vector load and one float4 store.
+//   ingest_est_kernel          everything else: one lane per output pixel, four taps at clamped indices.  The same bits as the packed
+//                              kernel where both apply.
+// ~1.6 MB of traffic at 384 x 512 float16 -> 480 x 640: launch-latency bound like the frame kernels.  Not timed yet.
 #include <math.h>
+#include <hip/hip_fp16.h>
 #include "mm3dgs_common.h"
 #include "fused_api.h"
 
@@ -111,4 +123,80 @@ void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* dep
   const size_t blocks = (size_t)blocks_per_row * (size_t)H;
   hipLaunchKernelGGL(ingest_scalar_kernel, dim3((unsigned)blocks), dim3(INGEST_WG), 0, s, Hs, Ws, rgb, depth, depth_scale, H, W, blocks_per_row,
                      out_color, out_depth);
+}
+
+// ---- monocular depth estimate ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double est_value(float v) { return (double)v; }
+__device__ __forceinline__ double est_value(__half v) { return (double)__half2float(v); }      // (exact: every float16 is a float32)
+__device__ __forceinline__ double est_value(uint16_t v) { return (double)v; }
+
+template <typename T>
+__global__ void __launch_bounds__(INGEST_WG)
+ingest_est_kernel(int Hs, int Ws, const T* __restrict__ est, double scale, int H, int W, int blocks_per_row, float* __restrict__ out) {
+  const int y = (int)(blockIdx.x / (unsigned)blocks_per_row);
+  const int x = (int)(blockIdx.x % (unsigned)blocks_per_row) * INGEST_WG + (int)threadIdx.x;
+  if (x >= W || y >= H) return;
+  const size_t o = (size_t)y * (size_t)W + (size_t)x;
+  if (Hs == H && Ws == W) {
+    out[o] = (float)(est_value(est[o]) * scale);
+    return;
+  }
+  const double sx = (double)Ws / (double)W, sy = (double)Hs / (double)H;
+  int x0, x1, y0, y1;
+  double a, b;
+  ingest_axis(x, sx, Ws, x0, x1, a);
+  ingest_axis(y, sy, Hs, y0, y1, b);
+  const size_t r0 = (size_t)y0 * (size_t)Ws, r1 = (size_t)y1 * (size_t)Ws;
+  const double p00 = est_value(est[r0 + (size_t)x0]), p01 = est_value(est[r0 + (size_t)x1]);
+  const double p10 = est_value(est[r1 + (size_t)x0]), p11 = est_value(est[r1 + (size_t)x1]);
+  const double top = (1.0 - a) * p00 + a * p01;
+  const double bot = (1.0 - a) * p10 + a * p11;
+  const double v = (1.0 - b) * top + b * bot;
+  out[o] = (float)(v * scale);
+}
+
+// four consecutive source values of one lane: a 16-byte load of float32, an 8-byte load of the 16-bit types
+__device__ __forceinline__ void est_load4(const float* p, size_t q, double v[4]) {
+  const float4 f = reinterpret_cast<const float4*>(p)[q];
+  v[0] = (double)f.x; v[1] = (double)f.y; v[2] = (double)f.z; v[3] = (double)f.w;
+}
+__device__ __forceinline__ void est_load4(const uint16_t* p, size_t q, double v[4]) {
+  const uint2 d = reinterpret_cast<const uint2*>(p)[q];      // little endian: the first value in the low half
+  v[0] = (double)(d.x & 0xffffu); v[1] = (double)(d.x >> 16); v[2] = (double)(d.y & 0xffffu); v[3] = (double)(d.y >> 16);
+}
+__device__ __forceinline__ void est_load4(const __half* p, size_t q, double v[4]) {
+  const uint2 d = reinterpret_cast<const uint2*>(p)[q];
+  v[0] = est_value(__ushort_as_half((unsigned short)(d.x & 0xffffu))); v[1] = est_value(__ushort_as_half((unsigned short)(d.x >> 16)));
+  v[2] = est_value(__ushort_as_half((unsigned short)(d.y & 0xffffu))); v[3] = est_value(__ushort_as_half((unsigned short)(d.y >> 16)));
+}
+
+// n_quads = H W / 4 groups of four pixels at equal sizes (W % 4 == 0)
+template <typename T>
+__global__ void __launch_bounds__(INGEST_WG)
+ingest_est_packed_kernel(size_t n_quads, const T* __restrict__ est, double scale, float4* __restrict__ out) {
+  const size_t q = (size_t)blockIdx.x * INGEST_WG + threadIdx.x;
+  if (q >= n_quads) return;
+  double v[4];
+  est_load4(est, q, v);
+  out[q] = make_float4((float)(v[0] * scale), (float)(v[1] * scale), (float)(v[2] * scale), (float)(v[3] * scale));
+}
+
+template <typename T>
+static void launch_ingest_est_t(int Hs, int Ws, const T* est, double scale, int H, int W, float* out, hipStream_t s) {
+  const uintptr_t src_mask = sizeof(T) == 4 ? 15 : 7;
+  if (Hs == H && Ws == W && (W & 3) == 0 && ((uintptr_t)est & src_mask) == 0 && ((uintptr_t)out & 15) == 0) {
+    const size_t n_quads = (size_t)H * (size_t)W / 4;
+    const size_t blocks = (n_quads + INGEST_WG - 1) / INGEST_WG;
+    hipLaunchKernelGGL(ingest_est_packed_kernel<T>, dim3((unsigned)blocks), dim3(INGEST_WG), 0, s, n_quads, est, scale, (float4*)out);
+    return;
+  }
+  const int blocks_per_row = (W + INGEST_WG - 1) / INGEST_WG;
+  const size_t blocks = (size_t)blocks_per_row * (size_t)H;
+  hipLaunchKernelGGL(ingest_est_kernel<T>, dim3((unsigned)blocks), dim3(INGEST_WG), 0, s, Hs, Ws, est, scale, H, W, blocks_per_row, out);
+}
+
+void launch_ingest_est(int Hs, int Ws, const void* est, int dtype, double scale, int H, int W, float* out, hipStream_t s) {
+  if (dtype == 0) launch_ingest_est_t(Hs, Ws, (const float*)est, scale, H, W, out, s);
+  else if (dtype == 1) launch_ingest_est_t(Hs, Ws, (const __half*)est, scale, H, W, out, s);
+  else launch_ingest_est_t(Hs, Ws, (const uint16_t*)est, scale, H, W, out, s);
 }

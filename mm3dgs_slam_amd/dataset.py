@@ -1,7 +1,8 @@
 """Recorded RGB-D sequences from disk: TUM-format and UT-MM-format directories (reference ``gradslam_datasets/tum.py``, ``utmm.py``,
 ``basedataset.py``), as a frame source with the protocol of ``slam.SyntheticSequence`` (``len``, ``seq[i] -> (color [3,H,W], depth
-[H,W], gt_pose [7] world->camera)`` on ``cfg["device"]``, ``poses``, ``tstamps``, ``tf``, ``imu(i)``; no ``est``: the monocular
-network is out of scope, so with ``use_gt_depth: false`` the loop uses the sensor depth).
+[H,W], gt_pose [7] world->camera)`` on ``cfg["device"]``, ``poses``, ``tstamps``, ``tf``, ``imu(i)``, and -- only with the config key
+``est_depth_dir`` -- ``est(i) -> [H,W]``, the monocular depth estimate; without the key there is no attribute ``est`` and with
+``use_gt_depth: false`` the loop uses the sensor depth).
 
 Directory (``inputdir/scene``): ``rgb.txt``, ``depth.txt``, ``groundtruth.txt`` or ``pose.txt`` (first line skipped), for UT-MM also
 ``imu.txt`` and ``tf.txt``; lines are ``stamp name`` / ``stamp tx ty tz qx qy qz qw`` / ``stamp <imu columns>``, separated by single
@@ -26,7 +27,18 @@ Frame ingest, chosen by ``cfg["ingest_on_device"]``:
          that is waited on before the slot is rewritten: a frame in flight is never overwritten.
 The formulas are meant to be ``cv2.resize``'s (INTER_LINEAR / INTER_NEAREST on float64 input); cv2 was not available, so that match is
 unchecked.  ``prefetch`` (default on): ONE worker thread decodes frame i + 1 into the free slot while frame i is tracked and mapped; it
-touches host memory only, and a prefetched frame is only a hint -- any access order gives the same frames."""
+touches host memory only, and a prefetched frame is only a hint -- any access order gives the same frames.
+
+Monocular depth estimates (``est_depth_dir``, a folder inside ``inputdir/scene``).  The depth network (MiDaS through torch.hub in the
+reference) stays out of scope; its raw per-frame output is read from disk and the reference's last step -- ``F.interpolate(prediction,
+size=(H, W), mode="bilinear", align_corners=False)`` of ``utils/depth_utils.py`` -- is done here.  The estimate of a kept colour frame is
+the file whose stem is the stem of the colour image's basename (``rgb/1305031452.791720.png`` -> ``est_depth/1305031452.791720.npy``, else
+``.png``): a ``.npy`` holds a 2-D C-contiguous float32 or float16 array at any resolution, used as it is; a ``.png`` is 16-bit greyscale
+(what MiDaS' run.py writes), its integers times ``cam.est_depth_scale`` (default 1).  Every kept frame needs its file (checked in the
+constructor) and all files have the first one's shape and dtype (the staging buffers are sized once).  ``est(i)`` is
+``ingest_est_host`` (float64 bilinear by ``_axis``, rounded once) on the host path and ``mm3dgs_ingest_est`` on the device path, where the
+raw array travels in the frame's staging slot: decoded by the same prefetch job, uploaded with the frame under the same event.  It
+returns a fresh tensor on every call (keyframes keep the estimate), the same in any access order.  Neither path has been timed."""
 from __future__ import annotations
 
 import ctypes as C
@@ -165,6 +177,67 @@ def ingest_device(rgb_dev, depth_dev, png_depth_scale, H, W):
     return color, d
 
 
+EST_DTYPES = {np.dtype(np.float32): 0, np.dtype(np.float16): 1, np.dtype(np.uint16): 2}      # the dtype codes of mm3dgs_ingest_est
+
+
+def resize_est_host(raw, H, W):
+    """float64 bilinear resize of a raw 2-D float32 / float16 / uint16 array [Hs,Ws] -> [H,W] by `_axis` (= F.interpolate with
+    align_corners=False); nothing is rounded to float32 yet.  Equal sizes: the values themselves, no blend."""
+    raw = np.asarray(raw)
+    if raw.ndim != 2 or raw.dtype not in EST_DTYPES:
+        raise ValueError(f"a depth estimate must be a 2-D float32, float16 or uint16 array, got {raw.dtype} {raw.shape}")
+    p = torch.as_tensor(raw.astype(np.int64) if raw.dtype == np.uint16 else np.ascontiguousarray(raw)).double()
+    Hs, Ws = p.shape
+    if (Hs, Ws) != (H, W):
+        x0, x1, a = _axis(W, Ws)
+        y0, y1, b = _axis(H, Hs)
+        a, b = a[None, :], b[:, None]
+        top = (1.0 - a) * p[y0][:, x0] + a * p[y0][:, x1]
+        bot = (1.0 - a) * p[y1][:, x0] + a * p[y1][:, x1]
+        p = (1.0 - b) * top + b * bot
+    return p
+
+
+def ingest_est_host(raw, scale, H, W, device="cpu"):
+    """The host path of the monocular estimate: raw [Hs,Ws] -> float32 [H,W] on `device`: `resize_est_host`, times `scale` in float64,
+    rounded once.  The fallback for ``device: cpu`` and the yardstick of ``mm3dgs_ingest_est``; always a fresh tensor."""
+    return (resize_est_host(raw, H, W) * float(scale)).float().to(device)
+
+
+def ingest_est_device(raw_dev, scale, H, W):
+    """``mm3dgs_ingest_est`` on the current stream: raw_dev a contiguous [Hs,Ws] float32 / float16 / 2-byte integer (the bits of uint16)
+    tensor on the GPU.  Returns a fresh float32 [H,W] tensor."""
+    from . import _lib
+    from .rasterizer import _stream
+    code = 0 if raw_dev.dtype == torch.float32 else 1 if raw_dev.dtype == torch.float16 else 2
+    if not raw_dev.is_cuda or raw_dev.dim() != 2 or not raw_dev.is_contiguous() or (code == 2 and (raw_dev.is_floating_point() or raw_dev.element_size() != 2)):
+        raise ValueError(f"ingest_est_device: a contiguous float32 / float16 / 16-bit integer [Hs,Ws] tensor on the GPU is needed, got "
+                         f"{raw_dev.dtype} {tuple(raw_dev.shape)} on {raw_dev.device}")
+    out = torch.empty(H, W, dtype=torch.float32, device=raw_dev.device)
+    _lib.check(_lib.load().mm3dgs_ingest_est(int(raw_dev.shape[0]), int(raw_dev.shape[1]), C.c_void_p(raw_dev.data_ptr()), code, float(scale),
+                                             int(H), int(W), C.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def decode_est(path):
+    """The raw monocular estimate of one frame: a 2-D C-contiguous float32 / float16 array from a .npy, uint16 from a 16-bit greyscale
+    .png.  Anything else is an error that names the file."""
+    if path.lower().endswith(".npy"):
+        try:
+            arr = np.load(path, allow_pickle=False)
+        except Exception as e:
+            raise ValueError(f"{path}: not a readable .npy array: {e}") from e
+        if arr.ndim != 2 or arr.dtype not in (np.float32, np.float16) or not arr.flags["C_CONTIGUOUS"] or arr.size == 0:
+            raise ValueError(f"{path}: a depth estimate must be a non-empty 2-D C-contiguous float32 or float16 array, got {arr.dtype} {arr.shape}"
+                             f"{'' if arr.flags['C_CONTIGUOUS'] else ' (not C-contiguous)'}")
+        return arr
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in ("I;16", "I;16L", "I;16B", "I;16N"):
+            raise ValueError(f"{path}: a depth estimate image must be 16-bit greyscale, got PIL mode {im.mode!r}")
+        return np.ascontiguousarray(np.asarray(im).astype(np.uint16, copy=False))
+
+
 def decode_png(color_path, depth_path):
     """(uint8 [Hs,Ws,3], uint16 [Hs,Ws]) with PIL.  Anything but 8-bit RGB / 16-bit greyscale is an error that names the file."""
     from PIL import Image
@@ -186,14 +259,24 @@ def quantise_frame(color, depth, png_depth_scale):
     return np.ascontiguousarray(rgb), np.ascontiguousarray(d)
 
 
-def write_tum_sequence(folder, frames, poses, tstamps):
+def write_tum_sequence(folder, frames, poses, tstamps, est=None):
     """Record frames as a TUM-format directory: `frames` = [(uint8 [H,W,3], uint16 [H,W])], `poses` = world->camera 7-vectors (the
-    package's layout), `tstamps` in seconds.  rgb/NNNN.png, depth/NNNN.png, rgb.txt, depth.txt, groundtruth.txt."""
+    package's layout), `tstamps` in seconds.  rgb/NNNN.png, depth/NNNN.png, rgb.txt, depth.txt, groundtruth.txt.  `est`: one 2-D float32 /
+    float16 array (or tensor) per frame, the monocular estimate at any resolution, written as est_depth/NNNN.npy (`est_depth_dir: est_depth`)."""
     from PIL import Image
     from scipy.spatial.transform import Rotation
     from .pose_utils import get_camera_from_tensor
     os.makedirs(os.path.join(folder, "rgb"), exist_ok=True)
     os.makedirs(os.path.join(folder, "depth"), exist_ok=True)
+    if est is not None:
+        if len(est) != len(frames):
+            raise ValueError(f"write_tum_sequence: {len(est)} estimates for {len(frames)} frames")
+        os.makedirs(os.path.join(folder, "est_depth"), exist_ok=True)
+        for n, e in enumerate(est):
+            e = np.ascontiguousarray(e.detach().cpu().numpy() if torch.is_tensor(e) else e)
+            if e.ndim != 2 or e.dtype not in (np.float32, np.float16):
+                raise ValueError(f"write_tum_sequence: estimate {n} must be a 2-D float32 or float16 array, got {e.dtype} {e.shape}")
+            np.save(os.path.join(folder, "est_depth", f"{n:04d}.npy"), e)
     rgb_txt, depth_txt, gt_txt = [], [], ["# timestamp tx ty tz qx qy qz qw"]
     for n, ((rgb, d), pose, t) in enumerate(zip(frames, poses, tstamps)):
         Image.fromarray(rgb, "RGB").save(os.path.join(folder, "rgb", f"{n:04d}.png"))
@@ -209,10 +292,20 @@ def write_tum_sequence(folder, frames, poses, tstamps):
 
 
 class _Slot:
-    """One staging slot: host arrays the decoder writes (pinned on the device path), their raw device copies, the event of the last upload."""
+    """One staging slot: host arrays the decoder writes (pinned on the device path), their raw device copies, the event of the last upload.
+    `est_like` (the first frame's raw estimate, or None) adds a buffer of its shape and dtype; est_idx / est_dev_idx say which frame's
+    estimate the host buffer and its device copy hold."""
 
-    def __init__(self, Hs, Ws, device, on_device):
+    def __init__(self, Hs, Ws, device, on_device, est_like=None):
         self.event = None
+        self.est, self.est_idx, self.est_dev_idx = None, None, None
+        if est_like is not None:
+            t = {0: torch.float32, 1: torch.float16, 2: torch.int16}[EST_DTYPES[est_like.dtype]]      # (int16: the bits of uint16)
+            self._est_t = torch.empty(est_like.shape, dtype=t)
+            if on_device:
+                self._est_t = self._est_t.pin_memory()
+                self.est_dev = torch.empty(est_like.shape, dtype=t, device=device)
+            self.est = self._est_t.numpy().view(est_like.dtype)
         if on_device:
             self._rgb_t = torch.empty(Hs, Ws, 3, dtype=torch.uint8).pin_memory()
             self._depth_t = torch.empty(Hs, Ws, dtype=torch.int16).pin_memory()      # (the bits of the uint16 image)
@@ -229,6 +322,17 @@ class _Slot:
     def upload(self):
         self.rgb_dev.copy_(self._rgb_t, non_blocking=True)
         self.depth_dev.copy_(self._depth_t, non_blocking=True)
+        if self.est is not None and self.est_idx is not None:
+            self.est_dev.copy_(self._est_t, non_blocking=True)
+            self.est_dev_idx = self.est_idx
+        self._record()
+
+    def upload_est(self):
+        self.est_dev.copy_(self._est_t, non_blocking=True)
+        self.est_dev_idx = self.est_idx
+        self._record()
+
+    def _record(self):
         if self.event is None:
             self.event = torch.cuda.Event()
         self.event.record()
@@ -237,11 +341,11 @@ class _Slot:
 class RecordedSequence:
     """See the module docstring.  Config keys (the reference's): dataset (tum | utmm), inputdir, scene, start_idx, stride,
     early_stop_idx, desired_height, desired_width, cam.{image_height, image_width, fx, fy, cx, cy, png_depth_scale}; plus
-    ingest_on_device and prefetch.  The constructor writes the intrinsics scaled to the desired size back into ``cfg["cam"]`` (Python
-    floats; float32 arithmetic of datautils.scale_intrinsics) -- build it BEFORE a Renderer is built from that cfg.  `frames` caps the
-    length (slam_top's --frames)."""
+    ingest_on_device, prefetch, est_depth_dir and cam.est_depth_scale.  The constructor writes the intrinsics scaled to the desired size
+    back into ``cfg["cam"]`` (Python floats; float32 arithmetic of datautils.scale_intrinsics) -- build it BEFORE a Renderer is built from
+    that cfg.  `frames` caps the length (slam_top's --frames).  `est_decoder` reads one estimate file (`decode_est`)."""
 
-    def __init__(self, cfg, frames=None, decoder=decode_png):
+    def __init__(self, cfg, frames=None, decoder=decode_png, est_decoder=decode_est):
         self.cfg = cfg
         self.name = str(cfg["dataset"]).lower()
         if self.name not in RECORDED_DATASETS:
@@ -272,7 +376,16 @@ class RecordedSequence:
         if self.on_device and self.device.type != "cuda":
             raise ValueError("ingest_on_device needs a CUDA device (there is no CPU kernel); use ingest_on_device: false")
         self.prefetch = bool(cfg.get("prefetch", True))
-        self._slots = [_Slot(self.Hs, self.Ws, self.device, self.on_device) for _ in range(2)]
+        self.est_paths, est_like = None, None
+        if cfg.get("est_depth_dir"):
+            self._est_decoder = est_decoder
+            self.est_depth_scale = float(cam.get("est_depth_scale", 1.0) or 1.0)
+            if not (self.est_depth_scale > 0.0 and np.isfinite(self.est_depth_scale)):
+                raise ValueError(f"cam.est_depth_scale must be finite and positive, got {self.est_depth_scale}")
+            self.est_paths = self._est_files(os.path.join(self.folder, str(cfg["est_depth_dir"])))
+            est_like = est_decoder(self.est_paths[0])
+            self.est = self._est      # bound on the instance: SLAM.step asks hasattr(seq, "est")
+        self._slots = [_Slot(self.Hs, self.Ws, self.device, self.on_device, est_like) for _ in range(2)]
         self._next, self._pending = 0, None
         self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="mm3dgs-decode") if self.prefetch else None
 
@@ -343,13 +456,53 @@ class RecordedSequence:
         return self.imus[i].to(self.device).type(torch.float32).clone()
 
     # ---- frames --------------------------------------------------------------------------------------------------------------------
+    def _est_files(self, folder):
+        """The estimate file of every kept colour frame (after slicing and the `frames` cap): same stem, .npy before .png."""
+        paths = []
+        for c in self.color_paths:
+            stem = os.path.splitext(os.path.basename(c))[0]
+            found = next((p for p in (os.path.join(folder, stem + ext) for ext in (".npy", ".png")) if os.path.isfile(p)), None)
+            if found is None:
+                raise ValueError(f"{os.path.join(folder, stem + '.npy')}: missing depth estimate of {c} (neither .npy nor .png)")
+            paths.append(found)
+        return paths
+
+    def _decode_est_into(self, i, slot):
+        slot.est_idx = None
+        raw = self._est_decoder(self.est_paths[i])
+        if raw.shape != slot.est.shape or raw.dtype != slot.est.dtype:
+            raise ValueError(f"{self.est_paths[i]}: depth estimate is {raw.dtype} {tuple(raw.shape)}, the first frame's "
+                             f"({self.est_paths[0]}) is {slot.est.dtype} {tuple(slot.est.shape)}")
+        np.copyto(slot.est, raw)
+        slot.est_idx = i
+
+    def _est(self, i):
+        """The monocular estimate of frame i, float32 [H,W] on the device: a fresh tensor on every call.  After ``seq[i]`` the slot still
+        holds the decoded (and, on the device path, uploaded) array; otherwise the file is decoded into the slot no prefetch writes to."""
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        slot = self._slots[1 - self._next]      # (a pending prefetch always targets _slots[_next])
+        if slot.est_idx != i:
+            slot.wait()
+            self._decode_est_into(i, slot)
+        scale = self.est_depth_scale if slot.est.dtype == np.uint16 else 1.0
+        if not self.on_device:
+            return ingest_est_host(slot.est, scale, self.H, self.W, self.device)
+        if slot.est_dev_idx != i:
+            slot.upload_est()
+        return ingest_est_device(slot.est_dev, scale, self.H, self.W)
+
     def _decode_into(self, i, slot):
+        if self.est_paths is not None:
+            slot.est_idx = None
         rgb, depth = self._decoder(self.color_paths[i], self.depth_paths[i])
         for arr, path, want in ((rgb, self.color_paths[i], (self.Hs, self.Ws, 3)), (depth, self.depth_paths[i], (self.Hs, self.Ws))):
             if tuple(arr.shape) != want:
                 raise ValueError(f"{path}: image is {tuple(arr.shape)}, cam.image_height / image_width say {want}")
         np.copyto(slot.rgb, rgb)
         np.copyto(slot.depth, depth)
+        if self.est_paths is not None:
+            self._decode_est_into(i, slot)
 
     def _staged(self, i):
         """The slot that holds the decoded frame i: the prefetched one if the hint was right, a synchronous decode otherwise."""

@@ -3,14 +3,17 @@
 
 The YAML schema is the reference's (configs/TUM.yml, configs/UTMM.yml).  A config with a non-empty `inputdir` and `dataset: tum` or
 `utmm` is read from disk (`mm3dgs_slam_amd.dataset.RecordedSequence`: TUM-format / UT-MM-format directory `inputdir/scene`, all
-frames or `--frames N` of them; `ingest_on_device` and `prefetch` choose how a frame gets to the device).  Every other config -- the
+frames or `--frames N` of them; `ingest_on_device` and `prefetch` choose how a frame gets to the device; `est_depth_dir` names the folder
+of per-frame monocular depth estimates).  Every other config -- the
 default `dataset: synthetic`, and the two configs the reference ships, whose `inputdir:` is empty -- runs on the in-memory synthetic
 RGB-D sequence (10 frames unless `--frames` says otherwise) with the config's hot-path settings (iteration budgets, learning rates,
-pipeline flags, intrinsics); Replica, EXR depth, colour undistortion and the monocular depth network stay out of scope.  On the synthetic
-sequence `use_gt_depth: false` (what configs/TUM.yml ships) and `tracking.dynamics_model: imu` are honoured: the
+pipeline flags, intrinsics); Replica, EXR depth, colour undistortion and the monocular depth network itself stay out of scope.  On the
+synthetic sequence `use_gt_depth: false` (what configs/TUM.yml ships) and `tracking.dynamics_model: imu` are honoured: the
 sequence provides a stand-in for the monocular estimate (`SyntheticSequence.est`, aligned per frame like slam/SLAM.py:411-448) and
-synthetic IMU rows (`SyntheticSequence.imu`); a recorded sequence has no estimate, so the sensor depth is used.  Only `niqe_kf` is forced
-off (it needs a downloaded network).
+synthetic IMU rows (`SyntheticSequence.imu`).  A recorded sequence honours `use_gt_depth: false` when the config names `est_depth_dir`, a
+folder in `inputdir/scene` with the network's raw output per colour frame (`<stem>.npy` float32 / float16, or a 16-bit `<stem>.png`):
+the estimate is resampled to the frame size as the reference's MiDaS.estimate_depth does and aligned per frame; without the key a
+recorded sequence has no estimate and the sensor depth is used.  Only `niqe_kf` is forced off (it needs a downloaded network).
 
 Outputs in `outputdir`, in the reference's formats (slam/SLAM.py:286-373,488-500): `point_cloud/iteration_<n>/point_cloud.ply` for
 every frame index in `save_iterations` and for the final map (attribute layout of slam/gaussian_model.py:205-257), `results.npz`

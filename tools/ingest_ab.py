@@ -18,7 +18,13 @@ The summary says whether the device path's median is below the host path's at BO
 Every run is a fresh SLAM object from the same seeds: frame 0 and `--warmup` frames untimed, then `--steps` frames timed like bench.py
 (host clock, device synchronised at both ends); the configurations alternate, `--repeats` times after one short untimed pass of each:
 host ingest without prefetch, device ingest without prefetch, device ingest with prefetch, and -- the ceiling -- an in-memory sequence
-built from the same quantised frames (what bench.py times: float32 frames already on the device)."""
+built from the same quantised frames (what bench.py times: float32 frames already on the device).
+
+(d) The monocular depth estimate of a recorded sequence (`est_depth_dir`): per-frame time of the host path (`ingest_est_host`: float64
+bilinear on the CPU, upload of 4 bytes per output pixel) against the device path (pinned raw array up non-blocking, `mm3dgs_ingest_est`),
+device synchronised, file decode excluded, alternating call by call, median of `--fetches` each after an untimed round; at 384x512
+float16 -> 480x640 (the network's output) and at 480x640 float32 native.  The two outputs are compared once per shape.  The device path
+stays governed by `ingest_on_device`; this part only reports."""
 import argparse
 import json
 import os
@@ -106,6 +112,40 @@ def fetch_times(args, root, scene, Hs, Ws, H, W, emit):
     return line
 
 
+def est_times(args, Hs, Ws, dtype, H, W, emit):
+    from mm3dgs_slam_amd.dataset import ingest_est_device, ingest_est_host
+    g = torch.Generator().manual_seed(5)
+    raws = [(torch.rand(Hs, Ws, generator=g) * 3000.0).to(dtype) for _ in range(args.distinct)]
+    pinned = [r.clone().pin_memory() for r in raws]
+    dev = torch.empty(Hs, Ws, dtype=dtype, device=DEV)
+
+    def host(k):
+        return ingest_est_host(raws[k].numpy(), 1.0, H, W, DEV)
+
+    def device(k):
+        dev.copy_(pinned[k], non_blocking=True)
+        return ingest_est_device(dev, 1.0, H, W)
+
+    h, d = host(1), device(1)
+    torch.cuda.synchronize()
+    agree = dict(bit_identical=bool(torch.equal(h, d)), max_abs_diff=float((h - d).abs().max()))
+    n = len(raws)
+    for k in range(2 * n):      # untimed round
+        host(k % n), device(k % n)
+    torch.cuda.synchronize()
+    ms = {"host": [], "device": []}
+    for k in range(args.fetches):
+        for name, fn in (("host", host), ("device", device)):
+            t0 = time.perf_counter()
+            fn(k % n)
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    q = lambda v: dict(median=round(statistics.median(v), 4), p10=round(float(np.percentile(v, 10)), 4), p90=round(float(np.percentile(v, 90)), 4))
+    emit(dict(part="d", what="monocular depth estimate, per frame, file decode excluded", shape=f"{Ws}x{Hs} {str(dtype).split('.')[-1]} -> {W}x{H}",
+              fetches=args.fetches, host_ms_per_frame=q(ms["host"]), device_ms_per_frame=q(ms["device"]),
+              upload_bytes_host=4 * H * W, upload_bytes_device=Hs * Ws * raws[0].element_size(), **agree))
+
+
 def decode_times(rec_paths, label, emit):
     from mm3dgs_slam_amd.dataset import decode_png
     ms = []
@@ -191,6 +231,9 @@ def main():
         paths = lambda scene, n: [(os.path.join(root, scene, "rgb", f"{i:04d}.png"), os.path.join(root, scene, "depth", f"{i:04d}.png")) for i in range(n)]
         decode_times(paths("bench", min(8, n_frames)), f"{W}x{H} (rendered synthetic frames)", emit)
         decode_times(paths("utmm_size", 4), "1280x660 (synthetic RGB-D frames)", emit)
+
+        est_times(args, 384, 512, torch.float16, H, W, emit)
+        est_times(args, H, W, torch.float32, H, W, emit)
 
         def recorded(on_device, prefetch):
             def make():
