@@ -68,9 +68,7 @@ typedef struct Mm3dgsHeader {
   uint32_t bin_cap;        /* 0: the tile bins are packed (bin of tile t = [ranges[t], ranges[t+1])); otherwise every tile owns a
                               fixed span of bin_cap pairs starting at t * bin_cap (MM3DGS_FWD_DIRECT_BINS) and ranges[t] holds
                               its length.  Written by every forward. */
-  uint32_t max_group_records; /* direct bins: most gradient records of one projection workgroup (256 Gaussians) since the host
-                                 last cleared it (sticky); every workgroup owns 16 * N_capacity / ceil(P / 256) records of the
-                                 backward scratch, a workgroup that needs more sets `overflow` */
+  uint32_t reserved8;         /* always 0 */
   uint32_t tile_order_tiles;  /* 0: workgroup -> tile by arithmetic; H << 16 | W: image_state holds a load-balanced workgroup -> tile table
                                  for an H x W image, written by the SLAM loop entry points from the list lengths of the last render
                                  (any permutation of the tiles renders the same image; only the speed depends on it) */
@@ -226,8 +224,9 @@ typedef struct Mm3dgsPoseAdam { /* torch.optim.Adam on (q; lr_q) and (t; lr_t); 
                                     scan).  A tile with more pairs than N_capacity / T sets `overflow`.  Needs STATE_CLEAN and
                                     SHORT_LISTS; ignored (packed bins) otherwise, or when the map is too large for the key layout
                                     (id and slot share 32 bits: spans of up to 8191 pairs to 512 k Gaussians, 4095 at 1 M, none
-                                    beyond 4 M).  The gradient records are
-                                    then laid out per projection workgroup (see Mm3dgsHeader.max_group_records). */
+                                    beyond 4 M).  The per-tile gradient
+                                    records are then laid out per projection workgroup (256 Gaussians): each owns
+                                    N_capacity / ceil(P / 256) of them, and one with more pairs than that sets `overflow` too. */
 #define MM3DGS_FWD_SHORT_LISTS 2 /* hint: no tile list exceeds 2048 splats -> one sort launch (longer lists stay correct
                                     through the global-memory path, only slower)                                        */
 #define MM3DGS_FWD_PROJECTED 16 /* mm3dgs_slam_forward / the FIRST view of mm3dgs_slam_map: projection + binning of this view were

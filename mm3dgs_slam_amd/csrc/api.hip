@@ -255,7 +255,7 @@ static bool slam_fused_sort(int flags) {
 }
 
 // direct bins (MM3DGS_FWD_DIRECT_BINS): one decision for the forward and the backward of a render
-struct DirectBins { bool on; uint32_t bin_cap, rec_cap, trec_cap; int nblocks, slot_bits; };
+struct DirectBins { bool on; uint32_t bin_cap, trec_cap; int nblocks, slot_bits; };
 static DirectBins slam_direct_bins(int flags, const CamDev& cd, int P, size_t N_capacity) {
   static const int no_direct = env_flag("MM3DGS_NO_DIRECT_BINS", 0);
   static const int no_fused_scan = env_flag("MM3DGS_NO_FUSED_SCAN", 0);
@@ -266,12 +266,10 @@ static DirectBins slam_direct_bins(int flags, const CamDev& cd, int P, size_t N_
   const size_t nb = (size_t)std::max(d.nblocks, 1);
   d.slot_bits = direct_slot_bits(P);
   d.bin_cap = (uint32_t)std::min<size_t>(N_capacity / (size_t)std::max(T, 1), (size_t)((1u << std::max(d.slot_bits, 1)) - 1u));
-  // records of the backward scratch per projection workgroup (the scratch holds NLIST records per pair of capacity)
-  d.rec_cap = (uint32_t)std::min<size_t>((size_t)NLIST * N_capacity / nb, 0xffffffffull / nb);
   // per-tile records (one per pair) per projection workgroup: the region holds N_capacity of them
   d.trec_cap = (uint32_t)std::min<size_t>(N_capacity / nb, 0xffffffffull / nb);
   d.on = (flags & MM3DGS_FWD_DIRECT_BINS) && (flags & MM3DGS_FWD_STATE_CLEAN) && slam_fused_sort(flags) && !no_direct && !no_fused_scan &&
-         P > 0 && d.slot_bits >= DIRECT_SLOT_BITS_MIN && T <= max_tiles && T <= MAX_LDS_TILES && d.bin_cap >= 32 && d.rec_cap >= 1024 && d.trec_cap >= 256 &&
+         P > 0 && d.slot_bits >= DIRECT_SLOT_BITS_MIN && T <= max_tiles && T <= MAX_LDS_TILES && d.bin_cap >= 32 && d.trec_cap >= 256 &&
          N_capacity >= 4 * (size_t)P;
   return d;
 }
@@ -313,7 +311,7 @@ static int slam_forward_impl(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInp
   cd.trec_cap = db.on ? db.trec_cap : 0u;
   if (db.on) {
     // projected: the previous mapping iteration's backward launch already projected and binned this view (slam_bwd_project_kernel)
-    if (!projected) { ProfScope ps(MM3DGS_PROF_PREPROCESS_FWD, s); launch_slam_project_bin(cd, P, slam_in(in), radii, g, iv, b, db.bin_cap, db.rec_cap, db.slot_bits, s, pose_chain); }
+    if (!projected) { ProfScope ps(MM3DGS_PROF_PREPROCESS_FWD, s); launch_slam_project_bin(cd, P, slam_in(in), radii, g, iv, b, db.bin_cap, db.slot_bits, s, pose_chain); }
     { ProfScope ps(track_dsub ? MM3DGS_PROF_TRACK_FWD_BWD : MM3DGS_PROF_COMPOSITE_FWD, s);
       if (track_dsub) launch_sort_composite_fwd_bwd_track(cd, g, iv, b, N_capacity, out_color, 1, s, *tl, db.nblocks, track_dsub, db.bin_cap, db.slot_bits, pose_chain);
       else launch_sort_composite_fwd6(cd, g, iv, b, N_capacity, out_color, 1, s, tl, db.nblocks, db.bin_cap, db.slot_bits); }
@@ -435,7 +433,7 @@ static int slam_backward_impl(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamIn
   if (fuse) {
     ProfScope ps(MM3DGS_PROF_PREPROCESS_BWD, s);
     launch_slam_bwd_project(cd, P, slam_in(in), (int32_t*)radii, g, image_view((void*)image_state, cd.H, cd.W), b, N_capacity, bw, sg, ma, fuse_next_pose,
-                            db_bwd.bin_cap, db_bwd.rec_cap, db_bwd.slot_bits, s);
+                            db_bwd.bin_cap, db_bwd.slot_bits, s);
   } else
   { ProfScope ps(MM3DGS_PROF_PREPROCESS_BWD, s); launch_slam_preprocess_bwd(cd, P, slam_in(in), radii, g, b, N_capacity, bw, sg, dL_dpose, pa, ma, s, pls.rows ? &pls : nullptr, prior_loss4, db_bwd.on, &iv.hdr->overflow); }
   return check_launch("slam_backward");
@@ -669,7 +667,7 @@ int mm3dgs_slam_adam_project(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInp
   sg.d_f_rest = in->sh_degree > 0 ? grads->d_f_rest : nullptr;
   { ProfScope ps(MM3DGS_PROF_ADAM, s);
     launch_slam_adam_project(cd, P, slam_in(in), radii, geom_view(geom_state, P > 0 ? P : 1), image_view(image_state, cd.H, cd.W), bin_view(binning_state, N_capacity),
-                             sg, ma, in->pose, db.bin_cap, db.rec_cap, db.slot_bits, s); }
+                             sg, ma, in->pose, db.bin_cap, db.slot_bits, s); }
   return check_launch("slam_adam_project");
 }
 

@@ -301,8 +301,7 @@ slam_preprocess_fwd_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ r
     {
       __shared__ uint32_t wtot[FB / 64];
       const int ln = threadIdx.x & 63, wvi = threadIdx.x >> 6;
-      // (the second scan -- the 4x4 blocks of every splat's block rectangle, blkoff / block_blk: the first Gaussian-major block record -- left in round 6:
-      //  block records are addressed by list position in every mode)
+      // (one scan only: block records are addressed by list position in every mode)
       const uint32_t x = wave_scan_incl((uint32_t)area);   // tiles touched
       if (ln == 63) wtot[wvi] = x;
       __syncthreads();
@@ -353,12 +352,13 @@ void launch_slam_preprocess_fwd(const CamDev& cam, int P, const SlamIn& in, int3
 // lane per Gaussian, two sweeps over its tile rectangle around a per-workgroup LDS histogram: sweep 1 counts the workgroup's
 // pairs per tile, one returning global atomic per *touched tile* reserves slots in the tile's span, sweep 2 hands them out
 // with LDS atomics and writes, per pair, the key (depth bits | id | slot) and the payload the sort needs to emit the block
-// lists without touching the splat again: the 16-bit block mask (tile_mask.h), the width of the splat's block rectangle and
-// the gradient record of the tile's first block.  Records need no global prefix either: projection workgroup w owns records
-// [w * rec_cap, (w + 1) * rec_cap) of the backward scratch (rec_cap = scratch capacity / workgroups, ~7x what a SLAM map
-// uses) and publishes its base as g.block_blk[w], where the backward projection looks it up as before.  A tile with more
-// than `cap` pairs drops the excess and the sort flags the overflow; a workgroup with more than rec_cap records flags it
-// here and lists none of the splats that do not fit (both sticky, like a packed bin that runs out of capacity).
+// lists without touching the splat again: the 16-bit block mask (tile_mask.h) and the pair's per-tile gradient record.  The
+// per-tile records (one per pair, BwdView.dtile) need no global prefix either: projection workgroup w owns records
+// [w * trec_cap, (w + 1) * trec_cap) with trec_cap = N_capacity / ceil(P / 256) (CamDev.trec_cap), a Gaussian's pairs
+// contiguous inside the span at g.tileoff[idx].  The block records are addressed by list position (composite.hip) and have
+// no span of their own.  A tile with more than `cap` pairs drops the excess and the sort flags the overflow; a workgroup
+// with more than trec_cap pairs flags it here, and its splats that do not fit get no per-tile record (~0u).  Both set the
+// sticky Mm3dgsHeader.overflow, like a packed bin that runs out of capacity.
 struct PairCtx {           // what a lane needs to emit the pairs of ITS Gaussian (broadcast lane by lane for huge splats)
   MaskConsts mc; BlkRect br; uint32_t khi, idbits; int minx, miny, w, area;
   uint32_t trec0;            // per-tile record of the splat's first pair (absolute; pair k of the tile rectangle, row-major: trec0 + k); ~0u: none
@@ -382,7 +382,7 @@ __device__ __forceinline__ uint32_t emit_pair(const PairCtx& c, int k, int ttx, 
 // The binning half of the projection kernels: every lane hands in the projection of ITS Gaussian (slam_project_one / _vals); hist = the
 // workgroup's [T] words of LDS, cleared by the caller before (the first barrier inside orders the clear).
 __device__ __forceinline__ void slam_bin_pairs(const CamDev& cam, int P, int idx, const Projected& pr, const GeomView& g, const ImageView& iv,
-                                               const BinView& b, uint32_t cap, uint32_t rec_cap, int slot_bits, uint32_t* hist) {
+                                               const BinView& b, uint32_t cap, int slot_bits, uint32_t* hist) {
   const int T = cam.gx * cam.gy;
   const int tid = threadIdx.x, lane = tid & 63, wvi = tid >> 6;
   const bool live = idx < P;
@@ -500,19 +500,19 @@ __device__ __forceinline__ int slam_bin_prologue(const CamDev& cam, const ImageV
 template <bool SH, int SHDIR = 0>
 __global__ void __launch_bounds__(FB)
 slam_project_bin_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radii, GeomView g, ImageView iv, BinView b, uint32_t cap,
-                        uint32_t rec_cap, int slot_bits, int want_poserec) {
+                        int slot_bits, int want_poserec) {
   extern __shared__ uint32_t hist[];     // [T]: pairs of this workgroup per tile, then the next slot of each touched tile
   const int idx = slam_bin_prologue(cam, iv, cap, hist);
   const Projected pr = slam_project_one<SH, SHDIR>(cam, P, idx, in, radii, g, want_poserec != 0);
-  slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
+  slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, slot_bits, hist);
 }
 
 void launch_slam_project_bin(const CamDev& cam, int P, const SlamIn& in, int32_t* radii, GeomView g, ImageView iv, BinView b, uint32_t bin_cap,
-                             uint32_t rec_cap, int slot_bits, hipStream_t s, bool want_poserec) {
+                             int slot_bits, hipStream_t s, bool want_poserec) {
   if (P <= 0) return;
   const int T = cam.gx * cam.gy;
   hipLaunchKernelGGL(SLAM_PICK_SH(slam_project_bin_kernel, in), dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, bin_cap,
-                     rec_cap, slot_bits, want_poserec && in.sh_deg <= 0 ? 1 : 0);
+                     slot_bits, want_poserec && in.sh_deg <= 0 ? 1 : 0);
 }
 
 // Sum of a Gaussian's per-tile gradient records (composite.hip's per-tile combine: one record per (tile, splat) pair, the pairs of a
@@ -950,7 +950,7 @@ template <bool WORLD>
 __global__ void __launch_bounds__(FB)
 slam_bwd_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radii, GeomView g, ImageView iv, BinView b, uint32_t N_cap,
                         const float* __restrict__ dsub, SlamGrads out, MapAdam ma, const float* __restrict__ next_pose, uint32_t cap,
-                        uint32_t rec_cap, int slot_bits) {
+                        int slot_bits) {
   extern __shared__ uint32_t hist[];
   // both views' uniforms before the first store of the kernel: the projection half used to fetch next_pose behind the Adam stores
   const PoseProj u = load_pose_proj(in.pose, cam.proj), un = load_pose_proj(next_pose, cam.proj);
@@ -960,17 +960,17 @@ slam_bwd_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radi
   //  workgroups of this half are still starting, and a partially stepped map is worse than either outcome)
   slam_bwd_body<false, true, WORLD, false, 0, true>(cam, P, in, u, radii, g, N_cap, dsub, nullptr, out, ma, &rg, &iv.hdr->overflow_seen);
   const Projected pr = slam_project_vals(cam, idx < P, idx, un.pose, un.PV, in.isotropic != 0, rg, radii, g, WORLD);
-  slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
+  slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, slot_bits, hist);
 }
 
 void launch_slam_bwd_project(const CamDev& cam, int P, const SlamIn& in, int32_t* radii, GeomView g, ImageView iv, BinView b, size_t N_cap,
-                             BwdView bw, const SlamGrads& out, const MapAdam& ma, const float* next_pose, uint32_t bin_cap, uint32_t rec_cap,
+                             BwdView bw, const SlamGrads& out, const MapAdam& ma, const float* next_pose, uint32_t bin_cap,
                              int slot_bits, hipStream_t s) {
   if (P <= 0) return;
   const uint32_t ncap = (uint32_t)(N_cap > 0xffffffffull ? 0xffffffffull : N_cap);
   const int T = cam.gx * cam.gy;
   hipLaunchKernelGGL(in.world ? slam_bwd_project_kernel<true> : slam_bwd_project_kernel<false>, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in,
-                     radii, g, iv, b, ncap, bw.dsub, out, ma, next_pose, bin_cap, rec_cap, slot_bits);
+                     radii, g, iv, b, ncap, bw.dsub, out, ma, next_pose, bin_cap, slot_bits);
 }
 
 // The multi-GPU window's optimiser step (slam/mapper.py:931-948 on all-reduced gradients) and the NEXT view's projection + binning in one launch: what
@@ -983,7 +983,7 @@ void launch_slam_bwd_project(const CamDev& cam, int P, const SlamIn& in, int32_t
 template <bool WORLD, bool SH = false, int SHDIR = 0>
 __global__ void __launch_bounds__(FB)
 slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ radii, GeomView g, ImageView iv, BinView b, SlamGrads gr, MapAdam ma,
-                         const float* __restrict__ next_pose, uint32_t cap, uint32_t rec_cap, int slot_bits) {
+                         const float* __restrict__ next_pose, uint32_t cap, int slot_bits) {
   static_assert(!SH || WORLD == (SHDIR == 2), "world-frame means take the direction from the camera centre, pre-transformed ones from the mean or the origin");
   extern __shared__ uint32_t hist[];
   const PoseProj un = load_pose_proj(next_pose, cam.proj);      // (before the first store of the kernel)
@@ -1046,21 +1046,21 @@ slam_adam_project_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ rad
   }
   if constexpr (SH) {
     const Projected pr = slam_project_vals<true, SHDIR>(cam, idx < P, idx, un.pose, un.PV, in.isotropic != 0, rg, radii, g, WORLD, false, rs, in.sh_deg);
-    slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
+    slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, slot_bits, hist);
   } else {
     const Projected pr = slam_project_vals(cam, idx < P, idx, un.pose, un.PV, in.isotropic != 0, rg, radii, g, WORLD);
-    slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, rec_cap, slot_bits, hist);
+    slam_bin_pairs(cam, P, idx, pr, g, iv, b, cap, slot_bits, hist);
   }
 }
 
 void launch_slam_adam_project(const CamDev& cam, int P, const SlamIn& in, int32_t* radii, GeomView g, ImageView iv, BinView b, const SlamGrads& gr,
-                              const MapAdam& ma, const float* next_pose, uint32_t bin_cap, uint32_t rec_cap, int slot_bits, hipStream_t s) {
+                              const MapAdam& ma, const float* next_pose, uint32_t bin_cap, int slot_bits, hipStream_t s) {
   if (P <= 0) return;
   const int T = cam.gx * cam.gy;
   // (ABI 212; api.hip admits world_means = 1 with sh_dir = 2 only, and sh_dir = 2 with world_means = 1 only)
   auto k = in.sh_deg <= 0 ? (in.world ? slam_adam_project_kernel<true> : slam_adam_project_kernel<false>)
          : in.sh_dir == 2 ? slam_adam_project_kernel<true, true, 2> : in.sh_dir == 1 ? slam_adam_project_kernel<false, true, 1> : slam_adam_project_kernel<false, true, 0>;
-  hipLaunchKernelGGL(k, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, gr, ma, next_pose, bin_cap, rec_cap, slot_bits);
+  hipLaunchKernelGGL(k, dim3((P + FB - 1) / FB), dim3(FB), (size_t)T * 4, s, cam, P, in, radii, g, iv, b, gr, ma, next_pose, bin_cap, slot_bits);
 }
 
 // b^t for a step counter t >= 1 by squaring, in double (pow() costs this one-lane code ~60 registers of the whole kernel it is inlined into)

@@ -3,6 +3,7 @@
 //   geom_state   : Splat[P] (48 B packed AoS record, gathered by id in the compositor) | depth[P] | rect[P] (2x u32)
 //                  | clamped[P] (u8, SH clamp bits) | tileoff[P] (u32, workgroup-local exclusive scan of tiles touched)
 //                  | block_tiles[ceil(P/256)+1] (u32, tiles touched per preprocess workgroup -> exclusive prefix)
+//                  | poserec[P] (POSEREC_F floats, tracking: GeomView below)
 //   image_state  : Mm3dgsHeader | tile_count[T] | ranges[T+1] | cursor[T] | subcount[16T] | final_T[H*W] | n_contrib[H*W]
 //   binning_state: keys[N_cap] (u64 = depth_bits<<32 | id; bins are contiguous per tile; after the sort: the bin in sorted order as
 //                  block mask | per-tile record << 32) | sublist[16*N_cap] (uint2 {id, -}: depth-ordered list of each 4x4-pixel block;
@@ -42,8 +43,6 @@ struct GeomView {
   uint8_t* clamped;   // [P]
   uint32_t* tileoff;  // [P]
   uint32_t* block_tiles;  // [ceil(P/256)+1]
-  uint32_t* blkoff;   // [P]  workgroup-local exclusive scan of the 4x4 blocks in each splat's block rectangle
-  uint32_t* block_blk;    // [ceil(P/256)+1]  blocks per preprocess workgroup -> exclusive prefix
   float* poserec;         // [P][POSEREC_F] (round 6, tracking): the linear map from a splat's screen-space gradient moments to dL/d(camera-space mean)
                           // and its world position -- written by the projection stage of mm3dgs_slam_track, applied per (block, splat) by the
                           // tracking compositor (composite.hip), so that a tracking iteration writes no gradient records at all
@@ -52,7 +51,7 @@ struct GeomView {
 static inline size_t geom_bytes_impl(int P) {
   size_t p = (size_t)P;
   return align_up(p * SPLAT_F * 4, 256) + align_up(p * 4, 256) + align_up(p * 8, 256) + align_up(p, 256) +
-         2 * (align_up(p * 4, 256) + align_up(((p + 255) / 256 + 1) * 4, 256)) + align_up(p * POSEREC_F * 4, 256);
+         align_up(p * 4, 256) + align_up(((p + 255) / 256 + 1) * 4, 256) + align_up(p * POSEREC_F * 4, 256);
 }
 static inline GeomView geom_view(void* base, int P) {
   size_t p = (size_t)P;
@@ -64,8 +63,6 @@ static inline GeomView geom_view(void* base, int P) {
   g.clamped = (uint8_t*)c;  c += align_up(p, 256);
   g.tileoff = (uint32_t*)c; c += align_up(p * 4, 256);
   g.block_tiles = (uint32_t*)c; c += align_up(((p + 255) / 256 + 1) * 4, 256);
-  g.blkoff = (uint32_t*)c;  c += align_up(p * 4, 256);
-  g.block_blk = (uint32_t*)c; c += align_up(((p + 255) / 256 + 1) * 4, 256);
   g.poserec = (float*)c;
   return g;
 }

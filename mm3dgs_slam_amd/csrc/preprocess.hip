@@ -131,8 +131,7 @@ preprocess_fwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
     {  // workgroup-local exclusive scan of tiles touched (this Gaussian's first pair index)
       __shared__ uint32_t wtot[PP_BLOCK / 64];
       const int ln = threadIdx.x & 63, wvi = threadIdx.x >> 6;
-      // (the second scan -- the 4x4 blocks of every splat's block rectangle, blkoff / block_blk: the first Gaussian-major block record -- left in round 6:
-      //  block records are addressed by list position in every mode)
+      // (one scan only: block records are addressed by list position in every mode)
       const uint32_t x = wave_scan_incl((uint32_t)area);   // tiles touched
       if (ln == 63) wtot[wvi] = x;
       __syncthreads();

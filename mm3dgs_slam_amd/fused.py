@@ -112,7 +112,7 @@ class FusedEngine:
         if P != self.P:
             # the map grows by a few percent per keyframe: buffers are sized for 1.25 P and re-used until outgrown (a fresh
             # hipMalloc of the ~0.5 GB scratch at every keyframe cost ~10 ms of the frame)
-            if P > getattr(self, "_cap_P", -1):
+            if P > self._cap_P:
                 self._cap_P = int(P * 1.25) + 1024
                 u8 = dict(dtype=torch.uint8, device=self.dev)
                 self.geom = torch.empty(self.lib.mm3dgs_geom_bytes(self._cap_P), **u8)
@@ -121,19 +121,7 @@ class FusedEngine:
             self.radii = self._radii_buf[:P]
             self.P = P
             self.grads = None
-        want = int((self.ratio if self.ratio is not None else 24.0) * max(P, 1) * 2.0) + self.MIN_PAIRS
-        self.direct = False
-        # direct bins (MM3DGS_FWD_DIRECT_BINS): every tile owns n_cap / T pairs, sized from the longest list seen so far; the key's low
-        # word holds the Gaussian id and the slot in the span, so the span is limited to 2^(32 - bits(P)) - 1 pairs (8191 up to 512 k
-        # Gaussians, 4095 at 1 M)
-        T = ((self.W + 15) // 16) * ((self.H + 15) // 16)
-        per_tile = int(self.max_tile_len * 1.5) + 128
-        slot_bits = min(13, 32 - max(int(P - 1).bit_length(), 1)) if P > 0 else 0
-        if self.DIRECT_BINS and self.max_tile_len <= self.FAST_PATH_MAX_LIST and slot_bits >= 10 and int(per_tile * 1.25) + 1 <= (1 << slot_bits) - 1:
-            want = max(want, T * per_tile)
-            # ... and every projection workgroup (256 Gaussians) 16 * n_cap / workgroups gradient records
-            want = max(want, ((P + 255) // 256) * (int(getattr(self, "max_group_records", 0) * 1.5) + 1024) // 16 + 1)
-            self.direct = True
+        want, self.direct = self.sizing(P, self.ratio, self.max_tile_len, self.H, self.W, self.MIN_PAIRS, self.DIRECT_BINS)
         if want > self.n_cap or (self.ratio is not None and self.n_cap > 4 * want):
             u8 = dict(dtype=torch.uint8, device=self.dev)
             self.n_cap = int(want * 1.25) if self.ratio is not None else want
@@ -155,9 +143,38 @@ class FusedEngine:
             self._flat_rest = n
             self._rest_rows = None
 
+    @staticmethod
+    def sizing(P, ratio, max_tile_len, H, W, min_pairs=MIN_PAIRS, direct_bins=DIRECT_BINS):
+        """(want, direct): the binning capacity in pairs that _ensure asks for, and whether it was sized per tile (direct bins).  Pure
+        host arithmetic over the map size, the pairs per Gaussian and the longest tile list seen so far (None / 1 << 30 before the
+        first header check) and the image size; min_pairs / direct_bins: an engine's own MIN_PAIRS / DIRECT_BINS where they were overridden."""
+        want = int((ratio if ratio is not None else 24.0) * max(P, 1) * 2.0) + min_pairs
+        # direct bins (MM3DGS_FWD_DIRECT_BINS): every tile owns n_cap / T pairs, sized from the longest list seen so far; the key's low
+        # word holds the Gaussian id and the slot in the span, so the span is limited to 2^(32 - bits(P)) - 1 pairs (8191 up to 512 k
+        # Gaussians, 4095 at 1 M)
+        T = ((W + 15) // 16) * ((H + 15) // 16)
+        per_tile = int(max_tile_len * 1.5) + 128
+        slot_bits = min(13, 32 - max(int(P - 1).bit_length(), 1)) if P > 0 else 0
+        if not (direct_bins and max_tile_len <= FusedEngine.FAST_PATH_MAX_LIST and slot_bits >= 10 and int(per_tile * 1.25) + 1 <= (1 << slot_bits) - 1):
+            return want, False
+        # ... and at least 64 pairs per projection workgroup (256 Gaussians).  This floor binds only for a huge map with almost no pairs
+        # per Gaussian; it is what the record capacity of the Gaussian-major design came to once its demand was 0, kept so that the
+        # capacities do not move.  It is NOT what the library asks of direct bins (N_capacity >= 4 P and >= 256 pairs per projection
+        # workgroup, mm3dgs_slam_direct_bins: below that it falls back to packed bins, which any capacity serves).
+        return max(want, T * per_tile, ((P + 255) // 256) * 64 + 1), True
+
+    # state that the methods below create on first use (class-level defaults: tests build engines with FusedEngine.__new__)
+    _cap_P = -1                  # Gaussians geom / radii are allocated for
+    _hdr_pin = None              # pinned host copy of the header's first words (check_capacity_begin)
+    _last_g = None               # the model of the last forward()
+    _checked_P = _checked_cap = -1      # map size and capacity at the last header check (headroom)
+    unchecked_tracking = None    # frame whose tracking loop skipped its header read (lazy check)
+    unrecovered_tracking_overflows = 0
+    overflows = 0                # header checks that found the overflow word set
     # f_rest rows per Gaussian that the flat gradient buffer carries (bind_rest_rows): the model's n_rest at an active SH degree > 0, else 0
     rest_rows = 0
     _flat_rest = 0
+    _rest_rows = None            # rest_grad's own buffer, while the flat buffer carries no f_rest block of the model's shape
 
     @property
     def flat_width(self):
@@ -177,11 +194,25 @@ class FusedEngine:
         shape = tuple(g._features_rest.shape)
         if self.grads is not None and "f_rest" in self.grads and tuple(self.grads["f_rest"].shape) == shape:
             return self.grads["f_rest"]
-        if getattr(self, "_rest_rows", None) is None or tuple(self._rest_rows.shape) != shape:
+        if self._rest_rows is None or tuple(self._rest_rows.shape) != shape:
             self._rest_rows = torch.zeros(shape, device=self.dev)
             if self.grads is not None:
                 self.grads["f_rest"] = self._rest_rows
         return self._rest_rows
+
+    @staticmethod
+    def _slam_grads(grads=None, stats=None, rest=None):
+        """Mm3dgsSlamGrads over the five gradient arrays of `grads` (a dict like self.grads) with `rest` as d_f_rest, and / or the
+        densification statistics `stats` = (max_radii2D, grad_accum, denom); what is None stays NULL."""
+        sg = _lib.Mm3dgsSlamGrads()
+        if grads is not None:
+            sg.d_xyz, sg.d_f_dc, sg.d_opacity = grads["xyz"].data_ptr(), grads["f_dc"].data_ptr(), grads["opacity"].data_ptr()
+            sg.d_scaling, sg.d_rotation = grads["scaling"].data_ptr(), grads["rotation"].data_ptr()
+            if rest is not None:
+                sg.d_f_rest = rest.data_ptr()
+        if stats is not None:
+            sg.max_radii2D, sg.grad_accum, sg.denom = (t.data_ptr() for t in stats)
+        return sg
 
     def _flags(self):
         """STATE_CLEAN | SHORT_LISTS (hint from the last header check) | DIRECT_BINS (the capacity was sized per tile)."""
@@ -231,11 +262,8 @@ class FusedEngine:
         (self.can_adam_project())."""
         P = int(g._xyz.shape[0])
         si = self.inputs(next_pose, g)
-        sg = _lib.Mm3dgsSlamGrads()
-        sg.d_xyz, sg.d_f_dc, sg.d_opacity = grads["xyz"].data_ptr(), grads["f_dc"].data_ptr(), grads["opacity"].data_ptr()
-        sg.d_scaling, sg.d_rotation = grads["scaling"].data_ptr(), grads["rotation"].data_ptr()
-        if si.sh_degree > 0:      # (ABI 212) the sixth group: f_rest stepped from the flat buffer's f_rest block
-            sg.d_f_rest = grads["f_rest"].data_ptr()
+        # (ABI 212) at an active SH degree the sixth group, f_rest, is stepped from the flat buffer's f_rest block
+        sg = self._slam_grads(grads, rest=grads["f_rest"] if si.sh_degree > 0 else None)
         self._pose_keepalive = next_pose
         _lib.check(self.lib.mm3dgs_slam_adam_project(C.byref(self.cam), P, C.byref(si), C.byref(sg), C.byref(map_adam), _p(self.radii), _p(self.geom),
                                                      _p(self.img_state), _p(self.binning), self.n_cap, self._flags(), _stream()))
@@ -261,15 +289,7 @@ class FusedEngine:
         si = self.inputs(views[0][0], g)
         sg = None
         if stats is not None or grads is not None:
-            sg = _lib.Mm3dgsSlamGrads()
-            if stats is not None:
-                sg.max_radii2D, sg.grad_accum, sg.denom = (t.data_ptr() for t in stats)
-            if grads is not None:
-                sg.d_xyz, sg.d_f_dc, sg.d_opacity = grads["xyz"].data_ptr(), grads["f_dc"].data_ptr(), grads["opacity"].data_ptr()
-                sg.d_scaling, sg.d_rotation = grads["scaling"].data_ptr(), grads["rotation"].data_ptr()
-                rest = self.rest_grad(g)
-                if rest is not None:
-                    sg.d_f_rest = rest.data_ptr()
+            sg = self._slam_grads(grads, stats, self.rest_grad(g) if grads is not None else None)
         flags = self._flags() | (_lib.FWD_KEEP_TILE_ORDER if keep_tile_order else 0) | (_lib.FWD_PROJECTED if projected else 0)
         self._views_keepalive = views      # the device work is asynchronous
         _lib.check(self.lib.mm3dgs_slam_map(len(views), arr, C.byref(self.cam), P, C.byref(si), _p(self.out), _p(self.radii), _p(self.geom),
@@ -314,11 +334,10 @@ class FusedEngine:
         are cleared, in stream order.  A caller that is about to drain the stream anyway (the pruning step's 4-byte read-back) calls
         this before and check_capacity_end after: one round trip instead of two, and nothing launched between the read-back and the
         next run."""
-        if getattr(self, "_hdr_pin", None) is None:
-            self._hdr_pin = torch.empty(9, dtype=torch.int32).pin_memory()
-        self._hdr_pin.copy_(self.img_state[:36].view(torch.int32), non_blocking=True)
+        if self._hdr_pin is None:
+            self._hdr_pin = torch.empty(4, dtype=torch.int32).pin_memory()
+        self._hdr_pin.copy_(self.img_state[:16].view(torch.int32), non_blocking=True)
         self.img_state[4:16].zero_()
-        self.img_state[32:36].zero_()
         return (self.P, self.n_cap)
 
     def check_capacity_end(self, token):
@@ -326,34 +345,33 @@ class FusedEngine:
         h = self._hdr_pin
         P, n_cap = token
         overflow, n_max = int(h[1]), int(h[3])
-        unchecked, self.unchecked_tracking = getattr(self, "unchecked_tracking", None), None
+        unchecked, self.unchecked_tracking = self.unchecked_tracking, None
         if overflow and unchecked is not None:
             # a tracking loop that skipped its own header read (lazy check, ample headroom) ran -- at least in part -- on an overflowed
             # forward: the kernels voided those pose steps (no optimiser step, no corruption), but the frame was tracked with fewer
             # iterations than configured.  By now the map has moved on, so the loop cannot be re-run; counted and said aloud.
-            self.unrecovered_tracking_overflows = getattr(self, "unrecovered_tracking_overflows", 0) + 1
+            self.unrecovered_tracking_overflows += 1
             warnings.warn(f"mm3dgs: the tracking loop of frame {unchecked} ran without a capacity check and the binning capacity overflowed since "
                           "(its pose steps from the first overflowing forward on were skipped on the device); capacity raised")
         self.max_tile_len = int(h[2])
-        self.max_group_records = max(getattr(self, "max_group_records", 0), int(h[8]))
         self.ratio = max(self.ratio or 0.0, n_max / max(P, 1))
-        self.overflows = getattr(self, "overflows", 0) + (1 if overflow else 0)
+        self.overflows += 1 if overflow else 0
         self._checked_P, self._checked_cap = P, n_cap
         return not overflow
 
     def headroom(self):
-        """Smallest ratio capacity / (largest demand seen) over the three capacities a forward can run out of (pairs, per-tile
-        span, gradient records per projection workgroup), for the CURRENT buffers and map size; 0 when nothing has been measured
-        for them yet (fresh buffers, a map that changed size since the last check)."""
-        cp = getattr(self, "_checked_P", -1)
+        """Smallest ratio capacity / (largest demand seen) over the two capacities of a forward that the header measures (pairs,
+        per-tile span), for the CURRENT buffers and map size; 0 when nothing has been measured for them yet (fresh buffers, a map
+        that changed size since the last check).  (The per-tile records of a projection workgroup, N_capacity / ceil(P / 256), are a
+        third way to overflow that the header has no maximum for and this figure does not model.)"""
+        cp = self._checked_P
         # (a map that shrank a little since the last check -- a pruning step -- can only need less)
-        if self.ratio is None or self.P <= 0 or not (0.9 * cp <= self.P <= cp) or getattr(self, "_checked_cap", -1) != self.n_cap:
+        if self.ratio is None or self.P <= 0 or not (0.9 * cp <= self.P <= cp) or self._checked_cap != self.n_cap:
             return 0.0
         T = ((self.W + 15) // 16) * ((self.H + 15) // 16)
         h = self.n_cap / max(self.ratio * self.P, 1.0)
         if self.direct:
             h = min(h, (self.n_cap // T) / max(self.max_tile_len, 1))
-            h = min(h, (16 * self.n_cap // max((self.P + 255) // 256, 1)) / max(getattr(self, "max_group_records", 0), 1))
         return h
 
     def loss_call(self, cfg, gt_color, ref):
@@ -361,15 +379,7 @@ class FusedEngine:
                                         _p(self.loss), _stream()))
 
     def backward(self, si, grads=None, stats=None, dpose=None, pose_adam=None, map_adam=None):
-        sg = _lib.Mm3dgsSlamGrads()
-        if grads is not None:
-            sg.d_xyz, sg.d_f_dc, sg.d_opacity = grads["xyz"].data_ptr(), grads["f_dc"].data_ptr(), grads["opacity"].data_ptr()
-            sg.d_scaling, sg.d_rotation = grads["scaling"].data_ptr(), grads["rotation"].data_ptr()
-            rest = self.rest_grad(self._last_g) if getattr(self, "_last_g", None) is not None else None
-            if rest is not None:
-                sg.d_f_rest = rest.data_ptr()
-        if stats is not None:
-            sg.max_radii2D, sg.grad_accum, sg.denom = (t.data_ptr() for t in stats)
+        sg = self._slam_grads(grads, stats, self.rest_grad(self._last_g) if grads is not None and self._last_g is not None else None)
         _lib.check(self.lib.mm3dgs_slam_backward(C.byref(self.cam), self.P, C.byref(si), _p(self.radii), _p(self.geom), _p(self.img_state),
                                                  _p(self.binning), self.n_cap, _p(self.dL), _p(self.scratch), C.byref(sg), _p(dpose),
                                                  C.byref(pose_adam) if pose_adam is not None else None,

@@ -43,7 +43,7 @@ def geom_offsets(P):
     nb = (P + 255) // 256 + 1
     o, c = {}, 0
     for name, size in (("splat", P * SPLAT_F * 4), ("depth", P * 4), ("rect", P * 8), ("clamped", P), ("tileoff", P * 4),
-                       ("block_tiles", nb * 4), ("blkoff", P * 4), ("block_blk", nb * 4), ("poserec", 0)):
+                       ("block_tiles", nb * 4), ("poserec", 0)):
         o[name] = c
         c += _al(size)
     return o
@@ -69,7 +69,7 @@ def bin_offsets(N):
 
 
 HDR = ("num_rendered", "overflow", "max_tile_len", "max_num_rendered", "fwd_wave_iters", "bwd_wave_iters", "bwd_wave_visits",
-       "bin_cap", "max_group_records", "tile_order_tiles", "overflow_seen", "mean_wave_steps")
+       "bin_cap", "reserved8", "tile_order_tiles", "overflow_seen", "mean_wave_steps")
 
 
 def _u32(buf, off, n):

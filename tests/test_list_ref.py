@@ -99,9 +99,12 @@ def test_buffer_offsets_follow_the_library_sizes():
     """The readers' layouts end where the library's own size functions say the buffers end (csrc/mm3dgs_common.h)."""
     from mm3dgs_slam_amd import _lib
     lib = _lib.load()      # (built by __graft_entry__.build(); its size functions are pure host arithmetic)
-    for P in (1, 255, 256, 1000, 300001):
+    al = lambda v: (v + 255) // 256 * 256
+    for P in (1, 255, 256, 257, 1000, 300001):
         o = lr.geom_offsets(P)
         assert o["poserec"] + lr._al(P * 20 * 4) == lib.mm3dgs_geom_bytes(P)
+        # splat | depth | rect | clamped | tileoff | block_tiles | poserec, written out
+        assert al(48 * P) + al(4 * P) + al(8 * P) + al(P) + al(4 * P) + al(4 * ((P + 255) // 256 + 1)) + al(80 * P) == lib.mm3dgs_geom_bytes(P)
     for H, W in ((48, 64), (120, 168), (1080, 1920)):
         o = lr.image_offsets(H, W)
         T = ((W + 15) // 16) * ((H + 15) // 16)

@@ -47,7 +47,7 @@ def map_loop(self, views, g, lcfg, stats, map_adam, grads=None):
     # geometry sub-arrays
     def up(x, a=256): return (x + a - 1) // a * a
     offs, c = {}, 0
-    for name, n in (("splat", P * 48), ("depth", P * 4), ("rect", P * 8), ("clamped", P), ("tileoff", P * 4), ("block_tiles", ((P + 255) // 256 + 1) * 4), ("blkoff", P * 4)):
+    for name, n in (("splat", P * 48), ("depth", P * 4), ("rect", P * 8), ("clamped", P), ("tileoff", P * 4), ("block_tiles", ((P + 255) // 256 + 1) * 4)):
         offs[name] = (c, c + n); c += up(n)
     ga, gb = a["geom"], b["geom"]
     for name, (s, e) in offs.items():
