@@ -470,6 +470,39 @@ int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb /*[Hs,Ws,3]*/, const 
 int mm3dgs_ingest_est(int Hs, int Ws, const void* est /*[Hs,Ws]*/, int dtype /*0 float32, 1 float16, 2 uint16*/, double scale, int H, int W,
                       float* out /*[H,W]*/, void* stream);
 
+/* ---- debug mosaic: rows x cols panels of H x W float32 images -> one interleaved uint8 image, two launches ------------------------------
+ * The frame of the reference's debug video (slam/SLAM.py:233-276: 2 x 3, colour | render | |render - colour| over three coloured depth images)
+ * and of SLAM.render() (:148-195: an image over its coloured depth) composed on the device; only the finished bytes go to the host.
+ * kind, a, b: HOST arrays of rows * cols entries, panel (r, c) at index r * cols + c; a[p], b[p] are device pointers, 4-byte aligned (planes
+ * of a [6,H,W] render qualify).  rows * cols <= 8.  Panel (r, c) fills out[r H : (r+1) H, c W : (c+1) W, :]; out is uint8 [rows H, cols W, 3],
+ * any byte alignment.  Per pixel (y, x) and channel ch of a panel:
+ *   kind 0, colour: a is [3,H,W]; v = a[ch,y,x]; byte = Q(v).
+ *   kind 1, absolute difference: a, b are [3,H,W]; v = fabsf(a[ch,y,x] - b[ch,y,x]), one float32 subtraction; byte = Q(v).
+ *   kind 2, depth colour map: a is [H,W]; lo, hi = the minimum and maximum over all H W values, both NaN if any value is NaN (torch.min /
+ *     torch.max); t = (a[y,x] - lo) / (hi - lo) with float32 operators and the correctly rounded IEEE division; t < 0 -> 0, t > 1 -> 1, a
+ *     NaN stays NaN; byte = lut[min((int)(t * 256), 255)][ch] (matplotlib's table lookup), and a NaN t gives 0 in all three channels
+ *     (matplotlib's "bad" colour).  Hence a panel that holds a NaN, or whose values are all equal (hi == lo: 0 / 0), is (0, 0, 0) throughout;
+ *     the other panels are not affected.  b[p] is ignored.
+ *   lut: device uint8 [256,3], RGB, already quantised by the caller with the rule Q it wants for the table's float64 entries.
+ *   Q, the quantiser of kinds 0 and 1: p = (double)v * 255, exact (a float32 times 255 has at most 32 significant bits).
+ *     quant 0: NaN or p < 0 -> 0; p >= 255 -> 255; otherwise (uint8)trunc(p).  On [0,1] this is the reference's (vid_image * 255).to(torch.uint8)
+ *              on the float64 tensor its torch.cat produces; outside [0,1] the reference is undefined and this library saturates.
+ *     quant 1: NaN -> 0; otherwise (uint8)trunc(min(max(p + 0.5, 0), 255)), the sum rounded once in double: torchvision.utils.save_image's
+ *              mul(255).add_(0.5).clamp_(0, 255) on float64.
+ *   bgr != 0 swaps the first and the third output byte of every pixel (what the reference hands its video writer); kind 2 included.
+ * Against the host path of the Python package (debug_frames.compose_host): the same bytes, every one.
+ * work: mm3dgs_mosaic_work_bytes(H, W, rows, cols) bytes of device memory, 8-byte aligned, contents irrelevant before and after.  Two
+ * launches on `stream` -- per-panel partial (min, max, NaN flag) records into work, then compose; the first only when a kind-2 panel is
+ * present --, no atomics, no host synchronisation; min and max are exact in any order, so the same inputs give the same bytes on every call.
+ * Nothing outside out[0 : rows H cols W 3] is written.  -1 (nothing is launched): a non-positive size, more than 8 panels or more than 2^28
+ * pixels in all, a NULL kind or a, a kind outside 0..2, a NULL a[p], a NULL b or b[p] for kind 1, a NULL lut with a kind-2 panel present, a
+ * quant other than 0 / 1, NULL work / out, a work that is not 8-byte or an image that is not 4-byte aligned.  mm3dgs_mosaic_work_bytes
+ * returns 0 for a shape that mm3dgs_mosaic rejects. */
+size_t mm3dgs_mosaic_work_bytes(int H, int W, int rows, int cols);
+int mm3dgs_mosaic(int H, int W, int rows, int cols, const int32_t* kind /*host [rows*cols]*/, const float* const* a /*host [rows*cols], device pointers*/,
+                  const float* const* b /*host [rows*cols], device pointers or NULL entries*/, const uint8_t* lut /*device [256,3]*/,
+                  int quant /*0 truncate, 1 round*/, int bgr, void* work, uint8_t* out /*[rows*H, cols*W, 3]*/, void* stream);
+
 /* ---- optional per-kernel timing (HIP events recorded on the caller's stream around each launch) ------------
  * Used by bench.py's roofline leg.  mm3dgs_profile_read() waits for the recorded events, returns the number of
  * (timed) launches and their summed duration since the previous read, and resets the counters. */
@@ -530,7 +563,8 @@ const char* mm3dgs_last_error(void);
         library at exactly 213): mm3dgs_align_depth_work_bytes / mm3dgs_align_depth (the monocular depth estimate's least-squares fit to
         the map, its fit record and its application on the device); mm3dgs_ingest_frame (raw uint8 RGB + uint16 depth -> the float32 frame,
         one launch); mm3dgs_ingest_est (the monocular depth network's raw output, float32 / float16 / uint16 at any size -> the float32
-        estimate at frame size, one launch); a caller that needs them looks the symbols up */
+        estimate at frame size, one launch); mm3dgs_mosaic_work_bytes / mm3dgs_mosaic (the debug video's and SLAM.render()'s panel
+        mosaic as one uint8 image, composed on the device); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

@@ -98,6 +98,8 @@ _SIGS = {
     "mm3dgs_align_depth": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
     "mm3dgs_ingest_frame": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_double, C.c_int, C.c_int, _P, _P, _P]),
     "mm3dgs_ingest_est": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P]),
+    "mm3dgs_mosaic_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mm3dgs_mosaic": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "mm3dgs_covisibility_ratio": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
     "mm3dgs_prune_mask": (C.c_int, [C.c_int, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     "mm3dgs_compact_work_bytes": (C.c_size_t, [C.c_size_t]),

@@ -735,6 +735,35 @@ int mm3dgs_ingest_est(int Hs, int Ws, const void* est, int dtype, double scale, 
   return check_launch("ingest_est");
 }
 
+static bool mosaic_shape_ok(int H, int W, int rows, int cols) {
+  return H > 0 && W > 0 && rows > 0 && cols > 0 && rows * (long long)cols <= MOSAIC_MAX_PANELS &&
+         (size_t)rows * (size_t)H * (size_t)cols * (size_t)W <= ((size_t)1 << 28);
+}
+
+size_t mm3dgs_mosaic_work_bytes(int H, int W, int rows, int cols) { return mosaic_shape_ok(H, W, rows, cols) ? mosaic_work_bytes(rows, cols) : 0; }
+
+int mm3dgs_mosaic(int H, int W, int rows, int cols, const int32_t* kind, const float* const* a, const float* const* b, const uint8_t* lut, int quant,
+                  int bgr, void* work, uint8_t* out, void* stream) {
+  if (H <= 0 || W <= 0 || rows <= 0 || cols <= 0) return fail(-1, "mosaic: %d x %d panels of %d x %d (all must be positive)", rows, cols, H, W);
+  if (!mosaic_shape_ok(H, W, rows, cols))
+    return fail(-1, "mosaic: %d x %d panels of %d x %d (at most %d panels and 2^28 pixels)", rows, cols, H, W, MOSAIC_MAX_PANELS);
+  if (!kind || !a || !work || !out) return fail(-1, "mosaic: NULL argument (kind, a, work and out are required)");
+  if (quant != 0 && quant != 1) return fail(-1, "mosaic: quant = %d (0 truncate, 1 round)", quant);
+  if ((uintptr_t)work & 7) return fail(-1, "mosaic: work must be 8-byte aligned");
+  MosaicPanels panels = {};
+  for (int p = 0; p < rows * cols; p++) {
+    if (kind[p] < 0 || kind[p] > 2) return fail(-1, "mosaic: panel %d has kind %d (0 colour, 1 absolute difference, 2 depth)", p, kind[p]);
+    if (!a[p] || (kind[p] == 1 && !(b && b[p]))) return fail(-1, "mosaic: panel %d (kind %d) has a NULL image", p, kind[p]);
+    if (kind[p] == 2 && !lut) return fail(-1, "mosaic: panel %d is a depth panel and lut is NULL", p);
+    if (((uintptr_t)a[p] & 3) || (kind[p] == 1 && ((uintptr_t)b[p] & 3))) return fail(-1, "mosaic: panel %d has an image that is not 4-byte aligned", p);
+    panels.kind[p] = kind[p];
+    panels.a[p] = a[p];
+    panels.b[p] = kind[p] == 1 ? b[p] : nullptr;
+  }
+  launch_mosaic(H, W, rows, cols, panels, lut, quant, bgr != 0, work, out, (hipStream_t)stream);
+  return check_launch("mosaic");
+}
+
 int mm3dgs_prune_mask(int P, const float* opacity, const float* log_scales, const float* max_radii2D, float min_opacity, float max_scale,
                       float max_screen_size, uint8_t* keep, uint32_t* n_pruned_accum, void* stream) {
   if (P < 0) return fail(-1, "P < 0");

@@ -126,3 +126,11 @@ void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* dep
 // the monocular depth estimate (ingest.hip): raw [Hs,Ws] float32 (dtype 0) / float16 (1) / uint16 (2) -> float32 [H,W], bilinear, times
 // scale, one launch; arguments as the entry point has checked them
 void launch_ingest_est(int Hs, int Ws, const void* est, int dtype, double scale, int H, int W, float* out, hipStream_t s);
+// debug mosaic (mosaic.hip): rows x cols panels of H x W float32 images -> one interleaved uint8 image [rows H, cols W, 3]; kind 0 colour
+// (a [3,H,W]), 1 |a - b|, 2 depth (a [H,W]) through the caller's quantised colour table lut [256,3]; work = mosaic_work_bytes(rows, cols)
+// bytes, 8-byte aligned; at most 2^28 pixels and MOSAIC_MAX_PANELS panels, kinds and pointers as the entry point has checked them
+#define MOSAIC_MAX_PANELS 8
+struct MosaicPanels { const float* a[MOSAIC_MAX_PANELS]; const float* b[MOSAIC_MAX_PANELS]; int kind[MOSAIC_MAX_PANELS]; };
+size_t mosaic_work_bytes(int rows, int cols);
+void launch_mosaic(int H, int W, int rows, int cols, const MosaicPanels& panels, const uint8_t* lut, int quant, int bgr, void* work, uint8_t* out,
+                   hipStream_t s);

@@ -15,6 +15,7 @@ iterations; ``get_covisible_gaussians`` ignores its ``min_kf`` a
 """
 from __future__ import annotations
 
+import os
 import time
 from collections import defaultdict
 from random import randint
@@ -366,6 +367,11 @@ class Mapper:
             kf_list.append(-1)
             if self.need_new_keyframe(idx, camera_pose, gt_color, gt_depth, est_depth):
                 new_gaussians_mask, new_vis_mask = self.initialize_new_gaussians(idx, camera_pose, gt_color, gt_depth, est_depth)
-                self.add_keyframe(idx, camera_pose, gt_color, gt_depth, est_depth)
+                new_kf = self.add_keyframe(idx, camera_pose, gt_color, gt_depth, est_depth)
+                if self.cfg["debug"].get("save_keyframes", False) and "outputdir" in self.cfg:      # slam/mapper.py:991-1000
+                    from . import debug_frames
+                    path = os.path.join(self.cfg["outputdir"], "keyframes")
+                    os.makedirs(path, exist_ok=True)
+                    debug_frames.save_png(debug_frames.keyframe_u8(new_kf.gt_color), os.path.join(path, f"{new_kf.idx:05d}.png"))
         self.optimize_map(idx, self.num_iter, kf_list, new_gaussians_mask, camera_pose, gt_color, gt_depth, est_depth)
         return new_vis_mask

@@ -8,7 +8,9 @@ Harness outputs in the reference's formats: ``save_map`` = ``out
 psnr_list, ssim_list, lpips_list, avg_tracking_it_time, avg_mapping_it_time), and resuming from a checkpoint when the
 configuration carries ``iteration`` (``:90-104`` map + poses, ``slam/mapper.py:65-71`` keyframes + covisibility graph).  Frame
 sources: ``SyntheticSequence`` here, recorded TUM / UT-MM directories in ``dataset.RecordedSequence``.  The Replica and other loaders, the
-monocular depth network, debug videos and LPIPS (a downloaded network; its list stays empty) are out of scope."""
+monocular depth network and LPIPS (a downloaded network; its list stays empty) are out of scope.  Debug outputs
+(``debug_frames.py``): ``debug.create_video`` writes the reference's per-frame 2 x 3 mosaic (``:233-276,450-485``) as numbered PNG files under
+``outputdir/debug_video/``, ``debug.save_keyframes`` one PNG per keyframe (mapper.py), ``render()`` the image-over-depth pairs of ``:148-195``."""
 from __future__ import annotations
 
 import math
@@ -220,6 +222,7 @@ class SLAM:
         self.mapper = MapperCls(cfg, self.gaussians, self.renderer, self.estimate_pose_list, n_img=n, window=window)
         self.gt_pose_list = [None] * n
         self.depth_fits, self.depth_fit_frames = [], []      # depth_align_on_device: the fit record (on the device) of every fitted frame, and its index
+        self.frame_sink = None      # debug.create_video: the PNG writer of outputdir/debug_video, opened by the first frame, closed by run()
         if resume is not None:
             dev = cfg["device"]
             for i, p in enumerate(resume["pose_est"][:n]):
@@ -258,10 +261,50 @@ class SLAM:
                     self.depth_fit_frames.append(idx)
             else:
                 est_scaled = scale_depth_estimate(self.cfg, idx, est, depth, render, resumed="iteration" in self.cfg)
+        video = bool(self.cfg["debug"].get("create_video", False)) and "outputdir" in self.cfg
+        if video and idx > 0:      # slam/SLAM.py:450-453: the tracked frame over the map as it was
+            self.save_video_frame(idx, color, depth, est_scaled, "track")
         if idx == 0:
             self.mapper.camera_extent = float((est_scaled if mono else depth).max()) / self.cfg["scene_radius_depth_ratio"]
-        self.mapper.run_frame(idx, color, depth, est_scaled)
+        new_vis_mask = self.mapper.run_frame(idx, color, depth, est_scaled)
         self.gt_pose_list[idx] = gt_pose.detach().clone()
+        if video:                  # slam/SLAM.py:473-485: after mapping; the pixels that seeded Gaussians when the frame became a keyframe
+            self.save_video_frame(idx, color, depth, est_scaled if new_vis_mask is None else new_vis_mask.float(), "map")
+
+    def save_video_frame(self, idx, gt_color, gt_depth, third, name):
+        """One frame of the debug video (slam/SLAM.py:233-276): the map rendered once at the estimated pose of frame `idx`, then the 2 x 3
+        mosaic  colour | render | |render - colour|  over  sensor depth | rendered depth | `third`, the depth images through viridis --
+        composed by debug_frames.compose (one mm3dgs_mosaic call on a GPU) and handed to the PNG writer thread.  `third` is the rescaled
+        depth estimate (the sensor depth itself with `use_gt_depth`, the reference's other branch) or the mask of newly seeded pixels.  `run()`
+        closes the writer; a caller that steps the frames itself calls `self.frame_sink.close()` when it is done."""
+        from . import debug_frames as df
+        with torch.no_grad():
+            result = self.renderer.render(self.gaussians, camera_pose=self.estimate_pose_list[idx])
+            image, depth = result["render"], result["depth"][0]
+            frame = df.compose([(df.COLOR, gt_color, None), (df.COLOR, image, None), (df.ABSDIFF, image, gt_color),
+                                (df.DEPTH, gt_depth, None), (df.DEPTH, depth, None), (df.DEPTH, third, None)], 2, 3, quant=0, bgr=False)
+            if self.frame_sink is None:
+                self.frame_sink = df.FrameSink(os.path.join(self.cfg["outputdir"], "debug_video"))
+            return self.frame_sink.put(frame, idx, name)
+
+    def render(self, every=50):
+        """slam/SLAM.py:148-195: for every frame with `idx % every == 0` that has an estimated pose, `outputdir/render/render{idx:05d}.png`
+        (the map rendered at the estimated pose over its coloured rendered depth) and `gt{idx:05d}.png` (the frame over its coloured sensor
+        depth), quantised as torchvision.utils.save_image does.  Returns the paths written."""
+        from . import debug_frames as df
+        path = os.path.join(self.cfg["outputdir"], "render")
+        os.makedirs(path, exist_ok=True)
+        written = []
+        with torch.no_grad():
+            for idx in range(len(self.seq)):
+                if idx % int(every) != 0 or self.estimate_pose_list[idx] is None:
+                    continue
+                gt_color, gt_depth, _ = self.seq[idx]
+                result = self.renderer.render(self.gaussians, camera_pose=self.estimate_pose_list[idx])
+                for stem, color, depth in (("render", result["render"], result["depth"][0]), ("gt", gt_color, gt_depth)):
+                    written.append(os.path.join(path, f"{stem}{idx:05d}.png"))
+                    df.save_png(df.compose([(df.COLOR, color, None), (df.DEPTH, depth, None)], 2, 1, quant=1, bgr=False), written[-1])
+        return written
 
     def run(self, progress=None, reraise=True):
         """slam/SLAM.py:375-503: every frame; `save_iterations` checkpoints on the way; with an `outputdir` the final map (as
@@ -285,6 +328,12 @@ class SLAM:
             print(e)
             print("\nSLAM failed. Saving map and results.\n")
         finally:
+            if self.frame_sink is not None:      # debug.create_video: wait for the PNG writer (a frame it could not write is reported, not raised)
+                try:
+                    self.frame_sink.close()
+                except Exception as e3:      # noqa: BLE001
+                    print(f"(debug video: {e3!r})")
+                self.frame_sink = None
             if "outputdir" in self.cfg and last_idx > 0:
                 try:
                     with torch.no_grad():

@@ -19,7 +19,10 @@ Outputs in `outputdir`, in the reference's formats (slam/SLAM.py:286-373,488-500
 every frame index in `save_iterations` and for the final map (attribute layout of slam/gaussian_model.py:205-257), `results.npz`
 with the reference's keys (pose_est, pose_gt, keyframes, ate_rmse, psnr_list, ssim_list, lpips_list [empty: LPIPS needs a downloaded
 network], avg_tracking_it_time / avg_mapping_it_time with debug.get_runtime_stats).  A config that carries `iteration: <n>` resumes
-from that checkpoint (map, poses, keyframes, covisibility graph), like the reference.
+from that checkpoint (map, poses, keyframes, covisibility graph), like the reference.  `debug.create_video: true` adds `debug_video/`
+(one PNG per frame of the reference's debug video: after tracking and after mapping; INTEGRATION.md has the ffmpeg line that makes the
+video), `debug.save_keyframes: true` adds `keyframes/<idx>.png`, and `--render` adds `render/render<idx>.png` + `render/gt<idx>.png` for
+every 50th frame (the reference's `SLAM.render()`).  None of them changes a pose.
 """
 import argparse
 import os
@@ -62,6 +65,7 @@ def main():
     ap.add_argument("--config", type=str, default=None, help="YAML config in the reference's schema")
     ap.add_argument("--frames", type=int, default=None, help="frames to run (default: 10 synthetic frames, or the whole recorded sequence)")
     ap.add_argument("--gaussians", type=int, default=150000, help="size of the synthetic ground-truth scene")
+    ap.add_argument("--render", action="store_true", help="after the run, write render / ground-truth image pairs of every 50th frame to outputdir/render")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
     from mm3dgs_slam_amd.slam import SLAM
@@ -76,7 +80,8 @@ def main():
                 cfg[k] = v
     cfg["mapping"]["niqe_kf"] = False
     dbg = dict(cfg.get("debug") or {})
-    cfg["debug"] = {"get_runtime_stats": bool(dbg.get("get_runtime_stats", False)), "create_video": False, "save_keyframes": False}
+    cfg["debug"] = {"get_runtime_stats": bool(dbg.get("get_runtime_stats", False)), "create_video": bool(dbg.get("create_video", False)),
+                    "save_keyframes": bool(dbg.get("save_keyframes", False))}
     cfg.setdefault("outputdir", "output/" + (str(cfg.get("scene") or "recorded") if sequence_source(cfg) == "recorded" else "synthetic"))
     outdir = cfg["outputdir"]
     os.makedirs(outdir, exist_ok=True)
@@ -94,6 +99,8 @@ def main():
     slam.run(progress, reraise=False)          # (the reference's behaviour on a failed frame: print, save, carry on -- reported by the exit code below); checkpoints, the final map and results.npz are written inside (reference formats)
     res = np.load(os.path.join(outdir, "results.npz"), allow_pickle=True)
     print(f"Average Trajectory Error RMSE: {float(res['ate_rmse'])} m; {1.0 / np.mean(times[1:]):.2f} frames/s after frame 0; outputs in {outdir}")
+    if args.render:
+        print(f"{len(slam.render())} images in {os.path.join(outdir, 'render')}")
     if slam.failure is not None:      # (the reference prints the exception and saves what it has, slam/SLAM.py:494-503; the exit code says so too)
         sys.exit(1)
 
