@@ -220,6 +220,7 @@ static void warn_env_once() {
 }
 
 // ---- fused SLAM iteration ----------------------------------------------------------------------------------------
+// Every entry point below checks ALL of its arguments first and launches afterwards: a refused call has enqueued nothing.
 static SlamIn slam_in(const Mm3dgsSlamInputs* in) {
   SlamIn s;
   s.pose = in->pose; s.xyz = in->xyz; s.f_dc = in->f_dc; s.opacity = in->opacity; s.scaling = in->scaling;
@@ -229,13 +230,14 @@ static SlamIn slam_in(const Mm3dgsSlamInputs* in) {
   s.sh_dir = s.sh_deg ? in->sh_dir : 0;
   return s;
 }
-static int check_slam(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in) {
+// need_pose = false: the mapping loop, which renders its views' poses and ignores in->pose
+static int check_slam(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, bool need_pose = true) {
   warn_env_once();
   if (!cam || !in) return fail(-1, "NULL argument");
   if (cam->image_height <= 0 || cam->image_width <= 0) return fail(-1, "bad image size");
   if (P < 0) return fail(-1, "P < 0");
   if (!cam->bg || !cam->projmatrix) return fail(-1, "camera device pointers missing");
-  if (!in->pose) return fail(-1, "pose is NULL");
+  if (need_pose && !in->pose) return fail(-1, "pose is NULL");
   if (P > 0 && (!in->xyz || !in->f_dc || !in->opacity || !in->scaling || !in->rotation)) return fail(-1, "NULL Gaussian parameter");
   if (in->sh_degree < 0 || in->sh_degree > 3) return fail(-2, "sh_degree %d outside 0..3", in->sh_degree);
   if (in->sh_dir < 0 || in->sh_dir > 2) return fail(-2, "sh_dir %d outside 0..2", in->sh_dir);
@@ -274,79 +276,135 @@ static DirectBins slam_direct_bins(int flags, const CamDev& cd, int P, size_t N_
   return d;
 }
 
-// The SLAM loops refresh image_state's load-balanced workgroup -> tile table (binning.hip) once per call, from the list lengths of the
-// last render; the compositors honour it while the header says it matches the grid (persistent state only: a per-call memset clears it).
-static bool slam_tile_table(int flags) { return (flags & MM3DGS_FWD_STATE_CLEAN) && !env_flag("MM3DGS_NO_TILE_ORDER", 0); }
-static void slam_refresh_tile_order(const Mm3dgsCamera* cam, void* image_state, int flags, void* stream) {
-  if (!cam || !image_state || !slam_tile_table(flags) || cam->image_height <= 0 || cam->image_width <= 0) return;
-  if (flags & MM3DGS_FWD_KEEP_TILE_ORDER) return;      // (a table left by an earlier call is honoured while its key matches the image size)
-  const CamDev cd = cam_dev(cam);
-  launch_tile_order(cd.gx * cd.gy, cd.H, cd.W, image_view(image_state, cd.H, cd.W), (hipStream_t)stream);
+// What the launches of one C call share, built and checked once per call (slam_call); the loops only move in.pose.
+struct SlamCall {
+  hipStream_t s; int P; size_t N_cap; int flags;
+  CamDev cd;         // with the SLAM fields every launch sees: bg_extras, tile_table, trec_cap
+  CamDev cd_fwd;     // cd + what the forward's binning launches read: sort_single, state_clean, fused_scan
+  SlamIn in;         // in.pose: the view the next launch renders
+  GeomView g; ImageView iv; BinView b;
+  BwdView bw;        // (zero without a backward scratch)
+  DirectBins db; bool fused_sort;
+  float* out_color; int32_t* radii;
+  bool sh() const { return in.sh_deg > 0; }   // an ACTIVE SH degree: standalone loss kernels, mapping-mode compositor, sixth Adam group
+};
+// what a call needs beside the three state buffers and radii: out_color | backward_scratch; SLAM_POSE_LATER: in->pose is not read (check_slam)
+enum { SLAM_OUT = 1, SLAM_SCRATCH = 2, SLAM_POSE_LATER = 4 };
+static int slam_call(SlamCall& c, const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, float* out_color, int32_t* radii, void* geom_state,
+                     void* image_state, void* binning_state, size_t N_capacity, void* backward_scratch, int flags, void* stream, int need) {
+  if (int rc = check_slam(cam, P, in, !(need & SLAM_POSE_LATER))) return rc;
+  if (!geom_state || !image_state || !binning_state || (P > 0 && !radii) || ((need & SLAM_OUT) && !out_color) ||
+      ((need & SLAM_SCRATCH) && !backward_scratch)) return fail(-1, "NULL buffer");
+  c.s = (hipStream_t)stream; c.P = P; c.N_cap = N_capacity; c.flags = flags;
+  c.in = slam_in(in);
+  c.out_color = out_color; c.radii = radii;
+  c.cd = cam_dev(cam);
+  c.g = geom_view(geom_state, P > 0 ? P : 1);
+  c.iv = image_view(image_state, c.cd.H, c.cd.W);
+  c.b = bin_view(binning_state, N_capacity);
+  c.bw = backward_scratch ? bwd_view(backward_scratch, P, N_capacity) : BwdView{};
+  c.cd.bg_extras = 1;
+  // image_state's load-balanced workgroup -> tile table (binning.hip): the compositors honour it while the header says it matches the grid
+  // (persistent state only: a per-call memset clears it)
+  c.cd.tile_table = ((flags & MM3DGS_FWD_STATE_CLEAN) && !env_flag("MM3DGS_NO_TILE_ORDER", 0)) ? 1 : 0;
+  // short lists (the SLAM regime): the per-tile sort runs inside the forward compositing launch
+  c.fused_sort = slam_fused_sort(flags);
+  // direct bins: the host sized the binning state as T x (per-tile capacity), so projection and binning are one launch
+  c.db = slam_direct_bins(flags, c.cd, P, N_capacity);
+  c.cd.trec_cap = c.db.on ? c.db.trec_cap : 0u;
+  c.cd_fwd = c.cd;
+  c.cd_fwd.sort_single = (flags & MM3DGS_FWD_SHORT_LISTS) ? 1 : 0;
+  c.cd_fwd.state_clean = (flags & MM3DGS_FWD_STATE_CLEAN) ? 1 : 0;
+  // persistent clean state + a tile grid that fits two LDS words per tile: fold the scan into the scatter workgroups
+  c.cd_fwd.fused_scan = ((flags & MM3DGS_FWD_STATE_CLEAN) && P > 0 && c.cd.gx * c.cd.gy <= MAX_FUSED_SCAN_TILES && !env_flag("MM3DGS_NO_FUSED_SCAN", 0)) ? 1 : 0;
+  return 0;
 }
 
-static int slam_forward_impl(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, float* out_color, int32_t* radii,
-                             void* geom_state, void* image_state, void* binning_state, size_t N_capacity, int flags, void* stream,
-                             const TrackLoss* tl, float* track_dsub = nullptr, bool projected = false, bool pose_chain = false) {
-  int rc = check_slam(cam, P, in);
-  if (rc) return rc;
-  if (!out_color || !geom_state || !image_state || !binning_state || (P > 0 && !radii)) return fail(-1, "NULL buffer");
-  hipStream_t s = (hipStream_t)stream;
-  CamDev cd = cam_dev(cam);
-  GeomView g = geom_view(geom_state, P > 0 ? P : 1);
-  ImageView iv = image_view(image_state, cd.H, cd.W);
-  BinView b = bin_view(binning_state, N_capacity);
-  if (!(flags & MM3DGS_FWD_STATE_CLEAN))
-    if (hipMemsetAsync(image_state, 0, iv.zero_bytes, s) != hipSuccess) return fail(-10, "memset failed");
-  cd.sort_single = (flags & MM3DGS_FWD_SHORT_LISTS) ? 1 : 0;
-  cd.bg_extras = 1;
-  cd.state_clean = (flags & MM3DGS_FWD_STATE_CLEAN) ? 1 : 0;
-  cd.tile_table = slam_tile_table(flags) ? 1 : 0;
-  // persistent clean state + a tile grid that fits two LDS words per tile: fold the scan into the scatter workgroups
-  cd.fused_scan = ((flags & MM3DGS_FWD_STATE_CLEAN) && P > 0 && cd.gx * cd.gy <= MAX_FUSED_SCAN_TILES && !env_flag("MM3DGS_NO_FUSED_SCAN", 0)) ? 1 : 0;
-  // short lists (the SLAM regime): the per-tile sort runs inside the forward compositing launch
-  const bool fused_sort = slam_fused_sort(flags);
-  if (tl && !fused_sort) return fail(-1, "internal: folded tracking loss needs the fused sort path");
-  // direct bins: the host sized the binning state as T x (per-tile capacity), so projection and binning are one launch
-  const DirectBins db = slam_direct_bins(flags, cd, P, N_capacity);
-  cd.trec_cap = db.on ? db.trec_cap : 0u;
-  if (db.on) {
-    // projected: the previous mapping iteration's backward launch already projected and binned this view (slam_bwd_project_kernel)
-    if (!projected) { ProfScope ps(MM3DGS_PROF_PREPROCESS_FWD, s); launch_slam_project_bin(cd, P, slam_in(in), radii, g, iv, b, db.bin_cap, db.slot_bits, s, pose_chain); }
-    { ProfScope ps(track_dsub ? MM3DGS_PROF_TRACK_FWD_BWD : MM3DGS_PROF_COMPOSITE_FWD, s);
-      if (track_dsub) launch_sort_composite_fwd_bwd_track(cd, g, iv, b, N_capacity, out_color, 1, s, *tl, db.nblocks, track_dsub, db.bin_cap, db.slot_bits, pose_chain);
-      else launch_sort_composite_fwd6(cd, g, iv, b, N_capacity, out_color, 1, s, tl, db.nblocks, db.bin_cap, db.slot_bits); }
+// The SLAM loops rebuild the workgroup -> tile table once per call, from the list lengths of the last render.
+static void slam_refresh_tile_order(const SlamCall& c) {
+  if (!c.cd.tile_table || (c.flags & MM3DGS_FWD_KEEP_TILE_ORDER)) return;      // (a table left by an earlier call is honoured while its key matches the image size)
+  launch_tile_order(c.cd.gx * c.cd.gy, c.cd.H, c.cd.W, c.iv, c.s);
+}
+
+struct SlamFwd {
+  const TrackLoss* tl = nullptr;    // loss folded into the compositor's epilogue (needs the fused sort path)
+  float* track_dsub = nullptr;      // tracking: the backward compositor runs in the forward launch and writes here
+  bool projected = false;           // an earlier launch already projected and binned this view (slam_bwd_project / slam_adam_project; direct bins only)
+  bool pose_chain = false;
+};
+static int slam_forward(const SlamCall& c, const SlamFwd& o) {
+  const CamDev& cd = c.cd_fwd;
+  const hipStream_t s = c.s;
+  if (o.tl && !c.fused_sort) return fail(-1, "internal: folded tracking loss needs the fused sort path");
+  if (!cd.state_clean)
+    if (hipMemsetAsync(c.iv.hdr, 0, c.iv.zero_bytes, s) != hipSuccess) return fail(-10, "memset failed");
+  const int prof_fwd = (c.fused_sort && o.track_dsub) ? MM3DGS_PROF_TRACK_FWD_BWD : MM3DGS_PROF_COMPOSITE_FWD;
+  if (c.db.on) {
+    const DirectBins& db = c.db;
+    if (!o.projected) { ProfScope ps(MM3DGS_PROF_PREPROCESS_FWD, s); launch_slam_project_bin(cd, c.P, c.in, c.radii, c.g, c.iv, c.b, db.bin_cap, db.slot_bits, s, o.pose_chain); }
+    { ProfScope ps(prof_fwd, s);
+      if (o.track_dsub) launch_sort_composite_fwd_bwd_track(cd, c.g, c.iv, c.b, c.N_cap, c.out_color, 1, s, *o.tl, db.nblocks, o.track_dsub, db.bin_cap, db.slot_bits, o.pose_chain);
+      else launch_sort_composite_fwd6(cd, c.g, c.iv, c.b, c.N_cap, c.out_color, 1, s, o.tl, db.nblocks, db.bin_cap, db.slot_bits); }
     return check_launch("slam_forward");
   }
-  { ProfScope ps(MM3DGS_PROF_PREPROCESS_FWD, s); launch_slam_preprocess_fwd(cd, P, slam_in(in), radii, g, iv, s, nullptr, false, pose_chain); }
-  if (!cd.fused_scan) { ProfScope ps(MM3DGS_PROF_SCAN, s); launch_scan_tiles(cd.gx * cd.gy, P, g, iv, s, (flags & MM3DGS_FWD_STATE_CLEAN) ? 1 : 0); }
-  { ProfScope ps(MM3DGS_PROF_BIN_SORT, s); launch_scatter_sort(cd, P, g, iv, b, N_capacity, nullptr, s, fused_sort); }
-  { ProfScope ps((fused_sort && track_dsub) ? MM3DGS_PROF_TRACK_FWD_BWD : MM3DGS_PROF_COMPOSITE_FWD, s);
-    if (fused_sort && track_dsub) launch_sort_composite_fwd_bwd_track(cd, g, iv, b, N_capacity, out_color, (cd.fused_scan || cd.state_clean) ? 1 : 0, s, *tl, 0, track_dsub, 0, DIRECT_SLOT_BITS_MAX, pose_chain);
-    else if (fused_sort) launch_sort_composite_fwd6(cd, g, iv, b, N_capacity, out_color, (cd.fused_scan || cd.state_clean) ? 1 : 0, s, tl);
-    else launch_composite_fwd(cd, 6, g, iv, b, N_capacity, out_color, s); }
+  const int clean = (cd.fused_scan || cd.state_clean) ? 1 : 0;
+  { ProfScope ps(MM3DGS_PROF_PREPROCESS_FWD, s); launch_slam_preprocess_fwd(cd, c.P, c.in, c.radii, c.g, c.iv, s, nullptr, false, o.pose_chain); }
+  if (!cd.fused_scan) { ProfScope ps(MM3DGS_PROF_SCAN, s); launch_scan_tiles(cd.gx * cd.gy, c.P, c.g, c.iv, s, cd.state_clean); }
+  { ProfScope ps(MM3DGS_PROF_BIN_SORT, s); launch_scatter_sort(cd, c.P, c.g, c.iv, c.b, c.N_cap, nullptr, s, c.fused_sort); }
+  { ProfScope ps(prof_fwd, s);
+    if (c.fused_sort && o.track_dsub) launch_sort_composite_fwd_bwd_track(cd, c.g, c.iv, c.b, c.N_cap, c.out_color, clean, s, *o.tl, 0, o.track_dsub, 0, DIRECT_SLOT_BITS_MAX, o.pose_chain);
+    else if (c.fused_sort) launch_sort_composite_fwd6(cd, c.g, c.iv, c.b, c.N_cap, c.out_color, clean, s, o.tl);
+    else launch_composite_fwd(cd, 6, c.g, c.iv, c.b, c.N_cap, c.out_color, s); }
   return check_launch("slam_forward");
 }
 
 int mm3dgs_slam_visibility(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, int32_t* radii, uint32_t* seen_count, void* geom_state,
                            void* stream) {
-  int rc = check_slam(cam, P, in);
-  if (rc) return rc;
+  if (int rc = check_slam(cam, P, in)) return rc;
   if (!geom_state || (P > 0 && !radii)) return fail(-1, "NULL buffer");
-  CamDev cd = cam_dev(cam);
-  GeomView g = geom_view(geom_state, P > 0 ? P : 1);
-  ImageView iv = {};
-  launch_slam_preprocess_fwd(cd, P, slam_in(in), radii, g, iv, (hipStream_t)stream, seen_count, true);
+  launch_slam_preprocess_fwd(cam_dev(cam), P, slam_in(in), radii, geom_view(geom_state, P > 0 ? P : 1), ImageView{}, (hipStream_t)stream, seen_count, true);
   return check_launch("slam_visibility");
 }
 
 int mm3dgs_slam_forward(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, float* out_color, int32_t* radii,
                         void* geom_state, void* image_state, void* binning_state, size_t N_capacity, int flags, void* stream) {
-  return slam_forward_impl(cam, P, in, out_color, radii, geom_state, image_state, binning_state, N_capacity, flags, stream, nullptr, nullptr,
-                           (flags & MM3DGS_FWD_PROJECTED) != 0);
+  SlamCall c;
+  if (int rc = slam_call(c, cam, P, in, out_color, radii, geom_state, image_state, binning_state, N_capacity, nullptr, flags, stream, SLAM_OUT)) return rc;
+  return slam_forward(c, {.projected = (flags & MM3DGS_FWD_PROJECTED) != 0});
 }
 
+// ---- ABI structs -> the kernels' structs, with their rules (NULL: all zero) ----
+// sh: the gradient outputs need d_f_rest too; stats: take the densification statistics (mm3dgs_slam_adam_project ignores them)
+static int slam_grads_dev(const Mm3dgsSlamGrads* grads, bool sh, bool stats, SlamGrads& sg) {
+  sg = {};
+  if (!grads) return 0;
+  const bool any = grads->d_xyz || grads->d_f_dc || grads->d_opacity || grads->d_scaling || grads->d_rotation;
+  const bool all = grads->d_xyz && grads->d_f_dc && grads->d_opacity && grads->d_scaling && grads->d_rotation;
+  if (any && !all) return fail(-2, "Gaussian gradient outputs must be all set or all NULL");
+  if (all && sh && !grads->d_f_rest) return fail(-2, "sh_degree > 0: the gradient outputs need d_f_rest too");
+  sg.d_xyz = grads->d_xyz; sg.d_f_dc = grads->d_f_dc; sg.d_opacity = grads->d_opacity; sg.d_scaling = grads->d_scaling;
+  sg.d_rotation = grads->d_rotation; sg.d_f_rest = (all && sh) ? grads->d_f_rest : nullptr;
+  if (!stats) return 0;
+  if (grads->max_radii2D && (!grads->grad_accum || !grads->denom)) return fail(-2, "statistics outputs must be all set or all NULL");
+  sg.max_radii2D = grads->max_radii2D; sg.grad_accum = grads->grad_accum; sg.denom = grads->denom;
+  return 0;
+}
+// (pose_adam NULL or without a pose: no step)
+static int pose_adam_dev(const Mm3dgsPoseAdam* pose_adam, PoseAdam& pa) {
+  pa = {};
+  if (!pose_adam || !pose_adam->pose) return 0;
+  if (!pose_adam->m || !pose_adam->v || !pose_adam->step) return fail(-2, "pose Adam state missing");
+  pa.pose = pose_adam->pose; pa.m = pose_adam->m; pa.v = pose_adam->v; pa.step = pose_adam->step;
+  pa.lr_q = pose_adam->lr_q; pa.lr_t = pose_adam->lr_t; pa.beta1 = pose_adam->beta1; pa.beta2 = pose_adam->beta2; pa.eps = (float)pose_adam->eps;
+  if (pose_adam->prior_pose && (pose_adam->prior_w_t != 0.f || pose_adam->prior_w_q != 0.f)) {
+    pa.prior = pose_adam->prior_pose; pa.prior_w_t = pose_adam->prior_w_t; pa.prior_w_q = pose_adam->prior_w_q;
+  }
+  pa.best = pose_adam->best;
+  return 0;
+}
 // Mm3dgsMapAdam -> the kernels' scalars: formed in double, rounded once to float (torch.optim.Adam does this arithmetic on Python floats)
-static int map_adam_dev(const Mm3dgsMapAdam* map_adam, MapAdam& ma) {
+static int map_adam_dev(const Mm3dgsMapAdam* map_adam, bool sh, MapAdam& ma) {
+  ma = {};
   if (map_adam->step < 1) return fail(-1, "map Adam step must be >= 1");
   for (int i = 0; i < 5; i++) {
     if (!map_adam->param[i] || !map_adam->exp_avg[i] || !map_adam->exp_avg_sq[i]) return fail(-2, "map Adam group %d has a NULL pointer", i);
@@ -358,96 +416,80 @@ static int map_adam_dev(const Mm3dgsMapAdam* map_adam, MapAdam& ma) {
   ma.bc2s = (float)sqrt(1.0 - pow(map_adam->beta2, (double)map_adam->step));
   ma.opt_mask = map_adam->opt_mask;
   ma.rp = map_adam->rest_param; ma.rm = map_adam->rest_exp_avg; ma.rv = map_adam->rest_exp_avg_sq;
+  if (sh && !ma.rp) return fail(-2, "sh_degree > 0: the map Adam state needs the f_rest group (rest_param / rest_exp_avg / rest_exp_avg_sq)");
   if (ma.rp && (!ma.rm || !ma.rv)) return fail(-2, "map Adam: the f_rest group has a NULL moment pointer");
   ma.rest_step_size = (float)(map_adam->rest_lr / (1.0 - pow(map_adam->beta1, (double)map_adam->step)));
   ma.on = 1;
   return 0;
 }
 
-static int slam_backward_impl(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, const int32_t* radii,
-                              const void* geom_state, const void* image_state, const void* binning_state, size_t N_capacity,
-                              const float* dL_dout, void* backward_scratch, const Mm3dgsSlamGrads* grads, float* dL_dpose,
-                              const Mm3dgsPoseAdam* pose_adam, const Mm3dgsMapAdam* map_adam, int flags, void* stream, const TrackLoss* tl,
-                              float* prior_loss4 = nullptr, int dl_planes = 6, bool compositor_done = false, const float* fuse_next_pose = nullptr,
-                              bool* fused_out = nullptr, bool pose_chain = false) {
+struct SlamBwd {
+  const float* dL_dout = nullptr;
+  SlamGrads grads = {}; float* dL_dpose = nullptr; PoseAdam pose_adam = {}; MapAdam map_adam = {};
+  const TrackLoss* tl = nullptr;     // loss folded into the compositor's prologue
+  float* prior_loss4 = nullptr;      // tracking: where the pose finish adds the pose prior's loss
+  int dl_planes = 6;                 // (launch_composite_bwd_slam)
+  bool compositor_done = false;      // the forward launch already ran the backward compositor (SlamFwd::track_dsub)
+  const float* next_pose = nullptr;  // the next mapping view: this launch may project and bin it too
+  bool pose_chain = false;
+};
+// Returns < 0: error | 0 | 1: the launch also projected and binned the view at o.next_pose (its forward is SlamFwd::projected).
+static int slam_backward(const SlamCall& c, const SlamBwd& o) {
+  const CamDev& cd = c.cd;
+  const hipStream_t s = c.s;
+  const TrackLoss* tl = o.tl;
+  const MapAdam& ma = o.map_adam;
   PoseLossScale pls = {nullptr, 0, 0.f, nullptr};
   if (tl && tl->defer_scale) { pls.rows = tl->partial; pls.nrows = ((tl->cfg.W + 15) / 16) * ((tl->cfg.H + 15) / 16); pls.w_l1 = tl->cfg.w_l1; pls.loss4 = tl->loss4; }
-  int rc = check_slam(cam, P, in);
-  if (rc) return rc;
-  if (!geom_state || !image_state || !binning_state || !dL_dout || !backward_scratch || (P > 0 && !radii)) return fail(-1, "NULL buffer");
-  hipStream_t s = (hipStream_t)stream;
-  CamDev cd = cam_dev(cam);
-  GeomView g = geom_view((void*)geom_state, P > 0 ? P : 1);
-  ImageView iv = image_view((void*)image_state, cd.H, cd.W);
-  BinView b = bin_view((void*)binning_state, N_capacity);
-  BwdView bw = bwd_view(backward_scratch, P, N_capacity);
-  cd.bg_extras = 1;
-  cd.tile_table = slam_tile_table(flags) ? 1 : 0;
-  const DirectBins db_bwd = slam_direct_bins(flags, cd, P, N_capacity);
-  cd.trec_cap = db_bwd.on ? db_bwd.trec_cap : 0u;
-  SlamGrads sg = {};
-  if (grads) {
-    const bool any = grads->d_xyz || grads->d_f_dc || grads->d_opacity || grads->d_scaling || grads->d_rotation;
-    const bool all = grads->d_xyz && grads->d_f_dc && grads->d_opacity && grads->d_scaling && grads->d_rotation;
-    if (any && !all) return fail(-2, "Gaussian gradient outputs must be all set or all NULL");
-    if (grads->max_radii2D && (!grads->grad_accum || !grads->denom)) return fail(-2, "statistics outputs must be all set or all NULL");
-    sg.d_xyz = grads->d_xyz; sg.d_f_dc = grads->d_f_dc; sg.d_opacity = grads->d_opacity; sg.d_scaling = grads->d_scaling;
-    sg.d_rotation = grads->d_rotation; sg.max_radii2D = grads->max_radii2D; sg.grad_accum = grads->grad_accum; sg.denom = grads->denom;
-    sg.d_f_rest = (all && in->sh_degree > 0) ? grads->d_f_rest : nullptr;
-    if (all && in->sh_degree > 0 && !grads->d_f_rest) return fail(-2, "sh_degree > 0: the gradient outputs need d_f_rest too");
-  }
-  PoseAdam pa = {};
-  if (pose_adam && pose_adam->pose) {
-    if (!pose_adam->m || !pose_adam->v || !pose_adam->step) return fail(-2, "pose Adam state missing");
-    pa.pose = pose_adam->pose; pa.m = pose_adam->m; pa.v = pose_adam->v; pa.step = pose_adam->step;
-    pa.lr_q = pose_adam->lr_q; pa.lr_t = pose_adam->lr_t; pa.beta1 = pose_adam->beta1; pa.beta2 = pose_adam->beta2; pa.eps = (float)pose_adam->eps;
-    if (pose_adam->prior_pose && (pose_adam->prior_w_t != 0.f || pose_adam->prior_w_q != 0.f)) {
-      pa.prior = pose_adam->prior_pose; pa.prior_w_t = pose_adam->prior_w_t; pa.prior_w_q = pose_adam->prior_w_q;
-    }
-    pa.best = pose_adam->best;
-  }
-  MapAdam ma;
-  memset(&ma, 0, sizeof(ma));
-  if (map_adam)
-    if (int rc2 = map_adam_dev(map_adam, ma)) return rc2;
-  const bool sh = in->sh_degree > 0 && in->f_rest;
-  if (sh && ma.on && !ma.rp) return fail(-2, "sh_degree > 0: the map Adam state needs the f_rest group");
   // (an active SH degree > 0: the pose gradient runs through the colours' viewing direction, so even a tracking iteration needs the colour sums of
   //  the mapping-layout records)
-  const bool tracking = sg.d_xyz == nullptr && !ma.on && !sh;
+  const bool tracking = o.grads.d_xyz == nullptr && !ma.on && !c.sh();
   if (tl && !tracking && !tl->dmaps) return fail(-1, "internal: a loss folded into the mapping backward needs the SSIM maps");
-  if (pose_chain && !tracking) return fail(-1, "internal: the pose chain is a tracking-mode path");
-  if (!compositor_done)
+  if (o.pose_chain && !tracking) return fail(-1, "internal: the pose chain is a tracking-mode path");
+  if (!o.compositor_done)
   { ProfScope ps(tracking ? MM3DGS_PROF_COMPOSITE_BWD_TRACK : MM3DGS_PROF_COMPOSITE_BWD, s);
-    launch_composite_bwd_slam(cd, tracking, g, iv, b, N_capacity, dL_dout, bw.dsub, s, tl, dl_planes, pose_chain); }
-  if (pose_chain) {
+    launch_composite_bwd_slam(cd, tracking, c.g, c.iv, c.b, c.N_cap, o.dL_dout, c.bw.dsub, s, tl, o.dl_planes, o.pose_chain); }
+  if (o.pose_chain) {
     // the tracking compositor applied the pose chain per (block, splat) and left one pose-gradient row per TILE at the head of the scratch: no
     // gradient records, no backward projection -- the pose finish sums the rows (GeomView.poserec, composite.hip)
     ProfScope ps(MM3DGS_PROF_PREPROCESS_BWD, s);
-    launch_slam_pose_finish(bw.dsub, cd.gx * cd.gy, in->pose, dL_dpose, pa, s, pls.rows ? &pls : nullptr, prior_loss4, &iv.hdr->overflow);
+    launch_slam_pose_finish(c.bw.dsub, cd.gx * cd.gy, c.in.pose, o.dL_dpose, o.pose_adam, s, pls.rows ? &pls : nullptr, o.prior_loss4, &c.iv.hdr->overflow);
     return check_launch("slam_backward");
   }
   // mapping run, direct bins, in-kernel Adam, no pose step: this launch also projects and bins the NEXT iteration's view
-  const bool fuse = fuse_next_pose && !tracking && ma.on && db_bwd.on && !dL_dpose && !pa.pose && !sg.d_xyz && !sh;
-  if (fused_out) *fused_out = fuse;
-  if (fuse) {
-    ProfScope ps(MM3DGS_PROF_PREPROCESS_BWD, s);
-    launch_slam_bwd_project(cd, P, slam_in(in), (int32_t*)radii, g, image_view((void*)image_state, cd.H, cd.W), b, N_capacity, bw, sg, ma, fuse_next_pose,
-                            db_bwd.bin_cap, db_bwd.slot_bits, s);
-  } else
-  { ProfScope ps(MM3DGS_PROF_PREPROCESS_BWD, s); launch_slam_preprocess_bwd(cd, P, slam_in(in), radii, g, b, N_capacity, bw, sg, dL_dpose, pa, ma, s, pls.rows ? &pls : nullptr, prior_loss4, db_bwd.on, &iv.hdr->overflow); }
-  return check_launch("slam_backward");
+  const bool fuse = o.next_pose && !tracking && ma.on && c.db.on && !o.dL_dpose && !o.pose_adam.pose && !o.grads.d_xyz && !c.sh();
+  { ProfScope ps(MM3DGS_PROF_PREPROCESS_BWD, s);
+    if (fuse) launch_slam_bwd_project(cd, c.P, c.in, c.radii, c.g, c.iv, c.b, c.N_cap, c.bw, o.grads, ma, o.next_pose, c.db.bin_cap, c.db.slot_bits, s);
+    else launch_slam_preprocess_bwd(cd, c.P, c.in, c.radii, c.g, c.b, c.N_cap, c.bw, o.grads, o.dL_dpose, o.pose_adam, ma, s, pls.rows ? &pls : nullptr, o.prior_loss4, c.db.on, &c.iv.hdr->overflow); }
+  const int rc = check_launch("slam_backward");
+  return rc ? rc : (fuse ? 1 : 0);
 }
 
 int mm3dgs_slam_backward(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, const int32_t* radii,
                          const void* geom_state, const void* image_state, const void* binning_state, size_t N_capacity,
                          const float* dL_dout, void* backward_scratch, const Mm3dgsSlamGrads* grads, float* dL_dpose,
                          const Mm3dgsPoseAdam* pose_adam, const Mm3dgsMapAdam* map_adam, int flags, void* stream) {
-  return slam_backward_impl(cam, P, in, radii, geom_state, image_state, binning_state, N_capacity, dL_dout, backward_scratch, grads, dL_dpose,
-                            pose_adam, map_adam, flags, stream, nullptr);
+  SlamCall c;
+  if (int rc = slam_call(c, cam, P, in, nullptr, (int32_t*)radii, (void*)geom_state, (void*)image_state, (void*)binning_state, N_capacity, backward_scratch,
+                         flags, stream, SLAM_SCRATCH)) return rc;
+  if (!dL_dout) return fail(-1, "NULL buffer");
+  SlamBwd o = {.dL_dout = dL_dout, .dL_dpose = dL_dpose};
+  if (int rc = slam_grads_dev(grads, c.sh(), true, o.grads)) return rc;
+  if (int rc = pose_adam_dev(pose_adam, o.pose_adam)) return rc;
+  if (map_adam)
+    if (int rc = map_adam_dev(map_adam, c.sh(), o.map_adam)) return rc;
+  return std::min(slam_backward(c, o), 0);
 }
 
+// ---- image losses; work buffer: sums (256 B) | dmaps [9,H,W] float | partial [16x16 tiles][12] double ----
 static size_t loss_rows(int H, int W) { return (size_t)((W + 15) / 16) * ((H + 15) / 16); }
+static size_t loss_dmaps_bytes(int H, int W) { return align_up((size_t)9 * H * W * 4, 256); }
+size_t mm3dgs_loss_work_bytes(int H, int W) { return 256 + loss_dmaps_bytes(H, W) + align_up(loss_rows(H, W) * 12 * 8, 256); }
+struct LossWork { double* sums; float* dmaps; double* partial; };
+static LossWork loss_work_view(void* work, int H, int W) {
+  char* c = (char*)work;
+  return {(double*)c, (float*)(c + 256), (double*)(c + 256 + loss_dmaps_bytes(H, W))};
+}
 static LossCfg loss_cfg_dev(const Mm3dgsLossConfig* c) {
   LossCfg lc;
   lc.H = c->H; lc.W = c->W; lc.w_l1 = c->w_l1; lc.w_ssim = c->w_ssim; lc.w_pearson = c->w_pearson; lc.l1_mask = c->l1_mask;
@@ -465,23 +507,24 @@ static int loss_cfg_check(const Mm3dgsLossConfig* c, const float* ref) {
   if (c->w_depth_l1 != 0.f && c->w_pearson != 0.f) return fail(-2, "the depth-L1 and Pearson terms are exclusive");
   return 0;
 }
-size_t mm3dgs_loss_work_bytes(int H, int W) {
-  return 256 + align_up((size_t)9 * H * W * 4, 256) + align_up(loss_rows(H, W) * 12 * 8, 256);
+// what the standalone loss kernels (launch_loss) ask of the image size
+static int loss_size_check(const Mm3dgsLossConfig* c) {
+  if (c->H <= 0 || c->W <= 0) return fail(-1, "bad image size");
+  if ((double)c->H * c->W * 36.0 >= 4294967296.0) return fail(-1, "image too large for the loss kernels' 32-bit offsets");
+  return 0;
+}
+static int slam_loss(const LossCfg& lc, const float* out6, const float* gt_color, const float* ref, const LossWork& w, float* dL, float* loss4, hipStream_t s) {
+  ProfScope ps(MM3DGS_PROF_LOSS, s);
+  launch_loss(lc, out6, gt_color, ref, w.dmaps, w.sums, w.partial, dL, loss4, s);
+  return check_launch("loss");
 }
 
 int mm3dgs_loss(const Mm3dgsLossConfig* c, const float* out6, const float* gt_color, const float* ref, void* work, float* dL,
                 float* loss4, void* stream) {
   if (!c || !out6 || !gt_color || !work || !dL) return fail(-1, "NULL argument");
-  if (c->H <= 0 || c->W <= 0) return fail(-1, "bad image size");
-  if ((double)c->H * c->W * 36.0 >= 4294967296.0) return fail(-1, "image too large for the loss kernels' 32-bit offsets");
+  if (int rc = loss_size_check(c)) return rc;
   if (int rc = loss_cfg_check(c, ref)) return rc;
-  LossCfg lc = loss_cfg_dev(c);
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(MM3DGS_PROF_LOSS, s);
-  char* w = (char*)work;
-  launch_loss(lc, out6, gt_color, ref, (float*)(w + 256), (double*)w, (double*)(w + 256 + align_up((size_t)9 * c->H * c->W * 4, 256)), dL,
-              loss4, s);
-  return check_launch("loss");
+  return slam_loss(loss_cfg_dev(c), out6, gt_color, ref, loss_work_view(work, c->H, c->W), dL, loss4, (hipStream_t)stream);
 }
 
 int mm3dgs_slam_track(int n_iter, const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, float* out_color, int32_t* radii,
@@ -489,54 +532,48 @@ int mm3dgs_slam_track(int n_iter, const Mm3dgsCamera* cam, int P, const Mm3dgsSl
                       const Mm3dgsLossConfig* loss_cfg, const float* gt_color, const float* ref, void* loss_work, float* dL_dout,
                       float* loss4, void* backward_scratch, const Mm3dgsPoseAdam* pose_adam, void* stream) {
   if (n_iter < 0) return fail(-1, "n_iter < 0");
-  if (!pose_adam || !pose_adam->pose) return fail(-2, "tracking needs the pose Adam state");
-  Mm3dgsSlamGrads none;
-  memset(&none, 0, sizeof(none));
   if (!loss_cfg || !gt_color || !loss_work || !dL_dout) return fail(-1, "NULL argument");
+  SlamCall c;
+  if (int rc = slam_call(c, cam, P, in, out_color, radii, geom_state, image_state, binning_state, N_capacity, backward_scratch, fwd_flags, stream,
+                         SLAM_OUT | SLAM_SCRATCH)) return rc;
+  PoseAdam pa;
+  if (int rc = pose_adam_dev(pose_adam, pa)) return rc;
+  if (!pa.pose) return fail(-2, "tracking needs the pose Adam state");
   if (int rc = loss_cfg_check(loss_cfg, ref)) return rc;
-  // without SSIM every loss term is per pixel: fold the loss into the compositors (two launches and the gradient image
-  // round trip less per iteration); needs the sort + forward-composite kernel (its workgroup = one 16x16 loss tile)
-  const int no_fold = env_flag("MM3DGS_NO_FOLDED_LOSS", 0);   // read per call: tests compare both paths in one process
-  const bool sh = in->sh_degree > 0 && in->f_rest;      // (active SH degree > 0: standalone loss kernels, mapping-mode compositor, no pose chain -- see slam_backward_impl)
-  const bool fold = !no_fold && !sh && !loss_is_variant(loss_cfg) && loss_cfg->w_ssim == 0.f && slam_fused_sort(fwd_flags) && cam->image_height > 0 && cam->image_width > 0;
+  // The per-call developer switches are read here, once per call: tests compare both sides of each in one process.
+  // fold: without SSIM every loss term is per pixel, so the loss runs inside the compositors (two launches and the gradient image round trip
+  // less per iteration); needs the sort + forward-composite kernel (its workgroup = one 16x16 loss tile).  An active SH degree keeps the
+  // standalone loss kernels, the mapping-mode compositor and the gradient records (slam_backward).
+  const bool fold = !env_flag("MM3DGS_NO_FOLDED_LOSS", 0) && !c.sh() && !loss_is_variant(loss_cfg) && loss_cfg->w_ssim == 0.f && c.fused_sort;
+  // masked L1 only: no loss-finish launch, 1/n goes to the pose gradient ...
+  const bool defer_scale = fold && loss_cfg->w_pearson == 0.f;
+  // ... and the backward compositor runs in the forward launch
+  const bool fuse_track = defer_scale && !env_flag("MM3DGS_NO_FUSED_TRACK", 0);
+  // the pose chain: the projection writes every splat's { Kp, Kq, x }, the tracking compositor applies it per (block, splat) and leaves one pose row
+  // per tile: no gradient records, no per-tile combine, no backward-projection launch (three launches per iteration).  The shipped mode only (means
+  // pre-transformed: the world-frame mode's pose gradient also runs through the covariance rotation)
+  const bool pose_chain = !c.in.world && !c.sh() && !env_flag("MM3DGS_NO_POSE_CHAIN", 0) &&
+                          bwd_bytes_impl(P, N_capacity) >= (size_t)c.cd.gx * c.cd.gy * 32 * sizeof(float);
+  if (fold && (loss_cfg->H != c.cd.H || loss_cfg->W != c.cd.W)) return fail(-1, "loss and camera image sizes differ");
+  if (!fold)
+    if (int rc = loss_size_check(loss_cfg)) return rc;
+  const LossCfg lc = loss_cfg_dev(loss_cfg);
+  const LossWork lw = loss_work_view(loss_work, loss_cfg->H, loss_cfg->W);
   TrackLoss tl = {};
-  if (fold) {
-    tl.cfg = loss_cfg_dev(loss_cfg);
-    char* w = (char*)loss_work;
-    tl.gt = gt_color; tl.ref = ref; tl.out = out_color; tl.sums = (const double*)w;
-    tl.partial = (double*)(w + 256 + align_up((size_t)9 * loss_cfg->H * loss_cfg->W * 4, 256));
-    tl.loss4 = loss4;
-    tl.defer_scale = loss_cfg->w_pearson == 0.f ? 1 : 0;   // masked L1 only: no loss-finish launch, 1/n goes to the pose gradient
-    if (loss_cfg->H != cam->image_height || loss_cfg->W != cam->image_width) return fail(-1, "loss and camera image sizes differ");
-  }
-  // masked L1 alone (normalisation deferred to the pose gradient): the backward compositor runs in the forward launch
-  const bool fuse_track = fold && tl.defer_scale && !env_flag("MM3DGS_NO_FUSED_TRACK", 0) && backward_scratch;
-  float* track_dsub = nullptr;
-  if (fuse_track) {
-    track_dsub = bwd_view(backward_scratch, P, N_capacity).dsub;
-  }
-  // round 6: the pose chain -- the projection writes every splat's { Kp, Kq, x }, the tracking compositor applies it per (block, splat) and leaves one
-  // pose row per tile: no gradient records, no per-tile combine, no backward-projection launch (three launches per iteration).  The shipped mode only
-  // (means pre-transformed: the world-frame mode's pose gradient also runs through the covariance rotation); MM3DGS_NO_POSE_CHAIN keeps the record path
-  // (read per call: tests compare both in one process)
-  const bool pose_chain = !in->world_means && !sh && backward_scratch && !env_flag("MM3DGS_NO_POSE_CHAIN", 0) &&
-                          bwd_bytes_impl(P, N_capacity) >= (size_t)tiles_x(cam->image_width) * tiles_y(cam->image_height) * 32 * sizeof(float);
-  if (n_iter > 0) slam_refresh_tile_order(cam, image_state, fwd_flags, stream);
+  tl.cfg = lc; tl.gt = gt_color; tl.ref = ref; tl.out = out_color; tl.sums = lw.sums; tl.partial = lw.partial; tl.loss4 = loss4;
+  tl.defer_scale = defer_scale ? 1 : 0;
+  const SlamFwd fwd = {.tl = fold ? &tl : nullptr, .track_dsub = fuse_track ? c.bw.dsub : nullptr, .pose_chain = pose_chain};
+  const SlamBwd bwd = {.dL_dout = dL_dout, .pose_adam = pa, .tl = fwd.tl, .prior_loss4 = loss4, .compositor_done = fuse_track, .pose_chain = pose_chain};
+  if (n_iter > 0) slam_refresh_tile_order(c);
   for (int it = 0; it < n_iter; it++) {
-    int rc = slam_forward_impl(cam, P, in, out_color, radii, geom_state, image_state, binning_state, N_capacity, fwd_flags, stream, fold ? &tl : nullptr, track_dsub, false, pose_chain);
-    if (rc) return rc;
-    if (fold) {
-      if (!tl.defer_scale) {
-        ProfScope ps(MM3DGS_PROF_LOSS, (hipStream_t)stream);
-        launch_loss_finish(tl.cfg, (double*)loss_work, tl.partial, (hipStream_t)stream);
-      }
-    } else {
-      rc = mm3dgs_loss(loss_cfg, out_color, gt_color, ref, loss_work, dL_dout, loss4, stream);
-      if (rc) return rc;
+    if (int rc = slam_forward(c, fwd)) return rc;
+    if (!fold) {
+      if (int rc = slam_loss(lc, out_color, gt_color, ref, lw, dL_dout, loss4, c.s)) return rc;
+    } else if (!defer_scale) {
+      ProfScope ps(MM3DGS_PROF_LOSS, c.s);
+      launch_loss_finish(lc, lw.sums, lw.partial, c.s);
     }
-    rc = slam_backward_impl(cam, P, in, radii, geom_state, image_state, binning_state, N_capacity, dL_dout, backward_scratch, &none,
-                            nullptr, pose_adam, nullptr, fwd_flags, stream, fold ? &tl : nullptr, loss4, 6, fuse_track, nullptr, nullptr, pose_chain);
-    if (rc) return rc;
+    if (int rc = slam_backward(c, bwd); rc < 0) return rc;
   }
   return 0;
 }
@@ -546,75 +583,66 @@ int mm3dgs_slam_map(int n_iter, const Mm3dgsMapView* views, const Mm3dgsCamera* 
                     const Mm3dgsLossConfig* loss_cfg, void* loss_work, float* dL_dout, float* loss4, void* backward_scratch,
                     const Mm3dgsSlamGrads* grads_stats, const Mm3dgsMapAdam* map_adam, void* stream) {
   if (n_iter < 0) return fail(-1, "n_iter < 0");
-  if (n_iter > 0 && (!views || !in)) return fail(-1, "NULL argument");
+  if (!views || !loss_cfg || !loss_work || !dL_dout) return fail(-1, "NULL argument");
+  SlamCall c;
+  if (int rc = slam_call(c, cam, P, in, out_color, radii, geom_state, image_state, binning_state, N_capacity, backward_scratch, fwd_flags, stream,
+                         SLAM_OUT | SLAM_SCRATCH | SLAM_POSE_LATER)) return rc;
   if (n_iter > 0 && !map_adam && !(grads_stats && grads_stats->d_xyz)) return fail(-1, "neither an Adam state nor gradient outputs");
-  Mm3dgsSlamGrads sg;
-  memset(&sg, 0, sizeof(sg));
-  if (grads_stats) sg = *grads_stats;
-  Mm3dgsMapAdam ad;
-  memset(&ad, 0, sizeof(ad));
-  if (map_adam) ad = *map_adam;
-  Mm3dgsSlamInputs si = *in;
-  if (n_iter > 0 && (!loss_cfg || !loss_work || !dL_dout)) return fail(-1, "NULL argument");
-  // SSIM losses on the fused-sort path (the shipped mapping loss): the forward compositor's epilogue writes the per-tile L1 /
-  // Pearson rows, the SSIM kernel's extra workgroup reduces them, and the gradient image has four planes: two launches per
-  // iteration for the loss instead of three (no finishing launch), the loss values only once, at the end of the run
-  const int no_rows = env_flag("MM3DGS_NO_FORWARD_ROWS", 0);   // read per call: tests compare both paths in one process
-  const bool rows = n_iter > 0 && !no_rows && !loss_is_variant(loss_cfg) && loss_cfg->w_ssim != 0.f && slam_fused_sort(fwd_flags) && loss_cfg->H == cam->image_height &&
-                    loss_cfg->W == cam->image_width;
-  TrackLoss tl = {};
-  LossCfg lc = {};
-  char* w = (char*)loss_work;
-  double* sums = (double*)w;
-  float* dmaps = (float*)(w + 256);
-  double* partial = n_iter > 0 ? (double*)(w + 256 + align_up((size_t)9 * loss_cfg->H * loss_cfg->W * 4, 256)) : nullptr;
-  if (rows) {
-    lc = loss_cfg_dev(loss_cfg);
-    tl.cfg = lc; tl.out = out_color; tl.sums = sums; tl.partial = partial; tl.loss4 = nullptr; tl.defer_scale = 0;
+  SlamBwd bwd = {.dL_dout = dL_dout};
+  if (int rc = slam_grads_dev(grads_stats, c.sh(), true, bwd.grads)) return rc;
+  Mm3dgsMapAdam ad = {};      // (the caller's, with the step counter this loop advances)
+  if (map_adam) {
+    ad = *map_adam;
+    if (int rc = map_adam_dev(&ad, c.sh(), bwd.map_adam)) return rc;
   }
-  // the backward launch of iteration `it` projects and bins the view of iteration `it + 1` when nothing stands between them (direct bins,
-  // in-kernel Adam, neither view steps its pose); MM3DGS_NO_FUSED_PROJECT keeps the two launches apart (tests compare both, bit for bit)
-  const int no_fuse_proj = env_flag("MM3DGS_NO_FUSED_PROJECT", 0);
-  bool projected = (fwd_flags & MM3DGS_FWD_PROJECTED) != 0;     // (view 0 only: mm3dgs_slam_adam_project launched its projection + binning)
-  if (n_iter > 0) slam_refresh_tile_order(cam, image_state, fwd_flags, stream);
   for (int it = 0; it < n_iter; it++) {
-    if (!views[it].pose || !views[it].gt_color) return fail(-1, "view %d: NULL pose or colour target", it);
-    if (loss_cfg->w_pearson != 0.f && !views[it].ref_depth_or_null) return fail(-2, "view %d: Pearson term needs a reference depth", it);
-    if ((loss_cfg->w_depth_l1 != 0.f || (loss_cfg->l1_mask & 2)) && !views[it].ref_depth_or_null) return fail(-2, "view %d: depth-L1 term needs a reference depth", it);
-    si.pose = views[it].pose;
-    int rc;
+    const Mm3dgsMapView& v = views[it];
+    if (!v.pose || !v.gt_color) return fail(-1, "view %d: NULL pose or colour target", it);
+    if (v.pose_adam_or_null && v.dpose_out_or_null) return fail(-2, "view %d: either a pose step or a pose-gradient output", it);
+    if (int rc = loss_cfg_check(loss_cfg, v.ref_depth_or_null)) return rc;
+    if (int rc = pose_adam_dev(v.pose_adam_or_null, bwd.pose_adam)) return rc;
+  }
+  // The per-call developer switches are read here, once per call: tests compare both sides of each in one process.
+  // rows: SSIM losses on the fused-sort path (the shipped mapping loss): the forward compositor's epilogue writes the per-tile L1 / Pearson rows,
+  // the SSIM kernel's extra workgroup reduces them, and the gradient image has four planes: two launches per iteration for the loss instead of
+  // three (no finishing launch), the loss values only once, at the end of the run
+  const bool rows = !env_flag("MM3DGS_NO_FORWARD_ROWS", 0) && !loss_is_variant(loss_cfg) && loss_cfg->w_ssim != 0.f && c.fused_sort &&
+                    loss_cfg->H == c.cd.H && loss_cfg->W == c.cd.W;
+  // ... and the gradient-image pass itself runs in the backward compositor's prologue (TrackLoss::dmaps)
+  const bool fold_grad = rows && !env_flag("MM3DGS_NO_FOLDED_LOSS", 0);
+  // the backward launch of iteration `it` projects and bins the view of iteration `it + 1` when nothing stands between them (direct bins,
+  // in-kernel Adam, neither view steps its pose or hands its pose gradient out: slam_backward has the rest of the rule)
+  const bool fuse_proj = rows && map_adam && !env_flag("MM3DGS_NO_FUSED_PROJECT", 0);
+  if (!rows)
+    if (int rc = loss_size_check(loss_cfg)) return rc;
+  const LossCfg lc = loss_cfg_dev(loss_cfg);
+  const LossWork lw = loss_work_view(loss_work, loss_cfg->H, loss_cfg->W);
+  TrackLoss tl = {};
+  tl.cfg = lc; tl.out = out_color; tl.sums = lw.sums; tl.partial = lw.partial; tl.dmaps = fold_grad ? lw.dmaps : nullptr;
+  bwd.tl = fold_grad ? &tl : nullptr;
+  bwd.dl_planes = rows ? 4 : 6;
+  bool projected = (fwd_flags & MM3DGS_FWD_PROJECTED) != 0;     // (view 0 only: mm3dgs_slam_adam_project launched its projection + binning)
+  if (n_iter > 0) slam_refresh_tile_order(c);
+  for (int it = 0; it < n_iter; it++) {
+    const Mm3dgsMapView& v = views[it];
+    c.in.pose = v.pose;
+    tl.gt = v.gt_color; tl.ref = v.ref_depth_or_null;
+    if (int rc = slam_forward(c, {.tl = rows ? &tl : nullptr, .projected = projected})) return rc;
     if (rows) {
-      tl.gt = views[it].gt_color; tl.ref = views[it].ref_depth_or_null;
-      rc = slam_forward_impl(cam, P, &si, out_color, radii, geom_state, image_state, binning_state, N_capacity, fwd_flags, stream, &tl, nullptr, projected);
-      if (rc) return rc;
-      // the gradient-image pass itself runs in the backward compositor's prologue (tl.dmaps set) unless MM3DGS_NO_FOLDED_LOSS asks
-      // for the separate launch
-      const bool fold_grad = !env_flag("MM3DGS_NO_FOLDED_LOSS", 0);
-      { ProfScope ps(MM3DGS_PROF_LOSS, (hipStream_t)stream);
-        launch_loss_after_forward_rows(lc, out_color, tl.gt, tl.ref, dmaps, sums, partial, fold_grad ? nullptr : dL_dout, (hipStream_t)stream); }
-      if (loss4 && it == n_iter - 1) launch_loss_finish(lc, sums, partial, (hipStream_t)stream, loss4);
-      rc = check_launch("loss");
-      if (rc) return rc;
-      tl.dmaps = fold_grad ? dmaps : nullptr;
-      if (views[it].pose_adam_or_null && views[it].dpose_out_or_null) return fail(-2, "view %d: either a pose step or a pose-gradient output", it);
-      const float* next_pose = (!no_fuse_proj && map_adam && it + 1 < n_iter && !views[it].pose_adam_or_null && !views[it + 1].pose_adam_or_null &&
-                                !views[it].dpose_out_or_null && views[it + 1].pose) ? views[it + 1].pose : nullptr;
-      projected = false;
-      rc = slam_backward_impl(cam, P, &si, radii, geom_state, image_state, binning_state, N_capacity, dL_dout, backward_scratch, &sg, views[it].dpose_out_or_null,
-                              views[it].pose_adam_or_null, map_adam ? &ad : nullptr, fwd_flags, stream, fold_grad ? &tl : nullptr, nullptr, 4, false,
-                              next_pose, &projected);
-    } else {
-      // (MM3DGS_FWD_PROJECTED speaks of view 0 only)
-      rc = mm3dgs_slam_forward(cam, P, &si, out_color, radii, geom_state, image_state, binning_state, N_capacity,
-                               it == 0 ? fwd_flags : (fwd_flags & ~MM3DGS_FWD_PROJECTED), stream);
-      if (rc) return rc;
-      rc = mm3dgs_loss(loss_cfg, out_color, views[it].gt_color, views[it].ref_depth_or_null, loss_work, dL_dout, loss4, stream);
-      if (rc) return rc;
-      rc = mm3dgs_slam_backward(cam, P, &si, radii, geom_state, image_state, binning_state, N_capacity, dL_dout, backward_scratch, &sg,
-                                views[it].dpose_out_or_null, views[it].pose_adam_or_null, map_adam ? &ad : nullptr, fwd_flags, stream);
-    }
-    if (rc) return rc;
+      { ProfScope ps(MM3DGS_PROF_LOSS, c.s);
+        launch_loss_after_forward_rows(lc, out_color, tl.gt, tl.ref, lw.dmaps, lw.sums, lw.partial, fold_grad ? nullptr : dL_dout, c.s); }
+      if (loss4 && it == n_iter - 1) launch_loss_finish(lc, lw.sums, lw.partial, c.s, loss4);
+      if (int rc = check_launch("loss")) return rc;
+    } else if (int rc = slam_loss(lc, out_color, tl.gt, tl.ref, lw, dL_dout, loss4, c.s)) return rc;
+    bwd.dL_dpose = v.dpose_out_or_null;
+    (void)pose_adam_dev(v.pose_adam_or_null, bwd.pose_adam);      // (checked above)
+    if (map_adam)
+      if (int rc = map_adam_dev(&ad, c.sh(), bwd.map_adam)) return rc;
     ad.step++;
+    bwd.next_pose = (fuse_proj && it + 1 < n_iter && !v.pose_adam_or_null && !views[it + 1].pose_adam_or_null && !v.dpose_out_or_null) ? views[it + 1].pose : nullptr;
+    const int rc = slam_backward(c, bwd);
+    if (rc < 0) return rc;
+    projected = rc == 1;
   }
   return 0;
 }
@@ -644,30 +672,18 @@ int mm3dgs_slam_direct_bins(const Mm3dgsCamera* cam, int P, size_t N_capacity, i
 
 int mm3dgs_slam_adam_project(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInputs* in, const Mm3dgsSlamGrads* grads, const Mm3dgsMapAdam* adam,
                              int32_t* radii, void* geom_state, void* image_state, void* binning_state, size_t N_capacity, int fwd_flags, void* stream) {
-  int rc = check_slam(cam, P, in);
-  if (rc) return rc;
-  if (!grads || !adam || !geom_state || !image_state || !binning_state || (P > 0 && !radii)) return fail(-1, "NULL argument");
-  if (!grads->d_xyz || !grads->d_f_dc || !grads->d_opacity || !grads->d_scaling || !grads->d_rotation) return fail(-2, "all five gradient arrays are needed");
+  SlamCall c;
+  if (int rc = slam_call(c, cam, P, in, nullptr, radii, geom_state, image_state, binning_state, N_capacity, nullptr, fwd_flags, stream, 0)) return rc;
+  if (!grads || !adam) return fail(-1, "NULL argument");
   // (ABI 212) an active SH degree: the sixth group -- its gradient array and its Adam state -- or nothing is launched
-  if (in->sh_degree > 0 && !grads->d_f_rest) return fail(-2, "sh_degree %d needs grads->d_f_rest", in->sh_degree);
-  if (in->sh_degree > 0 && (!adam->rest_param || !adam->rest_exp_avg || !adam->rest_exp_avg_sq))
-    return fail(-2, "sh_degree %d needs the f_rest group of the map Adam (rest_param / rest_exp_avg / rest_exp_avg_sq)", in->sh_degree);
-  hipStream_t s = (hipStream_t)stream;
-  CamDev cd = cam_dev(cam);
-  cd.bg_extras = 1;
-  cd.tile_table = slam_tile_table(fwd_flags) ? 1 : 0;
-  const DirectBins db = slam_direct_bins(fwd_flags, cd, P, N_capacity);
-  if (!db.on) return fail(-3, "mm3dgs_slam_adam_project needs direct bins (flags / map size / capacity)");
-  cd.trec_cap = db.trec_cap;
+  SlamGrads sg;
+  if (int rc = slam_grads_dev(grads, c.sh(), false, sg)) return rc;
+  if (!sg.d_xyz) return fail(-2, "all five gradient arrays are needed");
   MapAdam ma;
-  memset(&ma, 0, sizeof(ma));
-  if ((rc = map_adam_dev(adam, ma))) return rc;
-  SlamGrads sg = {};
-  sg.d_xyz = grads->d_xyz; sg.d_f_dc = grads->d_f_dc; sg.d_opacity = grads->d_opacity; sg.d_scaling = grads->d_scaling; sg.d_rotation = grads->d_rotation;
-  sg.d_f_rest = in->sh_degree > 0 ? grads->d_f_rest : nullptr;
-  { ProfScope ps(MM3DGS_PROF_ADAM, s);
-    launch_slam_adam_project(cd, P, slam_in(in), radii, geom_view(geom_state, P > 0 ? P : 1), image_view(image_state, cd.H, cd.W), bin_view(binning_state, N_capacity),
-                             sg, ma, in->pose, db.bin_cap, db.slot_bits, s); }
+  if (int rc = map_adam_dev(adam, c.sh(), ma)) return rc;
+  if (!c.db.on) return fail(-3, "mm3dgs_slam_adam_project needs direct bins (flags / map size / capacity)");
+  { ProfScope ps(MM3DGS_PROF_ADAM, c.s);
+    launch_slam_adam_project(c.cd, P, c.in, radii, c.g, c.iv, c.b, sg, ma, c.in.pose, c.db.bin_cap, c.db.slot_bits, c.s); }
   return check_launch("slam_adam_project");
 }
 

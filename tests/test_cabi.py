@@ -116,3 +116,64 @@ def test_product_sources_carry_no_retired_baseline_switch():
         text = open(f, errors="replace").read()
         for name in retired:
             assert name not in text, (f, name)
+
+
+# The table of test_slam_entry_points_refuse_bad_host_arguments, run in a child process: a crash is the child's exit status, not a dead pytest.
+# Every case passes the six device buffers (out_color, radii, geom_state, image_state, binning_state, backward_scratch) as NULL, so no order of
+# the library's checks reaches a launch; the pointers inside the host structs are never followed by the host and may be anything non-null.
+_BAD_ARGUMENT_CASES = r"""
+import ctypes as C, json
+from mm3dgs_slam_amd import _lib
+lib = _lib.load()
+FAKE = 0x1000
+cam = _lib.Mm3dgsCamera(image_height=48, image_width=64, tanfovx=1.0, tanfovy=1.0, scale_modifier=1.0, bg=FAKE, viewmatrix=FAKE, projmatrix=FAKE, campos=FAKE)
+si = _lib.Mm3dgsSlamInputs(pose=FAKE, xyz=FAKE, f_dc=FAKE, opacity=FAKE, scaling=FAKE, rotation=FAKE)
+pose_adam = _lib.Mm3dgsPoseAdam(pose=FAKE, m=FAKE, v=FAKE, step=FAKE, lr_q=1e-3, lr_t=1e-3, beta1=0.9, beta2=0.999, eps=1e-8)
+map_adam = _lib.Mm3dgsMapAdam(beta1=0.9, beta2=0.999, eps=1e-15, step=1)
+for i in range(5):
+    map_adam.param[i] = map_adam.exp_avg[i] = map_adam.exp_avg_sq[i] = FAKE
+grads = _lib.Mm3dgsSlamGrads(d_xyz=FAKE, d_f_dc=FAKE, d_opacity=FAKE, d_scaling=FAKE, d_rotation=FAKE)
+views = (_lib.Mm3dgsMapView * 1)(_lib.Mm3dgsMapView(pose=FAKE, gt_color=FAKE))
+FLAGS = _lib.FWD_STATE_CLEAN | _lib.FWD_SHORT_LISTS | _lib.FWD_DIRECT_BINS      # the fused-sort paths: the loops' fold / rows decisions are reached
+P, N_CAP, NULL = 1000, 1 << 16, None
+results = []
+def case(name, fn, *args):
+    rc = fn(*args)
+    results.append([name, rc, (lib.mm3dgs_last_error() or b"").decode()])
+for n_iter in (0, 1):
+    for w_ssim in (0.0, 0.2):
+        lcfg = _lib.Mm3dgsLossConfig(H=48, W=64, w_l1=1.0 - w_ssim, w_ssim=w_ssim)
+        for null in ("cam", "in", "loss_cfg", "pose_adam", "views"):
+            a = dict(cam=C.byref(cam), loss_cfg=C.byref(lcfg), pose_adam=C.byref(pose_adam), views=views)
+            a["in"] = C.byref(si)
+            a[null] = NULL
+            tag = f"n_iter={n_iter} w_ssim={w_ssim} {null}=NULL"
+            if null != "views":
+                case("track " + tag, lib.mm3dgs_slam_track, n_iter, a["cam"], P, a["in"], NULL, NULL, NULL, NULL, NULL, N_CAP, FLAGS, a["loss_cfg"], FAKE, NULL,
+                     FAKE, FAKE, FAKE, NULL, a["pose_adam"], NULL)
+            if null != "pose_adam":
+                case("map " + tag, lib.mm3dgs_slam_map, n_iter, a["views"], a["cam"], P, a["in"], NULL, NULL, NULL, NULL, NULL, N_CAP, FLAGS, a["loss_cfg"], FAKE,
+                     FAKE, FAKE, NULL, NULL, C.byref(map_adam), NULL)
+for null in ("cam", "in"):
+    c, i = (NULL if null == "cam" else C.byref(cam)), (NULL if null == "in" else C.byref(si))
+    case(f"forward {null}=NULL", lib.mm3dgs_slam_forward, c, P, i, NULL, NULL, NULL, NULL, NULL, N_CAP, FLAGS, NULL)
+    case(f"backward {null}=NULL", lib.mm3dgs_slam_backward, c, P, i, NULL, NULL, NULL, NULL, N_CAP, FAKE, NULL, NULL, NULL, NULL, C.byref(map_adam), FLAGS, NULL)
+    case(f"visibility {null}=NULL", lib.mm3dgs_slam_visibility, c, P, i, NULL, NULL, NULL, NULL)
+    case(f"adam_project {null}=NULL", lib.mm3dgs_slam_adam_project, c, P, i, C.byref(grads), C.byref(map_adam), NULL, NULL, NULL, NULL, N_CAP, FLAGS, NULL)
+print("RESULTS " + json.dumps(results))
+"""
+
+
+def test_slam_entry_points_refuse_bad_host_arguments():
+    """The SLAM entry points answer a NULL camera, inputs, loss configuration, pose Adam state or view table with -1 and a message, whatever
+    n_iter and whichever loss path the flags and weights select -- no argument is read before it is checked (the child process exits 0)."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-c", _BAD_ARGUMENT_CASES], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    results = json.loads(next(l for l in r.stdout.splitlines() if l.startswith("RESULTS "))[len("RESULTS "):])
+    assert len(results) == 2 * 2 * (4 + 4) + 2 * 4
+    for name, rc, err in results:
+        assert rc == -1 and err, (name, rc, err)
