@@ -434,6 +434,42 @@ size_t mm3dgs_align_depth_work_bytes(int H, int W);
 int mm3dgs_align_depth(int H, int W, const float* est /*[H,W]*/, const float* depth /*[H,W]*/, const float* silhouette_or_null /*[H,W]*/,
                        float sil_min, float est_min, void* work, double* fit /*[16], device*/, float* out_or_null /*[H,W]*/, void* stream);
 
+/* ---- image evaluation: PSNR, SSIM and depth L1 / RMSE of one rendered frame against the recorded one, two launches ---------------------
+ * The per-frame scoring of the reference's evaluation (slam/SLAM.py:197-231: utils/image_utils.py:17-19 psnr, utils/loss_utils.py:95-154 ssim)
+ * plus a depth metric, as one row of sixteen doubles on the device.  image, gt: [3,H,W] float32; depth, gt_depth: [H,W] float32, both given or
+ * both NULL; window: the HOST's 11 float32 taps of the SSIM window; row: [16] doubles on the device, 8-byte aligned -- it may point into a
+ * larger table (table + 16 k), so a whole evaluation fills one tensor and is read back once.
+ *   colour, per channel c:  sse_c = sum ((double)image - (double)gt)^2 over the H W pixels (widened first, subtracted in double);
+ *                           mse_c = sse_c / (H W).
+ *   SSIM, per channel c:    the map of utils/loss_utils.py:95-154 -- 2-D window = outer product of `window`, zero padding 5, C1 = 0.01^2,
+ *                           C2 = 0.03^2 -- with the moments and the map in float32 (the separable strips of the mapping loss, mm3dgs_loss;
+ *                           the map's quotient is one correctly rounded division); each map value is widened and summed in double: ssim_sum_c.
+ *   depth:                  a pixel is valid when 0 < gt_depth < +inf, a strict float32 test: NaN, +-0, negative and +inf are invalid.
+ *                           n = the number of valid pixels, l1 = sum |(double)depth - (double)gt_depth|, l2 = the sum of its square, over the
+ *                           valid pixels.  A NaN of `depth` at a valid pixel propagates; at an invalid pixel `depth` does not reach the sums.
+ *   row[0]     psnr        the mean over c of 20 log10(1 / sqrt(mse_c)) -- eval_utils.psnr(...).mean(); mse_c == 0 gives +inf, as torch does
+ *   row[1]     ssim        (sum over c of ssim_sum_c) / (3 H W)
+ *   row[2]     depth_l1    l1 / n; NaN when n == 0 or when the depth pointers are NULL
+ *   row[3]     n           0 when the depth pointers are NULL
+ *   row[4..6]  mse_c
+ *   row[7..9]  ssim_sum_c / (H W)
+ *   row[10]    depth_rmse  sqrt(l2 / n); NaN when n == 0 or when the depth pointers are NULL
+ *   row[11..15] zeros
+ * Against the host path of the Python package (eval_utils.image_metrics_host, float64 throughout): rows 0, 2, 3, 4..6 and 10 to the rounding of
+ * another summation order in double (1e-9 relative is generous; n exactly), rows 1 and 7..9 to the distance of a float32 evaluation of the map
+ * from the float64 one (tests/test_gpu_eval.py).
+ * work: mm3dgs_eval_image_work_bytes(H, W) bytes of device memory, 8-byte aligned, contents irrelevant before and after.  The images need no
+ * more than a float's alignment (planes of a [6,H,W] render qualify).  Two launches on `stream` -- one 256-lane workgroup per 16x16-pixel tile
+ * writes a row of double partial sums into work, then one workgroup adds the rows in a fixed order and writes row[0:16] --, no atomics, no
+ * arrival counter, no host synchronisation; the same inputs give the same bits on every call.  Nothing outside row[0:16] and
+ * work[0:work_bytes] is written.  -1 (nothing is launched): a non-positive size or more than 2^28 pixels, a NULL image, gt, window, work or row,
+ * exactly one of the two depth pointers, a work or row that is not 8-byte aligned, an image that is not 4-byte aligned.
+ * mm3dgs_eval_image_work_bytes returns 0 for a shape that mm3dgs_eval_image rejects. */
+size_t mm3dgs_eval_image_work_bytes(int H, int W);
+int mm3dgs_eval_image(int H, int W, const float* image /*[3,H,W]*/, const float* gt /*[3,H,W]*/, const float* depth_or_null /*[H,W]*/,
+                      const float* gt_depth_or_null /*[H,W]*/, const float* window /*host [11]*/, void* work, double* row /*[16], device*/,
+                      void* stream);
+
 /* ---- frame ingest: raw sensor bytes -> the two images the SLAM loops consume, in one launch ------------------------------------------
  * rgb: uint8 interleaved [Hs,Ws,3] on the device, any byte alignment; depth_or_null: uint16 [Hs,Ws], 2-byte aligned.  out_color [3,H,W]
  * float32 in [0,1]; out_depth_or_null [H,W] float32 in metres, required iff depth is given (a colour-only call passes NULL for both).
@@ -564,7 +600,8 @@ const char* mm3dgs_last_error(void);
         the map, its fit record and its application on the device); mm3dgs_ingest_frame (raw uint8 RGB + uint16 depth -> the float32 frame,
         one launch); mm3dgs_ingest_est (the monocular depth network's raw output, float32 / float16 / uint16 at any size -> the float32
         estimate at frame size, one launch); mm3dgs_mosaic_work_bytes / mm3dgs_mosaic (the debug video's and SLAM.render()'s panel
-        mosaic as one uint8 image, composed on the device); a caller that needs them looks the symbols up */
+        mosaic as one uint8 image, composed on the device); mm3dgs_eval_image_work_bytes / mm3dgs_eval_image (PSNR, SSIM and depth L1 of a
+        rendered frame as one row of a device table); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

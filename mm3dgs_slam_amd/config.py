@@ -15,6 +15,9 @@ _TUM = {
     # use_gt_depth false: the per-frame least-squares fit of the monocular estimate to the map from mm3dgs_align_depth (two launches,
     # sums and solve in double) instead of the torch operator graph; opt-in, it also records every frame's fit (results.npz: depth_align)
     "depth_align_on_device": False, "white_background": False,
+    # the evaluation at the end of a run (PSNR, SSIM, and the depth L1 the host chain does not have) from mm3dgs_eval_image: two launches per
+    # frame into a table on the device, one read-back per evaluation; opt-in (results.npz: eval_table, eval_frames, depth_l1_list)
+    "eval_on_device": False,
     "scene_radius_depth_ratio": 2, "desired_height": 480, "desired_width": 640,
     "debug": {"get_runtime_stats": False, "create_video": False, "save_keyframes": False},
     "pipeline": {"convert_SHs_python": False, "compute_cov3D_python": False, "transform_means_python": True,

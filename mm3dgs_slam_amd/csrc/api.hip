@@ -723,6 +723,24 @@ int mm3dgs_align_depth(int H, int W, const float* est, const float* depth, const
   return check_launch("align_depth");
 }
 
+static bool eval_shape_ok(int H, int W) { return H > 0 && W > 0 && (size_t)H * (size_t)W <= ((size_t)1 << 28); }
+
+size_t mm3dgs_eval_image_work_bytes(int H, int W) { return eval_shape_ok(H, W) ? eval_image_work_bytes(H, W) : 0; }
+
+int mm3dgs_eval_image(int H, int W, const float* image, const float* gt, const float* depth_or_null, const float* gt_depth_or_null,
+                      const float* window, void* work, double* row, void* stream) {
+  if (H <= 0 || W <= 0) return fail(-1, "eval_image: H = %d, W = %d (both must be positive)", H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "eval_image: %d x %d has more than 2^28 pixels", H, W);
+  if (!image || !gt || !window || !work || !row) return fail(-1, "eval_image: NULL argument (image, gt, window, work and row are required)");
+  if ((depth_or_null != nullptr) != (gt_depth_or_null != nullptr))
+    return fail(-1, "eval_image: depth and gt_depth must both be given or both be NULL");
+  if (((uintptr_t)work | (uintptr_t)row) & 7) return fail(-1, "eval_image: work and row must be 8-byte aligned");
+  if (((uintptr_t)image | (uintptr_t)gt | (uintptr_t)depth_or_null | (uintptr_t)gt_depth_or_null) & 3)
+    return fail(-1, "eval_image: the images must be 4-byte aligned");
+  launch_eval_image(H, W, image, gt, depth_or_null, gt_depth_or_null, window, (double*)work, row, (hipStream_t)stream);
+  return check_launch("eval_image");
+}
+
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
                         float* out_color, float* out_depth_or_null, void* stream) {
   if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);

@@ -119,6 +119,11 @@ void launch_propagate_imu(const float* pm1, const float* pm2, const float* imu6,
 size_t align_depth_work_bytes(int H, int W);
 void launch_align_depth(int H, int W, const float* est, const float* depth, const float* sil, float sil_min, float est_min, double* rows,
                         double* fit, float* out, hipStream_t s);
+// image evaluation (eval.hip): PSNR / SSIM / depth L1 of one frame into row[16] (device); rows = the work buffer of
+// eval_image_work_bytes(H, W); depth and gt_depth are both NULL or both given; window = the host's 11 SSIM taps; H W <= 2^28
+size_t eval_image_work_bytes(int H, int W);
+void launch_eval_image(int H, int W, const float* image, const float* gt, const float* depth, const float* gt_depth, const float* window,
+                       double* rows, double* row, hipStream_t s);
 // frame ingest (ingest.hip): raw uint8 RGB [Hs,Ws,3] + uint16 depth [Hs,Ws] -> colour [3,H,W] in [0,1] + depth [H,W] in metres, one
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,

@@ -19,30 +19,6 @@
 // Channel layout of `out`: 0..2 RGB, 3 depth (alpha-weighted z), 4 silhouette, 5 depth^2.
 #include "loss_tile.h"
 
-// fixed-order reduction of the tile rows by one 256-lane workgroup: lane = 16 * rowgroup + column.  cols_mask selects the
-// columns to sum (a column that another workgroup of the same launch is still writing must not be read).
-__device__ __forceinline__ void reduce_rows_256(const double* __restrict__ partial, int nrows, unsigned cols_mask, double (*part)[16], double* tot) {
-  const int col = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  if (col < 12 && ((cols_mask >> col) & 1u)) {
-    int r = grp;
-    for (; r + 48 < nrows; r += 64) {
-      a0 += partial[(size_t)r * 12 + col]; a1 += partial[(size_t)(r + 16) * 12 + col];
-      a2 += partial[(size_t)(r + 32) * 12 + col]; a3 += partial[(size_t)(r + 48) * 12 + col];
-    }
-    for (; r < nrows; r += 16) a0 += partial[(size_t)r * 12 + col];
-  }
-  part[grp][col] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; q++) t += part[q][threadIdx.x];
-    tot[threadIdx.x] = t;
-  }
-  __syncthreads();
-}
-
 __device__ __forceinline__ void pearson_terms(double n, double sx, double sxx, double st, double stt, double sxt, double& rho,
                                               double& cxx, double& ctt) {
   cxx = sxx - sx * sx / n;
@@ -122,7 +98,6 @@ ssim_maps_kernel(LossCfg cfg, const float* __restrict__ out, const float* __rest
   const int tile = blockIdx.x;
   const int x0 = (tile % tiles_x) * LT, y0 = (tile / tiles_x) * LT;
   const uint32_t HW = (uint32_t)cfg.H * (uint32_t)cfg.W;   // 32-bit element offsets (9 H W < 2^31 is checked by the API): 64-bit address temporaries spilled
-  const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
   const int tid = threadIdx.x;
   const HaloIdx hx = halo_index(cfg, x0, y0);
   const Rsrc r_out = make_rsrc(out, HW * 24u), r_gt = make_rsrc(gt, HW * 12u), r_dm = make_rsrc(dmaps, HW * 36u);
@@ -153,77 +128,19 @@ ssim_maps_kernel(LossCfg cfg, const float* __restrict__ out, const float* __rest
       }
     }
     if (ROWS) l1 += fabsf(sI[ty + HALO][tx + HALO] - sG[ty + HALO][tx + HALO]);
-    // horizontal pass: 26 rows x 8 strips of 2 outputs (208 of the 256 lanes); 12 inputs per image as six 8-byte reads
-    if (tid < LW * 8) {
-      const int row = tid >> 3, s = tid & 7;
-      float a[12], b[12];
-      const float2* ra = (const float2*)&sI[row][2 * s];
-      const float2* rb = (const float2*)&sG[row][2 * s];
-#pragma unroll
-      for (int v = 0; v < 6; v++) {
-        const float2 qa = ra[v], qb = rb[v];
-        a[2 * v] = qa.x; a[2 * v + 1] = qa.y; b[2 * v] = qb.x; b[2 * v + 1] = qb.y;
-      }
-      float m1[2] = {0.f, 0.f}, m2[2] = {0.f, 0.f}, e11[2] = {0.f, 0.f}, e22[2] = {0.f, 0.f}, e12[2] = {0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 12; i++) {
-        const float aa = a[i] * a[i], bb = b[i] * b[i], ab = a[i] * b[i];
-#pragma unroll
-        for (int o = 0; o < 2; o++) {
-          const int k = i - o;
-          if (k >= 0 && k < 11) {
-            const float w = cfg.window[k];
-            m1[o] = fmaf(w, a[i], m1[o]); m2[o] = fmaf(w, b[i], m2[o]);
-            e11[o] = fmaf(w, aa, e11[o]); e22[o] = fmaf(w, bb, e22[o]); e12[o] = fmaf(w, ab, e12[o]);
-          }
-        }
-      }
-      *(float2*)&hS[0][row][2 * s] = make_float2(m1[0], m1[1]);
-      *(float2*)&hS[1][row][2 * s] = make_float2(m2[0], m2[1]);
-      *(float2*)&hS[2][row][2 * s] = make_float2(e11[0], e11[1]);
-      *(float2*)&hS[3][row][2 * s] = make_float2(e22[0], e22[1]);
-      *(float2*)&hS[4][row][2 * s] = make_float2(e12[0], e12[1]);
-    }
+    ssim_moments_hpass(cfg.window, sI, sG, hS, tid);      // (loss_tile.h: the strips are shared with the image evaluation)
     __syncthreads();
-    // vertical pass: one output per lane (all 256), 11 rows of each moment.  (Two horizontally adjacent outputs per lane on 128 lanes -- half the
-    // LDS reads -- keep ten moments live in a kernel that is held to 96 registers: 7 - 14 of them spill, 15.8 us instead of 12.3: DESIGN.md section 4)
-    constexpr int NO = 1;
-    const int vx = tx, vy = ty;
-    {
-      float st[5][NO];
-#pragma unroll
-      for (int q = 0; q < 5; q++) {
-        float acc[NO];
-#pragma unroll
-        for (int o = 0; o < NO; o++) acc[o] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; k++) {
-          acc[0] = fmaf(cfg.window[k], hS[q][vy + k][vx], acc[0]);
-        }
-#pragma unroll
-        for (int o = 0; o < NO; o++) st[q][o] = acc[o];
-      }
-#pragma unroll
-      for (int o = 0; o < NO; o++) {
-        const int opx = x0 + vx + o, opy = y0 + vy;
-        if (opx < cfg.W && opy < cfg.H) {
-          const uint32_t opix = (uint32_t)opy * (uint32_t)cfg.W + (uint32_t)opx;
-          const float m1 = st[0][o], m2 = st[1][o];
-          const float s1 = st[2][o] - m1 * m1, s2 = st[3][o] - m2 * m2, s12 = st[4][o] - m1 * m2;
-          const float A1 = 2.f * m1 * m2 + C1, A2 = 2.f * s12 + C2, B1 = m1 * m1 + m2 * m2 + C1, B2 = s1 + s2 + C2;
-          // v_rcp_f32 (1 ulp) instead of three IEEE divisions (their scale / fixup sequences held ~40 registers live)
-          const float rB1 = __builtin_amdgcn_rcpf(B1), rB2 = __builtin_amdgcn_rcpf(B2);
-          const float inv = rB1 * rB2;
-          const float f = A1 * A2 * inv;
-          ssim_sum += f;
-          const float df_dm1 = 2.f * m2 * A2 * inv - f * 2.f * m1 * rB1;
-          const float df_ds1 = -f * rB2;
-          const float df_ds12 = 2.f * A1 * inv;
-          bst(r_dm, (uint32_t)(ch * 3 + 0) * HW + opix, df_dm1 - 2.f * m1 * df_ds1 - m2 * df_ds12);  // d/d mu1 (total)
-          bst(r_dm, (uint32_t)(ch * 3 + 1) * HW + opix, df_ds1);                                     // d/d E[x^2]
-          bst(r_dm, (uint32_t)(ch * 3 + 2) * HW + opix, df_ds12);                                    // d/d E[xy]
-        }
-      }
+    float st[5];
+    ssim_moments_vpass(cfg.window, hS, tx, ty, st);
+    if (inside) {
+      const SsimPx p = ssim_px(st);
+      ssim_sum += p.f;
+      const float df_dm1 = 2.f * p.m2 * p.A2 * p.inv - p.f * 2.f * p.m1 * p.rB1;
+      const float df_ds1 = -p.f * p.rB2;
+      const float df_ds12 = 2.f * p.A1 * p.inv;
+      bst(r_dm, (uint32_t)(ch * 3 + 0) * HW + pix, df_dm1 - 2.f * p.m1 * df_ds1 - p.m2 * df_ds12);  // d/d mu1 (total)
+      bst(r_dm, (uint32_t)(ch * 3 + 1) * HW + pix, df_ds1);                                         // d/d E[x^2]
+      bst(r_dm, (uint32_t)(ch * 3 + 2) * HW + pix, df_ds12);                                        // d/d E[xy]
     }
   }
   if constexpr (ROWS) {

@@ -1,5 +1,6 @@
-// Tile-level pieces of the image-loss kernels shared between loss.hip and the backward compositor (composite.hip), which folds the
-// gradient-image pass of the mapping loss into its prologue.
+// Tile-level pieces of the image-loss kernels shared between loss.hip, the backward compositor (composite.hip), which folds the
+// gradient-image pass of the mapping loss into its prologue, and the image evaluation (eval.hip), which scores a frame with the same
+// SSIM moments.
 #pragma once
 #include "mm3dgs_common.h"
 #include "fused_api.h"
@@ -23,18 +24,109 @@ __device__ __forceinline__ void bst(Rsrc r, uint32_t elem, float v) { __builtin_
 
 struct HaloIdx { int off[3], lds[3]; };   // a lane's three elements of the 26x26 halo region: global offset (-1: outside the image), LDS index (-1: none)
 
-__device__ __forceinline__ HaloIdx halo_index(const LossCfg& cfg, int x0, int y0) {
+__device__ __forceinline__ HaloIdx halo_index(int H, int W, int x0, int y0) {
   HaloIdx h;
 #pragma unroll
   for (int e = 0; e < 3; e++) {
     const int i = threadIdx.x + e * 256;
     const int ly = i / LW, lx = i - ly * LW;
     const int gx = x0 + lx - HALO, gy = y0 + ly - HALO;
-    const bool in = i < LW * LW && gx >= 0 && gx < cfg.W && gy >= 0 && gy < cfg.H;
-    h.off[e] = in ? gy * cfg.W + gx : -1;
+    const bool in = i < LW * LW && gx >= 0 && gx < W && gy >= 0 && gy < H;
+    h.off[e] = in ? gy * W + gx : -1;
     h.lds[e] = i < LW * LW ? ly * SW + lx : -1;
   }
   return h;
+}
+__device__ __forceinline__ HaloIdx halo_index(const LossCfg& cfg, int x0, int y0) { return halo_index(cfg.H, cfg.W, x0, y0); }
+
+// ---- the separable 11x11 moments of SSIM, shared by ssim_maps_kernel (loss.hip) and eval_tile_kernel (eval.hip) ------------------------
+// The staged 26x26 halo regions sI / sG (zero outside the image) -> the five windowed moments E[x], E[y], E[x^2], E[y^2], E[xy] of the
+// tile's 256 pixels, both passes on register strips.
+// horizontal pass: 26 rows x 8 strips of 2 outputs (208 of the 256 lanes); 12 inputs per image as six 8-byte reads
+__device__ __forceinline__ void ssim_moments_hpass(const float (&window)[11], const float (*sI)[SW], const float (*sG)[SW], float (*hS)[LW][HW_],
+                                                   int tid) {
+  if (tid < LW * 8) {
+    const int row = tid >> 3, s = tid & 7;
+    float a[12], b[12];
+    const float2* ra = (const float2*)&sI[row][2 * s];
+    const float2* rb = (const float2*)&sG[row][2 * s];
+#pragma unroll
+    for (int v = 0; v < 6; v++) {
+      const float2 qa = ra[v], qb = rb[v];
+      a[2 * v] = qa.x; a[2 * v + 1] = qa.y; b[2 * v] = qb.x; b[2 * v + 1] = qb.y;
+    }
+    float m1[2] = {0.f, 0.f}, m2[2] = {0.f, 0.f}, e11[2] = {0.f, 0.f}, e22[2] = {0.f, 0.f}, e12[2] = {0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+      const float aa = a[i] * a[i], bb = b[i] * b[i], ab = a[i] * b[i];
+#pragma unroll
+      for (int o = 0; o < 2; o++) {
+        const int k = i - o;
+        if (k >= 0 && k < 11) {
+          const float w = window[k];
+          m1[o] = fmaf(w, a[i], m1[o]); m2[o] = fmaf(w, b[i], m2[o]);
+          e11[o] = fmaf(w, aa, e11[o]); e22[o] = fmaf(w, bb, e22[o]); e12[o] = fmaf(w, ab, e12[o]);
+        }
+      }
+    }
+    *(float2*)&hS[0][row][2 * s] = make_float2(m1[0], m1[1]);
+    *(float2*)&hS[1][row][2 * s] = make_float2(m2[0], m2[1]);
+    *(float2*)&hS[2][row][2 * s] = make_float2(e11[0], e11[1]);
+    *(float2*)&hS[3][row][2 * s] = make_float2(e22[0], e22[1]);
+    *(float2*)&hS[4][row][2 * s] = make_float2(e12[0], e12[1]);
+  }
+}
+// vertical pass: one output per lane (all 256), 11 rows of each moment.  (Two horizontally adjacent outputs per lane on 128 lanes -- half the
+// LDS reads -- keep ten moments live in a kernel that is held to 96 registers: 7 - 14 of them spill, 15.8 us instead of 12.3: DESIGN.md section 4)
+__device__ __forceinline__ void ssim_moments_vpass(const float (&window)[11], const float (*hS)[LW][HW_], int vx, int vy, float (&st)[5]) {
+#pragma unroll
+  for (int q = 0; q < 5; q++) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 11; k++) acc = fmaf(window[k], hS[q][vy + k][vx], acc);
+    st[q] = acc;
+  }
+}
+// the SSIM map value f = A1 A2 / (B1 B2) of one pixel from its five moments, with the terms its derivatives need (C1 = 0.01^2, C2 = 0.03^2);
+// f is the loss kernels' quotient through v_rcp_f32 -- the evaluation, which is not held to 96 registers, divides (A1 A2) / (B1 B2) itself
+struct SsimPx { float m1, m2, A1, A2, B1, B2, rB1, rB2, inv, f; };
+__device__ __forceinline__ SsimPx ssim_px(const float (&st)[5]) {
+  const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+  SsimPx p;
+  p.m1 = st[0]; p.m2 = st[1];
+  const float s1 = st[2] - p.m1 * p.m1, s2 = st[3] - p.m2 * p.m2, s12 = st[4] - p.m1 * p.m2;
+  p.A1 = 2.f * p.m1 * p.m2 + C1; p.A2 = 2.f * s12 + C2;
+  // (the fused product is m1 m1, stated: under contraction either product of m1 m1 + m2 m2 may become the fma's, and which one decides the last bit)
+  p.B1 = fmaf(p.m1, p.m1, p.m2 * p.m2) + C1; p.B2 = s1 + s2 + C2;
+  // v_rcp_f32 (1 ulp) instead of three IEEE divisions (their scale / fixup sequences held ~40 registers live)
+  p.rB1 = __builtin_amdgcn_rcpf(p.B1); p.rB2 = __builtin_amdgcn_rcpf(p.B2);
+  p.inv = p.rB1 * p.rB2;
+  p.f = p.A1 * p.A2 * p.inv;
+  return p;
+}
+
+// fixed-order reduction of rows of 12 doubles by one 256-lane workgroup: lane = 16 * rowgroup + column.  cols_mask selects the
+// columns to sum (a column that another workgroup of the same launch is still writing must not be read).
+__device__ __forceinline__ void reduce_rows_256(const double* __restrict__ partial, int nrows, unsigned cols_mask, double (*part)[16], double* tot) {
+  const int col = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  if (col < 12 && ((cols_mask >> col) & 1u)) {
+    int r = grp;
+    for (; r + 48 < nrows; r += 64) {
+      a0 += partial[(size_t)r * 12 + col]; a1 += partial[(size_t)(r + 16) * 12 + col];
+      a2 += partial[(size_t)(r + 32) * 12 + col]; a3 += partial[(size_t)(r + 48) * 12 + col];
+    }
+    for (; r < nrows; r += 16) a0 += partial[(size_t)r * 12 + col];
+  }
+  part[grp][col] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    double t = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; q++) t += part[q][threadIdx.x];
+    tot[threadIdx.x] = t;
+  }
+  __syncthreads();
 }
 
 // dL/d(rendered image) of the lane's pixel (tx = tid % 16, ty = tid / 16 of tile `tile`) for the four planes that receive a loss:

@@ -23,12 +23,17 @@ def l2_loss(network_output, gt):
 _window_cache = {}
 
 
+def window_1d(size: int = 11) -> torch.Tensor:
+    """utils/loss_utils.py:95-98: the normalised Gaussian taps, sigma 1.5, as float32 values."""
+    g = torch.tensor([math.exp(-((i - size // 2) ** 2) / (2 * 1.5 ** 2)) for i in range(size)])
+    return (g / g.sum()).float()
+
+
 def _window(size: int, channel: int, like: torch.Tensor) -> torch.Tensor:
     key = (size, channel, like.device, like.dtype)
     w = _window_cache.get(key)
     if w is None:
-        g = torch.tensor([math.exp(-((i - size // 2) ** 2) / (2 * 1.5 ** 2)) for i in range(size)])
-        g = (g / g.sum()).float()
+        g = window_1d(size)
         w = (g[:, None] @ g[None, :]).expand(channel, 1, size, size).contiguous().to(like)
         _window_cache[key] = w
     return w

@@ -5,7 +5,8 @@ tracked, ``camera_extent = max(depth) / scene_radius_depth_ratio`` is fixed on f
 Harness outputs in the reference's formats: ``save_map`` = ``outputdir/point_cloud/iteration_<n>/point_cloud.ply``
 (``SLAM.py:286-292``), ``save_iterations`` checkpoints inside ``run`` (``:488-492``) and the final map (``:497-500``),
 ``save_results`` = ``outputdir/results.npz`` with the reference's key set (``:294-373``: pose_est, pose_gt, keyframes, ate_rmse,
-psnr_list, ssim_list, lpips_list, avg_tracking_it_time, avg_mapping_it_time), and resuming from a checkpoint when the
+psnr_list, ssim_list, lpips_list, avg_tracking_it_time, avg_mapping_it_time; `eval_on_device` adds eval_table, eval_frames and
+depth_l1_list), and resuming from a checkpoint when the
 configuration carries ``iteration`` (``:90-104`` map + poses, ``slam/mapper.py:65-71`` keyframes + covisibility graph).  Frame
 sources: ``SyntheticSequence`` here, recorded TUM / UT-MM directories in ``dataset.RecordedSequence``.  The Replica and other loaders, the
 monocular depth network and LPIPS (a downloaded network; its list stays empty) are out of scope.  Debug outputs
@@ -197,6 +198,15 @@ class _FixedMap:
         self.get_features = torch.cat([G["f_dc"], torch.zeros(G["f_dc"].shape[0], n_rest, 3, device=G["f_dc"].device)], 1)
 
 
+def print_image_metrics(psnr_list, ssim_list, depth_l1_list=None):
+    """slam/SLAM.py:348-349: the means over the evaluated frames (LPIPS is out of scope); the depth L1 when the evaluation has one."""
+    if len(psnr_list):
+        print("  PSNR : {:>12.7f}".format(np.array(psnr_list).mean()))
+        print("  SSIM : {:>12.7f}".format(np.array(ssim_list).mean()))
+    if depth_l1_list is not None and len(depth_l1_list):
+        print("  Depth L1 : {:>12.7f} m".format(np.array(depth_l1_list).mean()))
+
+
 class SLAM:
     def __init__(self, cfg, sequence, rasterizer_cls=None, settings_cls=None, render_mode="fused", window=None, native_loops=None):
         self.cfg = cfg
@@ -222,6 +232,9 @@ class SLAM:
         self.mapper = MapperCls(cfg, self.gaussians, self.renderer, self.estimate_pose_list, n_img=n, window=window)
         self.gt_pose_list = [None] * n
         self.depth_fits, self.depth_fit_frames = [], []      # depth_align_on_device: the fit record (on the device) of every fitted frame, and its index
+        self.eval_table = self.eval_frames = None      # eval_on_device: the [n_eval, 16] float64 table of the last evaluate_images and its frame indices
+        if cfg.get("eval_on_device", False) and not str(cfg["device"]).startswith("cuda"):
+            raise ValueError("eval_on_device needs a CUDA device (there is no CPU kernel); use eval_on_device: false")
         self.frame_sink = None      # debug.create_video: the PNG writer of outputdir/debug_video, opened by the first frame, closed by run()
         if resume is not None:
             dev = cfg["device"]
@@ -353,9 +366,19 @@ class SLAM:
         self.gaussians.save_ply(os.path.join(path, "point_cloud.ply"))
         return os.path.join(path, "point_cloud.ply")
 
+    def _eval_frames(self, last_idx):
+        every = int(self.cfg.get("eval_every", 1))
+        return [idx for idx in range(last_idx) if idx == 0 or (idx + 1) % every == 0]
+
     def evaluate_images(self, last_idx):
         """PSNR / SSIM of the map rendered from the estimated pose of frame 0 and every `eval_every`-th frame (slam/SLAM.py:197-231;
-        LPIPS needs a downloaded network and is left out: its list stays empty)."""
+        LPIPS needs a downloaded network and is left out: its list stays empty).  With `eval_on_device` every frame is scored by
+        mm3dgs_eval_image into its row of one [n_eval, 16] table on the device (eval_utils.image_metrics_device: two launches, also the depth
+        L1 against the sensor depth) and the table is read back once, after the loop; it stays in `self.eval_table` (float64) with the frame
+        indices in `self.eval_frames`, and the two lists are its columns 0 and 1 as the float32 values the host chain returns."""
+        self.eval_table = self.eval_frames = None
+        if self.cfg.get("eval_on_device", False):
+            return self._evaluate_images_device(last_idx)
         from .eval_utils import psnr
         from .loss_utils import ssim
         every = int(self.cfg.get("eval_every", 1))
@@ -370,6 +393,24 @@ class SLAM:
                 ssim_list.append(ssim(image, color).detach().cpu().numpy())
         return psnr_list, ssim_list, []
 
+    def _evaluate_images_device(self, last_idx):
+        from .eval_utils import image_metrics_device
+        if not str(self.cfg["device"]).startswith("cuda"):
+            raise ValueError("eval_on_device needs a CUDA device (there is no CPU kernel); use eval_on_device: false")
+        frames = self._eval_frames(last_idx)
+        table = torch.zeros(len(frames), 16, dtype=torch.float64, device=self.cfg["device"])
+        with torch.no_grad():
+            for k, idx in enumerate(frames):
+                color, gt_depth = self.seq[idx][0], self.seq[idx][1]
+                result = self.renderer.render(self.gaussians, camera_pose=self.estimate_pose_list[idx])
+                depth = None if gt_depth is None else result["depth"][0]
+                image_metrics_device(result["render"], color, depth, gt_depth, table[k])
+        self.eval_table = table.cpu().numpy()      # the one read-back of the evaluation
+        self.eval_frames = np.asarray(frames, dtype=np.int64)
+        psnr_list = [np.asarray(v, dtype=np.float32) for v in self.eval_table[:, 0]]
+        ssim_list = [np.asarray(v, dtype=np.float32) for v in self.eval_table[:, 1]]
+        return psnr_list, ssim_list, []
+
     def save_results(self, last_idx):
         """results.npz with the key set, shapes and types of slam/SLAM.py:294-373 (np.load(..., allow_pickle=True) reads the keyframe
         dicts back, as slam/mapper.py:65-71 does)."""
@@ -382,6 +423,10 @@ class SLAM:
         _, results["ate_rmse"] = evaluate_ate_rmse(est, gt, method="umeyama")          # on the raw (world->camera) vectors, as the reference does
         psnr_list, ssim_list, lpips_list = self.evaluate_images(last_idx)
         results["psnr_list"], results["ssim_list"], results["lpips_list"] = psnr_list, ssim_list, lpips_list
+        if self.cfg.get("eval_on_device", False) and self.eval_table is not None:      # the whole table, the frames of its rows and the depth L1 the host chain does not have
+            results["eval_table"], results["eval_frames"] = self.eval_table, self.eval_frames
+            results["depth_l1_list"] = [np.asarray(v) for v in self.eval_table[:, 2]]
+        print_image_metrics(psnr_list, ssim_list, results.get("depth_l1_list"))
         if self.cfg["debug"]["get_runtime_stats"]:
             results["avg_tracking_it_time"] = self.tracker.tracking_time_sum / max(self.tracker.tracking_iter_count, 1) * 1000
             results["avg_mapping_it_time"] = self.mapper.mapping_time_sum / max(self.mapper.mapping_iter_count, 1) * 1000

@@ -22,7 +22,14 @@ network], avg_tracking_it_time / avg_mapping_it_time with debug.get_runtime_stat
 from that checkpoint (map, poses, keyframes, covisibility graph), like the reference.  `debug.create_video: true` adds `debug_video/`
 (one PNG per frame of the reference's debug video: after tracking and after mapping; INTEGRATION.md has the ffmpeg line that makes the
 video), `debug.save_keyframes: true` adds `keyframes/<idx>.png`, and `--render` adds `render/render<idx>.png` + `render/gt<idx>.png` for
-every 50th frame (the reference's `SLAM.render()`).  None of them changes a pose.
+every 50th frame (the reference's `SLAM.render()`).  None of them changes a pose.  `eval_on_device: true` scores the evaluated frames on
+the device (`mm3dgs_eval_image`: PSNR, SSIM and the depth L1 against the sensor depth, one read-back) and adds `eval_table`, `eval_frames` and
+`depth_l1_list` to `results.npz`.
+
+`--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
+`outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
+prints mean PSNR and SSIM (depth L1 with `eval_on_device`), `ATE RMSE` and `ATE RMSE c2w` -- the reference's scripts/eval_image.py and the
+printing part of scripts/eval_traj.py; plots stay out of scope.  It writes nothing.
 """
 import argparse
 import os
@@ -60,12 +67,48 @@ def build_sequence(cfg, frames=None, gaussians=150000):
     return SyntheticSequence(cfg, 10 if frames is None else frames, gaussians, seed=0)
 
 
+def evaluate_checkpoint(cfg, seq, iteration=None):
+    """`--eval`: score a finished run from its checkpoint (the reference's scripts/eval_image.py and the printing part of scripts/eval_traj.py).
+    Resumes the map `outputdir/point_cloud/iteration_<n>` (`iteration`, else the config's `iteration`, else the largest one on disk) and the
+    poses of `outputdir/results.npz`, runs no frame, renders and scores frame 0 and every `eval_every`-th frame of `seq` at the stored poses
+    (`SLAM.evaluate_images`; on the device with `eval_on_device`) and aligns the stored trajectories.  Prints the means and returns them with
+    the lists; writes nothing: results.npz and the map stay as they are."""
+    import copy
+    from mm3dgs_slam_amd.eval_utils import camera_centers, evaluate_ate_rmse
+    from mm3dgs_slam_amd.slam import SLAM, print_image_metrics
+    cfg = copy.deepcopy(cfg)
+    outdir = cfg["outputdir"]
+    if iteration is None:
+        iteration = cfg.get("iteration")
+    if iteration is None:
+        names = os.listdir(os.path.join(outdir, "point_cloud"))
+        iteration = max(int(n[len("iteration_"):]) for n in names if n.startswith("iteration_"))
+    cfg["iteration"] = int(iteration)
+    slam = SLAM(cfg, seq)
+    stored = np.load(os.path.join(outdir, "results.npz"), allow_pickle=True)
+    est, gt = stored["pose_est"], stored["pose_gt"]
+    last_idx = min(len(est), len(seq))
+    with torch.no_grad():
+        psnr_list, ssim_list, _ = slam.evaluate_images(last_idx)
+    out = {"iteration": int(iteration), "psnr_list": psnr_list, "ssim_list": ssim_list, "eval_table": slam.eval_table, "eval_frames": slam.eval_frames,
+           "depth_l1_list": None if slam.eval_table is None else [np.asarray(v) for v in slam.eval_table[:, 2]]}
+    _, out["ate_rmse"] = evaluate_ate_rmse(est, gt, method="umeyama")
+    _, out["ate_rmse_c2w"] = evaluate_ate_rmse(camera_centers(est).numpy(), camera_centers(gt).numpy(), method="umeyama")
+    print(f"Evaluation of {outdir} at iteration {iteration}: {len(psnr_list)} of {last_idx} frames")
+    print_image_metrics(psnr_list, ssim_list, out["depth_l1_list"])
+    print(f"  ATE RMSE : {out['ate_rmse']} m")
+    print(f"  ATE RMSE c2w : {out['ate_rmse_c2w']} m")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=None, help="YAML config in the reference's schema")
     ap.add_argument("--frames", type=int, default=None, help="frames to run (default: 10 synthetic frames, or the whole recorded sequence)")
     ap.add_argument("--gaussians", type=int, default=150000, help="size of the synthetic ground-truth scene")
     ap.add_argument("--render", action="store_true", help="after the run, write render / ground-truth image pairs of every 50th frame to outputdir/render")
+    ap.add_argument("--eval", action="store_true", help="run no frame: score the finished run in outputdir from its checkpoint (PSNR, SSIM, depth L1 with eval_on_device, ATE RMSE)")
+    ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
     from mm3dgs_slam_amd.slam import SLAM
@@ -84,6 +127,9 @@ def main():
                     "save_keyframes": bool(dbg.get("save_keyframes", False))}
     cfg.setdefault("outputdir", "output/" + (str(cfg.get("scene") or "recorded") if sequence_source(cfg) == "recorded" else "synthetic"))
     outdir = cfg["outputdir"]
+    if args.eval:
+        evaluate_checkpoint(cfg, build_sequence(cfg, args.frames, args.gaussians), args.iteration)
+        return
     os.makedirs(outdir, exist_ok=True)
     seq = build_sequence(cfg, args.frames, args.gaussians)
     slam = SLAM(cfg, seq)
