@@ -470,6 +470,50 @@ int mm3dgs_eval_image(int H, int W, const float* image /*[3,H,W]*/, const float*
                       const float* gt_depth_or_null /*[H,W]*/, const float* window /*host [11]*/, void* work, double* row /*[16], device*/,
                       void* stream);
 
+/* ---- fused coloured point cloud: the valid pixels of one RGB-D view lifted to world points and appended to a growing cloud ---------------
+ * The computational core of the reference's scripts/visualizer.py (rgbd2pcd, :69-112), one call per view; with a voxel size only the first
+ * point that ever reached a voxel is kept, so the cloud of a whole run stays small and is the same on every run.
+ * color [3,H,W], depth [H,W], silhouette_or_null [H,W]: float32 on the device, 4-byte aligned; pose: the 7 floats (qw qx qy qz tx ty tz) of the
+ * world->camera pose on the device, the quaternion is normalised here; fx, fy, cx, cy: host doubles.
+ *   valid pixel   depth > 0 && depth < +inf && (depth_max <= 0 || depth <= depth_max) && (silhouette == NULL || silhouette > sil_min), strict
+ *                 float32 comparisons on the inputs: a NaN fails.
+ *   position      p_c = ((u - cx) / fx z, (v - cy) / fy z, z) with the integer pixel indices u, v (no half-pixel offset: the reference's
+ *                 convention and mm3dgs_seed_gaussians'), p_w = R^T (p_c - t); evaluated in double from the float32 inputs, rounded once to
+ *                 float32 at the store.
+ *   row           16 bytes {float x, y, z; uint32 rgba}, one 16-byte store; each channel (uint8)(min(max(c, 0), 1) * 255.0f + 0.5f) in float32,
+ *                 NaN gives 0; alpha 255; red in the low byte: the bytes in memory are r g b a.
+ *   rows          [cap] rows, 16-byte aligned.  counters[0] is the number of rows already there: a call appends behind them.
+ *   voxel == 0    every valid pixel becomes a row, in raster order (count, scan, scatter by rank: no atomic decides a position); table ignored.
+ *   voxel > 0     cell per axis = floor((double)x_f32 / voxel) of the float32 value that is stored; a point with some |cell| >= 2^20 (or a
+ *                 position that is not a number) is dropped and counted as out of range; with the cells (i, j, k): key = (i + 2^20) << 42 |
+ *                 (j + 2^20) << 21 | (k + 2^20).  table: `slots` (a power of two, 64 <= slots <= 2^40) pairs {uint64 key, uint64 ticket}, 16-byte aligned, all
+ *                 ones when empty (mm3dgs_pointcloud_reset), open addressing from a multiplicative hash, linear probing over at most
+ *                 min(128, slots) slots; a point that finds neither its key nor an empty slot there is dropped and counted as probe_fail.
+ *                 ticket = (uint64)view << 32 | pixel index; the caller increases `view` from call to call, so a voxel keeps the first
+ *                 point that reached it in stream order (view, then raster) and a view's rows are final when its call returns.  The rows a
+ *                 call appends are its voxels' representatives in raster order: the set and the order of the rows do not depend on the order
+ *                 in which the atomics of the claim land (tests/test_gpu_pointcloud.py: equal to a host first-occurrence selection, bit for
+ *                 bit).  Rows that would land at or beyond cap are not written and counted as capacity_dropped.
+ *   counters      uint64[8] on the device, 8-byte aligned, cumulative since mm3dgs_pointcloud_reset: [0] rows in the cloud (<= cap), [1] valid
+ *                 pixels, [2] merged into a voxel that has its point, [3] out of range, [4] probe_fail, [5] capacity_dropped, [6] views, [7] 0;
+ *                 [1] == [0] + [2] + [3] + [4] + [5] after every call.
+ * work: mm3dgs_pointcloud_work_bytes(H, W) bytes of device memory, 8-byte aligned, contents irrelevant before and after.  Three launches on
+ * `stream` without a voxel size, four with one (claim: 64-bit atomicCAS / atomicMin on the table; select + count; one-workgroup scan, which
+ * also updates the counters; scatter); every loop is bounded, a full table or a full row buffer ends as a count; no host synchronisation.
+ * Nothing outside rows[counters[0] : cap], the table, counters[0:8] and work[0:work_bytes] is written.
+ * mm3dgs_pointcloud_reset sets the table (NULL: none) to all ones and the counters to zero.
+ * -1 (nothing is launched): H or W <= 0 or more than 2^28 pixels; a NULL color, depth, pose, rows, counters or work; a voxel that is negative
+ * or not finite; voxel > 0 with a NULL table or with slots not a power of two in [64, 2^40]; fx or fy zero or not finite, cx or cy not finite;
+ * rows or table not 16-byte aligned, counters or work not 8-byte aligned, an image or the pose not 4-byte aligned.
+ * mm3dgs_pointcloud_work_bytes returns 0 for a shape that mm3dgs_pointcloud_add_view rejects. */
+size_t mm3dgs_pointcloud_work_bytes(int H, int W);
+int mm3dgs_pointcloud_reset(void* table_or_null, uint64_t slots, uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_pointcloud_add_view(int H, int W, double fx, double fy, double cx, double cy, const float* pose /*[7], device*/,
+                               const float* color /*[3,H,W]*/, const float* depth /*[H,W]*/, const float* silhouette_or_null /*[H,W]*/,
+                               float sil_min, float depth_max, double voxel, uint32_t view, void* rows /*[cap] x 16 bytes*/, uint64_t cap,
+                               void* table_or_null /*[slots] x 16 bytes*/, uint64_t slots, uint64_t* counters /*[8], device*/, void* work,
+                               void* stream);
+
 /* ---- frame ingest: raw sensor bytes -> the two images the SLAM loops consume, in one launch ------------------------------------------
  * rgb: uint8 interleaved [Hs,Ws,3] on the device, any byte alignment; depth_or_null: uint16 [Hs,Ws], 2-byte aligned.  out_color [3,H,W]
  * float32 in [0,1]; out_depth_or_null [H,W] float32 in metres, required iff depth is given (a colour-only call passes NULL for both).
@@ -601,7 +645,8 @@ const char* mm3dgs_last_error(void);
         one launch); mm3dgs_ingest_est (the monocular depth network's raw output, float32 / float16 / uint16 at any size -> the float32
         estimate at frame size, one launch); mm3dgs_mosaic_work_bytes / mm3dgs_mosaic (the debug video's and SLAM.render()'s panel
         mosaic as one uint8 image, composed on the device); mm3dgs_eval_image_work_bytes / mm3dgs_eval_image (PSNR, SSIM and depth L1 of a
-        rendered frame as one row of a device table); a caller that needs them looks the symbols up */
+        rendered frame as one row of a device table); mm3dgs_pointcloud_work_bytes / mm3dgs_pointcloud_reset / mm3dgs_pointcloud_add_view
+        (the fused coloured point cloud of a run, one call per view, first point per voxel); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

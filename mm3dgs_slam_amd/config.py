@@ -18,6 +18,11 @@ _TUM = {
     # the evaluation at the end of a run (PSNR, SSIM, and the depth L1 the host chain does not have) from mm3dgs_eval_image: two launches per
     # frame into a table on the device, one read-back per evaluation; opt-in (results.npz: eval_table, eval_frames, depth_l1_list)
     "eval_on_device": False,
+    # after the run, the reconstruction as a fused coloured point cloud (outputdir/pointcloud/cloud.ply + trajectory.ply; pointcloud.py,
+    # mm3dgs_pointcloud_add_view): every `every`-th frame (None: mapping.kf_every) lifted to world points -- source "render": the map
+    # rendered at the estimated pose where the silhouette exceeds sil_min, "sensor": the frame's own colour and depth --, depths beyond
+    # max_depth dropped (0: no limit), one point per `voxel`-sized cell (0: no thinning), at most max_points rows; opt-in, changes no pose
+    "pointcloud": {"export": False, "every": None, "voxel": 0.01, "source": "render", "sil_min": 0.99, "max_depth": 0, "max_points": 16777216},
     "scene_radius_depth_ratio": 2, "desired_height": 480, "desired_width": 640,
     "debug": {"get_runtime_stats": False, "create_video": False, "save_keyframes": False},
     "pipeline": {"convert_SHs_python": False, "compute_cov3D_python": False, "transform_means_python": True,

@@ -741,6 +741,50 @@ int mm3dgs_eval_image(int H, int W, const float* image, const float* gt, const f
   return check_launch("eval_image");
 }
 
+// ---- fused point cloud (pointcloud.hip) ------------------------------------------------------------------------------------
+static bool pointcloud_slots_ok(uint64_t slots) { return slots >= 64 && slots <= ((uint64_t)1 << 40) && (slots & (slots - 1)) == 0; }
+
+size_t mm3dgs_pointcloud_work_bytes(int H, int W) { return eval_shape_ok(H, W) ? pointcloud_work_bytes(H, W) : 0; }
+
+int mm3dgs_pointcloud_reset(void* table_or_null, uint64_t slots, uint64_t* counters, void* stream) {
+  if (!counters) return fail(-1, "pointcloud_reset: counters is NULL");
+  if ((uintptr_t)counters & 7) return fail(-1, "pointcloud_reset: counters must be 8-byte aligned");
+  if (table_or_null && !pointcloud_slots_ok(slots))
+    return fail(-1, "pointcloud_reset: slots = %llu (a power of two, at least 64, at most 2^40)", (unsigned long long)slots);
+  if ((uintptr_t)table_or_null & 15) return fail(-1, "pointcloud_reset: table must be 16-byte aligned");
+  launch_pointcloud_reset(table_or_null, slots, counters, (hipStream_t)stream);
+  return check_launch("pointcloud_reset");
+}
+
+int mm3dgs_pointcloud_add_view(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
+                               const float* silhouette_or_null, float sil_min, float depth_max, double voxel, uint32_t view, void* rows,
+                               uint64_t cap, void* table_or_null, uint64_t slots, uint64_t* counters, void* work, void* stream) {
+  if (H <= 0 || W <= 0) return fail(-1, "pointcloud_add_view: H = %d, W = %d (both must be positive)", H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "pointcloud_add_view: %d x %d has more than 2^28 pixels", H, W);
+  if (!color || !depth || !pose || !rows || !counters || !work)
+    return fail(-1, "pointcloud_add_view: NULL argument (color, depth, pose, rows, counters and work are required)");
+  if (!(voxel >= 0.0) || !isfinite(voxel)) return fail(-1, "pointcloud_add_view: voxel = %g (must be finite and not negative)", voxel);
+  if (voxel > 0.0 && !table_or_null) return fail(-1, "pointcloud_add_view: voxel = %g needs a table", voxel);
+  if (voxel > 0.0 && !pointcloud_slots_ok(slots))
+    return fail(-1, "pointcloud_add_view: slots = %llu (a power of two, at least 64, at most 2^40)", (unsigned long long)slots);
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "pointcloud_add_view: fx = %g, fy = %g (finite, not 0)", fx, fy);
+  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "pointcloud_add_view: cx = %g, cy = %g (must be finite)", cx, cy);
+  if (((uintptr_t)rows | (uintptr_t)table_or_null) & 15) return fail(-1, "pointcloud_add_view: rows and table must be 16-byte aligned");
+  if (((uintptr_t)counters | (uintptr_t)work) & 7) return fail(-1, "pointcloud_add_view: counters and work must be 8-byte aligned");
+  if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)silhouette_or_null | (uintptr_t)pose) & 3)
+    return fail(-1, "pointcloud_add_view: the images and the pose must be 4-byte aligned");
+  PointCloudView v;
+  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
+  v.pose = pose; v.color = color; v.depth = depth; v.sil = silhouette_or_null;
+  v.sil_min = sil_min; v.depth_max = depth_max; v.voxel = voxel; v.view = view;
+  v.table = voxel > 0.0 ? (unsigned long long*)table_or_null : nullptr;      // voxel == 0: no thinning, a table is ignored
+  v.slots = v.table ? slots : 0;
+  v.hash_shift = 64;
+  for (uint64_t s = v.slots; s > 1; s >>= 1) v.hash_shift--;
+  launch_pointcloud_add_view(v, rows, cap, counters, work, (hipStream_t)stream);
+  return check_launch("pointcloud_add_view");
+}
+
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
                         float* out_color, float* out_depth_or_null, void* stream) {
   if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);

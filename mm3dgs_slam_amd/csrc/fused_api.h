@@ -124,6 +124,21 @@ void launch_align_depth(int H, int W, const float* est, const float* depth, cons
 size_t eval_image_work_bytes(int H, int W);
 void launch_eval_image(int H, int W, const float* image, const float* gt, const float* depth, const float* gt_depth, const float* window,
                        double* rows, double* row, hipStream_t s);
+// fused point cloud (pointcloud.hip): one view's valid pixels lifted to world points and appended to rows (16 B each) from counters[0],
+// thinned to the first point per voxel through the caller's table when voxel > 0 (table NULL otherwise); work = the buffer of
+// pointcloud_work_bytes(H, W); H W <= 2^28, slots a power of two >= 64 and hash_shift = 64 - log2(slots), as the entry point has checked
+struct PointCloudView {
+  int H, W;
+  double fx, fy, cx, cy;
+  const float* pose; const float* color; const float* depth; const float* sil;
+  float sil_min, depth_max;
+  double voxel;
+  uint32_t view;
+  unsigned long long* table; uint64_t slots; int hash_shift;
+};
+size_t pointcloud_work_bytes(int H, int W);
+void launch_pointcloud_reset(void* table, uint64_t slots, uint64_t* counters, hipStream_t s);
+void launch_pointcloud_add_view(const PointCloudView& v, void* rows, uint64_t cap, uint64_t* counters, void* work, hipStream_t s);
 // frame ingest (ingest.hip): raw uint8 RGB [Hs,Ws,3] + uint16 depth [Hs,Ws] -> colour [3,H,W] in [0,1] + depth [H,W] in metres, one
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,

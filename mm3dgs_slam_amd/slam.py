@@ -11,7 +11,8 @@ configuration carries ``iteration`` (``:90-104`` map + poses, ``slam/mapper.py:6
 sources: ``SyntheticSequence`` here, recorded TUM / UT-MM directories in ``dataset.RecordedSequence``.  The Replica and other loaders, the
 monocular depth network and LPIPS (a downloaded network; its list stays empty) are out of scope.  Debug outputs
 (``debug_frames.py``): ``debug.create_video`` writes the reference's per-frame 2 x 3 mosaic (``:233-276,450-485``) as numbered PNG files under
-``outputdir/debug_video/``, ``debug.save_keyframes`` one PNG per keyframe (mapper.py), ``render()`` the image-over-depth pairs of ``:148-195``."""
+``outputdir/debug_video/``, ``debug.save_keyframes`` one PNG per keyframe (mapper.py), ``render()`` the image-over-depth pairs of ``:148-195``.  ``pointcloud.export`` / ``export_pointcloud()``
+(``pointcloud.py``): the reconstruction as a fused coloured point cloud and the camera path, ``outputdir/pointcloud/cloud.ply`` + ``trajectory.ply``."""
 from __future__ import annotations
 
 import math
@@ -236,6 +237,7 @@ class SLAM:
         if cfg.get("eval_on_device", False) and not str(cfg["device"]).startswith("cuda"):
             raise ValueError("eval_on_device needs a CUDA device (there is no CPU kernel); use eval_on_device: false")
         self.frame_sink = None      # debug.create_video: the PNG writer of outputdir/debug_video, opened by the first frame, closed by run()
+        self.pointcloud_export = None      # pointcloud.export: the paths and counters of the last export_pointcloud()
         if resume is not None:
             dev = cfg["device"]
             for i, p in enumerate(resume["pose_est"][:n]):
@@ -319,6 +321,56 @@ class SLAM:
                     df.save_png(df.compose([(df.COLOR, color, None), (df.DEPTH, depth, None)], 2, 1, quant=1, bgr=False), written[-1])
         return written
 
+    def export_pointcloud(self, path=None, every=None, voxel=None, source=None):
+        """The reconstruction as a fused coloured point cloud (pointcloud.py; the core of the reference's scripts/visualizer.py): for every
+        frame with `idx % every == 0` that has an estimated pose one view at that pose -- `source` "render": the map rendered there, with
+        the rendered silhouette as the surface test (> `pointcloud.sil_min`, the reference's 0.99); "sensor": the frame's own colour and
+        sensor depth -- is lifted to world points, and the first point of every `voxel`-sized cell is kept.  Writes `path/cloud.ply` and
+        `path/trajectory.ply` (default `outputdir/pointcloud`); arguments left None come from the `pointcloud` config block.  One
+        mm3dgs_pointcloud_add_view call per view on a GPU, the host statement on `device: cpu`.  Returns the two paths and the counters;
+        raises RuntimeError when points were dropped for lack of room (`pointcloud.max_points`)."""
+        from . import pointcloud as pc
+        from .config import _TUM
+        opt = dict(_TUM["pointcloud"], **(self.cfg.get("pointcloud") or {}))
+        every = int(every if every is not None else (opt["every"] or self.cfg["mapping"]["kf_every"]))
+        voxel = float(opt["voxel"] if voxel is None else voxel)
+        source = str(opt["source"] if source is None else source)
+        if source not in ("render", "sensor"):
+            raise ValueError(f"pointcloud.source = {source!r} (render / sensor)")
+        if every < 1:
+            raise ValueError(f"pointcloud.every = {every} (must be positive)")
+        path = os.path.join(self.cfg["outputdir"], "pointcloud") if path is None else path
+        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
+        on_device = str(self.cfg["device"]).startswith("cuda")
+        Builder = pc.PointCloudBuilder if on_device else pc.HostPointCloudBuilder
+        builder = Builder(H, W, self.cfg["cam"], voxel=voxel, max_points=int(opt["max_points"]), sil_min=float(opt["sil_min"]),
+                          depth_max=float(opt["max_depth"]), device=self.cfg["device"])
+        poses = []
+        with torch.no_grad():
+            for idx in range(len(self.seq)):
+                pose = self.estimate_pose_list[idx]
+                if pose is None:
+                    continue
+                poses.append(pose.detach())
+                if idx % every != 0:
+                    continue
+                if source == "render":
+                    result = self.renderer.render(self.gaussians, camera_pose=pose)
+                    builder.add(result["render"], result["depth"][0], result["depth"][1], pose)
+                else:
+                    color, depth, _ = self.seq[idx]
+                    if depth is None:
+                        raise ValueError(f'pointcloud.source "sensor": frame {idx} has no sensor depth')
+                    builder.add(color, depth, None, pose)
+        counters = builder.finish()
+        os.makedirs(path, exist_ok=True)
+        out = {"cloud": pc.write_ply(os.path.join(path, "cloud.ply"), builder.rows()),
+               "trajectory": pc.write_trajectory_ply(os.path.join(path, "trajectory.ply"), torch.stack(poses) if poses else np.zeros((0, 7))),
+               "counters": counters}
+        self.pointcloud_export = out      # what the last export wrote (run() calls this without a caller to hand it to)
+        print(f"Point cloud: {counters['rows']} points from {counters['views']} views ({counters['valid']} valid pixels, voxel {voxel} m) in {out['cloud']}")
+        return out
+
     def run(self, progress=None, reraise=True):
         """slam/SLAM.py:375-503: every frame; `save_iterations` checkpoints on the way; with an `outputdir` the final map (as
         iteration <last_idx>) and results.npz at the end -- also when a frame raised: the reference catches the exception, prints it
@@ -356,6 +408,11 @@ class SLAM:
                     if self.failure is None:
                         raise
                     print(f"(while saving after the failure above: {e2!r})")
+                if (self.cfg.get("pointcloud") or {}).get("export", False):      # after results.npz, which it does not touch; reported, never raised
+                    try:
+                        self.export_pointcloud()
+                    except Exception as e4:      # noqa: BLE001
+                        print(f"(point cloud export: {e4!r})")
         if self.failure is not None and reraise:
             raise self.failure
 

@@ -24,7 +24,10 @@ from that checkpoint (map, poses, keyframes, covisibility graph), like the refer
 video), `debug.save_keyframes: true` adds `keyframes/<idx>.png`, and `--render` adds `render/render<idx>.png` + `render/gt<idx>.png` for
 every 50th frame (the reference's `SLAM.render()`).  None of them changes a pose.  `eval_on_device: true` scores the evaluated frames on
 the device (`mm3dgs_eval_image`: PSNR, SSIM and the depth L1 against the sensor depth, one read-back) and adds `eval_table`, `eval_frames` and
-`depth_l1_list` to `results.npz`.
+`depth_l1_list` to `results.npz`.  `--pointcloud` (or `pointcloud.export: true`) adds `pointcloud/cloud.ply`, the reconstruction as a fused coloured
+point cloud (the map rendered at every `pointcloud.every`-th estimated pose, lifted to world points, one point per `pointcloud.voxel`; binary PLY, `float x y z;
+uchar red green blue alpha`), and `pointcloud/trajectory.ply`, the camera path -- the computational core of the reference's scripts/visualizer.py, for MeshLab or
+CloudCompare; `--pointcloud --eval` writes the two files from the checkpoint without running a frame.
 
 `--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
 `outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
@@ -67,24 +70,31 @@ def build_sequence(cfg, frames=None, gaussians=150000):
     return SyntheticSequence(cfg, 10 if frames is None else frames, gaussians, seed=0)
 
 
+def resume_checkpoint(cfg, seq, iteration=None):
+    """A SLAM object resumed from `outputdir/point_cloud/iteration_<n>` (`iteration`, else the config's `iteration`, else the largest one on
+    disk) with the poses and keyframes of `outputdir/results.npz`; runs no frame.  Returns it with the iteration."""
+    import copy
+    from mm3dgs_slam_amd.slam import SLAM
+    cfg = copy.deepcopy(cfg)
+    if iteration is None:
+        iteration = cfg.get("iteration")
+    if iteration is None:
+        names = os.listdir(os.path.join(cfg["outputdir"], "point_cloud"))
+        iteration = max(int(n[len("iteration_"):]) for n in names if n.startswith("iteration_"))
+    cfg["iteration"] = int(iteration)
+    return SLAM(cfg, seq), int(iteration)
+
+
 def evaluate_checkpoint(cfg, seq, iteration=None):
     """`--eval`: score a finished run from its checkpoint (the reference's scripts/eval_image.py and the printing part of scripts/eval_traj.py).
     Resumes the map `outputdir/point_cloud/iteration_<n>` (`iteration`, else the config's `iteration`, else the largest one on disk) and the
     poses of `outputdir/results.npz`, runs no frame, renders and scores frame 0 and every `eval_every`-th frame of `seq` at the stored poses
     (`SLAM.evaluate_images`; on the device with `eval_on_device`) and aligns the stored trajectories.  Prints the means and returns them with
     the lists; writes nothing: results.npz and the map stay as they are."""
-    import copy
     from mm3dgs_slam_amd.eval_utils import camera_centers, evaluate_ate_rmse
-    from mm3dgs_slam_amd.slam import SLAM, print_image_metrics
-    cfg = copy.deepcopy(cfg)
+    from mm3dgs_slam_amd.slam import print_image_metrics
     outdir = cfg["outputdir"]
-    if iteration is None:
-        iteration = cfg.get("iteration")
-    if iteration is None:
-        names = os.listdir(os.path.join(outdir, "point_cloud"))
-        iteration = max(int(n[len("iteration_"):]) for n in names if n.startswith("iteration_"))
-    cfg["iteration"] = int(iteration)
-    slam = SLAM(cfg, seq)
+    slam, iteration = resume_checkpoint(cfg, seq, iteration)
     stored = np.load(os.path.join(outdir, "results.npz"), allow_pickle=True)
     est, gt = stored["pose_est"], stored["pose_gt"]
     last_idx = min(len(est), len(seq))
@@ -101,6 +111,16 @@ def evaluate_checkpoint(cfg, seq, iteration=None):
     return out
 
 
+def export_pointcloud_checkpoint(cfg, seq, iteration=None):
+    """`--pointcloud --eval`: the fused point cloud of a finished run from its checkpoint, without running a frame (the offline part of the
+    reference's scripts/visualizer.py): resumes like `evaluate_checkpoint` and calls `SLAM.export_pointcloud` with the config's
+    `pointcloud` block.  Adds `outputdir/pointcloud/` (cloud.ply, trajectory.ply) and touches nothing else.  Returns what the export returns."""
+    slam, iteration = resume_checkpoint(cfg, seq, iteration)
+    out = slam.export_pointcloud()
+    out["iteration"] = iteration
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=None, help="YAML config in the reference's schema")
@@ -108,6 +128,7 @@ def main():
     ap.add_argument("--gaussians", type=int, default=150000, help="size of the synthetic ground-truth scene")
     ap.add_argument("--render", action="store_true", help="after the run, write render / ground-truth image pairs of every 50th frame to outputdir/render")
     ap.add_argument("--eval", action="store_true", help="run no frame: score the finished run in outputdir from its checkpoint (PSNR, SSIM, depth L1 with eval_on_device, ATE RMSE)")
+    ap.add_argument("--pointcloud", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the fused coloured point cloud and the camera path to outputdir/pointcloud (the config's `pointcloud` block)")
     ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
@@ -128,8 +149,14 @@ def main():
     cfg.setdefault("outputdir", "output/" + (str(cfg.get("scene") or "recorded") if sequence_source(cfg) == "recorded" else "synthetic"))
     outdir = cfg["outputdir"]
     if args.eval:
-        evaluate_checkpoint(cfg, build_sequence(cfg, args.frames, args.gaussians), args.iteration)
+        seq = build_sequence(cfg, args.frames, args.gaussians)
+        if args.pointcloud:
+            export_pointcloud_checkpoint(cfg, seq, args.iteration)
+        else:
+            evaluate_checkpoint(cfg, seq, args.iteration)
         return
+    if args.pointcloud:
+        cfg["pointcloud"] = dict(cfg.get("pointcloud") or {}, export=True)
     os.makedirs(outdir, exist_ok=True)
     seq = build_sequence(cfg, args.frames, args.gaussians)
     slam = SLAM(cfg, seq)
