@@ -7,7 +7,8 @@ same (file:line are into ``slam/gaussian_model.py``):
   optimiser   Adam(lr=0, eps=1e-15), one group per parameter, names xyz f_dc f_rest opacity scaling rotation rgb (:143-195)
   surgery     densification_postfix -> cat_tensors_to_optimizer (:418-487), prune -> prune_points -> _prune_optimizer
               (:380-417, :574-588): parameters are REPLACED by fresh ``nn.Parameter`` objects, so a gradient computed
-              before the prune never reaches ``optimizer.step()`` (SURVEY.md section 3.3 -- reproduced on purpose)
+              before the prune never reaches ``optimizer.step()`` (SURVEY.md section 3.3 -- reproduced on purpose); every
+              form of it, torch or device, is one walk: ``_rebuild_groups``
   densify     densify_and_clone / densify_and_split / densify / densify_and_prune (:490-592), reset_opacity and
               replace_tensor_to_optimizer (:259-264, :360-378); the split samples come from general_utils.densify_normals
               (a stateless generator the device path reproduces) instead of torch.normal
@@ -16,14 +17,27 @@ PLY import/export keeps the reference's attribute order (:205-257) with a depend
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 from torch import nn
 
+from . import _lib
 from .general_utils import (build_rotation, build_scaling_rotation, densify_normals, get_expon_lr_func, inverse_sigmoid,
                             strip_symmetric)
+from .rasterizer import _ptr, _stream
 
 _GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "rgb")
+_ATTRS = dict(xyz="_xyz", f_dc="_features_dc", f_rest="_features_rest", opacity="_opacity", scaling="_scaling",
+              rotation="_rotation", rgb="_rgb")                     # optimiser group -> the model's attribute
+_STATS = ("xyz_gradient_accum", "denom", "max_radii2D")          # the densification statistics: one row per Gaussian, like the groups
+
+
+def _library():
+    """The C ABI the device surgery calls.  With ``_stream`` the seam of this module: a CPU test replaces the two module attributes
+    and runs the same host bookkeeping on host tensors."""
+    return _lib.load()
 
 
 def draw_densify_seed():
@@ -95,12 +109,11 @@ class GaussianModel:
 
     # ---- optimiser ----------------------------------------------------------------------------------------------
     def _params(self):
-        return dict(xyz=self._xyz, f_dc=self._features_dc, f_rest=self._features_rest, opacity=self._opacity,
-                    scaling=self._scaling, rotation=self._rotation, rgb=self._rgb)
+        return {name: getattr(self, attr) for name, attr in _ATTRS.items()}
 
     def _assign(self, t):
-        self._xyz, self._features_dc, self._features_rest = t["xyz"], t["f_dc"], t["f_rest"]
-        self._opacity, self._scaling, self._rotation, self._rgb = t["opacity"], t["scaling"], t["rotation"], t["rgb"]
+        for name, tensor in t.items():
+            setattr(self, _ATTRS[name], tensor)
 
     def training_setup(self):
         m = self.cfg["mapping"]
@@ -126,22 +139,48 @@ class GaussianModel:
                 group["lr"] = self.xyz_scheduler_args(iteration)
                 return group["lr"]
 
-    def _rebuild_groups(self, transform_param, transform_state):
-        """Replace every group's parameter by ``transform_param(old)`` (a new leaf) and carry the Adam moments
-        through ``transform_state`` -- the reference's cat/prune surgery."""
+    def _install(self, group, tensor, state):
+        """`tensor` becomes the parameter of `group` and of the model: a fresh leaf that requires a gradient and has none (a gradient
+        computed before the surgery never reaches ``optimizer.step()``), with `state` (None or empty: no
+        Adam state) keyed by it and the old parameter's key gone."""
+        self.optimizer.state.pop(group["params"][0], None)
+        new = nn.Parameter(tensor.requires_grad_(True))
+        if state:
+            self.optimizer.state[new] = state
+        group["params"][0] = new
+        self._assign({group["name"]: new})
+        return new
+
+    def _rebuild_groups(self, remake, only=None):
+        """Row surgery -- the reference's cat/prune surgery and every device form of it walk the optimiser's groups here and nowhere
+        else.  ``remake(name, role, tensor)`` says what becomes of each tensor: role "param" for a group's parameter, "exp_avg" /
+        "exp_avg_sq" for its Adam moments (a group without moments is not asked, and loses whatever state it had; the step counter
+        stays with the moments), "stat" for the three statistics, `name` then being the attribute.  `only` restricts the walk to one
+        group.  Bumps `generation`; returns the new parameters by group name."""
         out = {}
         self.generation += 1
         for group in self.optimizer.param_groups:
+            name = group["name"]
+            if only not in (None, name):
+                continue
             old = group["params"][0]
-            state = self.optimizer.state.pop(old, None)
-            new = nn.Parameter(transform_param(group["name"], old.detach()).requires_grad_(True))
+            state = self.optimizer.state.get(old)
+            tensor = remake(name, "param", old.detach())
             if state is not None and "exp_avg" in state:
-                state["exp_avg"] = transform_state(group["name"], state["exp_avg"])
-                state["exp_avg_sq"] = transform_state(group["name"], state["exp_avg_sq"])
-                self.optimizer.state[new] = state
-            group["params"][0] = new
-            out[group["name"]] = new
+                for role in ("exp_avg", "exp_avg_sq"):
+                    state[role] = remake(name, role, state[role])
+            else:
+                state = None
+            out[name] = self._install(group, tensor, state)
+        for attr in _STATS:
+            setattr(self, attr, remake(attr, "stat", getattr(self, attr)))
         return out
+
+    def _drop_grads(self):
+        """What a surgery that moves no row leaves of itself: the tensors stay in place (the values the rebuild would produce), the
+        gradients go, because the rebuild would hand the optimiser fresh parameters without them."""
+        for group in self.optimizer.param_groups:
+            group["params"][0].grad = None
 
     # ---- snapshot / restore (overflow recovery of the native mapping loop, fused.py) -----------------------------------
     def snapshot(self):
@@ -152,24 +191,20 @@ class GaussianModel:
             p = group["params"][0]
             st = self.optimizer.state.get(p, {})
             groups.append((group["name"], p.detach().clone(), {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}, group["lr"]))
-        return dict(groups=groups, stats=(self.xyz_gradient_accum.clone(), self.denom.clone(), self.max_radii2D.clone()))
+        return dict(groups=groups, stats=tuple(getattr(self, attr).clone() for attr in _STATS))
 
     def restore(self, snap):
-        """Back to a ``snapshot()`` (which stays valid: tensors are copied again)."""
+        """Back to a ``snapshot()`` (which stays valid: tensors are copied again).  Not a row surgery: whole state dicts (step counter
+        included) and the learning rates come from the snapshot whatever the groups hold now, so it walks on its own and shares
+        `_install` with `_rebuild_groups`."""
         by_name = {name: (p, st, lr) for name, p, st, lr in snap["groups"]}
-        out = {}
         self.generation += 1
         for group in self.optimizer.param_groups:
-            self.optimizer.state.pop(group["params"][0], None)
             p, st, lr = by_name[group["name"]]
-            new = nn.Parameter(p.clone().requires_grad_(True))
-            if st:
-                self.optimizer.state[new] = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}
-            group["params"][0] = new
+            self._install(group, p.clone(), {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()})
             group["lr"] = lr
-            out[group["name"]] = new
-        self._assign(out)
-        self.xyz_gradient_accum, self.denom, self.max_radii2D = (t.clone() for t in snap["stats"])
+        for attr, t in zip(_STATS, snap["stats"]):
+            setattr(self, attr, t.clone())
 
     # ---- device-side surgery (csrc/compact.hip through the C ABI; CUDA tensors only) ---------------------------------------
     def _native(self):
@@ -178,117 +213,76 @@ class GaussianModel:
     def prune_mask_device(self, min_opacity, extent, max_screen_size=None, counter_ptr=None):
         """The pruning predicate of ``prune`` evaluated by one kernel: returns the uint8 keep mask; the number of pruned
         Gaussians is ADDED to the device word at ``counter_ptr`` (no host synchronisation)."""
-        import ctypes as C
-        from . import _lib
-        from .rasterizer import _stream
-        lib = _lib.load()
         P = int(self._xyz.shape[0])
         keep = torch.empty(P, dtype=torch.uint8, device=self._xyz.device)
         if counter_ptr is None:
             self._prune_counter = torch.zeros(1, dtype=torch.int32, device=self._xyz.device)
             counter_ptr = self._prune_counter.data_ptr()
         radii = self.max_radii2D if max_screen_size is not None else None
-        _lib.check(lib.mm3dgs_prune_mask(P, C.c_void_p(self._opacity.data_ptr()), C.c_void_p(self._scaling.data_ptr()),
-                                         C.c_void_p(radii.data_ptr()) if radii is not None else None, float(min_opacity), float(0.1 * extent),
-                                         float(max_screen_size if max_screen_size is not None else 0.0), C.c_void_p(keep.data_ptr()),
-                                         C.c_void_p(counter_ptr), _stream()))
+        _lib.check(_library().mm3dgs_prune_mask(P, _ptr(self._opacity), _ptr(self._scaling), _ptr(radii), float(min_opacity),
+                                                float(0.1 * extent), float(max_screen_size if max_screen_size is not None else 0.0),
+                                                _ptr(keep), C.c_void_p(counter_ptr), _stream()))
         return keep
 
     def compact_device(self, keep):
         """``prune_points(~keep)`` with the order-preserving compaction kernels: one plan (counts + scan), ONE 4-byte read-back
         for the new size, one scatter launch over every parameter, Adam moment and statistic (instead of a nonzero and ~24
         index_select launches).  Nothing to prune leaves every tensor in place, like ``prune_points``."""
-        import ctypes as C
-        from . import _lib
-        from .rasterizer import _stream
-        lib = _lib.load()
         P = int(keep.shape[0])
-        dev = keep.device
-        work = torch.empty(lib.mm3dgs_compact_work_bytes(P), dtype=torch.uint8, device=dev)
-        n_keep = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.mm3dgs_compact_plan(P, C.c_void_p(keep.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(n_keep.data_ptr()), _stream()))
-        n = int(n_keep.item())
+        lib, dev = _library(), keep.device
+        work, n = self._plan_rows(lib, keep)
         if n == P:
-            for group in self.optimizer.param_groups:
-                group["params"][0].grad = None
-            return
-        pairs = []                      # (old tensor, new tensor)
+            return self._drop_grads()      # nothing pruned: every tensor object stays, `generation` too, no table is built
+        table, pairs = (_lib.Mm3dgsCompactArray * 32)(), []      # (24 arrays at most: 7 parameters, 14 moments, 3 statistics)
 
-        def moved(t):
+        def moved(name, role, t):
             new = torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-            pairs.append((t.detach(), new))
+            width = int(t[0].numel())          # (P > n >= 0: there is a row 0)
+            if width:                          # a zero-width array (f_rest at SH degree 0) has no bytes to move and stays out
+                e = table[len(pairs)]
+                e.src, e.dst, e.width = t.data_ptr(), new.data_ptr(), width
+                pairs.append((t, new))
             return new
-        out = {}
-        self.generation += 1
-        for group in self.optimizer.param_groups:
-            old = group["params"][0]
-            state = self.optimizer.state.pop(old, None)
-            new = nn.Parameter(moved(old).requires_grad_(True))
-            if state is not None and "exp_avg" in state:
-                state["exp_avg"], state["exp_avg_sq"] = moved(state["exp_avg"]), moved(state["exp_avg_sq"])
-                self.optimizer.state[new] = state
-            group["params"][0] = new
-            out[group["name"]] = new
-        self._assign(out)
-        self.xyz_gradient_accum, self.denom, self.max_radii2D = moved(self.xyz_gradient_accum), moved(self.denom), moved(self.max_radii2D)
-        table = (_lib.Mm3dgsCompactArray * 32)()
-        k = 0
-        for old, new in pairs:
-            w = int(old[0].numel()) if old.shape[0] > 0 else 0
-            if w == 0:
-                continue
-            table[k].src, table[k].dst, table[k].width = old.data_ptr(), new.data_ptr(), w
-            k += 1
+        self._rebuild_groups(moved)
         if n == 0:
             return      # every Gaussian pruned: the empty tensors are in place (their data_ptr() is NULL, nothing to move)
-        _lib.check(lib.mm3dgs_compact_rows(P, C.c_void_p(keep.data_ptr()), C.c_void_p(work.data_ptr()), table, k, _stream()))
+        _lib.check(lib.mm3dgs_compact_rows(P, _ptr(keep), _ptr(work), table, len(pairs), _stream()))
         self._surgery_keepalive = (pairs, keep, work)      # the launch is asynchronous
+
+    @staticmethod
+    def _plan_rows(lib, keep):
+        """The plan of an order-preserving compaction by the uint8 mask `keep` (counts + scan into the work buffer the row kernels
+        read) and its ONE 4-byte read-back.  Returns (work buffer, number of rows kept)."""
+        work = torch.empty(lib.mm3dgs_compact_work_bytes(keep.shape[0]), dtype=torch.uint8, device=keep.device)
+        n_keep = torch.zeros(1, dtype=torch.int32, device=keep.device)
+        _lib.check(lib.mm3dgs_compact_plan(keep.shape[0], _ptr(keep), _ptr(work), _ptr(n_keep), _stream()))
+        return work, int(n_keep.item())
 
     def seed_device(self, color, depth, mask, pose, fx, fy, cx, cy):
         """``densification_postfix`` with the rows of the new Gaussians written by the seeding kernel: one Gaussian per pixel of
         ``mask`` (bool [H,W], raster order), initialised as slam/mapper.py:437-474,644-668 do.  Returns the number added."""
-        import ctypes as C
-        from . import _lib
-        from .rasterizer import _stream
-        lib = _lib.load()
-        dev = depth.device
+        lib, dev = _library(), depth.device
         H, W = depth.shape
         keep = mask.reshape(-1).to(torch.uint8).contiguous()
-        work = torch.empty(lib.mm3dgs_compact_work_bytes(H * W), dtype=torch.uint8, device=dev)
-        n_new = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.mm3dgs_compact_plan(H * W, C.c_void_p(keep.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(n_new.data_ptr()), _stream()))
-        n = int(n_new.item())           # (a keyframe event: the new size must be known to allocate)
+        work, n = self._plan_rows(lib, keep)           # (a keyframe event: the new size must be known to allocate)
         P = int(self._xyz.shape[0])
 
-        def grown(t, zero_tail):
-            new = (torch.zeros if zero_tail else torch.empty)((P + n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-            if P:
-                new[:P].copy_(t.detach())
+        def grown(name, role, t):
+            # parameters: the kernel writes the tail; moments: zero tail; statistics: zeros, not carried (as densification_postfix)
+            new = (torch.empty if role == "param" else torch.zeros)((P + n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+            if P and role != "stat":       # (an empty map: nothing is copied from the old tensors)
+                new[:P].copy_(t)
             return new
-        out = {}
-        self.generation += 1
-        for group in self.optimizer.param_groups:
-            old = group["params"][0]
-            state = self.optimizer.state.pop(old, None)
-            new = nn.Parameter(grown(old, False).requires_grad_(True))
-            if state is not None and "exp_avg" in state:
-                state["exp_avg"], state["exp_avg_sq"] = grown(state["exp_avg"], True), grown(state["exp_avg_sq"], True)
-                self.optimizer.state[new] = state
-            group["params"][0] = new
-            out[group["name"]] = new
-        self._assign(out)
+        # n == 0 still rebuilds (fresh parameter objects, generation bumped), as densification_postfix with empty extensions does
+        self._rebuild_groups(grown)
         so = _lib.Mm3dgsSeedOutputs()
-        so.xyz, so.f_dc, so.f_rest = self._xyz.data_ptr(), self._features_dc.data_ptr(), self._features_rest.data_ptr()
-        so.opacity, so.scaling, so.rotation, so.rgb = self._opacity.data_ptr(), self._scaling.data_ptr(), self._rotation.data_ptr(), self._rgb.data_ptr()
+        for name, attr in _ATTRS.items():
+            setattr(so, name, getattr(self, attr).data_ptr())
         color, depth, pose = color.contiguous().float(), depth.contiguous().float(), pose.detach().contiguous().float()
         if n:
-            _lib.check(lib.mm3dgs_seed_gaussians(H, W, C.c_void_p(color.data_ptr()), C.c_void_p(depth.data_ptr()), C.c_void_p(keep.data_ptr()),
-                                                 C.c_void_p(work.data_ptr()), C.c_void_p(pose.data_ptr()), float(fx), float(fy), float(cx), float(cy),
-                                                 P, C.byref(so), int(self._features_rest.shape[1]), _stream()))
-        self.xyz_gradient_accum = torch.zeros((P + n, 1), device=dev)
-        self.denom = torch.zeros((P + n, 1), device=dev)
-        self.max_radii2D = torch.zeros((P + n,), device=dev)
-        self._surgery_keepalive = (keep, work, color, depth, pose)
+            _lib.check(lib.mm3dgs_seed_gaussians(H, W, _ptr(color), _ptr(depth), _ptr(keep), _ptr(work), _ptr(pose), float(fx), float(fy),
+                                                 float(cx), float(cy), P, C.byref(so), int(self._features_rest.shape[1]), _stream()))
+        self._surgery_keepalive = (keep, work, color, depth, pose)      # the launch is asynchronous
         return n
 
     def densify_device(self, max_grad, extent, seed, N=2):
@@ -296,53 +290,39 @@ class GaussianModel:
         order-preserving ranks), ONE 12-byte read-back of {n_keep, n_clone, n_split} to size the new tensors, one scatter launch
         that writes every destination row of every parameter, Adam moment and statistic.  Returns the parent row of every new row
         (int32), or None when nothing was selected (tensors left in place, gradients dropped, statistics zeroed)."""
-        import ctypes as C
-        from . import _lib
-        from .rasterizer import _stream
-        lib = _lib.load()
+        lib, dev = _library(), self._xyz.device
         P = int(self._xyz.shape[0])
-        dev = self._xyz.device
         work = torch.empty(lib.mm3dgs_densify_work_bytes(P), dtype=torch.uint8, device=dev)
         counts = torch.empty(3, dtype=torch.int32, device=dev)
-        _lib.check(lib.mm3dgs_densify_plan(P, C.c_void_p(self.xyz_gradient_accum.data_ptr()), C.c_void_p(self.denom.data_ptr()),
-                                           C.c_void_p(self._scaling.data_ptr()), float(max_grad), float(self.percent_dense * extent),
-                                           C.c_void_p(work.data_ptr()), C.c_void_p(counts.data_ptr()), _stream()))
+        _lib.check(lib.mm3dgs_densify_plan(P, _ptr(self.xyz_gradient_accum), _ptr(self.denom), _ptr(self._scaling), float(max_grad),
+                                           float(self.percent_dense * extent), _ptr(work), _ptr(counts), _stream()))
         n_keep, n_clone, n_split = (int(v) for v in counts.tolist())
         if n_clone == 0 and n_split == 0:
             self._drop_grads_and_stats()
             return None
         n = n_keep + n_clone + N * n_split
+        # the kernel finds xyz / scaling / rotation by their position in Mm3dgsDensifyState.group
+        assert tuple(group["name"] for group in self.optimizer.param_groups) == _GROUPS
         st = _lib.Mm3dgsDensifyState()
-        keep = []
+        fields = dict(param=("src", "dst"), exp_avg=("m_src", "m_dst"), exp_avg_sq=("v_src", "v_dst"))
+        old = []
 
-        def fresh(t):
+        def fresh(name, role, t):
             new = torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-            keep.append(t)
+            old.append(t)
+            if role != "stat":
+                e = st.group[_GROUPS.index(name)]           # (the moment pointers of a group without moments stay NULL)
+                setattr(e, fields[role][0], t.data_ptr())
+                setattr(e, fields[role][1], new.data_ptr())
+                if role == "param":
+                    e.width = int(t[0].numel()) if P else 0
             return new
-        out = {}
-        self.generation += 1
-        for gi, group in enumerate(self.optimizer.param_groups):
-            assert group["name"] == _GROUPS[gi]       # (the kernel finds xyz / scaling / rotation by position)
-            old = group["params"][0].detach()
-            state = self.optimizer.state.pop(group["params"][0], None)
-            new = nn.Parameter(fresh(old).requires_grad_(True))
-            e = st.group[gi]
-            e.src, e.dst, e.width = old.data_ptr(), new.data_ptr(), int(old[0].numel()) if P else 0
-            if state is not None and "exp_avg" in state:
-                m, v = state["exp_avg"], state["exp_avg_sq"]
-                state["exp_avg"], state["exp_avg_sq"] = fresh(m), fresh(v)
-                e.m_src, e.m_dst, e.v_src, e.v_dst = m.data_ptr(), state["exp_avg"].data_ptr(), v.data_ptr(), state["exp_avg_sq"].data_ptr()
-                self.optimizer.state[new] = state
-            group["params"][0] = new
-            out[group["name"]] = new
-        self._assign(out)
-        self.xyz_gradient_accum, self.denom, self.max_radii2D = fresh(self.xyz_gradient_accum), fresh(self.denom), fresh(self.max_radii2D)
-        st.grad_accum, st.denom, st.max_radii2D = self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(), self.max_radii2D.data_ptr()
+        self._rebuild_groups(fresh)
+        st.grad_accum, st.denom, st.max_radii2D = (getattr(self, attr).data_ptr() for attr in _STATS)      # (destinations only)
         parent = torch.empty(n, dtype=torch.int32, device=dev)
         st.parent = parent.data_ptr()
-        _lib.check(lib.mm3dgs_densify_rows(P, C.c_void_p(work.data_ptr()), n_keep, n_clone, n_split, N, int(seed) & 0xFFFFFFFF, C.byref(st),
-                                           _stream()))
-        self._surgery_keepalive = (keep, work)      # the launch is asynchronous
+        _lib.check(lib.mm3dgs_densify_rows(P, _ptr(work), n_keep, n_clone, n_split, N, int(seed) & 0xFFFFFFFF, C.byref(st), _stream()))
+        self._surgery_keepalive = (old, work)      # the launch is asynchronous
         return parent
 
     def prune_points(self, mask):
@@ -351,26 +331,20 @@ class GaussianModel:
         # object and Adam moment in place -- the same values the rebuild would produce
         idx = torch.nonzero(~mask, as_tuple=False).squeeze(1)
         if idx.numel() == mask.numel():
-            # the rebuild would hand the optimiser fresh parameters WITHOUT gradients, which is what makes the reference's
-            # optimizer.step() of a pruning iteration a no-op: keep that
-            for group in self.optimizer.param_groups:
-                group["params"][0].grad = None
-            return
-        self._assign(self._rebuild_groups(lambda n, p: p.index_select(0, idx), lambda n, s: s.index_select(0, idx)))
-        self.xyz_gradient_accum = self.xyz_gradient_accum.index_select(0, idx)
-        self.denom = self.denom.index_select(0, idx)
-        self.max_radii2D = self.max_radii2D.index_select(0, idx)
+            return self._drop_grads()
+        self._rebuild_groups(lambda name, role, t: t.index_select(0, idx))
 
     def densification_postfix(self, new_xyz, new_features_dc, new_features_rest, new_opacities, new_scaling,
                               new_rotation, new_rgb):
         ext = dict(xyz=new_xyz, f_dc=new_features_dc, f_rest=new_features_rest, opacity=new_opacities,
                    scaling=new_scaling, rotation=new_rotation, rgb=new_rgb)
-        self._assign(self._rebuild_groups(lambda n, p: torch.cat((p, ext[n].to(p)), 0),
-                                          lambda n, s: torch.cat((s, torch.zeros_like(ext[n]).to(s)), 0)))
-        n, dev = self._xyz.shape[0], self.cfg["device"]
-        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
-        self.denom = torch.zeros((n, 1), device=dev)
-        self.max_radii2D = torch.zeros((n,), device=dev)
+        n, dev = self._xyz.shape[0] + new_xyz.shape[0], self.cfg["device"]
+
+        def extended(name, role, t):
+            if role == "stat":          # zeros at the new length, not carried
+                return torch.zeros((n,) + tuple(t.shape[1:]), device=dev)
+            return torch.cat((t, (ext[name] if role == "param" else torch.zeros_like(ext[name])).to(t)), 0)
+        self._rebuild_groups(extended)
 
     def prune(self, min_opacity, extent, max_screen_size=None, lazy_mask=False):
         """Returns the mask of the pruned Gaussians; lazy_mask: a zero-argument callable that produces it (the native loop only needs it
@@ -392,9 +366,8 @@ class GaussianModel:
     def _drop_grads_and_stats(self):
         """densification_postfix with nothing to add: the tensors stay in place (same values as the rebuild), the gradients go (the
         rebuild would hand the optimiser fresh parameters without them) and the statistics are zeroed, as the postfix always does."""
-        for group in self.optimizer.param_groups:
-            group["params"][0].grad = None
-        torch._foreach_zero_([self.xyz_gradient_accum, self.denom, self.max_radii2D])
+        self._drop_grads()
+        torch._foreach_zero_([getattr(self, attr) for attr in _STATS])
 
     @torch.no_grad()
     def densify_and_clone(self, grads, grad_threshold, scene_extent):
@@ -471,28 +444,20 @@ class GaussianModel:
         return mask[~prune_mask]
 
     def replace_tensor_to_optimizer(self, tensor, name):
-        """The group `name` gets `tensor` as a fresh parameter with zeroed Adam moments (:360-378)."""
-        out = {}
-        self.generation += 1
-        for group in self.optimizer.param_groups:
-            if group["name"] != name:
-                continue
-            state = self.optimizer.state.pop(group["params"][0], None)
-            new = nn.Parameter(tensor.requires_grad_(True))
-            if state is not None:
-                state["exp_avg"] = torch.zeros_like(tensor)
-                state["exp_avg_sq"] = torch.zeros_like(tensor)
-                self.optimizer.state[new] = state
-            group["params"][0] = new
-            out[name] = new
-        return out
+        """The group `name` gets `tensor` as a fresh parameter with zeroed Adam moments (:360-378): the walk restricted to one group,
+        the rows and with them the statistics staying as they are.  Returns {name: the new parameter}."""
+        def replaced(_, role, t):
+            if role == "stat":
+                return t
+            return tensor if role == "param" else torch.zeros_like(tensor)
+        return self._rebuild_groups(replaced, only=name)
 
     @torch.no_grad()
     def reset_opacity(self):
         """opacity = inverse_sigmoid(min(sigmoid(opacity), 0.01)), moments of the opacity group zeroed (:259-264).  No loop calls it
         (the reference has no call site)."""
         op = self.get_opacity.detach()
-        self._opacity = self.replace_tensor_to_optimizer(inverse_sigmoid(torch.min(op, torch.ones_like(op) * 0.01)), "opacity")["opacity"]
+        self.replace_tensor_to_optimizer(inverse_sigmoid(torch.min(op, torch.ones_like(op) * 0.01)), "opacity")
 
     def add_densification_stats(self, viewspace_point_tensor, update_filter):
         self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1,

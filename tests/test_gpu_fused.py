@@ -1148,6 +1148,7 @@ def test_device_prune_compaction_matches_the_torch_surgery():
     csrc/compact.hip) against the torch path (slam/gaussian_model.py:380-451,574-588 mirrored in prune_points): same rows, same order."""
     import copy
     from mm3dgs_slam_amd.gaussian_model import GaussianModel
+    from tests import densify_util as du
     cfg, g, R, pose, color, depth = _setup(P=5000, H=120, W=160, seed=15)
     gen = torch.Generator().manual_seed(4)
     with torch.no_grad():
@@ -1160,25 +1161,27 @@ def test_device_prune_compaction_matches_the_torch_surgery():
         p.grad = torch.randn_like(p)
     g.optimizer.step()
     g.xyz_gradient_accum = torch.rand(5000, 1, device=DEV); g.denom = torch.rand(5000, 1, device=DEV)
-    ref = copy.deepcopy(g)
-    extent = 1.3
-    monkey_native = g._native
-    ref._native = lambda: False                     # force the torch mirror on the copy
-    mask_ref = ref.prune(0.005, extent, 100.0)
-    mask_dev = g.prune(0.005, extent, 100.0)
-    torch.cuda.synchronize()
-    assert 100 < int(mask_ref.sum()) < 4900
-    assert torch.equal(mask_ref, mask_dev)
-    for name in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation", "_rgb", "xyz_gradient_accum", "denom", "max_radii2D"):
-        assert torch.equal(getattr(g, name).detach(), getattr(ref, name).detach()), name
-    for ga, gb in zip(g.optimizer.param_groups, ref.optimizer.param_groups):
-        sa, sb = g.optimizer.state[ga["params"][0]], ref.optimizer.state[gb["params"][0]]
-        assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), ga["name"]
-    # nothing to prune: every tensor object stays, gradients are dropped (the reference's no-op optimiser step)
-    before = g._xyz
-    g._xyz.grad = torch.zeros_like(g._xyz)
-    g.prune(0.0, 1e9, None)
-    assert g._xyz is before and g._xyz.grad is None
+    # second input: fixture G12 (SH degree 3: f_rest has 15 rows of its own to move; the reference's moments), its own thresholds
+    f = du.load()
+    for g, min_opacity, extent in ((g, 0.005, 1.3), (du.model_from_fixture(f, DEV), float(f["min_opacity"]), float(f["extent"]))):
+        P = int(g._xyz.shape[0])
+        ref = copy.deepcopy(g)
+        ref._native = lambda: False                     # force the torch mirror on the copy
+        mask_ref = ref.prune(min_opacity, extent, 100.0)
+        mask_dev = g.prune(min_opacity, extent, 100.0)
+        torch.cuda.synchronize()
+        assert 100 < int(mask_ref.sum()) < P - 100
+        assert torch.equal(mask_ref, mask_dev)
+        for name in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation", "_rgb", "xyz_gradient_accum", "denom", "max_radii2D"):
+            assert torch.equal(getattr(g, name).detach(), getattr(ref, name).detach()), name
+        for ga, gb in zip(g.optimizer.param_groups, ref.optimizer.param_groups):
+            sa, sb = g.optimizer.state[ga["params"][0]], ref.optimizer.state[gb["params"][0]]
+            assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), ga["name"]
+        # nothing to prune: every tensor object stays, gradients are dropped (the reference's no-op optimiser step)
+        before = g._xyz
+        g._xyz.grad = torch.zeros_like(g._xyz)
+        g.prune(0.0, 1e9, None)
+        assert g._xyz is before and g._xyz.grad is None
 
 
 def test_device_seeding_matches_the_reference_fixture_g7_and_the_torch_mirror():
