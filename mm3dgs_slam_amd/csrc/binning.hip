@@ -75,35 +75,10 @@ void launch_scan_tiles(int T, int P, GeomView g, ImageView iv, hipStream_t s, in
 //   sweep 1 counts the workgroup's overlaps per tile in LDS; one returning global atomic per *touched tile* reserves
 //   a contiguous span in that tile's bin; sweep 2 hands out slots inside the spans with returning LDS atomics.
 // Spatially coherent Gaussian order (SLAM maps) turns ~2.3 global atomics per Gaussian into a few per workgroup.
-// A Gaussian whose rectangle covers more than 32 tiles is spread over the whole wave (rectangle broadcast with
-// readlane) so that one huge splat does not serialise a wave for thousands of iterations.
+// Both sweeps are sweep_rect (mm3dgs_common.h), which spreads a rectangle of more than 32 tiles over the whole wave.
 // (Measured and rejected in round 6: the pair's Gaussian-major index in the key's low word and payload[pair] = id | block mask written HERE, so that the
 //  sort's emission reads one word per sorted entry instead of gathering five arrays by id: the per-pair mask arithmetic runs at a few lanes per wave in
 //  this sweep -- scatter 105 -> 209 us at 1080p / 3 M Gaussians for 406 -> 340 us of sort.)
-template <bool WRITE>
-__device__ __forceinline__ void sweep_rect(uint32_t* cnt, int gx, int minx, int miny, int w, int area, unsigned long long key,
-                                           unsigned long long* keys, uint32_t N_cap, int lane) {
-  unsigned long long big = __ballot(area > 32);
-  if (area > 0 && area <= 32) {
-    for (int k = 0; k < area; k++) {
-      uint32_t slot = atomicAdd(&cnt[(miny + k / w) * gx + minx + k % w], 1u);
-      if (WRITE && slot < N_cap) keys[slot] = key;
-    }
-  }
-  while (big) {
-    const int src = __ffsll((long long)big) - 1;
-    big &= big - 1;
-    const int sminx = __builtin_amdgcn_readlane(minx, src), sminy = __builtin_amdgcn_readlane(miny, src);
-    const int sw = __builtin_amdgcn_readlane(w, src), sarea = __builtin_amdgcn_readlane(area, src);
-    const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, src), khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), src);
-    const unsigned long long skey = ((unsigned long long)khi << 32) | klo;
-    for (int k = lane; k < sarea; k += 64) {
-      uint32_t slot = atomicAdd(&cnt[(sminy + k / sw) * gx + sminx + k % sw], 1u);
-      if (WRITE && slot < N_cap) keys[slot] = skey;
-    }
-  }
-}
-
 __global__ void __launch_bounds__(256)
 scatter_keys_kernel(int P, int gx, int T, GeomView g, ImageView iv, BinView b, uint32_t N_cap, int lds_tiles) {
   extern __shared__ uint32_t hist[];

@@ -18,6 +18,64 @@
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
 __device__ __forceinline__ float4 ld4u(const float* p) { const f4u v = *(const f4u*)p; return make_float4(v.x, v.y, v.z, v.w); }
+// Sum of a Gaussian's per-tile gradient records (the backward compositor's per-tile combine wrote one record per (tile, splat) pair, the
+// pairs of a Gaussian -- its tile rectangle, row-major -- contiguous from record `first`): the first NF floats of each of its `area` records,
+// `stride` floats apart (NF: 7 tracking, 10 mapping, 12 generic), into acc0 | acc1 | acc2.  Every lane of the wave must call it.
+// Rectangles of up to 16 tiles -- practically every splat of a SLAM map -- are summed by their own lane, four records in flight, in
+// ascending pair order, as whole float4s: what the last one picks up past NF floats (or past a record shorter than NF) belongs to the
+// next record, and the caller drops it.  A bigger rectangle is read by the whole wave (lane-strided, then a fixed-order DPP reduction),
+// float by float and never past a record's end: the last record ends the buffer.  Deterministic either way.
+// skip4: bit k set = own pair k (k < 4) was listed nowhere by the binning kernel and its record never written.
+template <int NF>
+__device__ __forceinline__ void gather_records(int area, uint32_t first, const float* __restrict__ dtile, int stride, float4& acc0, float4& acc1,
+                                               float4& acc2, uint32_t skip4) {
+  const int lane = threadIdx.x & 63;
+  const bool big = area > 16;
+  const int n_own = big ? 0 : area;
+  for (int k0 = 0; __ballot(k0 < n_own) != 0ull; k0 += 4) {
+    float4 a[4], b4[4], c4[4];
+    bool on[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      on[u] = k0 + u < n_own && !((skip4 >> (k0 + u)) & 1u);
+      const float* r = dtile + (on[u] ? (size_t)(first + (uint32_t)(k0 + u)) * stride : (size_t)0);
+      a[u] = ld4u(r); b4[u] = ld4u(r + 4);
+      c4[u] = NF > 8 ? ld4u(r + 8) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      acc0.x += on[u] ? a[u].x : 0.f; acc0.y += on[u] ? a[u].y : 0.f; acc0.z += on[u] ? a[u].z : 0.f; acc0.w += on[u] ? a[u].w : 0.f;
+      acc1.x += on[u] ? b4[u].x : 0.f; acc1.y += on[u] ? b4[u].y : 0.f; acc1.z += on[u] ? b4[u].z : 0.f; acc1.w += on[u] ? b4[u].w : 0.f;
+      if (NF > 8) acc2.x += on[u] ? c4[u].x : 0.f;
+      if (NF > 9) acc2.y += on[u] ? c4[u].y : 0.f;
+      if (NF > 10) acc2.z += on[u] ? c4[u].z : 0.f;
+      if (NF > 11) acc2.w += on[u] ? c4[u].w : 0.f;
+    }
+  }
+  for (unsigned long long bigs = __ballot(big); bigs; bigs &= bigs - 1ull) {
+    const int src = __ffsll((long long)bigs) - 1;
+    const int sarea = __builtin_amdgcn_readlane(area, src);
+    const uint32_t sfirst = (uint32_t)__builtin_amdgcn_readlane((int)first, src);
+    const uint32_t sskip = (uint32_t)__builtin_amdgcn_readlane((int)skip4, src);
+    float v[12];
+#pragma unroll
+    for (int f = 0; f < 12; f++) v[f] = 0.f;
+    for (int k = lane; k < sarea; k += 64) {
+      if (k < 4 && ((sskip >> k) & 1u)) continue;
+      const float* r = dtile + (size_t)(sfirst + (uint32_t)k) * stride;
+#pragma unroll
+      for (int f = 0; f < NF; f++) v[f] += f < stride ? r[f] : 0.f;
+    }
+#pragma unroll
+    for (int f = 0; f < NF; f++) v[f] = wave_sum(v[f]);
+    if (lane == src) {
+      acc0 = make_float4(v[0], v[1], v[2], v[3]);
+      acc1 = make_float4(v[4], v[5], v[6], v[7]);
+      if (NF > 8) acc2 = make_float4(v[8], v[9], v[10], v[11]);
+    }
+  }
+}
+
 // zero the NV floats of a record
 template <int NV>
 __device__ __forceinline__ void zero_record(float* r) {

@@ -69,15 +69,7 @@ __device__ __forceinline__ void slam_cov3d_vals(const float q[4], const float ls
   sm[0] = mod * expf(ls[0]);
   sm[1] = isotropic ? sm[0] : mod * expf(ls[1]);
   sm[2] = isotropic ? sm[0] : mod * expf(ls[2]);
-  float Mx[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int k = 0; k < 3; k++) Mx[i][k] = R[i][k] * sm[k];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) S3[i][j] = Mx[i][0] * Mx[j][0] + Mx[i][1] * Mx[j][1] + Mx[i][2] * Mx[j][2];
+  cov3d_from_scaled_R(R, sm, S3);
 }
 
 __device__ __forceinline__ void slam_cov3d(const SlamIn& in, int idx, float mod, float S3[3][3], float R[3][3], float sm[3],
@@ -202,18 +194,9 @@ __device__ __forceinline__ Projected slam_project_vals(const CamDev& cam, bool l
     float py = ((h.hy * h.pw + 1.f) * cam.H - 1.f) * 0.5f;
     if (det != 0.f && isfinite(px) && isfinite(py)) {
       float dinv = 1.f / det;
-      float mid = 0.5f * (e.a + e.c);
-      float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
-      float rf = ceilf(3.f * sqrtf(lam));
-      float gxf = (float)cam.gx + 1.f, gyf = (float)cam.gy + 1.f;
-      int minx = min(cam.gx, max(0, (int)fminf(fmaxf((px - rf) / TILE, -1.f), gxf)));
-      int miny = min(cam.gy, max(0, (int)fminf(fmaxf((py - rf) / TILE, -1.f), gyf)));
-      int maxx = min(cam.gx, max(0, (int)fminf(fmaxf((px + rf + (TILE - 1)) / TILE, -1.f), gxf)));
-      int maxy = min(cam.gy, max(0, (int)fminf(fmaxf((py + rf + (TILE - 1)) / TILE, -1.f), gyf)));
-      if ((maxx - minx) * (maxy - miny) > 0) {
-        o.rad = (int32_t)fminf(rf, 2.0e9f);
-        o.r0 = (uint32_t)minx | ((uint32_t)miny << 16);
-        o.r1 = (uint32_t)maxx | ((uint32_t)maxy << 16);
+      const TileRect tr = splat_tile_rect(cam, px, py, e.a, e.c, det);
+      if (tr.hit) {
+        o.rad = tr.rad; o.r0 = tr.r0; o.r1 = tr.r1;
         const float* fd = fd_raw;
         float c0 = SH_C0F * fd[0] + 0.5f, c1 = SH_C0F * fd[1] + 0.5f, c2 = SH_C0F * fd[2] + 0.5f;
         if constexpr (SH) {
@@ -295,42 +278,7 @@ slam_preprocess_fwd_kernel(CamDev cam, int P, SlamIn in, int32_t* __restrict__ r
     if (live && seen && rad > 0) seen[idx] += 1u;
     return;
   }
-  {
-    const int minx = r0 & 0xffff, miny = r0 >> 16, maxx = r1 & 0xffff, maxy = r1 >> 16;
-    const int w = maxx - minx, area = w * (maxy - miny);
-    {
-      __shared__ uint32_t wtot[FB / 64];
-      const int ln = threadIdx.x & 63, wvi = threadIdx.x >> 6;
-      // (one scan only: block records are addressed by list position in every mode)
-      const uint32_t x = wave_scan_incl((uint32_t)area);   // tiles touched
-      if (ln == 63) wtot[wvi] = x;
-      __syncthreads();
-      uint32_t pre = 0;
-      for (int q = 0; q < wvi; q++) pre += wtot[q];
-      if (live) g.tileoff[idx] = pre + x - (uint32_t)area;
-      if (threadIdx.x == FB - 1) g.block_tiles[blockIdx.x] = pre + x;
-    }
-    uint32_t* cnt = lds_tiles ? hist : iv.tile_count;
-    const int lane = threadIdx.x & 63;
-    unsigned long long big = __ballot(area > 32);
-    if (area > 0 && area <= 32)
-      for (int y = miny; y < maxy; y++)
-        for (int x = minx; x < maxx; x++) atomicAdd(&cnt[y * cam.gx + x], 1u);
-    while (big) {
-      const int src = __ffsll((long long)big) - 1;
-      big &= big - 1;
-      const int sminx = __builtin_amdgcn_readlane(minx, src), sminy = __builtin_amdgcn_readlane(miny, src);
-      const int sw = __builtin_amdgcn_readlane(w, src), sarea = __builtin_amdgcn_readlane(area, src);
-      for (int k = lane; k < sarea; k += 64) atomicAdd(&cnt[(sminy + k / sw) * cam.gx + sminx + k % sw], 1u);
-    }
-  }
-  if (lds_tiles) {
-    __syncthreads();
-    for (int t = threadIdx.x; t < T; t += FB) {
-      uint32_t c = hist[t];
-      if (c) atomicAdd(&iv.tile_count[t], c);
-    }
-  }
+  count_rect_tiles<FB>(cam.gx, T, lds_tiles, hist, live, idx, r0, r1, g, iv);
 }
 
 // runtime (sh_deg, sh_dir) -> instantiation of a projection kernel family K<SH, SHDIR>
@@ -515,58 +463,6 @@ void launch_slam_project_bin(const CamDev& cam, int P, const SlamIn& in, int32_t
                      slot_bits, want_poserec && in.sh_deg <= 0 ? 1 : 0);
 }
 
-// Sum of a Gaussian's per-tile gradient records (composite.hip's per-tile combine: one record per (tile, splat) pair, the pairs of a
-// Gaussian contiguous).  Every lane of the wave must call it.  Small rectangles (<= 16 tiles: practically every splat of a SLAM map)
-// are summed by their own lane, four records in flight, in ascending pair order; a bigger one is read by the whole wave (lane-strided,
-// then a fixed-order DPP reduction) -- deterministic either way.  Mapping records: 10 floats, tracking: 7 (composite_common.h).
-template <bool TRACK>
-__device__ __forceinline__ void gather_tile_records(int area, uint32_t first, const float* __restrict__ dtile, float4& acc0, float4& acc1, float4& acc2,
-                                                    uint32_t skip4) {
-  constexpr int RECF = TRACK ? REC_TRACK_F : REC_MAP_F;
-  const int lane = threadIdx.x & 63;
-  const bool big = area > 16;
-  const int n_own = big ? 0 : area;
-  for (int k0 = 0; __ballot(k0 < n_own) != 0ull; k0 += 4) {
-    float4 a[4], b4[4], c4[4];
-    bool on[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      on[u] = k0 + u < n_own && !((skip4 >> (k0 + u)) & 1u);      // (skip4: pairs the binning kernel listed nowhere -- their records were never written)
-      const float* r = dtile + (on[u] ? (size_t)(first + (uint32_t)(k0 + u)) * RECF : (size_t)0);
-      a[u] = ld4u(r); b4[u] = ld4u(r + 4);
-      c4[u] = TRACK ? make_float4(0.f, 0.f, 0.f, 0.f) : ld4u(r + 8);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      acc0.x += on[u] ? a[u].x : 0.f; acc0.y += on[u] ? a[u].y : 0.f; acc0.z += on[u] ? a[u].z : 0.f; acc0.w += on[u] ? a[u].w : 0.f;
-      acc1.x += on[u] ? b4[u].x : 0.f; acc1.y += on[u] ? b4[u].y : 0.f; acc1.z += on[u] ? b4[u].z : 0.f; acc1.w += on[u] ? b4[u].w : 0.f;
-      if (!TRACK) { acc2.x += on[u] ? c4[u].x : 0.f; acc2.y += on[u] ? c4[u].y : 0.f; }
-    }
-  }
-  for (unsigned long long bigs = __ballot(big); bigs; bigs &= bigs - 1ull) {
-    const int src = __ffsll((long long)bigs) - 1;
-    const int sarea = __builtin_amdgcn_readlane(area, src);
-    const uint32_t sfirst = (uint32_t)__builtin_amdgcn_readlane((int)first, src);
-    const uint32_t sskip = (uint32_t)__builtin_amdgcn_readlane((int)skip4, src);
-    float v[RECF];
-#pragma unroll
-    for (int f = 0; f < RECF; f++) v[f] = 0.f;
-    for (int k = lane; k < sarea; k += 64) {
-      if (k < 4 && ((sskip >> k) & 1u)) continue;        // (an empty own pair of a 17..32-tile splat: its record was never written)
-      const float* r = dtile + (size_t)(sfirst + (uint32_t)k) * RECF;
-#pragma unroll
-      for (int f = 0; f < RECF; f++) v[f] += r[f];
-    }
-#pragma unroll
-    for (int f = 0; f < RECF; f++) v[f] = wave_sum(v[f]);
-    if (lane == src) {
-      acc0 = make_float4(v[0], v[1], v[2], v[3]);
-      acc1 = make_float4(v[4], v[5], v[6], TRACK ? 0.f : v[RECF > 7 ? 7 : 0]);
-      if (!TRACK) acc2 = make_float4(v[RECF > 8 ? 8 : 0], v[RECF > 9 ? 9 : 0], 0.f, 0.f);
-    }
-  }
-}
-
 // One Gaussian's row of N (1, 3 or 4) floats of an Adam group, stepped: ONE store per array -- parameters, first and second moments -- of the
 // row's width (dword / dwordx3 / dwordx4; rows are 4-byte aligned, which is all a global store needs).  A [P, 3] array's last row ends
 // the allocation: its store is 12 bytes, never 16.  Element by element with the three arrays interleaved -- the arrays may alias as far as
@@ -675,7 +571,8 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
       const bool fits = DIRECT ? (toff + (uint32_t)area <= cam.trec_cap) : true;
       if (!fits || (size_t)first + (size_t)area > (size_t)N_cap) area = 0;      // beyond the capacity (flagged by the forward): nothing was written
     }
-    gather_tile_records<TRACK>(area, first, dsub + (size_t)NLIST * (size_t)N_cap * SPLAT_F, acc0, acc1, acc2, DIRECT ? (clb >> 4) : 0u);
+    constexpr int RECF = TRACK ? REC_TRACK_F : REC_MAP_F;      // (composite_common.h; the records are packed: stride = size)
+    gather_records<RECF>(area, first, dsub + (size_t)NLIST * (size_t)N_cap * SPLAT_F, RECF, acc0, acc1, acc2, DIRECT ? (clb >> 4) : 0u);
     cl_bits = clb;
   }
   const bool skip = ovf_word != 0u;
@@ -718,19 +615,7 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
       }
       float GA[2][3], dS[3][3], dA[2][3];
       cov2d_grad_to_dA(e, S3, conic_grad_to_cov2d(e.a, e.b, e.c, gA, gB, gC), GA, dA);
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) dS[i][j] = e.A[0][i] * GA[0][j] + e.A[1][i] * GA[1][j];
-      // dSigma3 is symmetric in exact arithmetic; in float32 the two triangles round differently, and their difference IS the rotation
-      // gradient of an isotropic Gaussian with identity rotation (every freshly seeded one, slam/mapper.py:644-668): rounding noise that
-      // Adam(eps=1e-15) turns into full +-lr steps of the quaternion.  torch's autograd of Sigma = L L^T forms (dSigma + dSigma^T) L and
-      // is exactly zero there; so is this once the triangles are averaged (found with the G9 runs of the reference's own classes:
-      // pose error to the reference 1.4e-5 -> 8e-8 after the first tracked frame).
-      {
-        const float s01 = 0.5f * (dS[0][1] + dS[1][0]), s02 = 0.5f * (dS[0][2] + dS[2][0]), s12 = 0.5f * (dS[1][2] + dS[2][1]);
-        dS[0][1] = s01; dS[1][0] = s01; dS[0][2] = s02; dS[2][0] = s02; dS[1][2] = s12; dS[2][1] = s12;
-      }
+      cov2d_grad_to_dcov3d(e.A, GA, dS);
       // transform mode: view = identity, dJ[r][k] = dA[r][k].  World mode: A = J R  ->  dJ = dA R^T, and the pose's rotation receives
       // dR[k][i] += sum_r J[r][k] dA[r][i]  (J = [[J00, 0, J02], [0, J11, J12]]) -- the "-w-pose" gradient through the view matrix
       float dJ00 = dA[0][0], dJ02 = dA[0][2], dJ11 = dA[1][1], dJ12 = dA[1][2];
@@ -749,13 +634,8 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
       }
       float dm[3];
       dJ_to_dmean(cam, e, dJ00, dJ02, dJ11, dJ12, dm);
-      const HomPoint h = hom_project(PV, p);
-      const float hx = h.hx, hy = h.hy, pw = h.pw;
-      const float gnx = gpx * 0.5f * cam.W, gny = gpy * 0.5f * cam.H;
-      gnorm = sqrtf(gnx * gnx + gny * gny);
-      const float dhx = gnx * pw, dhy = gny * pw, dhw = -(gnx * hx + gny * hy) * pw * pw;
-#pragma unroll
-      for (int i = 0; i < 3; i++) dm[i] += PV[i * 4 + 0] * dhx + PV[i * 4 + 1] * dhy + PV[i * 4 + 3] * dhw;
+      const ScreenGrad sg = pixel_grad_to_dmean(cam, PV, hom_project(PV, p), gpx, gpy, dm);
+      gnorm = sqrtf(sg.gnx * sg.gnx + sg.gny * sg.gny);
       if (!world) dm[2] += dz_tot;          // transform mode: the depth bundle's z IS the camera-space z
       if constexpr (SH) {
         // colour = clamp(sum_k b_k(dir) sh_k + 0.5), dir = p / |p|: the basis values weight the coefficient gradients, the basis' direction
@@ -824,17 +704,8 @@ __device__ __forceinline__ void slam_bwd_body(const CamDev& cam, int P, const Sl
         dfd[2] = (cl & 4) ? 0.f : SH_C0F * dc2;
         const float o = 1.f / (1.f + expf(-op_raw));
         dlogit = M0 * (1.f - o);   // sum G dL/dalpha = M0 / o, times d sigmoid = o (1 - o)
-        float dM[3][3], dR[3][3], ds[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-          for (int k = 0; k < 3; k++) dM[i][k] = 2.f * (dS[i][0] * R[0][k] + dS[i][1] * R[1][k] + dS[i][2] * R[2][k]) * sm[k];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          ds[k] = cam.scale_modifier * (dM[0][k] * R[0][k] + dM[1][k] * R[1][k] + dM[2][k] * R[2][k]);
-#pragma unroll
-          for (int i = 0; i < 3; i++) dR[i][k] = dM[i][k] * sm[k];
-        }
+        float dR[3][3], ds[3];
+        dcov3d_to_scale_rot(dS, R, sm, cam.scale_modifier, ds, dR);
         // scales = exp(log-scales): d/dlog = ds * s (sm already carries scale_modifier, ds carries the other factor)
         const float inv_mod = 1.f / cam.scale_modifier;
         if (in.isotropic) {

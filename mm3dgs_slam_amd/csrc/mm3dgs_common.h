@@ -349,4 +349,65 @@ __device__ __forceinline__ float wave_sum(float v) {
   v = wave_sum_to_lane63(v);
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+
+// ---- tile rectangles, one lane per Gaussian ----------------------------------------------------------------------
+// One returning atomic on cnt[tile] per tile of this lane's rectangle (minx, miny, width w, `area` tiles; area 0: none); WRITE: the slot it
+// returns takes the lane's key.  Every lane of the wave must call it: a rectangle of more than 32 tiles is spread over the whole wave
+// (broadcast with readlane) so that one huge splat does not serialise a wave for thousands of iterations.
+template <bool WRITE>
+__device__ __forceinline__ void sweep_rect(uint32_t* cnt, int gx, int minx, int miny, int w, int area, unsigned long long key,
+                                           unsigned long long* keys, uint32_t N_cap, int lane) {
+  unsigned long long big = __ballot(area > 32);
+  if (area > 0 && area <= 32) {
+    int x = minx, y = miny;      // (row-major with running coordinates: no division per tile)
+    for (int k = 0; k < area; k++) {
+      uint32_t slot = atomicAdd(&cnt[y * gx + x], 1u);
+      if (WRITE && slot < N_cap) keys[slot] = key;
+      if (++x == minx + w) { x = minx; y++; }
+    }
+  }
+  while (big) {
+    const int src = __ffsll((long long)big) - 1;
+    big &= big - 1;
+    const int sminx = __builtin_amdgcn_readlane(minx, src), sminy = __builtin_amdgcn_readlane(miny, src);
+    const int sw = __builtin_amdgcn_readlane(w, src), sarea = __builtin_amdgcn_readlane(area, src);
+    const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, src), khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), src);
+    const unsigned long long skey = ((unsigned long long)khi << 32) | klo;
+    for (int k = lane; k < sarea; k += 64) {
+      uint32_t slot = atomicAdd(&cnt[(sminy + k / sw) * gx + sminx + k % sw], 1u);
+      if (WRITE && slot < N_cap) keys[slot] = skey;
+    }
+  }
+}
+
+// Tile counting of a projection workgroup of BLOCK lanes (every lane calls it with its Gaussian's rectangle r0 / r1, zero when culled or
+// past the map's end): the workgroup-local exclusive scan of tiles touched -> g.tileoff (this Gaussian's first pair index) and
+// g.block_tiles, then the overlaps per tile into iv.tile_count -- through the workgroup's LDS histogram `hist` (lds_tiles = T, cleared by
+// the caller behind a barrier) or, on a grid too big for it (lds_tiles = 0), with global atomics.
+template <int BLOCK>
+__device__ __forceinline__ void count_rect_tiles(int gx, int T, int lds_tiles, uint32_t* hist, bool live, int idx, uint32_t r0, uint32_t r1,
+                                                 const GeomView& g, const ImageView& iv) {
+  const int minx = r0 & 0xffff, miny = r0 >> 16, maxx = r1 & 0xffff, maxy = r1 >> 16;
+  const int w = maxx - minx, area = w * (maxy - miny);
+  const int lane = threadIdx.x & 63, wvi = threadIdx.x >> 6;
+  {
+    __shared__ uint32_t wtot[BLOCK / 64];
+    // (one scan only: block records are addressed by list position in every mode)
+    const uint32_t x = wave_scan_incl((uint32_t)area);   // tiles touched
+    if (lane == 63) wtot[wvi] = x;
+    __syncthreads();
+    uint32_t pre = 0;
+    for (int q = 0; q < wvi; q++) pre += wtot[q];
+    if (live) g.tileoff[idx] = pre + x - (uint32_t)area;
+    if (threadIdx.x == BLOCK - 1) g.block_tiles[blockIdx.x] = pre + x;
+  }
+  sweep_rect<false>(lds_tiles ? hist : iv.tile_count, gx, minx, miny, w, area, 0ull, nullptr, 0u, lane);
+  if (lds_tiles) {
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += BLOCK) {
+      uint32_t c = hist[t];
+      if (c) atomicAdd(&iv.tile_count[t], c);
+    }
+  }
+}
 #endif

@@ -80,6 +80,19 @@ __device__ __forceinline__ void quat_to_R(const float* q, float R[3][3]) {
   R[2][0] = 2.f * (x * z - r * y); R[2][1] = 2.f * (y * z + r * x); R[2][2] = 1.f - 2.f * (x * x + y * y);
 }
 
+// Sigma3 = Mx Mx^T with Mx = R diag(sm)
+__device__ __forceinline__ void cov3d_from_scaled_R(const float R[3][3], const float sm[3], float S3[3][3]) {
+  float Mx[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) Mx[i][k] = R[i][k] * sm[k];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) S3[i][j] = Mx[i][0] * Mx[j][0] + Mx[i][1] * Mx[j][1] + Mx[i][2] * Mx[j][2];
+}
+
 // Sigma3 (symmetric, full 3x3) from scale/rotation or from the 6 upper-triangular values.
 __device__ __forceinline__ void load_cov3d(int idx, const float* scales, const float* rots, const float* cov3d,
                                            float mod, float S3[3][3], float R[3][3], float sm[3]) {
@@ -92,15 +105,7 @@ __device__ __forceinline__ void load_cov3d(int idx, const float* scales, const f
     float q[4] = {rots[(size_t)idx * 4], rots[(size_t)idx * 4 + 1], rots[(size_t)idx * 4 + 2], rots[(size_t)idx * 4 + 3]};
     quat_to_R(q, R);
     sm[0] = mod * scales[(size_t)idx * 3]; sm[1] = mod * scales[(size_t)idx * 3 + 1]; sm[2] = mod * scales[(size_t)idx * 3 + 2];
-    float Mx[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int k = 0; k < 3; k++) Mx[i][k] = R[i][k] * sm[k];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) S3[i][j] = Mx[i][0] * Mx[j][0] + Mx[i][1] * Mx[j][1] + Mx[i][2] * Mx[j][2];
+    cov3d_from_scaled_R(R, sm, S3);
   }
 }
 
@@ -144,9 +149,27 @@ __device__ __forceinline__ void ewa_project(const CamDev& cam, const float* V, c
   e.c = AS[1][0] * e.A[1][0] + AS[1][1] * e.A[1][1] + AS[1][2] * e.A[1][2] + 0.3f;
 }
 
-
-// preprocess.hip (hipcc's default contraction) keeps its own copies of the conic -> cov2D step and of dR -> dq: routed through the helpers
-// below its kernels kept their registers but not their instruction stream, and bit-identity of the generic kernels was not established.
+// Radius and tile rectangle of a splat at pixel (px, py) with 2D covariance diagonal (a, c) and determinant det: 3 sigma of the larger
+// eigenvalue, clipped to the tile grid.  r0 = minx | miny << 16, r1 = maxx | maxy << 16 (GeomView.rect); hit: the rectangle holds a tile.
+struct TileRect { uint32_t r0, r1; int32_t rad; bool hit; };
+__device__ __forceinline__ TileRect splat_tile_rect(const CamDev& cam, float px, float py, float a, float c, float det) {
+  TileRect t = {0u, 0u, 0, false};
+  float mid = 0.5f * (a + c);
+  float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
+  float rf = ceilf(3.f * sqrtf(lam));
+  float gxf = (float)cam.gx + 1.f, gyf = (float)cam.gy + 1.f;
+  int minx = min(cam.gx, max(0, (int)fminf(fmaxf((px - rf) / TILE, -1.f), gxf)));
+  int miny = min(cam.gy, max(0, (int)fminf(fmaxf((py - rf) / TILE, -1.f), gyf)));
+  int maxx = min(cam.gx, max(0, (int)fminf(fmaxf((px + rf + (TILE - 1)) / TILE, -1.f), gxf)));
+  int maxy = min(cam.gy, max(0, (int)fminf(fmaxf((py + rf + (TILE - 1)) / TILE, -1.f), gyf)));
+  t.hit = (maxx - minx) * (maxy - miny) > 0;
+  if (t.hit) {
+    t.rad = (int32_t)fminf(rf, 2.0e9f);
+    t.r0 = (uint32_t)minx | ((uint32_t)miny << 16);
+    t.r1 = (uint32_t)maxx | ((uint32_t)maxy << 16);
+  }
+  return t;
+}
 
 // Homogeneous projection of a point p under the row-vector matrix PV: clip x, y, w and pw = 1 / (w + 1e-7).
 struct HomPoint { float hx, hy, hw, pw; };
@@ -177,6 +200,8 @@ __device__ __forceinline__ Cov2dGrad conic_grad_to_cov2d(float a, float b, float
 }
 
 // d/d(2D covariance) -> GA = G2 A (2x3) and dA = 2 G2 A Sigma3, with A = J Wr of ewa_project (Sigma2 = A Sigma3 A^T)
+// (preprocess.hip, compiled under hipcc's default contraction, keeps its own copy of this one and of dcov3d_to_scale_rot: through the helpers its
+//  gradients moved in their last bits -- preprocess_bwd_kernel says which and by how much.  Every other helper here serves both files bit for bit.)
 __device__ __forceinline__ void cov2d_grad_to_dA(const Ewa& e, const float S3[3][3], const Cov2dGrad& g, float GA[2][3], float dA[2][3]) {
   const float G2[2][2] = {{g.da, 0.5f * g.db}, {0.5f * g.db, g.dcc}};
 #pragma unroll
@@ -188,6 +213,50 @@ __device__ __forceinline__ void cov2d_grad_to_dA(const Ewa& e, const float S3[3]
   for (int j = 0; j < 3; j++)
 #pragma unroll
     for (int r = 0; r < 2; r++) dA[r][j] = 2.f * (GA[r][0] * S3[0][j] + GA[r][1] * S3[1][j] + GA[r][2] * S3[2][j]);
+}
+
+// dSigma3 = A^T G2 A from A and GA = G2 A.
+// dSigma3 is symmetric in exact arithmetic; in float32 the two triangles round differently, and their difference IS the rotation
+// gradient of an isotropic Gaussian with identity rotation (every freshly seeded one, slam/mapper.py:644-668): rounding noise that
+// Adam(eps=1e-15) turns into full +-lr steps of the quaternion.  torch's autograd of Sigma = L L^T forms (dSigma + dSigma^T) L and
+// is exactly zero there; so is this once the triangles are averaged (found with the G9 runs of the reference's own classes:
+// pose error to the reference 1.4e-5 -> 8e-8 after the first tracked frame).
+__device__ __forceinline__ void cov2d_grad_to_dcov3d(const float A[2][3], const float GA[2][3], float dS[3][3]) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) dS[i][j] = A[0][i] * GA[0][j] + A[1][i] * GA[1][j];
+  const float s01 = 0.5f * (dS[0][1] + dS[1][0]), s02 = 0.5f * (dS[0][2] + dS[2][0]), s12 = 0.5f * (dS[1][2] + dS[2][1]);
+  dS[0][1] = s01; dS[1][0] = s01; dS[0][2] = s02; dS[2][0] = s02; dS[1][2] = s12; dS[2][1] = s12;
+}
+
+// dSigma3 -> d/d(scales) and dL/dR through Sigma3 = Mx Mx^T, Mx = R diag(sm), sm = mod * scales:  dMx = 2 dSigma3 Mx
+__device__ __forceinline__ void dcov3d_to_scale_rot(const float dS[3][3], const float R[3][3], const float sm[3], float mod, float ds[3],
+                                                    float dR[3][3]) {
+  float dM[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int k = 0; k < 3; k++) dM[i][k] = 2.f * (dS[i][0] * R[0][k] + dS[i][1] * R[1][k] + dS[i][2] * R[2][k]) * sm[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    ds[k] = mod * (dM[0][k] * R[0][k] + dM[1][k] * R[1][k] + dM[2][k] * R[2][k]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) dR[i][k] = dM[i][k] * sm[k];
+  }
+}
+
+// d/d(pixel position) (gpx, gpy) -> d/d(NDC) (gnx, gny) -> d/d(clip x, y, w) -> added to dm, the gradient of the point h was projected from:
+// pix = ((ndc + 1) S - 1) / 2, ndc = hom.xy / (hom.w + 1e-7)
+struct ScreenGrad { float gnx, gny, dhx, dhy, dhw; };
+__device__ __forceinline__ ScreenGrad pixel_grad_to_dmean(const CamDev& cam, const float* PV, const HomPoint& h, float gpx, float gpy, float dm[3]) {
+  ScreenGrad s;
+  s.gnx = gpx * 0.5f * cam.W;
+  s.gny = gpy * 0.5f * cam.H;
+  s.dhx = s.gnx * h.pw; s.dhy = s.gny * h.pw; s.dhw = -(s.gnx * h.hx + s.gny * h.hy) * h.pw * h.pw;
+#pragma unroll
+  for (int i = 0; i < 3; i++) dm[i] += PV[i * 4 + 0] * s.dhx + PV[i * 4 + 1] * s.dhy + PV[i * 4 + 3] * s.dhw;
+  return s;
 }
 
 // d/dJ (the four non-zero entries of the perspective Jacobian) -> d/d(view-space mean), the +-1.3 tan-fov clamp of ewa_project included

@@ -56,31 +56,19 @@ preprocess_fwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
   int32_t rad = 0;
   uint32_t r0 = 0, r1 = 0;
   if (live && tz > 0.2f) {
-    float hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
-    float hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
-    float hw = p[0] * PV[3] + p[1] * PV[7] + p[2] * PV[11] + PV[15];
-    float pw = 1.f / (hw + 1e-7f);
+    const HomPoint h = hom_project(PV, p);
     float S3[3][3], R[3][3], sm[3];
     load_cov3d(idx, scales, rots, cov3d, cam.scale_modifier, S3, R, sm);
     Ewa e;
     ewa_project(cam, V, p, S3, e);
     float det = e.a * e.c - e.b * e.b;
-    float px = ((hx * pw + 1.f) * cam.W - 1.f) * 0.5f;
-    float py = ((hy * pw + 1.f) * cam.H - 1.f) * 0.5f;
+    float px = ((h.hx * h.pw + 1.f) * cam.W - 1.f) * 0.5f;
+    float py = ((h.hy * h.pw + 1.f) * cam.H - 1.f) * 0.5f;
     if (det != 0.f && isfinite(px) && isfinite(py)) {
       float dinv = 1.f / det;
-      float mid = 0.5f * (e.a + e.c);
-      float lam = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
-      float rf = ceilf(3.f * sqrtf(lam));
-      float gxf = (float)cam.gx + 1.f, gyf = (float)cam.gy + 1.f;
-      int minx = min(cam.gx, max(0, (int)fminf(fmaxf((px - rf) / TILE, -1.f), gxf)));
-      int miny = min(cam.gy, max(0, (int)fminf(fmaxf((py - rf) / TILE, -1.f), gyf)));
-      int maxx = min(cam.gx, max(0, (int)fminf(fmaxf((px + rf + (TILE - 1)) / TILE, -1.f), gxf)));
-      int maxy = min(cam.gy, max(0, (int)fminf(fmaxf((py + rf + (TILE - 1)) / TILE, -1.f), gyf)));
-      if ((maxx - minx) * (maxy - miny) > 0) {
-        rad = (int32_t)fminf(rf, 2.0e9f);
-        r0 = (uint32_t)minx | ((uint32_t)miny << 16);
-        r1 = (uint32_t)maxx | ((uint32_t)maxy << 16);
+      const TileRect tr = splat_tile_rect(cam, px, py, e.a, e.c, det);
+      if (tr.hit) {
+        rad = tr.rad; r0 = tr.r0; r1 = tr.r1;
         float col[MM3DGS_MAX_CHANNELS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         int nsh = 0;
         if (shs) {
@@ -124,43 +112,7 @@ preprocess_fwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
     g.rect[(size_t)idx * 2] = r0;
     g.rect[(size_t)idx * 2 + 1] = r1;
   }
-  // count overlaps per tile
-  {
-    const int minx = r0 & 0xffff, miny = r0 >> 16, maxx = r1 & 0xffff, maxy = r1 >> 16;
-    const int w = maxx - minx, area = w * (maxy - miny);
-    {  // workgroup-local exclusive scan of tiles touched (this Gaussian's first pair index)
-      __shared__ uint32_t wtot[PP_BLOCK / 64];
-      const int ln = threadIdx.x & 63, wvi = threadIdx.x >> 6;
-      // (one scan only: block records are addressed by list position in every mode)
-      const uint32_t x = wave_scan_incl((uint32_t)area);   // tiles touched
-      if (ln == 63) wtot[wvi] = x;
-      __syncthreads();
-      uint32_t pre = 0;
-      for (int q = 0; q < wvi; q++) pre += wtot[q];
-      if (live) g.tileoff[idx] = pre + x - (uint32_t)area;
-      if (threadIdx.x == PP_BLOCK - 1) g.block_tiles[blockIdx.x] = pre + x;
-    }
-    uint32_t* cnt = lds_tiles ? hist : iv.tile_count;
-    const int lane = threadIdx.x & 63;
-    unsigned long long big = __ballot(area > 32);
-    if (area > 0 && area <= 32)
-      for (int y = miny; y < maxy; y++)
-        for (int x = minx; x < maxx; x++) atomicAdd(&cnt[y * cam.gx + x], 1u);
-    while (big) {  // a splat covering many tiles is spread over the whole wave
-      const int src = __ffsll((long long)big) - 1;
-      big &= big - 1;
-      const int sminx = __builtin_amdgcn_readlane(minx, src), sminy = __builtin_amdgcn_readlane(miny, src);
-      const int sw = __builtin_amdgcn_readlane(w, src), sarea = __builtin_amdgcn_readlane(area, src);
-      for (int k = lane; k < sarea; k += 64) atomicAdd(&cnt[(sminy + k / sw) * cam.gx + sminx + k % sw], 1u);
-    }
-  }
-  if (lds_tiles) {
-    __syncthreads();
-    for (int t = threadIdx.x; t < T; t += PP_BLOCK) {
-      uint32_t c = hist[t];
-      if (c) atomicAdd(&iv.tile_count[t], c);
-    }
-  }
+  count_rect_tiles<PP_BLOCK>(cam.gx, T, lds_tiles, hist, live, idx, r0, r1, g, iv);
 }
 
 void launch_preprocess_fwd(const CamDev& cam, int P, int M, int C, const float* means3D, const float* shs,
@@ -180,49 +132,6 @@ void launch_preprocess_fwd(const CamDev& cam, int P, int M, int C, const float* 
 // Camera gradients: 27 values per Gaussian (view rows 0..3 x cols 0..2, proj rows 0..3 x cols {0,1,3}, campos)
 // are reduced wave -> workgroup in registers/LDS, one partial row per workgroup is written, and a single-wave
 // finishing kernel adds the rows in double precision in a fixed order (deterministic, no atomics).
-// Sum of a Gaussian's per-tile gradient records (generic mode: 6 + C floats at a packed stride of `recf` floats).  Every lane of the wave must call
-// it.  Rectangles of up to 16 tiles are summed by their own lane, four records in flight, in ascending pair order; a bigger one is read by the whole
-// wave (lane-strided, then a fixed-order reduction) -- deterministic either way.  (fused.hip's gather_tile_records is the SLAM modes' instance.)
-__device__ __forceinline__ void gather_pair_records(int area, uint32_t first, const float* __restrict__ dtile, int recf, float4& acc0, float4& acc1,
-                                                    float4& acc2) {
-  const int lane = threadIdx.x & 63;
-  const bool big = area > 16;
-  const int n_own = big ? 0 : area;
-  for (int k0 = 0; __ballot(k0 < n_own) != 0ull; k0 += 4) {
-    float4 a[4], b4[4], c4[4];
-    bool on[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      on[u] = k0 + u < n_own;
-      const float* r = dtile + (on[u] ? (size_t)(first + (uint32_t)(k0 + u)) * recf : (size_t)0);
-      a[u] = ld4u(r); b4[u] = ld4u(r + 4); c4[u] = ld4u(r + 8);      // (a shorter record: the caller drops what belongs to the next one)
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      acc0.x += on[u] ? a[u].x : 0.f; acc0.y += on[u] ? a[u].y : 0.f; acc0.z += on[u] ? a[u].z : 0.f; acc0.w += on[u] ? a[u].w : 0.f;
-      acc1.x += on[u] ? b4[u].x : 0.f; acc1.y += on[u] ? b4[u].y : 0.f; acc1.z += on[u] ? b4[u].z : 0.f; acc1.w += on[u] ? b4[u].w : 0.f;
-      acc2.x += on[u] ? c4[u].x : 0.f; acc2.y += on[u] ? c4[u].y : 0.f; acc2.z += on[u] ? c4[u].z : 0.f; acc2.w += on[u] ? c4[u].w : 0.f;
-    }
-  }
-  for (unsigned long long bigs = __ballot(big); bigs; bigs &= bigs - 1ull) {
-    const int src = __ffsll((long long)bigs) - 1;
-    const int sarea = __builtin_amdgcn_readlane(area, src);
-    const uint32_t sfirst = (uint32_t)__builtin_amdgcn_readlane((int)first, src);
-    float v[12];
-#pragma unroll
-    for (int f = 0; f < 12; f++) v[f] = 0.f;
-    for (int k = lane; k < sarea; k += 64) {
-      const float* r = dtile + (size_t)(sfirst + (uint32_t)k) * recf;
-#pragma unroll
-      for (int f = 0; f < 12; f++) v[f] += f < recf ? r[f] : 0.f;
-    }
-#pragma unroll
-    for (int f = 0; f < 12; f++) v[f] = wave_sum(v[f]);
-    if (lane == src) {
-      acc0 = make_float4(v[0], v[1], v[2], v[3]); acc1 = make_float4(v[4], v[5], v[6], v[7]); acc2 = make_float4(v[8], v[9], v[10], v[11]);
-    }
-  }
-}
 
 #define NCAM 27
 // (developer timing probes, variant builds only -- results INVALID: -DMM3DGS_PPB_PROBE=<bits>  1: no record gather | 2: no dL/dSH store | 4: no SH row load)
@@ -269,7 +178,7 @@ preprocess_bwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
       }
     }
     if (!(MM3DGS_PPB_PROBE & 1))
-    gather_pair_records(area, first, dsub + (size_t)NLIST * (size_t)N_cap * SPLAT_F, GENERIC_RECF(C), acc0, acc1, acc2);
+    gather_records<12>(area, first, dsub + (size_t)NLIST * (size_t)N_cap * SPLAT_F, GENERIC_RECF(C), acc0, acc1, acc2, 0u);
     // a record shorter than 12 floats: what the last float4 picked up past its end belongs to the next record
     if (C < 6) { if (C < 3) { acc2.x = 0.f; } if (C < 4) acc2.y = 0.f; if (C < 5) acc2.z = 0.f; acc2.w = 0.f; if (C < 2) acc1.w = 0.f; if (C < 1) acc1.z = 0.f; }
   }
@@ -296,40 +205,21 @@ preprocess_bwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
       load_cov3d(idx, scales, rots, cov3d, cam.scale_modifier, S3, R, sm);
       Ewa e;
       ewa_project(cam, V, p, S3, e);
-      float a = e.a, b = e.b, c = e.c;
-      float det = a * c - b * b;
-      float idet = 1.f / det;
-      // conic = (c, -b, a)/det  ->  d/d(a,b,c)
-      // (G2 as 1/det [[gC, -gB/2], [-gB/2, gA]] + kappa adj(Sigma2), not the expanded closed form: mm3dgs_math.h conic_grad_to_cov2d says why)
-      float kappa = -(c * gA - b * gB + a * gC) * idet * idet;
-      float da = gC * idet + kappa * c;
-      float db = -gB * idet - 2.f * (kappa * b);
-      float dcc = gA * idet + kappa * a;
+      // conic -> Sigma2 -> (Sigma3, A = J Wr)
+      float GA[2][3], dS[3][3], dA[2][3];
+      const Cov2dGrad cg2 = conic_grad_to_cov2d(e.a, e.b, e.c, gA, gB, gC);
+      const float da = cg2.da, db = cg2.db, dcc = cg2.dcc;
+      // GA = G2 A and (below) dA = 2 GA Sigma3: mm3dgs_math.h cov2d_grad_to_dA, kept written out here.  Under this file's default contraction the
+      // compiler pairs the products of these sums differently once they come from the helper: against the open-coded kernel dL/dcov3D differed in
+      // 9 % of its words (2.4e-4 on values of 3e3), dL/dscales in 20 % (1.5e-5 on 3e2), dL/drotations in 24 %, dL/dmeans3D in 2 % and dL/dview
+      // in its last bit, on a 700-Gaussian scene.  (From the helper, dA also costs the MV = 16 instance ten VGPRs, 159 -> 169, and its third wave.)
       float G2[2][2] = {{da, 0.5f * db}, {0.5f * db, dcc}};
-      // GA = G2 * A (2x3)
-      float GA[2][3];
 #pragma unroll
       for (int i = 0; i < 3; i++) {
         GA[0][i] = G2[0][0] * e.A[0][i] + G2[0][1] * e.A[1][i];
         GA[1][i] = G2[1][0] * e.A[0][i] + G2[1][1] * e.A[1][i];
       }
-      // dSigma3 = A^T G2 A (symmetric)
-      float dS[3][3];
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) dS[i][j] = e.A[0][i] * GA[0][j] + e.A[1][i] * GA[1][j];
-      // dSigma3 is symmetric in exact arithmetic; in float32 the two triangles round differently, and their difference IS the rotation
-      // gradient of an isotropic Gaussian with identity rotation (every freshly seeded one, slam/mapper.py:644-668): rounding noise that
-      // Adam(eps=1e-15) turns into full +-lr steps of the quaternion.  torch's autograd of Sigma = L L^T forms (dSigma + dSigma^T) L and
-      // is exactly zero there; so is this once the triangles are averaged (found with the G9 runs of the reference's own classes:
-      // pose error to the reference 1.4e-5 -> 8e-8 after the first tracked frame).
-      {
-        const float s01 = 0.5f * (dS[0][1] + dS[1][0]), s02 = 0.5f * (dS[0][2] + dS[2][0]), s12 = 0.5f * (dS[1][2] + dS[2][1]);
-        dS[0][1] = s01; dS[1][0] = s01; dS[0][2] = s02; dS[2][0] = s02; dS[1][2] = s12; dS[2][1] = s12;
-      }
-      // dA = 2 G2 A Sigma3
-      float dA[2][3];
+      cov2d_grad_to_dcov3d(e.A, GA, dS);
 #pragma unroll
       for (int r = 0; r < 2; r++)
 #pragma unroll
@@ -339,26 +229,14 @@ preprocess_bwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
       float dJ02 = dA[0][0] * V[2] + dA[0][1] * V[6] + dA[0][2] * V[10];
       float dJ11 = dA[1][0] * V[1] + dA[1][1] * V[5] + dA[1][2] * V[9];
       float dJ12 = dA[1][0] * V[2] + dA[1][1] * V[6] + dA[1][2] * V[10];
-      float tz = e.t[2], itz = 1.f / tz, itz2 = itz * itz, itz3 = itz2 * itz;
-      float dtxc = -cam.focal_x * itz2 * dJ02;
-      float dtyc = -cam.focal_y * itz2 * dJ12;
       float dt[3];
-      dt[0] = e.in_x ? dtxc : 0.f;
-      dt[1] = e.in_y ? dtyc : 0.f;
-      dt[2] = -cam.focal_x * itz2 * dJ00 - cam.focal_y * itz2 * dJ11 + 2.f * cam.focal_x * e.txc * itz3 * dJ02 +
-              2.f * cam.focal_y * e.tyc * itz3 * dJ12;
+      dJ_to_dmean(cam, e, dJ00, dJ02, dJ11, dJ12, dt);
 #pragma unroll
       for (int i = 0; i < 3; i++) dmean[i] = V[i * 4 + 0] * dt[0] + V[i * 4 + 1] * dt[1] + V[i * 4 + 2] * dt[2];
-      // screen position: pix = ((ndc+1) S - 1)/2, ndc = hom.xy / (hom.w + 1e-7)
-      float hx = p[0] * PV[0] + p[1] * PV[4] + p[2] * PV[8] + PV[12];
-      float hy = p[0] * PV[1] + p[1] * PV[5] + p[2] * PV[9] + PV[13];
-      float hw = p[0] * PV[3] + p[1] * PV[7] + p[2] * PV[11] + PV[15];
-      float pw = 1.f / (hw + 1e-7f);
-      gnx = gpx * 0.5f * cam.W;
-      gny = gpy * 0.5f * cam.H;
-      float dhx = gnx * pw, dhy = gny * pw, dhw = -(gnx * hx + gny * hy) * pw * pw;
-#pragma unroll
-      for (int i = 0; i < 3; i++) dmean[i] += PV[i * 4 + 0] * dhx + PV[i * 4 + 1] * dhy + PV[i * 4 + 3] * dhw;
+      // screen position
+      const ScreenGrad sg = pixel_grad_to_dmean(cam, PV, hom_project(PV, p), gpx, gpy, dmean);
+      gnx = sg.gnx; gny = sg.gny;
+      const float dhx = sg.dhx, dhy = sg.dhy, dhw = sg.dhw;
       if (want_cam) {
         // view: from t = [p,1] V  and from Wr inside A = J Wr  (dWr = J^T dA ; V[i][j] = Wr[j][i])
         float ph[4] = {p[0], p[1], p[2], 1.f};
@@ -440,7 +318,8 @@ preprocess_bwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
           dc6[0] = dS[0][0]; dc6[1] = 2.f * dS[0][1]; dc6[2] = 2.f * dS[0][2];
           dc6[3] = dS[1][1]; dc6[4] = 2.f * dS[1][2]; dc6[5] = dS[2][2];
         } else {
-          // Sigma3 = Mx Mx^T, Mx = R diag(sm):  dMx = 2 dS Mx
+          // Sigma3 = Mx Mx^T, Mx = R diag(sm):  dMx = 2 dS Mx.  mm3dgs_math.h dcov3d_to_scale_rot, kept written out here: from the helper
+          // dL/dscales and dL/drotations differed from the open-coded kernel in 20 % of their words (last bits: 8e-6 on values of 1e2)
           float dM[3][3];
 #pragma unroll
           for (int i = 0; i < 3; i++)
@@ -454,14 +333,8 @@ preprocess_bwd_kernel(CamDev cam, int P, int M, int C, const float* __restrict__
 #pragma unroll
             for (int i = 0; i < 3; i++) dR[i][k] = dM[i][k] * sm[k];
           }
-          float r = rots[(size_t)idx * 4], x = rots[(size_t)idx * 4 + 1], y = rots[(size_t)idx * 4 + 2], z = rots[(size_t)idx * 4 + 3];
-          dq[0] = 2.f * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
-          dq[1] = 2.f * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - 2.f * x * dR[1][1] - r * dR[1][2] + z * dR[2][0] +
-                         r * dR[2][1] - 2.f * x * dR[2][2]);
-          dq[2] = 2.f * (-2.f * y * dR[0][0] + x * dR[0][1] + r * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r * dR[2][0] +
-                         z * dR[2][1] - 2.f * y * dR[2][2]);
-          dq[3] = 2.f * (-2.f * z * dR[0][0] - r * dR[0][1] + x * dR[0][2] + r * dR[1][0] - 2.f * z * dR[1][1] +
-                         y * dR[1][2] + x * dR[2][0] + y * dR[2][1]);
+          const float q[4] = {rots[(size_t)idx * 4], rots[(size_t)idx * 4 + 1], rots[(size_t)idx * 4 + 2], rots[(size_t)idx * 4 + 3]};
+          dR_to_dq(q, dR, dq);
         }
       }
     } else if (MV != 16 && !skip_g && shs && dshs) {

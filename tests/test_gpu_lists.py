@@ -144,6 +144,50 @@ def test_slam_forward_lists_match_the_host_reference(row):
     assert total.ambiguous_bits <= 1e-4 * 16 * total.pairs
 
 
+# 129 x 97 = 12 513 tiles: above MAX_LDS_TILES (12 288, mm3dgs_common.h), where the projection kernels' per-workgroup LDS histogram is off and
+# every lane counts its tiles in global memory
+WIDE = (700, 1552, 2064, 3, 0.0, 97)
+
+
+def _covering_rects(st):
+    """Per tile: how many of the tile rectangles read back from the state hold it."""
+    cnt = np.zeros((st.gy, st.gx), np.int64)
+    for x0, y0, x1, y1 in st.rect.cpu().numpy():
+        cnt[y0:y1, x0:x1] += 1
+    return cnt.reshape(-1)
+
+
+@pytest.mark.parametrize("path", ["generic", "slam_packed"])
+def test_tile_counts_on_a_grid_too_big_for_the_lds_histogram(path):
+    """The tile counting of preprocess_fwd_kernel (generic) and slam_preprocess_fwd_kernel (mm3dgs_slam_forward, packed bins; direct bins
+    do not exist at this size) with global atomics instead of the LDS histogram: the tile ranges are the per-tile counts of the covering
+    rectangles, own-lane (<= 32 tiles) and wave-cooperative (> 32 tiles) footprints both present, the header agrees, the counters are
+    left zero, and the lists of 32 tiles -- the longest among them -- match the host reference."""
+    cfg, g, R, pose, _ = _scene(*WIDE)
+    if path == "generic":
+        from mm3dgs_slam_amd import rasterizer as rz
+        r = R.render(g, pose)          # (keeps the autograd graph, which holds the binning state, alive while the lists are read)
+        torch.cuda.synchronize()
+        s = rz.last_state()
+        st = lr.ListState(s["geom"], s["img"], s["binning"], s["P"], s["H"], s["W"], s["N"], s["radii"])
+    else:
+        eng = _engine(R, False, 1 << 30)
+        eng.forward(pose, g, need_grads=False)
+        torch.cuda.synchronize()
+        assert not eng.direct
+        st = _slam_state(eng)
+    assert st.T == 129 * 97 and st.T > 12288
+    area = st.area().cpu().numpy()
+    assert ((area > 0) & (area <= 32)).any() and (area > 32).any(), np.bincount(np.minimum(area, 33))
+    lens = np.diff(st.ranges)
+    assert np.array_equal(lens, _covering_rects(st))
+    assert st.hdr["num_rendered"] == int(area.sum()) and st.hdr["overflow"] == 0, st.hdr
+    assert not st.tile_count.any(), "tile_count must be left zero"
+    tiles = sorted(set(np.linspace(0, st.T - 1, 31).astype(int).tolist()) | {int(lens.argmax())})
+    stats = lr.check_tiles(st, tiles, False)
+    _report(f"wide grid {path}", stats, f"footprints <= 32: {int(((area > 0) & (area <= 32)).sum())}, > 32: {int((area > 32).sum())}")
+
+
 def test_block_lists_agree_across_the_slam_entry_points():
     """Same map, same pose: the block lists (ids and counts) of packed bins with fused or separate sort launches, direct bins, and the
     tracking launch (mm3dgs_slam_track, pose chain on, one iteration at learning rate 0) with packed and with direct bins are identical
