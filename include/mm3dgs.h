@@ -514,6 +514,67 @@ int mm3dgs_pointcloud_add_view(int H, int W, double fx, double fy, double cx, do
                                void* table_or_null /*[slots] x 16 bytes*/, uint64_t slots, uint64_t* counters /*[8], device*/, void* work,
                                void* stream);
 
+/* ---- coloured triangle mesh: posed RGB-D views fused into a truncated signed distance volume, its zero level as an indexed mesh ---------
+ * What the point cloud leaves to a viewer: a surface.  The volume is the caller's, dense, x fastest, two device arrays over an nx x ny x nz
+ * lattice of sample points: tsdf_w float2 [nz][ny][nx] {truncated distance T in [-1, 1], observation weight W}, 8-byte aligned, and rgb_w
+ * float4 [nz][ny][nx] {running mean colour, colour weight}, 16-byte aligned.  Sample (i, j, k) sits at origin + voxel (i, j, k); origin:
+ * host double[3], voxel: host double.  All zeros is the empty volume (mm3dgs_tsdf_reset: three memsets, the counters too).  Every size is at
+ * least 2 and nx ny nz <= 2^30.
+ *
+ * mm3dgs_tsdf_integrate: one launch per view.  color, depth, silhouette_or_null, pose, fx, fy, cx, cy, sil_min, depth_max: as for
+ * mm3dgs_pointcloud_add_view.  One lane owns one sample of a slice, 64 consecutive x make a wave, a workgroup walks up to 8 z slices.  Per sample, in double from the float32 inputs:
+ *   camera point  p_c = R p_w + t (the quaternion is normalised here); skipped if z <= 0.
+ *   pixel         u = floor(fx x / z + cx + 0.5), v likewise: pixel centres at integer coordinates, the point cloud's and
+ *                 mm3dgs_seed_gaussians' convention; skipped if outside the image.
+ *   valid pixel   the point cloud's test, word for word (one shared function); skipped otherwise.
+ *   distance      sdf = depth - z; skipped if sdf < -trunc; s = min(1, sdf / trunc).
+ *   update        T <- (T W + s) / (W + 1), W <- W + 1, rounded to float32 once at the 8-byte store; only if sdf <= trunc the colour mean
+ *                 and its weight in the same way, from the pixel's float32 colour as it is (one 16-byte store).
+ * A skipped sample touches no volume memory: the decision falls before the first load from the volume.  No atomic except one integer add
+ * per workgroup and counter; no host synchronisation; the one loop has at most 8 rounds.  counters: uint64[8] on the device, 8-byte aligned, cumulative: [0] views, [1]
+ * distance updates, [2] colour updates, the rest 0.  Nothing outside tsdf_w, rgb_w and counters[0:3] is written.
+ * -1 (nothing is launched): H or W <= 0 or more than 2^28 pixels; a lattice size below 2 or more than 2^30 samples; a NULL color, depth, pose,
+ * origin, tsdf_w, rgb_w or counters; voxel or trunc not finite or not positive; an origin that is not finite; fx or fy zero or not finite,
+ * cx or cy not finite; rgb_w not 16-byte aligned, tsdf_w or counters not 8-byte aligned, an image or the pose not 4-byte aligned.
+ *
+ * mm3dgs_tsdf_mesh_plan / mm3dgs_tsdf_mesh_emit: marching tetrahedra.  Every lattice cube is cut into the six Kuhn tetrahedra, the paths
+ * from corner (0,0,0) to (1,1,1) along one axis permutation each, permutations in lexicographic order (x,y,z) (x,z,y) (y,x,z) (y,z,x)
+ * (z,x,y) (z,y,x); the cut is the same in every cube, so face diagonals agree between neighbours and the surface closes.
+ *   known, inside a sample is known if W >= min_weight (a NaN is not) and inside if T < 0; a cube is valid if its 8 corners are known.
+ *   vertex        lies on a lattice edge that leaves a sample q in one of the 7 directions d in {0,1}^3 \ {0} (d as a 3-bit number, x the
+ *                 low bit).  The edge carries a vertex iff its endpoints differ in `inside` and at least one valid cube contains it.  The
+ *                 vertex list is ordered by q in raster order (x fastest), then by d.
+ *   position      t = T0 / (T0 - T1) of the distances at q and q + d; p = origin + voxel (q + t d); colour c0 + t (c1 - c0) of the two
+ *                 endpoints' mean colours; all in double, rounded once to float32; the row and its colour bytes as in the point cloud:
+ *                 16 bytes {float x, y, z; uint32 rgba}, one 16-byte store.
+ *   triangles     int32[3] each; a corner's index is base[q] + popcount(mask[q] & ((1 << d) - 1)).  Ordered by cube (origin in raster order),
+ *                 then by tetrahedron, then by case order; wound so that the normal points from inside to outside (towards free space).
+ * plan leaves per sample {vertex base, 7-bit edge mask} and per cube its triangle base in work, and writes counters (uint64[8], device,
+ * 8-byte aligned, not cumulative): [0] vertices, [1] triangles, [2:8] 0.  emit (same lattice, volume and work as the plan before it)
+ * writes the rows and the triangles and counters [2] vertices written = min([0], vcap), [3] triangles written, [4] vertices dropped, [5]
+ * triangles dropped: a vertex at or beyond vcap is not written; a triangle at or beyond tcap, or one that references a vertex that was not
+ * written, is not written (its place, if below tcap, keeps what it held); [3] + [5] == [1].  The totals are exact while they are below
+ * 2^32; triangle indices are int32.  work: mm3dgs_tsdf_mesh_work_bytes bytes of device memory, 8-byte aligned, contents irrelevant before
+ * plan.  Five launches on `stream` for plan (no atomic at all: the edges are gathered from the cubes around them), two for emit (one
+ * integer add per wave for counters [3] and [5]); no atomic decides a position or an index, so the same volume gives the same bytes on
+ * every call; every loop is bounded; no host synchronisation.  Nothing outside work[0:work_bytes], counters[0:8], rows[0:vcap] and
+ * triangles[0:tcap] is written.
+ * -1 (nothing is launched): a lattice size below 2 or more than 2^30 samples; a NULL tsdf_w, work or counters (emit: also rgb_w, origin,
+ * and rows or triangles with a cap above 0); a min_weight that is not a number; voxel not finite or not positive, an origin that is not
+ * finite; rgb_w or rows not 16-byte aligned, tsdf_w, work or counters not 8-byte aligned, triangles not 4-byte aligned.
+ * mm3dgs_tsdf_mesh_work_bytes returns 0 for a lattice the calls reject. */
+int mm3dgs_tsdf_reset(int nx, int ny, int nz, void* tsdf_w, void* rgb_w, uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_tsdf_integrate(int H, int W, double fx, double fy, double cx, double cy, const float* pose /*[7], device*/,
+                          const float* color /*[3,H,W]*/, const float* depth /*[H,W]*/, const float* silhouette_or_null /*[H,W]*/,
+                          float sil_min, float depth_max, const double* origin /*host [3]*/, double voxel, double trunc, int nx, int ny,
+                          int nz, void* tsdf_w, void* rgb_w, uint64_t* counters /*[8], device*/, void* stream);
+size_t mm3dgs_tsdf_mesh_work_bytes(int nx, int ny, int nz);
+int mm3dgs_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters /*[8], device*/,
+                          void* stream);
+int mm3dgs_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void* rgb_w, const double* origin /*host [3]*/, double voxel,
+                          const void* work, void* rows /*[vcap] x 16 bytes*/, uint64_t vcap, void* triangles /*[tcap] x int32[3]*/,
+                          uint64_t tcap, uint64_t* counters /*[8], device*/, void* stream);
+
 /* ---- frame ingest: raw sensor bytes -> the two images the SLAM loops consume, in one launch ------------------------------------------
  * rgb: uint8 interleaved [Hs,Ws,3] on the device, any byte alignment; depth_or_null: uint16 [Hs,Ws], 2-byte aligned.  out_color [3,H,W]
  * float32 in [0,1]; out_depth_or_null [H,W] float32 in metres, required iff depth is given (a colour-only call passes NULL for both).
@@ -646,7 +707,9 @@ const char* mm3dgs_last_error(void);
         estimate at frame size, one launch); mm3dgs_mosaic_work_bytes / mm3dgs_mosaic (the debug video's and SLAM.render()'s panel
         mosaic as one uint8 image, composed on the device); mm3dgs_eval_image_work_bytes / mm3dgs_eval_image (PSNR, SSIM and depth L1 of a
         rendered frame as one row of a device table); mm3dgs_pointcloud_work_bytes / mm3dgs_pointcloud_reset / mm3dgs_pointcloud_add_view
-        (the fused coloured point cloud of a run, one call per view, first point per voxel); a caller that needs them looks the symbols up */
+        (the fused coloured point cloud of a run, one call per view, first point per voxel); mm3dgs_tsdf_reset / mm3dgs_tsdf_integrate /
+        mm3dgs_tsdf_mesh_work_bytes / mm3dgs_tsdf_mesh_plan / mm3dgs_tsdf_mesh_emit (the run as a coloured triangle mesh: views fused into
+        a truncated signed distance volume, marching tetrahedra over it); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

@@ -102,6 +102,12 @@ _SIGS = {
     "mm3dgs_pointcloud_reset": (C.c_int, [_P, C.c_uint64, _P, _P]),
     "mm3dgs_pointcloud_add_view": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.c_float, C.c_float,
                                              C.c_double, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, _P, _P, _P]),
+    "mm3dgs_tsdf_reset": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "mm3dgs_tsdf_integrate": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.c_float, C.c_float,
+                                        C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "mm3dgs_tsdf_mesh_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mm3dgs_tsdf_mesh_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P]),
+    "mm3dgs_tsdf_mesh_emit": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_double), C.c_double, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
     "mm3dgs_ingest_frame": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_double, C.c_int, C.c_int, _P, _P, _P]),
     "mm3dgs_ingest_est": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P]),
     "mm3dgs_mosaic_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

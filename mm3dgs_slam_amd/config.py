@@ -23,6 +23,13 @@ _TUM = {
     # rendered at the estimated pose where the silhouette exceeds sil_min, "sensor": the frame's own colour and depth --, depths beyond
     # max_depth dropped (0: no limit), one point per `voxel`-sized cell (0: no thinning), at most max_points rows; opt-in, changes no pose
     "pointcloud": {"export": False, "every": None, "voxel": 0.01, "source": "render", "sil_min": 0.99, "max_depth": 0, "max_points": 16777216},
+    # after the run, the reconstruction as a coloured triangle mesh (outputdir/mesh/mesh.ply; mesh.py, mm3dgs_tsdf_integrate +
+    # mm3dgs_tsdf_mesh_plan / _emit): the same views as the point cloud fused into a dense truncated signed distance volume of `voxel`-sized
+    # cells (trunc 0: 4 voxel) over `bounds` ([xmin, ymin, zmin, xmax, ymax, zmax]; None: the box of the views' lifted valid points, grown by
+    # trunc + voxel), then marching tetrahedra over the samples seen at least min_weight times; a lattice above max_voxels samples is an
+    # error; opt-in, changes no pose
+    "mesh": {"export": False, "every": None, "voxel": 0.02, "trunc": 0, "source": "render", "sil_min": 0.99, "max_depth": 0, "min_weight": 1,
+             "bounds": None, "max_voxels": 1 << 28},
     "scene_radius_depth_ratio": 2, "desired_height": 480, "desired_width": 640,
     "debug": {"get_runtime_stats": False, "create_video": False, "save_keyframes": False},
     "pipeline": {"convert_SHs_python": False, "compute_cov3D_python": False, "transform_means_python": True,

@@ -785,6 +785,76 @@ int mm3dgs_pointcloud_add_view(int H, int W, double fx, double fy, double cx, do
   return check_launch("pointcloud_add_view");
 }
 
+// ---- coloured triangle mesh (tsdf.hip) ---------------------------------------------------------------------------------------
+static bool tsdf_lattice_ok(int nx, int ny, int nz) {
+  return nx >= 2 && ny >= 2 && nz >= 2 && (size_t)nx * (size_t)ny <= ((size_t)1 << 30) && (size_t)nx * (size_t)ny * (size_t)nz <= ((size_t)1 << 30);
+}
+static bool tsdf_origin_ok(const double* o) { return o && isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]); }
+
+int mm3dgs_tsdf_reset(int nx, int ny, int nz, void* tsdf_w, void* rgb_w, uint64_t* counters, void* stream) {
+  if (!tsdf_lattice_ok(nx, ny, nz)) return fail(-1, "tsdf_reset: lattice %d x %d x %d (every size at least 2, at most 2^30 samples)", nx, ny, nz);
+  if (!tsdf_w || !rgb_w || !counters) return fail(-1, "tsdf_reset: NULL argument (tsdf_w, rgb_w and counters are required)");
+  if (((uintptr_t)tsdf_w | (uintptr_t)counters) & 7) return fail(-1, "tsdf_reset: tsdf_w and counters must be 8-byte aligned");
+  if ((uintptr_t)rgb_w & 15) return fail(-1, "tsdf_reset: rgb_w must be 16-byte aligned");
+  const size_t n = (size_t)nx * (size_t)ny * (size_t)nz;
+  if (hipMemsetAsync(tsdf_w, 0, n * 8, (hipStream_t)stream) != hipSuccess || hipMemsetAsync(rgb_w, 0, n * 16, (hipStream_t)stream) != hipSuccess ||
+      hipMemsetAsync(counters, 0, 64, (hipStream_t)stream) != hipSuccess)
+    return fail(-3, "tsdf_reset: hipMemsetAsync failed");
+  return 0;
+}
+
+int mm3dgs_tsdf_integrate(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
+                          const float* silhouette_or_null, float sil_min, float depth_max, const double* origin, double voxel, double trunc, int nx,
+                          int ny, int nz, void* tsdf_w, void* rgb_w, uint64_t* counters, void* stream) {
+  if (H <= 0 || W <= 0) return fail(-1, "tsdf_integrate: H = %d, W = %d (both must be positive)", H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "tsdf_integrate: %d x %d has more than 2^28 pixels", H, W);
+  if (!tsdf_lattice_ok(nx, ny, nz)) return fail(-1, "tsdf_integrate: lattice %d x %d x %d (every size at least 2, at most 2^30 samples)", nx, ny, nz);
+  if (!color || !depth || !pose || !origin || !tsdf_w || !rgb_w || !counters)
+    return fail(-1, "tsdf_integrate: NULL argument (color, depth, pose, origin, tsdf_w, rgb_w and counters are required)");
+  if (!(voxel > 0.0) || !isfinite(voxel) || !(trunc > 0.0) || !isfinite(trunc))
+    return fail(-1, "tsdf_integrate: voxel = %g, trunc = %g (both must be finite and positive)", voxel, trunc);
+  if (!tsdf_origin_ok(origin)) return fail(-1, "tsdf_integrate: the origin must be finite");
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "tsdf_integrate: fx = %g, fy = %g (finite, not 0)", fx, fy);
+  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "tsdf_integrate: cx = %g, cy = %g (must be finite)", cx, cy);
+  if ((uintptr_t)rgb_w & 15) return fail(-1, "tsdf_integrate: rgb_w must be 16-byte aligned");
+  if (((uintptr_t)tsdf_w | (uintptr_t)counters) & 7) return fail(-1, "tsdf_integrate: tsdf_w and counters must be 8-byte aligned");
+  if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)silhouette_or_null | (uintptr_t)pose) & 3)
+    return fail(-1, "tsdf_integrate: the images and the pose must be 4-byte aligned");
+  TsdfView v;
+  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
+  v.pose = pose; v.color = color; v.depth = depth; v.sil = silhouette_or_null;
+  v.sil_min = sil_min; v.depth_max = depth_max;
+  v.o[0] = origin[0]; v.o[1] = origin[1]; v.o[2] = origin[2]; v.voxel = voxel; v.trunc = trunc;
+  v.nx = nx; v.ny = ny; v.nz = nz;
+  launch_tsdf_integrate(v, tsdf_w, rgb_w, counters, (hipStream_t)stream);
+  return check_launch("tsdf_integrate");
+}
+
+size_t mm3dgs_tsdf_mesh_work_bytes(int nx, int ny, int nz) { return tsdf_lattice_ok(nx, ny, nz) ? tsdf_mesh_work_bytes(nx, ny, nz) : 0; }
+
+int mm3dgs_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, void* stream) {
+  if (!tsdf_lattice_ok(nx, ny, nz)) return fail(-1, "tsdf_mesh_plan: lattice %d x %d x %d (every size at least 2, at most 2^30 samples)", nx, ny, nz);
+  if (!tsdf_w || !work || !counters) return fail(-1, "tsdf_mesh_plan: NULL argument (tsdf_w, work and counters are required)");
+  if (!(min_weight == min_weight)) return fail(-1, "tsdf_mesh_plan: min_weight is not a number");
+  if (((uintptr_t)tsdf_w | (uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "tsdf_mesh_plan: tsdf_w, work and counters must be 8-byte aligned");
+  launch_tsdf_mesh_plan(nx, ny, nz, tsdf_w, min_weight, work, counters, (hipStream_t)stream);
+  return check_launch("tsdf_mesh_plan");
+}
+
+int mm3dgs_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void* rgb_w, const double* origin, double voxel, const void* work,
+                          void* rows, uint64_t vcap, void* triangles, uint64_t tcap, uint64_t* counters, void* stream) {
+  if (!tsdf_lattice_ok(nx, ny, nz)) return fail(-1, "tsdf_mesh_emit: lattice %d x %d x %d (every size at least 2, at most 2^30 samples)", nx, ny, nz);
+  if (!tsdf_w || !rgb_w || !origin || !work || !counters || (!rows && vcap) || (!triangles && tcap))
+    return fail(-1, "tsdf_mesh_emit: NULL argument (tsdf_w, rgb_w, origin, work and counters are required; rows and triangles unless their cap is 0)");
+  if (!(voxel > 0.0) || !isfinite(voxel)) return fail(-1, "tsdf_mesh_emit: voxel = %g (must be finite and positive)", voxel);
+  if (!tsdf_origin_ok(origin)) return fail(-1, "tsdf_mesh_emit: the origin must be finite");
+  if (((uintptr_t)rgb_w | (uintptr_t)rows) & 15) return fail(-1, "tsdf_mesh_emit: rgb_w and rows must be 16-byte aligned");
+  if (((uintptr_t)tsdf_w | (uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "tsdf_mesh_emit: tsdf_w, work and counters must be 8-byte aligned");
+  if ((uintptr_t)triangles & 3) return fail(-1, "tsdf_mesh_emit: triangles must be 4-byte aligned");
+  launch_tsdf_mesh_emit(nx, ny, nz, tsdf_w, rgb_w, origin, voxel, work, rows, vcap, triangles, tcap, counters, (hipStream_t)stream);
+  return check_launch("tsdf_mesh_emit");
+}
+
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
                         float* out_color, float* out_depth_or_null, void* stream) {
   if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);

@@ -139,6 +139,22 @@ struct PointCloudView {
 size_t pointcloud_work_bytes(int H, int W);
 void launch_pointcloud_reset(void* table, uint64_t slots, uint64_t* counters, hipStream_t s);
 void launch_pointcloud_add_view(const PointCloudView& v, void* rows, uint64_t cap, uint64_t* counters, void* work, hipStream_t s);
+// coloured triangle mesh (tsdf.hip): one view fused into the caller's dense volume (tsdf_w float2, rgb_w float4 over nx x ny x nz samples at
+// o + voxel (i, j, k), x fastest), and marching tetrahedra over it in two calls (plan: counts and bases into work = the buffer of
+// tsdf_mesh_work_bytes; emit: rows and triangles); every size >= 2 and nx ny nz <= 2^30, as the entry points have checked
+struct TsdfView {
+  int H, W;
+  double fx, fy, cx, cy;
+  const float* pose; const float* color; const float* depth; const float* sil;
+  float sil_min, depth_max;
+  double o[3], voxel, trunc;
+  int nx, ny, nz;
+};
+size_t tsdf_mesh_work_bytes(int nx, int ny, int nz);
+void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_t* counters, hipStream_t s);
+void launch_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s);
+void launch_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void* rgb_w, const double* origin, double voxel, const void* work, void* rows,
+                           uint64_t vcap, void* tris, uint64_t tcap, uint64_t* counters, hipStream_t s);
 // frame ingest (ingest.hip): raw uint8 RGB [Hs,Ws,3] + uint16 depth [Hs,Ws] -> colour [3,H,W] in [0,1] + depth [H,W] in metres, one
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,

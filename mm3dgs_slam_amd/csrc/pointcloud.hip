@@ -19,6 +19,7 @@
 #include <math.h>
 #include "compact_scan.h"
 #include "fused_api.h"
+#include "view_pixel.h"      // PcRigid / pc_rigid, view_pixel_valid, pc_quant (shared with tsdf.hip)
 
 #define PB 256
 #define PC_MAX_PROBE 128                 // slots a point may inspect; the table is sized for a load of at most 1/2
@@ -33,8 +34,6 @@ size_t pointcloud_work_bytes(int H, int W) {
   const size_t n = (size_t)H * (size_t)W;
   return 256 + pc_flag_bytes(n) + 4 * pc_count_bytes(n);
 }
-
-struct PcRigid { double R[3][3], t[3]; };
 
 struct PcPoint { float x, y, z; };
 
@@ -52,25 +51,9 @@ __device__ __forceinline__ PcPoint pc_backproject(const PointCloudView& v, const
   return p;
 }
 
-__device__ __forceinline__ PcRigid pc_rigid(const float* __restrict__ pose) {
-#pragma clang fp contract(off)
-  PcRigid o;
-  double w = pose[0], x = pose[1], y = pose[2], z = pose[3];
-  const double n = sqrt(w * w + x * x + y * y + z * z);
-  w /= n; x /= n; y /= n; z /= n;
-  o.R[0][0] = 1.0 - 2.0 * (y * y + z * z); o.R[0][1] = 2.0 * (x * y - w * z); o.R[0][2] = 2.0 * (x * z + w * y);
-  o.R[1][0] = 2.0 * (x * y + w * z); o.R[1][1] = 1.0 - 2.0 * (x * x + z * z); o.R[1][2] = 2.0 * (y * z - w * x);
-  o.R[2][0] = 2.0 * (x * z - w * y); o.R[2][1] = 2.0 * (y * z + w * x); o.R[2][2] = 1.0 - 2.0 * (x * x + y * y);
-  o.t[0] = pose[4]; o.t[1] = pose[5]; o.t[2] = pose[6];
-  return o;
-}
-
-// strict float32 tests on the inputs: NaN fails every one of them
+// the pixel test of view_pixel.h on this view's images
 __device__ __forceinline__ bool pc_valid(const PointCloudView& v, int i, float& z) {
-  z = v.depth[i];
-  bool ok = z > 0.f && z < INFINITY && (v.depth_max <= 0.f || z <= v.depth_max);
-  if (ok && v.sil) ok = v.sil[i] > v.sil_min;
-  return ok;
+  return view_pixel_valid(v.depth, v.sil, v.sil_min, v.depth_max, (size_t)i, z);
 }
 
 // voxel key of a stored position; false: some |cell| >= 2^20 (or not a number)
@@ -82,13 +65,6 @@ __device__ __forceinline__ bool pc_key(const PcPoint& p, double voxel, uint64_t&
 }
 
 __device__ __forceinline__ uint64_t pc_hash(uint64_t key, int shift) { return (key * 0x9E3779B97F4A7C15ull) >> shift; }
-
-__device__ __forceinline__ uint32_t pc_quant(float c) {
-#pragma clang fp contract(off)
-  c = c > 0.f ? c : 0.f;      // NaN -> 0
-  c = c < 1.f ? c : 1.f;
-  return (uint32_t)(uint8_t)(c * 255.0f + 0.5f);
-}
 
 __global__ void __launch_bounds__(PB) pc_claim_kernel(PointCloudView v) {
   const int n = v.H * v.W;

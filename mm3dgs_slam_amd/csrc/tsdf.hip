@@ -1,0 +1,359 @@
+// The reconstruction as a coloured triangle mesh (mm3dgs_tsdf_integrate / mm3dgs_tsdf_mesh_plan / mm3dgs_tsdf_mesh_emit; host statement:
+// mesh.integrate_host / mesh.mesh_host).  The volume is the caller's: tsdf_w float2 [nz][ny][nx] {truncated distance in [-1, 1], weight} and
+// rgb_w float4 [nz][ny][nx] {mean colour, colour weight} over a lattice of sample points origin + voxel (i, j, k), x fastest; zeros = empty.
+//
+//   tsdf_integrate_kernel   one launch per view, one lane per sample and slice, 64 consecutive x per wave (workgroup = 64 x by 4 y, walking
+//                           up to 8 z slices).  The sample is projected into the view in double (no contraction, so the host statement
+//                           rounds alike); z <= 0, a pixel outside the image or one that fails the point cloud's validity test
+//                           (view_pixel.h), or sdf < -trunc end the sample before anything is loaded from the volume: free space outside
+//                           the frustum costs arithmetic only.  Running means, rounded to float32 once at the 8- and 16-byte stores.
+//                           Counters: one integer add per workgroup and counter (with one per wave and slice, all of them on one word,
+//                           the adds were what a view cost: 832 us against 86 us over 256^3 samples, profiles/r15_mesh.jsonl).
+//   marching tetrahedra     every cube is cut into the six Kuhn tetrahedra (the monotone corner paths 0 -> 7, one per axis permutation),
+//                           the same cut in every cube.  Plan: tm_state (known / inside bits per sample), tm_cube (valid cubes and their
+//                           triangle counts), tm_edge (per sample the 7-bit mask of the directions d whose edge (q, d) carries a vertex:
+//                           endpoints differ in `inside` and one of the up to four cubes around the edge is valid -- gathered, no atomic),
+//                           tm_scan (one workgroup: scan_block_counts over both per-256 counts, the totals), tm_base (per-sample vertex base
+//                           and per-cube triangle base).  Emit: tm_vertex (one 16-byte row per vertex at base[q] + popcount(mask[q] below d)),
+//                           tm_triangle (int32[3] per triangle, by tetrahedron then case order).  No atomic decides a position or an index.
+#include <math.h>
+#include "compact_scan.h"
+#include "fused_api.h"
+#include "view_pixel.h"
+
+#define TB 256
+
+// ---- integration ----------------------------------------------------------------------------------------------------------------
+#define TZ 8      // z slices per workgroup: one add per workgroup and counter instead of one per wave and slice (every add lands on the same word)
+
+__global__ void __launch_bounds__(TB)
+tsdf_integrate_kernel(TsdfView v, float2* __restrict__ tsdf_w, float4* __restrict__ rgb_w, unsigned long long* __restrict__ counters, unsigned xb,
+                      unsigned yb) {
+#pragma clang fp contract(off)
+  __shared__ PcRigid g;      // the pose is the same for every sample: one lane normalises the quaternion for its workgroup
+  __shared__ uint32_t wsum[2][TB / 64];
+  const unsigned b = blockIdx.x;
+  const int i = (int)(b % xb) * 64 + (int)(threadIdx.x & 63);
+  const int j = (int)((b / xb) % yb) * 4 + (int)(threadIdx.x >> 6);
+  const int k0 = (int)(b / (xb * yb)) * TZ;
+  if (threadIdx.x == 0) g = pc_rigid(v.pose);
+  __syncthreads();
+  uint32_t nupd = 0, ncup = 0;
+  if (i < v.nx && j < v.ny) {
+    const size_t hw = (size_t)v.H * (size_t)v.W;
+    const double pw0 = v.o[0] + v.voxel * (double)i, pw1 = v.o[1] + v.voxel * (double)j;
+    for (int k = k0; k < k0 + TZ && k < v.nz; k++) {
+      const double pw2 = v.o[2] + v.voxel * (double)k;
+      const double z = g.R[2][0] * pw0 + g.R[2][1] * pw1 + g.R[2][2] * pw2 + g.t[2];
+      if (!(z > 0.0)) continue;
+      const double x = g.R[0][0] * pw0 + g.R[0][1] * pw1 + g.R[0][2] * pw2 + g.t[0];
+      const double y = g.R[1][0] * pw0 + g.R[1][1] * pw1 + g.R[1][2] * pw2 + g.t[1];
+      const double fu = floor(v.fx * x / z + v.cx + 0.5), fv = floor(v.fy * y / z + v.cy + 0.5);
+      if (!(fu >= 0.0 && fu < (double)v.W && fv >= 0.0 && fv < (double)v.H)) continue;      // (a NaN fails)
+      const size_t pix = (size_t)(int)fv * (size_t)v.W + (size_t)(int)fu;
+      float d;
+      if (!view_pixel_valid(v.depth, v.sil, v.sil_min, v.depth_max, pix, d)) continue;
+      const double sdf = (double)d - z;
+      if (sdf < -v.trunc) continue;
+      // the sample is seen: from here on the volume is read and written
+      double s = sdf / v.trunc;
+      s = s < 1.0 ? s : 1.0;
+      const size_t q = ((size_t)k * (size_t)v.ny + (size_t)j) * (size_t)v.nx + (size_t)i;
+      const float2 tw = tsdf_w[q];
+      const double T = (double)tw.x, W = (double)tw.y;
+      tsdf_w[q] = make_float2((float)((T * W + s) / (W + 1.0)), (float)(W + 1.0));      // one 8-byte store
+      nupd++;
+      if (sdf <= v.trunc) {
+        const float4 c = rgb_w[q];
+        const double Cw = (double)c.w;
+        rgb_w[q] = make_float4((float)(((double)c.x * Cw + (double)v.color[pix]) / (Cw + 1.0)), (float)(((double)c.y * Cw + (double)v.color[hw + pix]) / (Cw + 1.0)),
+                               (float)(((double)c.z * Cw + (double)v.color[2 * hw + pix]) / (Cw + 1.0)), (float)(Cw + 1.0));      // one 16-byte store
+        ncup++;
+      }
+    }
+  }
+  const uint32_t su = wave_scan_incl(nupd), sc = wave_scan_incl(ncup);      // (every lane is here)
+  if ((threadIdx.x & 63) == 63) { wsum[0][threadIdx.x >> 6] = su; wsum[1][threadIdx.x >> 6] = sc; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t tu = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3], tc = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
+    if (tu) atomicAdd(counters + 1, (unsigned long long)tu);
+    if (tc) atomicAdd(counters + 2, (unsigned long long)tc);
+    if (b == 0) atomicAdd(counters, 1ull);
+  }
+}
+
+void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_t* counters, hipStream_t s) {
+  const unsigned xb = (unsigned)((v.nx + 63) / 64), yb = (unsigned)((v.ny + 3) / 4), zb = (unsigned)((v.nz + TZ - 1) / TZ);
+  const size_t nb = (size_t)xb * yb * zb;      // <= 2^30 / 2 / 2: within the grid's 2^31 - 1
+  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)nb), dim3(TB), 0, s, v, (float2*)tsdf_w, (float4*)rgb_w, (unsigned long long*)counters, xb, yb);
+}
+
+// ---- marching tetrahedra --------------------------------------------------------------------------------------------------------
+// work = [256 B header: uint64 vertices, triangles][state byte per sample: bit 0 known, bit 1 inside][cube byte per sample: 0x80 valid | triangles]
+//        [edge mask byte per sample: bit d][uint32 vertex base per sample][uint32 triangle base per cube][per-256 vertex counts][per-256 triangle counts]
+struct TmWork { unsigned long long* hdr; uint8_t* state; uint8_t* cube; uint8_t* vmask; uint32_t* vbase; uint32_t* tbase; uint32_t* vcounts; uint32_t* tcounts; };
+static size_t tm_nb(size_t n) { return (n + TB - 1) / TB; }
+size_t tsdf_mesh_work_bytes(int nx, int ny, int nz) {
+  const size_t n = (size_t)nx * (size_t)ny * (size_t)nz;
+  return 256 + 3 * align_up(n, 256) + 2 * align_up(n * 4, 256) + 2 * align_up(tm_nb(n) * 4, 256);
+}
+static TmWork tm_work(void* base, size_t n) {
+  char* c = (char*)base;
+  TmWork w;
+  w.hdr = (unsigned long long*)c;  c += 256;
+  w.state = (uint8_t*)c;           c += align_up(n, 256);
+  w.cube = (uint8_t*)c;            c += align_up(n, 256);
+  w.vmask = (uint8_t*)c;           c += align_up(n, 256);
+  w.vbase = (uint32_t*)c;          c += align_up(n * 4, 256);
+  w.tbase = (uint32_t*)c;          c += align_up(n * 4, 256);
+  w.vcounts = (uint32_t*)c;        c += align_up(tm_nb(n) * 4, 256);
+  w.tcounts = (uint32_t*)c;
+  return w;
+}
+
+struct TmGrid { int nx, ny, nz; size_t n; };
+
+// The triangles of a positively oriented tetrahedron by its 4-bit inside mask (bit v: vertex v of the path is inside), as
+// count | six 3-bit edge ids << 2; edges 0..5 = the vertex pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  One vertex apart: the triangle of its
+// three edges; two and two: the quadrilateral (a,c) (a,d) (b,d) (b,c) as two triangles; wound so that the normal points from the inside
+// vertices to the outside ones (mesh.py derives the same table by rule and checks the winding numerically).
+#define TM1(a, b, c) (1u | (a##u << 2) | (b##u << 5) | (c##u << 8))
+#define TM2(a, b, c, d, e, f) (2u | (a##u << 2) | (b##u << 5) | (c##u << 8) | (d##u << 11) | (e##u << 14) | (f##u << 17))
+__device__ const uint32_t TM_CASES[16] = {0u, TM1(0, 1, 2), TM1(0, 4, 3), TM2(1, 2, 4, 1, 4, 3), TM1(1, 3, 5), TM2(0, 5, 2, 0, 3, 5), TM2(0, 4, 5, 0, 5, 1),
+                                          TM1(2, 4, 5), TM1(2, 5, 4), TM2(0, 1, 5, 0, 5, 4), TM2(0, 5, 3, 0, 2, 5), TM1(1, 5, 3), TM2(1, 3, 4, 1, 4, 2),
+                                          TM1(0, 3, 4), TM1(0, 2, 1), 0u};
+// cube corners (bit 0 x, bit 1 y, bit 2 z) of the path's two middle vertices, by tetrahedron = axis permutation in lexicographic order:
+// (x,y,z) (x,z,y) (y,x,z) (y,z,x) (z,x,y) (z,y,x); the odd permutations (1, 2, 5) mirror the tetrahedron: their triangles swap two corners
+__device__ const uint8_t TM_MID1[6] = {1, 1, 2, 2, 4, 4};
+__device__ const uint8_t TM_MID2[6] = {3, 5, 3, 6, 5, 6};
+#define TM_ODD 0x26u
+__device__ const uint8_t TM_EDGE_LO[6] = {0, 0, 0, 1, 1, 2};
+__device__ const uint8_t TM_EDGE_HI[6] = {1, 2, 3, 2, 3, 3};
+
+__device__ __forceinline__ size_t tm_corner(const TmGrid& g, unsigned c) {
+  return (size_t)(c & 1u) + (size_t)((c >> 1) & 1u) * (size_t)g.nx + (size_t)((c >> 2) & 1u) * (size_t)g.nx * (size_t)g.ny;
+}
+
+__device__ __forceinline__ void tm_coords(const TmGrid& g, size_t i, int& x, int& y, int& z) {
+  x = (int)(i % (size_t)g.nx);
+  y = (int)((i / (size_t)g.nx) % (size_t)g.ny);
+  z = (int)(i / ((size_t)g.nx * (size_t)g.ny));
+}
+
+// inclusive scan of v over the workgroup of TB lanes (every lane calls); wtot: TB / 64 words of LDS
+__device__ __forceinline__ uint32_t tm_block_scan(uint32_t v, uint32_t* wtot) {
+  const uint32_t x = wave_scan_incl(v);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 63) wtot[wv] = x;
+  __syncthreads();
+  uint32_t pre = 0;
+  for (int w = 0; w < wv; w++) pre += wtot[w];
+  return pre + x;
+}
+
+__global__ void __launch_bounds__(TB) tm_state_kernel(TmGrid g, const float2* __restrict__ tsdf_w, float min_weight, uint8_t* __restrict__ state) {
+  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+  if (i >= g.n) return;
+  const float2 tw = tsdf_w[i];
+  state[i] = (uint8_t)((tw.y >= min_weight ? 1 : 0) | (tw.x < 0.f ? 2 : 0));      // (a NaN weight is not known)
+}
+
+// the 8 corner states of the cube with origin i: all known -> valid; the inside bits by corner number
+__device__ __forceinline__ bool tm_cube_corners(const TmGrid& g, const uint8_t* __restrict__ state, size_t i, unsigned& inside) {
+  unsigned known = 1;
+  inside = 0;
+  for (unsigned c = 0; c < 8; c++) {
+    const unsigned s = state[i + tm_corner(g, c)];
+    known &= s;
+    inside |= ((s >> 1) & 1u) << c;
+  }
+  return (known & 1u) != 0;
+}
+
+__device__ __forceinline__ unsigned tm_tet_mask(unsigned inside, int k) {
+  return (inside & 1u) | (((inside >> TM_MID1[k]) & 1u) << 1) | (((inside >> TM_MID2[k]) & 1u) << 2) | (((inside >> 7) & 1u) << 3);
+}
+
+__global__ void __launch_bounds__(TB) tm_cube_kernel(TmGrid g, const uint8_t* __restrict__ state, uint8_t* __restrict__ cube, uint32_t* __restrict__ tcounts) {
+  __shared__ uint32_t wtot[TB / 64];
+  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+  uint32_t ntri = 0;
+  uint8_t out = 0;
+  if (i < g.n) {
+    int x, y, z;
+    tm_coords(g, i, x, y, z);
+    unsigned inside;
+    if (x < g.nx - 1 && y < g.ny - 1 && z < g.nz - 1 && tm_cube_corners(g, state, i, inside)) {
+      for (int k = 0; k < 6; k++) ntri += TM_CASES[tm_tet_mask(inside, k)] & 3u;
+      out = (uint8_t)(0x80u | ntri);
+    }
+    cube[i] = out;
+  }
+  const uint32_t incl = tm_block_scan(ntri, wtot);
+  if (threadIdx.x == TB - 1) tcounts[blockIdx.x] = incl;
+}
+
+__global__ void __launch_bounds__(TB)
+tm_edge_kernel(TmGrid g, const uint8_t* __restrict__ state, const uint8_t* __restrict__ cube, uint8_t* __restrict__ vmask, uint32_t* __restrict__ vcounts) {
+  __shared__ uint32_t wtot[TB / 64];
+  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+  unsigned mask = 0;
+  if (i < g.n) {
+    int x, y, z;
+    tm_coords(g, i, x, y, z);
+    const unsigned in0 = (state[i] >> 1) & 1u;
+    // valid cubes with origin q - e, e in {0,1}^3 (bit e of `around`); a cube beyond the lattice is not valid
+    unsigned around = 0;
+    for (unsigned e = 0; e < 8; e++) {
+      if (((e & 1u) && x == 0) || ((e & 2u) && y == 0) || ((e & 4u) && z == 0)) continue;
+      around |= (unsigned)(cube[i - tm_corner(g, e)] >> 7) << e;
+    }
+    for (unsigned d = 1; d < 8; d++) {
+      if (((d & 1u) && x == g.nx - 1) || ((d & 2u) && y == g.ny - 1) || ((d & 4u) && z == g.nz - 1)) continue;
+      // the cubes that contain the edge (q, d): origins q - e with e inside the zero bits of d
+      unsigned near = 0;
+      for (unsigned e = 0; e < 8; e++)
+        if (!(e & d)) near |= (around >> e) & 1u;
+      const unsigned in1 = (state[i + tm_corner(g, d)] >> 1) & 1u;
+      if (near && in0 != in1) mask |= 1u << d;
+    }
+    vmask[i] = (uint8_t)mask;
+  }
+  const uint32_t incl = tm_block_scan((uint32_t)__popc(mask), wtot);
+  if (threadIdx.x == TB - 1) vcounts[blockIdx.x] = incl;
+}
+
+__global__ void __launch_bounds__(1024)
+tm_scan_kernel(int nb, uint32_t* __restrict__ vcounts, uint32_t* __restrict__ tcounts, unsigned long long* __restrict__ hdr, unsigned long long* __restrict__ counters) {
+  __shared__ uint32_t totals[2];
+  scan_block_counts(nb, vcounts, &totals[0]);
+  __syncthreads();
+  scan_block_counts(nb, tcounts, &totals[1]);
+  if (threadIdx.x == 0) {      // (lane 0 wrote both totals itself)
+    hdr[0] = totals[0];
+    hdr[1] = totals[1];
+    counters[0] = totals[0];
+    counters[1] = totals[1];
+  }
+  if (threadIdx.x >= 2 && threadIdx.x < 8) counters[threadIdx.x] = 0ull;
+}
+
+__global__ void __launch_bounds__(TB)
+tm_base_kernel(TmGrid g, const uint8_t* __restrict__ cube, const uint8_t* __restrict__ vmask, const uint32_t* __restrict__ vpre, const uint32_t* __restrict__ tpre,
+               uint32_t* __restrict__ vbase, uint32_t* __restrict__ tbase) {
+  __shared__ uint32_t wv[TB / 64], wt[TB / 64];
+  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+  const uint32_t nv = i < g.n ? (uint32_t)__popc((unsigned)vmask[i]) : 0u, nt = i < g.n ? (uint32_t)(cube[i] & 0x7fu) : 0u;
+  const uint32_t iv = tm_block_scan(nv, wv), it = tm_block_scan(nt, wt);
+  if (i < g.n) {
+    vbase[i] = vpre[blockIdx.x] + iv - nv;
+    tbase[i] = tpre[blockIdx.x] + it - nt;
+  }
+}
+
+void launch_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s) {
+  TmGrid g;
+  g.nx = nx; g.ny = ny; g.nz = nz; g.n = (size_t)nx * (size_t)ny * (size_t)nz;
+  const TmWork w = tm_work(work, g.n);
+  const unsigned nb = (unsigned)tm_nb(g.n);
+  hipLaunchKernelGGL(tm_state_kernel, dim3(nb), dim3(TB), 0, s, g, (const float2*)tsdf_w, min_weight, w.state);
+  hipLaunchKernelGGL(tm_cube_kernel, dim3(nb), dim3(TB), 0, s, g, w.state, w.cube, w.tcounts);
+  hipLaunchKernelGGL(tm_edge_kernel, dim3(nb), dim3(TB), 0, s, g, w.state, w.cube, w.vmask, w.vcounts);
+  hipLaunchKernelGGL(tm_scan_kernel, dim3(1), dim3(1024), 0, s, (int)nb, w.vcounts, w.tcounts, w.hdr, (unsigned long long*)counters);
+  hipLaunchKernelGGL(tm_base_kernel, dim3(nb), dim3(TB), 0, s, g, w.cube, w.vmask, w.vcounts, w.tcounts, w.vbase, w.tbase);
+}
+
+struct TmEmit { double o[3], voxel; unsigned long long vcap, tcap; };
+
+__global__ void __launch_bounds__(TB)
+tm_vertex_kernel(TmGrid g, TmEmit e, const float2* __restrict__ tsdf_w, const float4* __restrict__ rgb_w, const uint8_t* __restrict__ vmask,
+                 const uint32_t* __restrict__ vbase, const unsigned long long* __restrict__ hdr, uint4* __restrict__ rows, unsigned long long* __restrict__ counters) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+  if (i == 0) {      // the counts of this emit: what the caps let through (the triangle kernel adds its two behind the kernel boundary)
+    const unsigned long long V = hdr[0], written = V < e.vcap ? V : e.vcap;
+    counters[2] = written;
+    counters[3] = 0ull;
+    counters[4] = V - written;
+    counters[5] = 0ull;
+  }
+  if (i >= g.n) return;
+  const unsigned mask = vmask[i];
+  if (!mask) return;
+  int q[3];
+  tm_coords(g, i, q[0], q[1], q[2]);
+  const double T0 = (double)tsdf_w[i].x;
+  const float4 c0 = rgb_w[i];
+  unsigned long long r = vbase[i];
+  for (unsigned d = 1; d < 8; d++) {
+    if (!((mask >> d) & 1u)) continue;
+    if (r < e.vcap) {
+      const size_t j = i + tm_corner(g, d);
+      const double T1 = (double)tsdf_w[j].x;
+      const float4 c1 = rgb_w[j];
+      const double t = T0 / (T0 - T1);
+      const float px = (float)(e.o[0] + e.voxel * ((double)q[0] + t * (double)(d & 1u)));
+      const float py = (float)(e.o[1] + e.voxel * ((double)q[1] + t * (double)((d >> 1) & 1u)));
+      const float pz = (float)(e.o[2] + e.voxel * ((double)q[2] + t * (double)((d >> 2) & 1u)));
+      const float cr = (float)((double)c0.x + t * ((double)c1.x - (double)c0.x));
+      const float cg = (float)((double)c0.y + t * ((double)c1.y - (double)c0.y));
+      const float cb = (float)((double)c0.z + t * ((double)c1.z - (double)c0.z));
+      rows[r] = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), pc_quant(cr) | (pc_quant(cg) << 8) | (pc_quant(cb) << 16) | 0xff000000u);
+    }
+    r++;
+  }
+}
+
+__global__ void __launch_bounds__(TB)
+tm_triangle_kernel(TmGrid g, TmEmit e, const uint8_t* __restrict__ state, const uint8_t* __restrict__ cube, const uint8_t* __restrict__ vmask,
+                   const uint32_t* __restrict__ vbase, const uint32_t* __restrict__ tbase, int* __restrict__ tris, unsigned long long* __restrict__ counters) {
+  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+  uint32_t written = 0, dropped = 0;
+  if (i < g.n && (cube[i] & 0x7fu)) {      // (a cube with triangles is valid and inside the lattice)
+    unsigned inside;
+    tm_cube_corners(g, state, i, inside);
+    unsigned long long r = tbase[i];
+    for (int k = 0; k < 6; k++) {
+      const uint32_t cs = TM_CASES[tm_tet_mask(inside, k)];
+      const unsigned corner[4] = {0u, TM_MID1[k], TM_MID2[k], 7u};
+      for (uint32_t s = 0; s < (cs & 3u); s++) {
+        uint32_t idx[3];
+        for (int a = 0; a < 3; a++) {
+          const unsigned edge = (cs >> (2 + 9 * s + 3 * a)) & 7u;
+          const unsigned lo = corner[TM_EDGE_LO[edge]], hi = corner[TM_EDGE_HI[edge]];
+          const size_t smp = i + tm_corner(g, lo);
+          idx[a] = vbase[smp] + (uint32_t)__popc((unsigned)vmask[smp] & ((1u << (hi ^ lo)) - 1u));
+        }
+        if ((TM_ODD >> k) & 1u) { const uint32_t t = idx[1]; idx[1] = idx[2]; idx[2] = t; }
+        if (r < e.tcap && idx[0] < e.vcap && idx[1] < e.vcap && idx[2] < e.vcap) {
+          tris[3 * r] = (int)idx[0];
+          tris[3 * r + 1] = (int)idx[1];
+          tris[3 * r + 2] = (int)idx[2];
+          written++;
+        } else {
+          dropped++;
+        }
+        r++;
+      }
+    }
+  }
+  const uint32_t sw = wave_scan_incl(written), sd = wave_scan_incl(dropped);
+  if ((threadIdx.x & 63) == 63) {
+    if (sw) atomicAdd(counters + 3, (unsigned long long)sw);
+    if (sd) atomicAdd(counters + 5, (unsigned long long)sd);
+  }
+}
+
+void launch_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void* rgb_w, const double* origin, double voxel, const void* work, void* rows,
+                           uint64_t vcap, void* tris, uint64_t tcap, uint64_t* counters, hipStream_t s) {
+  TmGrid g;
+  g.nx = nx; g.ny = ny; g.nz = nz; g.n = (size_t)nx * (size_t)ny * (size_t)nz;
+  const TmWork w = tm_work((void*)work, g.n);
+  TmEmit e;
+  e.o[0] = origin[0]; e.o[1] = origin[1]; e.o[2] = origin[2]; e.voxel = voxel; e.vcap = vcap; e.tcap = tcap;
+  const unsigned nb = (unsigned)tm_nb(g.n);
+  hipLaunchKernelGGL(tm_vertex_kernel, dim3(nb), dim3(TB), 0, s, g, e, (const float2*)tsdf_w, (const float4*)rgb_w, w.vmask, w.vbase, w.hdr, (uint4*)rows,
+                     (unsigned long long*)counters);
+  hipLaunchKernelGGL(tm_triangle_kernel, dim3(nb), dim3(TB), 0, s, g, e, w.state, w.cube, w.vmask, w.vbase, w.tbase, (int*)tris, (unsigned long long*)counters);
+}

@@ -12,7 +12,8 @@ sources: ``SyntheticSequence`` here, recorded TUM / UT-MM directories in ``datas
 monocular depth network and LPIPS (a downloaded network; its list stays empty) are out of scope.  Debug outputs
 (``debug_frames.py``): ``debug.create_video`` writes the reference's per-frame 2 x 3 mosaic (``:233-276,450-485``) as numbered PNG files under
 ``outputdir/debug_video/``, ``debug.save_keyframes`` one PNG per keyframe (mapper.py), ``render()`` the image-over-depth pairs of ``:148-195``.  ``pointcloud.export`` / ``export_pointcloud()``
-(``pointcloud.py``): the reconstruction as a fused coloured point cloud and the camera path, ``outputdir/pointcloud/cloud.ply`` + ``trajectory.ply``."""
+(``pointcloud.py``): the reconstruction as a fused coloured point cloud and the camera path, ``outputdir/pointcloud/cloud.ply`` + ``trajectory.ply``;
+``mesh.export`` / ``export_mesh()`` (``mesh.py``): the same views fused into a truncated signed distance volume and meshed, ``outputdir/mesh/mesh.ply``."""
 from __future__ import annotations
 
 import math
@@ -238,6 +239,7 @@ class SLAM:
             raise ValueError("eval_on_device needs a CUDA device (there is no CPU kernel); use eval_on_device: false")
         self.frame_sink = None      # debug.create_video: the PNG writer of outputdir/debug_video, opened by the first frame, closed by run()
         self.pointcloud_export = None      # pointcloud.export: the paths and counters of the last export_pointcloud()
+        self.mesh_export = None            # mesh.export: the path, counters and lattice of the last export_mesh()
         if resume is not None:
             dev = cfg["device"]
             for i, p in enumerate(resume["pose_est"][:n]):
@@ -321,6 +323,23 @@ class SLAM:
                     df.save_png(df.compose([(df.COLOR, color, None), (df.DEPTH, depth, None)], 2, 1, quant=1, bgr=False), written[-1])
         return written
 
+    def _export_views(self, every, source, block):
+        """The views of an export (`pointcloud`, `mesh`), one (color [3,H,W], depth [H,W], silhouette [H,W] or None, pose [7]) per frame with
+        `idx % every == 0` that has an estimated pose: `source` "render": the map rendered at that pose with its rendered silhouette;
+        "sensor": the frame's own colour and sensor depth."""
+        for idx in range(len(self.seq)):
+            pose = self.estimate_pose_list[idx]
+            if pose is None or idx % every != 0:
+                continue
+            if source == "render":
+                result = self.renderer.render(self.gaussians, camera_pose=pose)
+                yield result["render"], result["depth"][0], result["depth"][1], pose
+            else:
+                color, depth, _ = self.seq[idx]
+                if depth is None:
+                    raise ValueError(f'{block}.source "sensor": frame {idx} has no sensor depth')
+                yield color, depth, None, pose
+
     def export_pointcloud(self, path=None, every=None, voxel=None, source=None):
         """The reconstruction as a fused coloured point cloud (pointcloud.py; the core of the reference's scripts/visualizer.py): for every
         frame with `idx % every == 0` that has an estimated pose one view at that pose -- `source` "render": the map rendered there, with
@@ -345,23 +364,10 @@ class SLAM:
         Builder = pc.PointCloudBuilder if on_device else pc.HostPointCloudBuilder
         builder = Builder(H, W, self.cfg["cam"], voxel=voxel, max_points=int(opt["max_points"]), sil_min=float(opt["sil_min"]),
                           depth_max=float(opt["max_depth"]), device=self.cfg["device"])
-        poses = []
+        poses = [pose.detach() for pose in self.estimate_pose_list[:len(self.seq)] if pose is not None]
         with torch.no_grad():
-            for idx in range(len(self.seq)):
-                pose = self.estimate_pose_list[idx]
-                if pose is None:
-                    continue
-                poses.append(pose.detach())
-                if idx % every != 0:
-                    continue
-                if source == "render":
-                    result = self.renderer.render(self.gaussians, camera_pose=pose)
-                    builder.add(result["render"], result["depth"][0], result["depth"][1], pose)
-                else:
-                    color, depth, _ = self.seq[idx]
-                    if depth is None:
-                        raise ValueError(f'pointcloud.source "sensor": frame {idx} has no sensor depth')
-                    builder.add(color, depth, None, pose)
+            for view in self._export_views(every, source, "pointcloud"):
+                builder.add(*view)
         counters = builder.finish()
         os.makedirs(path, exist_ok=True)
         out = {"cloud": pc.write_ply(os.path.join(path, "cloud.ply"), builder.rows()),
@@ -369,6 +375,92 @@ class SLAM:
                "counters": counters}
         self.pointcloud_export = out      # what the last export wrote (run() calls this without a caller to hand it to)
         print(f"Point cloud: {counters['rows']} points from {counters['views']} views ({counters['valid']} valid pixels, voxel {voxel} m) in {out['cloud']}")
+        return out
+
+    def _mesh_bounds(self, every, source, sil_min, depth_max):
+        """The box [xmin, ymin, zmin, xmax, ymax, zmax] of the lifted valid points of an export's views (the point cloud's validity test and
+        back-projection, here with torch operators in float64); its six numbers are read back once, after the last view."""
+        cam = self.cfg["cam"]
+        lo = hi = None
+        for color, depth, sil, pose in self._export_views(every, source, "mesh"):
+            d = depth.detach().float()
+            ok = (d > 0) & torch.isfinite(d)
+            if depth_max > 0:
+                ok &= d <= depth_max
+            if sil is not None:
+                ok &= sil.detach().float() > sil_min
+            H, W = d.shape
+            v, u = torch.meshgrid(torch.arange(H, device=d.device, dtype=torch.float64), torch.arange(W, device=d.device, dtype=torch.float64), indexing="ij")
+            z = d.double()
+            p = pose.detach().double().reshape(7)
+            q = p[:4] / p[:4].norm()
+            w, x, y, zz = q[0], q[1], q[2], q[3]
+            R = torch.stack([torch.stack([1 - 2 * (y * y + zz * zz), 2 * (x * y - w * zz), 2 * (x * zz + w * y)]),
+                             torch.stack([2 * (x * y + w * zz), 1 - 2 * (x * x + zz * zz), 2 * (y * zz - w * x)]),
+                             torch.stack([2 * (x * zz - w * y), 2 * (y * zz + w * x), 1 - 2 * (x * x + y * y)])])
+            pc_ = torch.stack([(u - float(cam["cx"])) / float(cam["fx"]) * z, (v - float(cam["cy"])) / float(cam["fy"]) * z, z], -1).reshape(-1, 3)
+            pw = (pc_ - p[4:]) @ R                      # rows: R^T (p_c - t)
+            m = ok.reshape(-1, 1)
+            inf = torch.tensor(float("inf"), device=d.device, dtype=torch.float64)
+            a, b = torch.where(m, pw, inf).amin(0), torch.where(m, pw, -inf).amax(0)
+            lo, hi = (a, b) if lo is None else (torch.minimum(lo, a), torch.maximum(hi, b))
+        if lo is None:
+            raise ValueError("mesh export: no frame has an estimated pose")
+        box = torch.cat([lo, hi]).cpu().numpy()          # the one read-back
+        if not np.isfinite(box).all():
+            raise ValueError("mesh export: no view has a valid pixel (mesh.sil_min, mesh.max_depth)")
+        return box
+
+    def export_mesh(self, path=None, every=None, voxel=None, source=None):
+        """The reconstruction as a coloured triangle mesh (mesh.py): the views of `export_pointcloud` (`every`, `source`) fused into a dense
+        truncated signed distance volume of `mesh.voxel`-sized cells (`mesh.trunc`, 0: 4 voxel) over `mesh.bounds` -- None: a first pass
+        over the same views takes the box of their lifted valid points, which is grown by trunc + voxel, the origin snapped down to a
+        multiple of voxel --, then marching tetrahedra over the samples seen at least `mesh.min_weight` times.  Writes `path/mesh.ply`
+        (default `outputdir/mesh`): binary PLY, `float x y z; uchar red green blue alpha` per vertex, `list uchar int vertex_indices` per
+        face.  One mm3dgs_tsdf_integrate call per view and one mm3dgs_tsdf_mesh_plan / _emit pair on a GPU, the host statement on `device:
+        cpu`.  Returns the path, the counters and the lattice; raises ValueError when the lattice exceeds `mesh.max_voxels`."""
+        from . import mesh as ms
+        from .config import _TUM
+        opt = dict(_TUM["mesh"], **(self.cfg.get("mesh") or {}))
+        every = int(every if every is not None else (opt["every"] or self.cfg["mapping"]["kf_every"]))
+        voxel = float(opt["voxel"] if voxel is None else voxel)
+        source = str(opt["source"] if source is None else source)
+        trunc = float(opt["trunc"]) if float(opt["trunc"] or 0) > 0 else 4.0 * voxel
+        if source not in ("render", "sensor"):
+            raise ValueError(f"mesh.source = {source!r} (render / sensor)")
+        if every < 1:
+            raise ValueError(f"mesh.every = {every} (must be positive)")
+        if not (np.isfinite(voxel) and voxel > 0):
+            raise ValueError(f"mesh.voxel = {voxel} (must be positive)")
+        path = os.path.join(self.cfg["outputdir"], "mesh") if path is None else path
+        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
+        sil_min, depth_max = float(opt["sil_min"]), float(opt["max_depth"])
+        with torch.no_grad():
+            if opt["bounds"] is None:
+                box = self._mesh_bounds(every, source, sil_min, depth_max)
+                box[:3] -= trunc + voxel
+                box[3:] += trunc + voxel
+            else:
+                box = np.asarray(opt["bounds"], dtype=np.float64).reshape(6)
+            origin = np.floor(box[:3] / voxel) * voxel
+            dims = [max(int(np.ceil((box[3 + a] - origin[a]) / voxel)) + 1, 2) for a in range(3)]
+            if dims[0] * dims[1] * dims[2] > min(int(opt["max_voxels"]), ms.MAX_SAMPLES):
+                raise ValueError(f"mesh export: the box {box[:3].tolist()} .. {box[3:].tolist()} at mesh.voxel = {voxel} m is a lattice of "
+                                 f"{dims[0]} x {dims[1]} x {dims[2]} samples, more than mesh.max_voxels = {int(opt['max_voxels'])} (at most 2^30); raise "
+                                 f"mesh.voxel or mesh.max_voxels, or set mesh.bounds")
+            on_device = str(self.cfg["device"]).startswith("cuda")
+            Volume = ms.TsdfVolume if on_device else ms.HostTsdfVolume
+            volume = Volume(dims, origin, voxel, trunc, H, W, self.cfg["cam"], sil_min=sil_min, depth_max=depth_max, min_weight=float(opt["min_weight"]),
+                            device=self.cfg["device"])
+            for view in self._export_views(every, source, "mesh"):
+                volume.add(*view)
+            rows, triangles, counters = volume.extract()
+        os.makedirs(path, exist_ok=True)
+        out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles), "counters": counters, "lattice": tuple(dims),
+               "origin": origin.tolist(), "voxel": voxel, "trunc": trunc}
+        self.mesh_export = out      # what the last export wrote (run() calls this without a caller to hand it to)
+        print(f"Mesh: {counters['vertices']} vertices, {counters['triangles']} triangles from {counters['views']} views "
+              f"(lattice {dims[0]} x {dims[1]} x {dims[2]}, voxel {voxel} m) in {out['mesh']}")
         return out
 
     def run(self, progress=None, reraise=True):
@@ -413,6 +505,11 @@ class SLAM:
                         self.export_pointcloud()
                     except Exception as e4:      # noqa: BLE001
                         print(f"(point cloud export: {e4!r})")
+                if (self.cfg.get("mesh") or {}).get("export", False):            # likewise
+                    try:
+                        self.export_mesh()
+                    except Exception as e5:      # noqa: BLE001
+                        print(f"(mesh export: {e5!r})")
         if self.failure is not None and reraise:
             raise self.failure
 

@@ -27,7 +27,9 @@ the device (`mm3dgs_eval_image`: PSNR, SSIM and the depth L1 against the sensor 
 `depth_l1_list` to `results.npz`.  `--pointcloud` (or `pointcloud.export: true`) adds `pointcloud/cloud.ply`, the reconstruction as a fused coloured
 point cloud (the map rendered at every `pointcloud.every`-th estimated pose, lifted to world points, one point per `pointcloud.voxel`; binary PLY, `float x y z;
 uchar red green blue alpha`), and `pointcloud/trajectory.ply`, the camera path -- the computational core of the reference's scripts/visualizer.py, for MeshLab or
-CloudCompare; `--pointcloud --eval` writes the two files from the checkpoint without running a frame.
+CloudCompare; `--pointcloud --eval` writes the two files from the checkpoint without running a frame.  `--mesh` (or `mesh.export: true`) adds `mesh/mesh.ply`,
+the same views fused into a truncated signed distance volume and meshed by marching tetrahedra (a coloured triangle mesh, binary PLY); `--mesh --eval` likewise
+from the checkpoint.
 
 `--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
 `outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
@@ -121,6 +123,16 @@ def export_pointcloud_checkpoint(cfg, seq, iteration=None):
     return out
 
 
+def export_mesh_checkpoint(cfg, seq, iteration=None):
+    """`--mesh --eval`: the coloured triangle mesh of a finished run from its checkpoint, without running a frame: resumes like
+    `evaluate_checkpoint` and calls `SLAM.export_mesh` with the config's `mesh` block.  Adds `outputdir/mesh/` (mesh.ply) and touches nothing
+    else.  Returns what the export returns."""
+    slam, iteration = resume_checkpoint(cfg, seq, iteration)
+    out = slam.export_mesh()
+    out["iteration"] = iteration
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=None, help="YAML config in the reference's schema")
@@ -129,6 +141,7 @@ def main():
     ap.add_argument("--render", action="store_true", help="after the run, write render / ground-truth image pairs of every 50th frame to outputdir/render")
     ap.add_argument("--eval", action="store_true", help="run no frame: score the finished run in outputdir from its checkpoint (PSNR, SSIM, depth L1 with eval_on_device, ATE RMSE)")
     ap.add_argument("--pointcloud", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the fused coloured point cloud and the camera path to outputdir/pointcloud (the config's `pointcloud` block)")
+    ap.add_argument("--mesh", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the reconstruction as a coloured triangle mesh to outputdir/mesh/mesh.ply (the config's `mesh` block)")
     ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
@@ -152,11 +165,15 @@ def main():
         seq = build_sequence(cfg, args.frames, args.gaussians)
         if args.pointcloud:
             export_pointcloud_checkpoint(cfg, seq, args.iteration)
-        else:
+        if args.mesh:
+            export_mesh_checkpoint(cfg, seq, args.iteration)
+        if not (args.pointcloud or args.mesh):
             evaluate_checkpoint(cfg, seq, args.iteration)
         return
     if args.pointcloud:
         cfg["pointcloud"] = dict(cfg.get("pointcloud") or {}, export=True)
+    if args.mesh:
+        cfg["mesh"] = dict(cfg.get("mesh") or {}, export=True)
     os.makedirs(outdir, exist_ok=True)
     seq = build_sequence(cfg, args.frames, args.gaussians)
     slam = SLAM(cfg, seq)
