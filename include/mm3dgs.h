@@ -575,6 +575,72 @@ int mm3dgs_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void
                           const void* work, void* rows /*[vcap] x 16 bytes*/, uint64_t vcap, void* triangles /*[tcap] x int32[3]*/,
                           uint64_t tcap, uint64_t* counters /*[8], device*/, void* stream);
 
+/* ---- geometry scores: exact truncated nearest-neighbour distances between two point sets, and area-uniform samples of a mesh --------
+ * Host statement: mm3dgs_slam_amd/geometry.py (nn_distances_host, direction_row, sample_mesh_host).  A point set is [n] x 16 bytes
+ * {float x, y, z; uint32 rgba} on the device, 16-byte aligned (the point cloud's rows); only the position is read.
+ *
+ * The grid.  cell index = floor((double)x / cell) - origin_cell per axis, over gx x gy x gz cells, x fastest; origin_cell: host int64[3],
+ * |.| < 2^40; gx gy gz <= 2^26.  The caller takes origin_cell and the sizes from the reference set's bounding box.
+ * mm3dgs_nn_grid_build: counts per cell (integer atomic adds: a count does not depend on order), the exclusive prefix over the cells
+ * (per-256 block scans, then the one-workgroup 1024-wide scan), and the scatter of the positions into cell order.  Outputs: cell_start
+ * uint32 [gx gy gz + 1] (cell c holds the records cell_start[c] .. cell_start[c + 1]); sorted [n_ref] x 16 bytes {float x, y, z; uint32 row
+ * index}, of which the first counters[0] are written -- the order inside a cell depends on the atomics, no result of a query does;
+ * counters uint64[8], not cumulative: [0] rows in the grid, [1] rows skipped for a coordinate that is not finite, [2] finite rows outside
+ * the box (left out too), [3] cells, the rest 0.  work: mm3dgs_nn_grid_work_bytes bytes, 8-byte aligned, contents irrelevant before and
+ * after.  Six launches on `stream`, no host synchronisation.  Nothing outside cell_start, sorted, counters[0:8] and work is written.
+ *
+ * mm3dgs_nn_query: one lane per query row, 256-lane workgroups; grid arguments as they were given to the build.  For a finite query q
+ *   d(q) = min(max_dist, min_p |q - p|), the distance in double from the float32 coordinates: each coordinate widened, then subtracted,
+ *   three squares, a sum, a square root (no fused multiply-add); rounded to float32 once, at the store to dist_out [n_q].
+ *   clamped: the double distance > max_dist (an empty neighbourhood included); the stored value is (float)max_dist.
+ *   within:  the stored float32 value <= (float)threshold.
+ *   a query with a coordinate that is not finite stores NaN, enters no figure and is counted as skipped.
+ * The search visits the cells at Chebyshev ring r = 0, 1, 2, ... around the query's own cell (which may lie outside the grid), clipped to
+ * the grid, and stops after ring r when best <= r cell (every unsearched record is farther: the result is exact), after ring
+ * ceil(max_dist / cell) (at most 2^20), or when no further ring touches the grid; it starts at the first ring that touches the grid.  A
+ * row of cells along x is one range of records, so rings 0 and 1 are nine ranges.  Every loop is bounded by these numbers.
+ * row: double[8] on the device, 8-byte aligned: [0] n scored queries, [1] mean d, [2] rms d, [3] max d, [4] within / n, [5] clamped, [6]
+ * skipped, [7] 0 -- over the stored float32 values widened to double; [1:5] are 0 when n is 0.  Per workgroup one partial row in a fixed lane
+ * order, then one workgroup over the partial rows in a fixed order: no float atomic, the same inputs give the same bytes on every call,
+ * and dist_out does not depend on the order of the reference rows.  work: mm3dgs_nn_query_work_bytes bytes, 8-byte aligned, contents
+ * irrelevant before and after.  Two launches on `stream`, no host synchronisation.  Nothing outside dist_out[0:n_q], row[0:8] and work is written.
+ *
+ * mm3dgs_mesh_sample_plan / mm3dgs_mesh_sample_emit: vrows [n_vertices] x 16 bytes as above (the rgba is used), triangles int32 [m][3].
+ * With h(seed, t, k) = mix(mix(mix(seed ^ 0x9e3779b9) + t) + k) in uint32 arithmetic, mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ * x *= 0x846ca68b; x ^= x >> 16, and corners a, b, c widened to double (no fused multiply-add anywhere):
+ *   count     A = 0.5 |(b - a) x (c - a)|; n_t = min(floor(A density + h(seed, t, 0xffffffff) 2^-32), 2^23): stochastic rounding, so the
+ *             expected count is proportional to the area.  n_t = 0 and the triangle counts as degenerate when an index is outside
+ *             [0, n_vertices), a corner is not finite, or A is 0 or not finite.
+ *   sample j  r1 = h(seed, t, 2j) 2^-32, r2 = h(seed, t, 2j + 1) 2^-32; if r1 + r2 > 1 both become 1 - r; p = a + r1 (b - a) + r2 (c - a),
+ *             rounded once to float32; rgba of the corner with the largest of the weights (1 - r1 - r2, r1, r2), lowest index on a tie
+ *             (exact comparisons).  Samples are ordered by triangle, then j.
+ * plan writes counters (uint64[8], device, 8-byte aligned, not cumulative): [0] samples, [1] degenerate triangles, [4] m, [6] 1 when the
+ * samples exceed 2^32 - 1 (then emit writes nothing), the rest 0; it leaves the exclusive prefix of n_t in work.  emit (same mesh, density,
+ * seed and work as the plan before it) runs one lane per SAMPLE -- the lane finds its triangle by binary search in the prefix, so a
+ * wall-sized triangle does not serialise -- and writes rows [cap] x 16 bytes and counters [2] samples written = min([0], cap), [3] samples
+ * dropped; a sample at or beyond cap is not written.  work: mm3dgs_mesh_sample_work_bytes(m) bytes, 8-byte aligned, contents irrelevant
+ * before plan.  Three launches for plan, one for emit, no atomics, no host synchronisation.  Nothing outside work, counters[0:8] and
+ * rows[0:cap] is written.
+ *
+ * -1 (nothing is launched, nothing is written): n_ref, n_q or m of 0 or above 2^30; a grid size below 1 or more than 2^26 cells; cell or
+ * max_dist not finite or not positive; max_dist / cell above 2^20; a threshold that is negative or not finite; an origin_cell that is NULL
+ * or beyond +-2^40; n_vertices of 0 or above 2^31 - 1; density not finite or not positive; cap above 2^31; a NULL pointer (rows only with a
+ * cap above 0); a point set or sorted not 16-byte aligned, work, counters or row not 8-byte aligned, cell_start, dist_out or triangles not
+ * 4-byte aligned.  The *_work_bytes functions return 0 for sizes the calls reject. */
+size_t mm3dgs_nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz);
+int mm3dgs_nn_grid_build(uint64_t n_ref, const void* rows /*[n_ref] x 16 bytes*/, double cell, const int64_t* origin_cell /*host [3]*/, int gx, int gy,
+                         int gz, uint32_t* cell_start /*[gx gy gz + 1]*/, void* sorted /*[n_ref] x 16 bytes*/, uint64_t* counters /*[8], device*/,
+                         void* work, void* stream);
+size_t mm3dgs_nn_query_work_bytes(uint64_t n_q);
+int mm3dgs_nn_query(uint64_t n_q, const void* q_rows /*[n_q] x 16 bytes*/, uint64_t n_ref, double cell, const int64_t* origin_cell /*host [3]*/, int gx,
+                    int gy, int gz, const uint32_t* cell_start, const void* sorted, double max_dist, double threshold, float* dist_out /*[n_q]*/,
+                    double* row /*[8], device*/, void* work, void* stream);
+size_t mm3dgs_mesh_sample_work_bytes(uint64_t m);
+int mm3dgs_mesh_sample_plan(uint64_t n_vertices, const void* vrows /*[n_vertices] x 16 bytes*/, uint64_t m, const int32_t* triangles /*[m][3]*/,
+                            double density, uint32_t seed, void* work, uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_mesh_sample_emit(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed,
+                            const void* work, void* rows /*[cap] x 16 bytes*/, uint64_t cap, uint64_t* counters /*[8], device*/, void* stream);
+
 /* ---- frame ingest: raw sensor bytes -> the two images the SLAM loops consume, in one launch ------------------------------------------
  * rgb: uint8 interleaved [Hs,Ws,3] on the device, any byte alignment; depth_or_null: uint16 [Hs,Ws], 2-byte aligned.  out_color [3,H,W]
  * float32 in [0,1]; out_depth_or_null [H,W] float32 in metres, required iff depth is given (a colour-only call passes NULL for both).
@@ -709,7 +775,10 @@ const char* mm3dgs_last_error(void);
         rendered frame as one row of a device table); mm3dgs_pointcloud_work_bytes / mm3dgs_pointcloud_reset / mm3dgs_pointcloud_add_view
         (the fused coloured point cloud of a run, one call per view, first point per voxel); mm3dgs_tsdf_reset / mm3dgs_tsdf_integrate /
         mm3dgs_tsdf_mesh_work_bytes / mm3dgs_tsdf_mesh_plan / mm3dgs_tsdf_mesh_emit (the run as a coloured triangle mesh: views fused into
-        a truncated signed distance volume, marching tetrahedra over it); a caller that needs them looks the symbols up */
+        a truncated signed distance volume, marching tetrahedra over it); mm3dgs_nn_grid_work_bytes / mm3dgs_nn_grid_build /
+        mm3dgs_nn_query_work_bytes / mm3dgs_nn_query / mm3dgs_mesh_sample_work_bytes / mm3dgs_mesh_sample_plan / mm3dgs_mesh_sample_emit
+        (geometry scores of an export against a reference: exact truncated nearest-neighbour distances through a uniform grid, and
+        area-uniform samples of a triangle mesh); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

@@ -30,6 +30,15 @@ _TUM = {
     # error; opt-in, changes no pose
     "mesh": {"export": False, "every": None, "voxel": 0.02, "trunc": 0, "source": "render", "sil_min": 0.99, "max_depth": 0, "min_weight": 1,
              "bounds": None, "max_voxels": 1 << 28},
+    # after the run, the exported geometry scored against a reference surface (outputdir/geometry/metrics.json + accuracy.ply +
+    # completion.ply; geometry.py, mm3dgs_nn_grid_build / mm3dgs_nn_query / mm3dgs_mesh_sample_*): `estimate` mesh / pointcloud = what the
+    # `mesh` / `pointcloud` block exports (its every, source and sizes); `reference` "sensor" = the same frames' colour and sensor depth
+    # fused by the same builder at the ground-truth poses, or the path of a PLY cloud or mesh; accuracy, completion, completion ratio /
+    # precision / recall / F-score at `threshold`, Chamfer distance, from nearest-neighbour distances truncated at max_dist through a grid of
+    # `cell`-sized cells (0: threshold); meshes sampled at `density` points per m^2 (`seed`, at most max_samples); `align` none / horn /
+    # umeyama moves the estimate by the trajectory alignment first; opt-in, changes no pose and no other output
+    "geometry": {"eval": False, "estimate": "mesh", "reference": "sensor", "threshold": 0.05, "max_dist": 1.0,
+                 "density": 10000.0, "cell": 0, "seed": 0, "align": "none", "max_samples": 16777216},
     "scene_radius_depth_ratio": 2, "desired_height": 480, "desired_width": 640,
     "debug": {"get_runtime_stats": False, "create_video": False, "save_keyframes": False},
     "pipeline": {"convert_SHs_python": False, "compute_cov3D_python": False, "transform_means_python": True,

@@ -855,6 +855,103 @@ int mm3dgs_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void
   return check_launch("tsdf_mesh_emit");
 }
 
+// ---- geometry scores (geometry.hip) ----------------------------------------------------------------------------------------------
+#define NN_MAX_ROWS ((uint64_t)1 << 30)
+#define NN_MAX_CELLS ((size_t)1 << 26)
+#define NN_MAX_RINGS 1048576.0      // ceil(max_dist / cell) at most 2^20
+static bool nn_grid_ok(int gx, int gy, int gz) {
+  return gx >= 1 && gy >= 1 && gz >= 1 && (size_t)gx * (size_t)gy <= NN_MAX_CELLS && (size_t)gx * (size_t)gy * (size_t)gz <= NN_MAX_CELLS;
+}
+static bool nn_origin_ok(const int64_t* o) {
+  const int64_t lim = (int64_t)1 << 40;
+  return o && o[0] > -lim && o[0] < lim && o[1] > -lim && o[1] < lim && o[2] > -lim && o[2] < lim;
+}
+static NnGrid nn_grid(double cell, const int64_t* o, int gx, int gy, int gz) {
+  NnGrid g;
+  g.cell = cell; g.o[0] = (double)o[0]; g.o[1] = (double)o[1]; g.o[2] = (double)o[2]; g.gx = gx; g.gy = gy; g.gz = gz;
+  return g;
+}
+
+size_t mm3dgs_nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz) {
+  return (n_ref >= 1 && n_ref <= NN_MAX_ROWS && nn_grid_ok(gx, gy, gz)) ? nn_grid_work_bytes(n_ref, gx, gy, gz) : 0;
+}
+
+int mm3dgs_nn_grid_build(uint64_t n_ref, const void* rows, double cell, const int64_t* origin_cell, int gx, int gy, int gz, uint32_t* cell_start,
+                         void* sorted, uint64_t* counters, void* work, void* stream) {
+  if (n_ref < 1 || n_ref > NN_MAX_ROWS) return fail(-1, "nn_grid_build: n_ref = %llu (1 .. 2^30)", (unsigned long long)n_ref);
+  if (!nn_grid_ok(gx, gy, gz)) return fail(-1, "nn_grid_build: grid %d x %d x %d (every size at least 1, at most 2^26 cells)", gx, gy, gz);
+  if (!(cell > 0.0) || !isfinite(cell)) return fail(-1, "nn_grid_build: cell = %g (must be finite and positive)", cell);
+  if (!nn_origin_ok(origin_cell)) return fail(-1, "nn_grid_build: origin_cell is NULL or beyond +-2^40");
+  if (!rows || !cell_start || !sorted || !counters || !work)
+    return fail(-1, "nn_grid_build: NULL argument (rows, cell_start, sorted, counters and work are required)");
+  if (((uintptr_t)rows | (uintptr_t)sorted) & 15) return fail(-1, "nn_grid_build: rows and sorted must be 16-byte aligned");
+  if (((uintptr_t)counters | (uintptr_t)work) & 7) return fail(-1, "nn_grid_build: counters and work must be 8-byte aligned");
+  if ((uintptr_t)cell_start & 3) return fail(-1, "nn_grid_build: cell_start must be 4-byte aligned");
+  launch_nn_grid_build(nn_grid(cell, origin_cell, gx, gy, gz), n_ref, rows, cell_start, sorted, counters, work, (hipStream_t)stream);
+  return check_launch("nn_grid_build");
+}
+
+size_t mm3dgs_nn_query_work_bytes(uint64_t n_q) { return (n_q >= 1 && n_q <= NN_MAX_ROWS) ? nn_query_work_bytes(n_q) : 0; }
+
+int mm3dgs_nn_query(uint64_t n_q, const void* q_rows, uint64_t n_ref, double cell, const int64_t* origin_cell, int gx, int gy, int gz,
+                    const uint32_t* cell_start, const void* sorted, double max_dist, double threshold, float* dist_out, double* row, void* work,
+                    void* stream) {
+  if (n_q < 1 || n_q > NN_MAX_ROWS) return fail(-1, "nn_query: n_q = %llu (1 .. 2^30)", (unsigned long long)n_q);
+  if (n_ref < 1 || n_ref > NN_MAX_ROWS) return fail(-1, "nn_query: n_ref = %llu (1 .. 2^30)", (unsigned long long)n_ref);
+  if (!nn_grid_ok(gx, gy, gz)) return fail(-1, "nn_query: grid %d x %d x %d (every size at least 1, at most 2^26 cells)", gx, gy, gz);
+  if (!(cell > 0.0) || !isfinite(cell)) return fail(-1, "nn_query: cell = %g (must be finite and positive)", cell);
+  if (!(max_dist > 0.0) || !isfinite(max_dist)) return fail(-1, "nn_query: max_dist = %g (must be finite and positive)", max_dist);
+  if (!(threshold >= 0.0) || !isfinite(threshold)) return fail(-1, "nn_query: threshold = %g (must be finite and not negative)", threshold);
+  const double rings = ceil(max_dist / cell);
+  if (!(rings <= NN_MAX_RINGS)) return fail(-1, "nn_query: max_dist / cell = %g (at most 2^20 rings)", max_dist / cell);
+  if (!nn_origin_ok(origin_cell)) return fail(-1, "nn_query: origin_cell is NULL or beyond +-2^40");
+  if (!q_rows || !cell_start || !sorted || !dist_out || !row || !work)
+    return fail(-1, "nn_query: NULL argument (q_rows, cell_start, sorted, dist_out, row and work are required)");
+  if (((uintptr_t)q_rows | (uintptr_t)sorted) & 15) return fail(-1, "nn_query: q_rows and sorted must be 16-byte aligned");
+  if (((uintptr_t)row | (uintptr_t)work) & 7) return fail(-1, "nn_query: row and work must be 8-byte aligned");
+  if (((uintptr_t)cell_start | (uintptr_t)dist_out) & 3) return fail(-1, "nn_query: cell_start and dist_out must be 4-byte aligned");
+  launch_nn_query(nn_grid(cell, origin_cell, gx, gy, gz), n_q, q_rows, n_ref, cell_start, sorted, max_dist, threshold, (int)(rings < 1.0 ? 1.0 : rings),
+                  dist_out, row, work, (hipStream_t)stream);
+  return check_launch("nn_query");
+}
+
+#define MS_MAX_TRIANGLES ((uint64_t)1 << 30)
+size_t mm3dgs_mesh_sample_work_bytes(uint64_t m) { return (m >= 1 && m <= MS_MAX_TRIANGLES) ? mesh_sample_work_bytes(m) : 0; }
+
+static int mesh_sample_check(const char* who, uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* tris, double density, const void* work,
+                             const uint64_t* counters) {
+  if (m < 1 || m > MS_MAX_TRIANGLES) return fail(-1, "%s: m = %llu triangles (1 .. 2^30)", who, (unsigned long long)m);
+  if (n_vertices < 1 || n_vertices > ((uint64_t)1 << 31) - 1) return fail(-1, "%s: n_vertices = %llu (1 .. 2^31 - 1)", who, (unsigned long long)n_vertices);
+  if (!(density > 0.0) || !isfinite(density)) return fail(-1, "%s: density = %g (must be finite and positive)", who, density);
+  if (!vrows || !tris || !work || !counters) return fail(-1, "%s: NULL argument (vrows, triangles, work and counters are required)", who);
+  if ((uintptr_t)vrows & 15) return fail(-1, "%s: vrows must be 16-byte aligned", who);
+  if (((uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "%s: work and counters must be 8-byte aligned", who);
+  if ((uintptr_t)tris & 3) return fail(-1, "%s: triangles must be 4-byte aligned", who);
+  return 0;
+}
+static MeshSample mesh_sample(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* tris, double density, uint32_t seed) {
+  MeshSample ms;
+  ms.vrows = (const uint4*)vrows; ms.n_vertices = (uint32_t)n_vertices; ms.tris = tris; ms.m = (uint32_t)m; ms.density = density; ms.seed = seed;
+  return ms;
+}
+
+int mm3dgs_mesh_sample_plan(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed, void* work,
+                            uint64_t* counters, void* stream) {
+  if (mesh_sample_check("mesh_sample_plan", n_vertices, vrows, m, triangles, density, work, counters)) return -1;
+  launch_mesh_sample_plan(mesh_sample(n_vertices, vrows, m, triangles, density, seed), work, counters, (hipStream_t)stream);
+  return check_launch("mesh_sample_plan");
+}
+
+int mm3dgs_mesh_sample_emit(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed, const void* work,
+                            void* rows, uint64_t cap, uint64_t* counters, void* stream) {
+  if (mesh_sample_check("mesh_sample_emit", n_vertices, vrows, m, triangles, density, work, counters)) return -1;
+  if (cap > ((uint64_t)1 << 31)) return fail(-1, "mesh_sample_emit: cap = %llu (at most 2^31)", (unsigned long long)cap);
+  if (!rows && cap) return fail(-1, "mesh_sample_emit: rows is NULL with a cap above 0");
+  if ((uintptr_t)rows & 15) return fail(-1, "mesh_sample_emit: rows must be 16-byte aligned");
+  launch_mesh_sample_emit(mesh_sample(n_vertices, vrows, m, triangles, density, seed), work, rows, cap, counters, (hipStream_t)stream);
+  return check_launch("mesh_sample_emit");
+}
+
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
                         float* out_color, float* out_depth_or_null, void* stream) {
   if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);

@@ -155,6 +155,19 @@ void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_
 void launch_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s);
 void launch_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void* rgb_w, const double* origin, double voxel, const void* work, void* rows,
                            uint64_t vcap, void* tris, uint64_t tcap, uint64_t* counters, hipStream_t s);
+// geometry scores (geometry.hip): a uniform grid over a reference point set (16-byte rows), the exact truncated nearest-neighbour distance
+// of every query row with one row of eight figures, and area-uniform samples of a triangle mesh; sizes, pointers, cell, max_dist, rmax =
+// ceil(max_dist / cell) and density as the entry points have checked them (gx gy gz <= 2^26, at most 2^30 rows, rmax <= 2^20)
+struct NnGrid { double cell; double o[3]; int gx, gy, gz; };      // o: the origin cell per axis (an integer value)
+struct MeshSample { const uint4* vrows; uint32_t n_vertices; const int* tris; uint32_t m; double density; uint32_t seed; };
+size_t nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz);
+void launch_nn_grid_build(const NnGrid& g, uint64_t n_ref, const void* rows, void* cell_start, void* sorted, uint64_t* counters, void* work, hipStream_t s);
+size_t nn_query_work_bytes(uint64_t n_q);
+void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
+                     double threshold, int rmax, float* dist_out, double* row, void* work, hipStream_t s);
+size_t mesh_sample_work_bytes(uint64_t m);
+void launch_mesh_sample_plan(const MeshSample& ms, void* work, uint64_t* counters, hipStream_t s);
+void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint64_t cap, uint64_t* counters, hipStream_t s);
 // frame ingest (ingest.hip): raw uint8 RGB [Hs,Ws,3] + uint16 depth [Hs,Ws] -> colour [3,H,W] in [0,1] + depth [H,W] in metres, one
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,

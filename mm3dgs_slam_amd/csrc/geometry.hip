@@ -1,0 +1,476 @@
+// Geometry scores of an exported reconstruction against a reference surface (mm3dgs_nn_grid_build / mm3dgs_nn_query /
+// mm3dgs_mesh_sample_plan / mm3dgs_mesh_sample_emit; host statement: geometry.nn_distances_host / geometry.sample_mesh_host).  Point sets
+// are the cloud's 16-byte rows {float x, y, z; uint32 rgba}; the figures of one direction are one row of eight doubles on the device.
+//
+// Grid build (a uniform grid over the reference set, x fastest; cell = floor((double)x / cell) - origin_cell per axis):
+//   ng_zero_kernel     the per-cell counts and the eight counters to zero.
+//   ng_count_kernel    one lane per reference row: its cell (NN_NO_CELL for a row that is not finite or lies outside the box), one integer
+//                      atomicAdd on the cell's count -- a count does not depend on the order of its adds.
+//   ng_cellscan_kernel per 256 cells: the exclusive prefix inside the block and the block's total.
+//   ng_scan_kernel     one workgroup of 1024: scan_block_counts over the block totals (compact_scan.h), the total.
+//   ng_base_kernel     cell_start = block prefix + local prefix; the same value into the cell's fill cursor.
+//   ng_scatter_kernel  every row takes a slot of its cell (integer atomicAdd on the cursor) and stores one 16-byte record {x, y, z, row index}.
+//                      The order inside a cell depends on the atomics; a minimum over the cell does not.
+// Query (ng_query_kernel, one lane per query): the cells at Chebyshev ring r around the query's own cell, clipped to the grid, r = 0, 1, 2, ...;
+//   a row of cells along x is one contiguous range of records, so rings 0 and 1 together are at most nine ranges; the lane stops after ring r
+//   when best <= r cell (every unsearched record is farther), after ring ceil(max_dist / cell), or when no further ring touches the grid; a
+//   query outside the grid starts at the first ring that touches it.  Distances in double from the float32 coordinates, no contraction,
+//   rounded once at the store.  Per workgroup one row of partial sums in double, fixed lane order; ng_finish_kernel (one workgroup) adds the
+//   partial rows in a fixed order and writes the eight figures.  No float atomic: the same inputs give the same bytes on every call.
+// Sampler (area-uniform samples of a triangle mesh by stochastic rounding of area x density, a 32-bit integer mixer as the random source):
+//   ms_plan_kernel     one lane per triangle: n_t, the exclusive prefix inside the 256-block, the block's total and its degenerate count.
+//   ms_scan_kernel     one workgroup of 1024: scan_block_counts, the 64-bit total, the degenerate count, the counter block.
+//   ms_base_kernel     prefix[t] += block prefix.
+//   ms_emit_kernel     one lane per SAMPLE: binary search of its triangle in the exclusive prefix, then the sample's row.
+#include <math.h>
+#include "compact_scan.h"
+#include "fused_api.h"
+
+#define GB 256
+#define NN_NO_CELL 0xffffffffu
+#define NN_ROW 8      // doubles per partial row: sum d, sum d^2, max d, n, within, clamped, skipped, 0
+
+static size_t ng_nb(size_t n) { return (n + GB - 1) / GB; }
+
+// ---- grid build -------------------------------------------------------------------------------------------------------------------
+// work = [uint32 cell per reference row][uint32 count, then fill cursor, per cell][uint32 per 256 cells]
+struct NgWork { uint32_t* cellidx; uint32_t* cursor; uint32_t* bcounts; };
+size_t nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz) {
+  const size_t nc = (size_t)gx * (size_t)gy * (size_t)gz;
+  return align_up((size_t)n_ref * 4, 256) + align_up(nc * 4, 256) + align_up(ng_nb(nc) * 4, 256);
+}
+static NgWork ng_work(void* base, size_t n_ref, size_t nc) {
+  char* c = (char*)base;
+  NgWork w;
+  w.cellidx = (uint32_t*)c;  c += align_up(n_ref * 4, 256);
+  w.cursor = (uint32_t*)c;   c += align_up(nc * 4, 256);
+  w.bcounts = (uint32_t*)c;
+  return w;
+}
+
+__device__ __forceinline__ bool ng_finite(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }
+
+// the cell coordinates of a finite position, relative to the grid's origin cell, as doubles (they may lie outside the grid, or beyond an int)
+__device__ __forceinline__ void ng_cell(const NnGrid& g, float x, float y, float z, double (&c)[3]) {
+#pragma clang fp contract(off)
+  c[0] = floor((double)x / g.cell) - g.o[0];
+  c[1] = floor((double)y / g.cell) - g.o[1];
+  c[2] = floor((double)z / g.cell) - g.o[2];
+}
+
+__global__ void __launch_bounds__(GB) ng_zero_kernel(uint32_t* __restrict__ counts, size_t nc, unsigned long long* __restrict__ counters) {
+  const size_t step = (size_t)gridDim.x * GB;
+  for (size_t i = (size_t)blockIdx.x * GB + threadIdx.x; i < nc; i += step) counts[i] = 0u;
+  if (blockIdx.x == 0 && threadIdx.x < 8) counters[threadIdx.x] = 0ull;
+}
+
+__global__ void __launch_bounds__(GB)
+ng_count_kernel(NnGrid g, const uint4* __restrict__ rows, uint32_t n, uint32_t* __restrict__ cellidx, uint32_t* __restrict__ counts,
+                unsigned long long* __restrict__ counters) {
+  const uint32_t i = blockIdx.x * GB + threadIdx.x;
+  bool bad = false, out = false;
+  if (i < n) {
+    const uint4 r = rows[i];
+    const float x = __uint_as_float(r.x), y = __uint_as_float(r.y), z = __uint_as_float(r.z);
+    uint32_t cell = NN_NO_CELL;
+    if (!ng_finite(x, y, z)) {
+      bad = true;
+    } else {
+      double c[3];
+      ng_cell(g, x, y, z, c);
+      if (c[0] >= 0.0 && c[0] < (double)g.gx && c[1] >= 0.0 && c[1] < (double)g.gy && c[2] >= 0.0 && c[2] < (double)g.gz)
+        cell = ((uint32_t)(int)c[2] * (uint32_t)g.gy + (uint32_t)(int)c[1]) * (uint32_t)g.gx + (uint32_t)(int)c[0];
+      else
+        out = true;
+    }
+    cellidx[i] = cell;
+    if (cell != NN_NO_CELL) atomicAdd(&counts[cell], 1u);
+  }
+  const unsigned long long mb = __ballot(bad), mo = __ballot(out);
+  if ((threadIdx.x & 63) == 0) {      // integer adds: the sums do not depend on their order
+    if (mb) atomicAdd(counters + 1, (unsigned long long)__popcll(mb));
+    if (mo) atomicAdd(counters + 2, (unsigned long long)__popcll(mo));
+  }
+}
+
+// inclusive scan of v over the workgroup of GB lanes (every lane calls); wtot: GB / 64 words of LDS
+__device__ __forceinline__ uint32_t ng_block_scan(uint32_t v, uint32_t* wtot) {
+  const uint32_t x = wave_scan_incl(v);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 63) wtot[wv] = x;
+  __syncthreads();
+  uint32_t pre = 0;
+  for (int w = 0; w < wv; w++) pre += wtot[w];
+  return pre + x;
+}
+
+__global__ void __launch_bounds__(GB)
+ng_cellscan_kernel(const uint32_t* __restrict__ counts, size_t nc, uint32_t* __restrict__ cell_start, uint32_t* __restrict__ bcounts) {
+  __shared__ uint32_t wtot[GB / 64];
+  const size_t i = (size_t)blockIdx.x * GB + threadIdx.x;
+  const uint32_t v = i < nc ? counts[i] : 0u;
+  const uint32_t incl = ng_block_scan(v, wtot);
+  if (i < nc) cell_start[i] = incl - v;
+  if (threadIdx.x == GB - 1) bcounts[blockIdx.x] = incl;
+}
+
+__global__ void __launch_bounds__(1024)
+ng_scan_kernel(int nb, uint32_t* __restrict__ bcounts, uint32_t* __restrict__ cell_end, unsigned long long* __restrict__ counters, unsigned long long nc) {
+  __shared__ uint32_t total;
+  scan_block_counts(nb, bcounts, &total);
+  if (threadIdx.x == 0) {      // (lane 0 wrote `total` itself)
+    *cell_end = total;
+    counters[0] = total;
+    counters[3] = nc;
+  }
+}
+
+__global__ void __launch_bounds__(GB)
+ng_base_kernel(size_t nc, const uint32_t* __restrict__ bpre, uint32_t* __restrict__ cell_start, uint32_t* __restrict__ cursor) {
+  const size_t i = (size_t)blockIdx.x * GB + threadIdx.x;
+  if (i >= nc) return;
+  const uint32_t s = cell_start[i] + bpre[blockIdx.x];
+  cell_start[i] = s;
+  cursor[i] = s;
+}
+
+__global__ void __launch_bounds__(GB)
+ng_scatter_kernel(const uint4* __restrict__ rows, uint32_t n, const uint32_t* __restrict__ cellidx, uint32_t* __restrict__ cursor, uint4* __restrict__ sorted) {
+  const uint32_t i = blockIdx.x * GB + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t cell = cellidx[i];
+  if (cell == NN_NO_CELL) return;
+  const uint32_t slot = atomicAdd(&cursor[cell], 1u);
+  if (slot >= n) return;      // (cannot happen: the cursors start at the prefix of the same counts)
+  const uint4 r = rows[i];
+  sorted[slot] = make_uint4(r.x, r.y, r.z, i);      // one 16-byte store
+}
+
+void launch_nn_grid_build(const NnGrid& g, uint64_t n_ref, const void* rows, void* cell_start, void* sorted, uint64_t* counters, void* work, hipStream_t s) {
+  const size_t nc = (size_t)g.gx * (size_t)g.gy * (size_t)g.gz;
+  const NgWork w = ng_work(work, (size_t)n_ref, nc);
+  const unsigned nbc = (unsigned)ng_nb(nc), nbr = (unsigned)ng_nb((size_t)n_ref);
+  uint32_t* cs = (uint32_t*)cell_start;
+  hipLaunchKernelGGL(ng_zero_kernel, dim3(nbc < 4096u ? nbc : 4096u), dim3(GB), 0, s, w.cursor, nc, (unsigned long long*)counters);
+  hipLaunchKernelGGL(ng_count_kernel, dim3(nbr), dim3(GB), 0, s, g, (const uint4*)rows, (uint32_t)n_ref, w.cellidx, w.cursor, (unsigned long long*)counters);
+  hipLaunchKernelGGL(ng_cellscan_kernel, dim3(nbc), dim3(GB), 0, s, w.cursor, nc, cs, w.bcounts);
+  hipLaunchKernelGGL(ng_scan_kernel, dim3(1), dim3(1024), 0, s, (int)nbc, w.bcounts, cs + nc, (unsigned long long*)counters, (unsigned long long)nc);
+  hipLaunchKernelGGL(ng_base_kernel, dim3(nbc), dim3(GB), 0, s, nc, w.bcounts, cs, w.cursor);
+  hipLaunchKernelGGL(ng_scatter_kernel, dim3(nbr), dim3(GB), 0, s, (const uint4*)rows, (uint32_t)n_ref, w.cellidx, w.cursor, (uint4*)sorted);
+}
+
+// ---- query ------------------------------------------------------------------------------------------------------------------------
+size_t nn_query_work_bytes(uint64_t n_q) { return align_up(ng_nb((size_t)n_q) * NN_ROW * sizeof(double), 256); }
+
+struct NnQuery { double qx, qy, qz, best2; };
+
+// the records [b, e) against the query: squared distance in double (each coordinate widened, then subtracted; three squares, a sum)
+__device__ __forceinline__ void ng_scan_records(const uint4* __restrict__ sorted, uint32_t b, uint32_t e, uint32_t n_ref, NnQuery& q) {
+#pragma clang fp contract(off)
+  e = e < n_ref ? e : n_ref;
+  for (uint32_t p = b; p < e; p++) {
+    const uint4 v = sorted[p];      // one 16-byte load per candidate
+    const double dx = q.qx - (double)__uint_as_float(v.x), dy = q.qy - (double)__uint_as_float(v.y), dz = q.qz - (double)__uint_as_float(v.z);
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    q.best2 = d2 < q.best2 ? d2 : q.best2;
+  }
+}
+
+__device__ __forceinline__ int ng_lo(int c, int r) { return c - r > 0 ? c - r : 0; }
+__device__ __forceinline__ int ng_hi(int c, int r, int g) { return c + r < g - 1 ? c + r : g - 1; }
+
+// every cell within Chebyshev distance r of (cx, cy, cz), clipped to the grid: one range of records per row of cells
+__device__ __forceinline__ void ng_cube(const NnGrid& g, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted, uint32_t n_ref, int cx,
+                                        int cy, int cz, int r, NnQuery& q) {
+  const int x0 = ng_lo(cx, r), x1 = ng_hi(cx, r, g.gx);
+  if (x0 > x1) return;
+  for (int z = ng_lo(cz, r); z <= ng_hi(cz, r, g.gz); z++)
+    for (int y = ng_lo(cy, r); y <= ng_hi(cy, r, g.gy); y++) {
+      const size_t row = ((size_t)z * (size_t)g.gy + (size_t)y) * (size_t)g.gx;
+      ng_scan_records(sorted, cell_start[row + x0], cell_start[row + x1 + 1], n_ref, q);
+    }
+}
+
+// the cells at Chebyshev distance exactly r >= 1, clipped to the grid: whole rows on the four faces across y and z, two cells per row elsewhere
+__device__ __forceinline__ void ng_ring(const NnGrid& g, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted, uint32_t n_ref, int cx,
+                                        int cy, int cz, int r, NnQuery& q) {
+  const int x0 = ng_lo(cx, r), x1 = ng_hi(cx, r, g.gx);
+  for (int z = ng_lo(cz, r); z <= ng_hi(cz, r, g.gz); z++) {
+    const bool fz = z - cz == r || cz - z == r;
+    for (int y = ng_lo(cy, r); y <= ng_hi(cy, r, g.gy); y++) {
+      const size_t row = ((size_t)z * (size_t)g.gy + (size_t)y) * (size_t)g.gx;
+      if (fz || y - cy == r || cy - y == r) {
+        if (x0 <= x1) ng_scan_records(sorted, cell_start[row + x0], cell_start[row + x1 + 1], n_ref, q);
+      } else {
+        const int xa = cx - r, xb = cx + r;
+        if (xa >= 0 && xa < g.gx) ng_scan_records(sorted, cell_start[row + xa], cell_start[row + xa + 1], n_ref, q);
+        if (xb >= 0 && xb < g.gx) ng_scan_records(sorted, cell_start[row + xb], cell_start[row + xb + 1], n_ref, q);
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(GB)
+ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted,
+                uint32_t n_ref, double max_dist, float threshold, int rmax, float* __restrict__ dist_out, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  __shared__ double wsum[2][GB / 64];
+  __shared__ uint32_t wcnt[4][GB / 64];
+  __shared__ uint32_t smax;
+  const uint32_t i = blockIdx.x * GB + threadIdx.x;
+  if (threadIdx.x == 0) smax = 0u;
+  __syncthreads();
+  bool scored = false, skipped = false, clamped = false, within = false;
+  double dd = 0.0;
+  if (i < n_q) {
+    const uint4 r = qrows[i];
+    const float x = __uint_as_float(r.x), y = __uint_as_float(r.y), z = __uint_as_float(r.z);
+    float out;
+    if (!ng_finite(x, y, z)) {
+      skipped = true;
+      out = __uint_as_float(0x7fc00000u);
+    } else {
+      NnQuery q;
+      q.qx = (double)x; q.qy = (double)y; q.qz = (double)z; q.best2 = (double)INFINITY;
+      double c[3];
+      ng_cell(g, x, y, z, c);
+      // the first ring that touches the grid, and the last one that does (as doubles: a far query's cell may not fit an int)
+      const double gs[3] = {(double)g.gx, (double)g.gy, (double)g.gz};
+      double r0 = 0.0, rfar = 0.0;
+      for (int a = 0; a < 3; a++) {
+        const double below = -c[a], above = c[a] - (gs[a] - 1.0);
+        const double o = below > above ? below : above;      // > 0: cells outside the grid along this axis
+        r0 = o > r0 ? o : r0;
+        const double f = c[a] > (gs[a] - 1.0) - c[a] ? c[a] : (gs[a] - 1.0) - c[a];
+        rfar = f > rfar ? f : rfar;
+      }
+      if (r0 <= (double)rmax) {      // (else: nothing within max_dist)
+        const int cx = (int)c[0], cy = (int)c[1], cz = (int)c[2];      // |c| <= grid size + rmax here
+        const int last = rfar < (double)rmax ? (int)rfar : rmax;
+        int rr = r0 <= 1.0 ? 1 : (int)r0;
+        if (rr == 1) ng_cube(g, cell_start, sorted, n_ref, cx, cy, cz, 1, q);      // rings 0 and 1: nine ranges
+        else ng_ring(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
+        while (rr < last && !(sqrt(q.best2) <= (double)rr * g.cell)) {      // at most rmax trips
+          rr++;
+          ng_ring(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
+        }
+      }
+      const double d = sqrt(q.best2);
+      clamped = !(d <= max_dist);
+      out = clamped ? (float)max_dist : (float)d;      // the one rounding
+      within = out <= threshold;
+      scored = true;
+      dd = (double)out;
+      atomicMax(&smax, __float_as_uint(out));      // LDS, integer: a non-negative float orders as its bits
+    }
+    dist_out[i] = out;
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double s1 = wave_sum_to_lane63_f64(dd), s2 = wave_sum_to_lane63_f64(dd * dd);
+  const unsigned long long m[4] = {__ballot(scored), __ballot(within), __ballot(clamped), __ballot(skipped)};
+  if (lane == 63) { wsum[0][wv] = s1; wsum[1][wv] = s2; }
+  if (lane == 0)
+    for (int k = 0; k < 4; k++) wcnt[k][wv] = (uint32_t)__popcll(m[k]);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* row = partial + (size_t)blockIdx.x * NN_ROW;
+    row[0] = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
+    row[1] = (wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3]);
+    row[2] = (double)__uint_as_float(smax);
+    for (int k = 0; k < 4; k++) row[3 + k] = (double)(wcnt[k][0] + wcnt[k][1] + wcnt[k][2] + wcnt[k][3]);
+    row[7] = 0.0;
+  }
+}
+
+// one workgroup: lane t adds the partial rows t, t + 256, ... in index order, then the lanes are added in index order
+__global__ void __launch_bounds__(GB) ng_finish_kernel(const double* __restrict__ partial, int nrows, double* __restrict__ row) {
+  __shared__ double sh[GB][NN_ROW];
+  double a[NN_ROW];
+  for (int k = 0; k < NN_ROW; k++) a[k] = 0.0;
+  for (int r = threadIdx.x; r < nrows; r += GB)
+    for (int k = 0; k < NN_ROW; k++) {
+      const double v = partial[(size_t)r * NN_ROW + k];
+      a[k] = k == 2 ? (v > a[k] ? v : a[k]) : a[k] + v;
+    }
+  for (int k = 0; k < NN_ROW; k++) sh[threadIdx.x][k] = a[k];
+  __syncthreads();
+  if (threadIdx.x < NN_ROW) {
+    const int k = threadIdx.x;
+    double t = 0.0;
+    for (int l = 0; l < GB; l++) t = k == 2 ? (sh[l][k] > t ? sh[l][k] : t) : t + sh[l][k];
+    sh[0][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double sum = sh[0][0], sq = sh[0][1], mx = sh[0][2], n = sh[0][3], within = sh[0][4], clamped = sh[0][5], skipped = sh[0][6];
+    row[0] = n;
+    row[1] = n > 0.0 ? sum / n : 0.0;
+    row[2] = n > 0.0 ? sqrt(sq / n) : 0.0;
+    row[3] = mx;
+    row[4] = n > 0.0 ? within / n : 0.0;
+    row[5] = clamped;
+    row[6] = skipped;
+    row[7] = 0.0;
+  }
+}
+
+void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
+                     double threshold, int rmax, float* dist_out, double* row, void* work, hipStream_t s) {
+  const unsigned nb = (unsigned)ng_nb((size_t)n_q);
+  hipLaunchKernelGGL(ng_query_kernel, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q, (const uint32_t*)cell_start, (const uint4*)sorted,
+                     (uint32_t)n_ref, max_dist, (float)threshold, rmax, dist_out, (double*)work);
+  hipLaunchKernelGGL(ng_finish_kernel, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
+}
+
+// ---- surface sampler --------------------------------------------------------------------------------------------------------------
+// work = [256 B header: uint64 samples (0 when they exceed 32 bits)][uint32 exclusive prefix per triangle][2 x uint32 per 256 triangles: samples, degenerate]
+struct MsWork { unsigned long long* hdr; uint32_t* prefix; uint32_t* bcounts; uint32_t* dcounts; };
+size_t mesh_sample_work_bytes(uint64_t m) { return 256 + align_up((size_t)m * 4, 256) + 2 * align_up(ng_nb((size_t)m) * 4, 256); }
+static MsWork ms_work(void* base, size_t m) {
+  char* c = (char*)base;
+  MsWork w;
+  w.hdr = (unsigned long long*)c;  c += 256;
+  w.prefix = (uint32_t*)c;         c += align_up(m * 4, 256);
+  w.bcounts = (uint32_t*)c;        c += align_up(ng_nb(m) * 4, 256);
+  w.dcounts = (uint32_t*)c;
+  return w;
+}
+
+// the 32-bit mixer (geometry.py: mix32 / sample_hash state the same one)
+__device__ __forceinline__ uint32_t ms_mix(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ uint32_t ms_hash(uint32_t seed, uint32_t t, uint32_t k) { return ms_mix(ms_mix(ms_mix(seed ^ 0x9e3779b9u) + t) + k); }
+
+struct MsTri { double a[3], e1[3], e2[3]; uint32_t rgba[3]; };
+
+// the corners of triangle t widened to double; false: an index outside [0, n_vertices) or a corner that is not finite
+__device__ __forceinline__ bool ms_load(const MeshSample& ms, uint32_t t, MsTri& T) {
+#pragma clang fp contract(off)
+  const int i0 = ms.tris[3 * (size_t)t], i1 = ms.tris[3 * (size_t)t + 1], i2 = ms.tris[3 * (size_t)t + 2];
+  if (i0 < 0 || i1 < 0 || i2 < 0 || (unsigned)i0 >= ms.n_vertices || (unsigned)i1 >= ms.n_vertices || (unsigned)i2 >= ms.n_vertices) return false;
+  const uint4 a = ms.vrows[i0], b = ms.vrows[i1], c = ms.vrows[i2];
+  const float af[3] = {__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z)};
+  const float bf[3] = {__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)};
+  const float cf[3] = {__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)};
+  if (!ng_finite(af[0], af[1], af[2]) || !ng_finite(bf[0], bf[1], bf[2]) || !ng_finite(cf[0], cf[1], cf[2])) return false;
+  for (int k = 0; k < 3; k++) {
+    T.a[k] = (double)af[k];
+    T.e1[k] = (double)bf[k] - (double)af[k];
+    T.e2[k] = (double)cf[k] - (double)af[k];
+  }
+  T.rgba[0] = a.w; T.rgba[1] = b.w; T.rgba[2] = c.w;
+  return true;
+}
+
+// n_t = min(floor(A density + u_t), MS_TRI_MAX); 0 and `degenerate` for a triangle ms_load rejects or whose area is 0 or not finite
+#define MS_TRI_MAX 8388608.0      // 2^23: a 256-block's total stays below 2^32
+__device__ __forceinline__ uint32_t ms_count(const MeshSample& ms, uint32_t t, bool& degenerate) {
+#pragma clang fp contract(off)
+  MsTri T;
+  degenerate = true;
+  if (!ms_load(ms, t, T)) return 0u;
+  const double cx = T.e1[1] * T.e2[2] - T.e1[2] * T.e2[1], cy = T.e1[2] * T.e2[0] - T.e1[0] * T.e2[2], cz = T.e1[0] * T.e2[1] - T.e1[1] * T.e2[0];
+  const double A = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+  if (!(A > 0.0) || !(A < (double)INFINITY)) return 0u;
+  degenerate = false;
+  const double u = (double)ms_hash(ms.seed, t, 0xffffffffu) * 0x1p-32;
+  double nt = floor(A * ms.density + u);
+  nt = nt < MS_TRI_MAX ? nt : MS_TRI_MAX;
+  return (uint32_t)nt;
+}
+
+__global__ void __launch_bounds__(GB)
+ms_plan_kernel(MeshSample ms, uint32_t* __restrict__ prefix, uint32_t* __restrict__ bcounts, uint32_t* __restrict__ dcounts) {
+  __shared__ uint32_t wtot[GB / 64];
+  __shared__ uint32_t wdeg[GB / 64];
+  const uint32_t t = blockIdx.x * GB + threadIdx.x;
+  bool deg = false;
+  const uint32_t nt = t < ms.m ? ms_count(ms, t, deg) : 0u;
+  const uint32_t incl = ng_block_scan(nt, wtot);
+  if (t < ms.m) prefix[t] = incl - nt;
+  if (threadIdx.x == GB - 1) bcounts[blockIdx.x] = incl;
+  const unsigned long long md = __ballot(deg);
+  if ((threadIdx.x & 63) == 0) wdeg[threadIdx.x >> 6] = (uint32_t)__popcll(md);
+  __syncthreads();
+  if (threadIdx.x == 0) dcounts[blockIdx.x] = wdeg[0] + wdeg[1] + wdeg[2] + wdeg[3];
+}
+
+__global__ void __launch_bounds__(1024)
+ms_scan_kernel(int nb, uint32_t* __restrict__ bcounts, const uint32_t* __restrict__ dcounts, unsigned long long m, unsigned long long* __restrict__ hdr,
+               unsigned long long* __restrict__ counters) {
+  __shared__ unsigned long long sh[2][16];
+  __shared__ uint32_t total32;
+  // the 64-bit sums first: the scan overwrites the block totals with their prefix
+  unsigned long long s = 0ull, d = 0ull;
+  for (int i = threadIdx.x; i < nb; i += 1024) { s += bcounts[i]; d += dcounts[i]; }
+  for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off); d += __shfl_down(d, off); }      // integer sums: any order
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = d; }
+  __syncthreads();
+  scan_block_counts(nb, bcounts, &total32);
+  if (threadIdx.x == 0) {
+    unsigned long long total = 0ull, deg = 0ull;
+    for (int w = 0; w < 16; w++) { total += sh[0][w]; deg += sh[1][w]; }
+    const bool over = total > 0xffffffffull;      // the prefix is 32 bits wide: nothing can be emitted
+    hdr[0] = over ? 0ull : total;
+    counters[0] = total;
+    counters[1] = deg;
+    counters[2] = 0ull;
+    counters[3] = 0ull;
+    counters[4] = m;
+    counters[5] = 0ull;
+    counters[6] = over ? 1ull : 0ull;
+    counters[7] = 0ull;
+  }
+}
+
+__global__ void __launch_bounds__(GB) ms_base_kernel(uint32_t m, const uint32_t* __restrict__ bpre, uint32_t* __restrict__ prefix) {
+  const uint32_t t = blockIdx.x * GB + threadIdx.x;
+  if (t < m) prefix[t] += bpre[blockIdx.x];
+}
+
+void launch_mesh_sample_plan(const MeshSample& ms, void* work, uint64_t* counters, hipStream_t s) {
+  const MsWork w = ms_work(work, (size_t)ms.m);
+  const unsigned nb = (unsigned)ng_nb((size_t)ms.m);
+  hipLaunchKernelGGL(ms_plan_kernel, dim3(nb), dim3(GB), 0, s, ms, w.prefix, w.bcounts, w.dcounts);
+  hipLaunchKernelGGL(ms_scan_kernel, dim3(1), dim3(1024), 0, s, (int)nb, w.bcounts, w.dcounts, (unsigned long long)ms.m, w.hdr, (unsigned long long*)counters);
+  hipLaunchKernelGGL(ms_base_kernel, dim3(nb), dim3(GB), 0, s, ms.m, w.bcounts, w.prefix);
+}
+
+__global__ void __launch_bounds__(GB)
+ms_emit_kernel(MeshSample ms, const uint32_t* __restrict__ prefix, const unsigned long long* __restrict__ hdr, unsigned long long cap, uint4* __restrict__ rows,
+               unsigned long long* __restrict__ counters) {
+#pragma clang fp contract(off)
+  const unsigned long long total = hdr[0], written = total < cap ? total : cap;
+  const unsigned long long i = (unsigned long long)blockIdx.x * GB + threadIdx.x;
+  if (i == 0) {
+    counters[2] = written;
+    counters[3] = total - written;
+  }
+  if (i >= written) return;
+  // the triangle of sample i: the last t with prefix[t] <= i (a triangle without samples shares its prefix with its successor)
+  uint32_t lo = 0u, hi = ms.m;      // prefix[lo] <= i; hi: first index known to be beyond
+  for (int step = 0; step < 32 && hi - lo > 1u; step++) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if ((unsigned long long)prefix[mid] <= i) lo = mid; else hi = mid;
+  }
+  const uint32_t t = lo, j = (uint32_t)(i - prefix[t]);
+  MsTri T;
+  if (!ms_load(ms, t, T)) return;      // (a triangle with samples passed this test in the plan)
+  double r1 = (double)ms_hash(ms.seed, t, 2u * j) * 0x1p-32, r2 = (double)ms_hash(ms.seed, t, 2u * j + 1u) * 0x1p-32;
+  if (r1 + r2 > 1.0) { r1 = 1.0 - r1; r2 = 1.0 - r2; }
+  const double w0 = 1.0 - r1 - r2;      // exact: multiples of 2^-32
+  const float px = (float)(T.a[0] + r1 * T.e1[0] + r2 * T.e2[0]);
+  const float py = (float)(T.a[1] + r1 * T.e1[1] + r2 * T.e2[1]);
+  const float pz = (float)(T.a[2] + r1 * T.e1[2] + r2 * T.e2[2]);
+  const uint32_t rgba = (w0 >= r1 && w0 >= r2) ? T.rgba[0] : (r1 >= r2 ? T.rgba[1] : T.rgba[2]);      // the largest weight, lowest index on a tie
+  rows[i] = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), rgba);      // one 16-byte store
+}
+
+void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint64_t cap, uint64_t* counters, hipStream_t s) {
+  const MsWork w = ms_work((void*)work, (size_t)ms.m);
+  size_t nb = ng_nb((size_t)cap);
+  nb = nb < 1 ? 1 : nb;
+  hipLaunchKernelGGL(ms_emit_kernel, dim3((unsigned)nb), dim3(GB), 0, s, ms, w.prefix, w.hdr, (unsigned long long)cap, (uint4*)rows, (unsigned long long*)counters);
+}

@@ -13,7 +13,9 @@ monocular depth network and LPIPS (a downloaded network; its list stays empty) a
 (``debug_frames.py``): ``debug.create_video`` writes the reference's per-frame 2 x 3 mosaic (``:233-276,450-485``) as numbered PNG files under
 ``outputdir/debug_video/``, ``debug.save_keyframes`` one PNG per keyframe (mapper.py), ``render()`` the image-over-depth pairs of ``:148-195``.  ``pointcloud.export`` / ``export_pointcloud()``
 (``pointcloud.py``): the reconstruction as a fused coloured point cloud and the camera path, ``outputdir/pointcloud/cloud.ply`` + ``trajectory.ply``;
-``mesh.export`` / ``export_mesh()`` (``mesh.py``): the same views fused into a truncated signed distance volume and meshed, ``outputdir/mesh/mesh.ply``."""
+``mesh.export`` / ``export_mesh()`` (``mesh.py``): the same views fused into a truncated signed distance volume and meshed, ``outputdir/mesh/mesh.ply``; ``geometry.eval`` / ``evaluate_geometry()``
+(``geometry.py``): that mesh or cloud scored against a reference surface (accuracy, completion, completion ratio, F-score, Chamfer distance),
+``outputdir/geometry/metrics.json`` + ``accuracy.ply`` + ``completion.ply``."""
 from __future__ import annotations
 
 import math
@@ -240,6 +242,7 @@ class SLAM:
         self.frame_sink = None      # debug.create_video: the PNG writer of outputdir/debug_video, opened by the first frame, closed by run()
         self.pointcloud_export = None      # pointcloud.export: the paths and counters of the last export_pointcloud()
         self.mesh_export = None            # mesh.export: the path, counters and lattice of the last export_mesh()
+        self.geometry_eval = None          # geometry.eval: the comparison of the last evaluate_geometry()
         if resume is not None:
             dev = cfg["device"]
             for i, p in enumerate(resume["pose_est"][:n]):
@@ -323,14 +326,17 @@ class SLAM:
                     df.save_png(df.compose([(df.COLOR, color, None), (df.DEPTH, depth, None)], 2, 1, quant=1, bgr=False), written[-1])
         return written
 
-    def _export_views(self, every, source, block):
+    def _export_views(self, every, source, block, poses=None):
         """The views of an export (`pointcloud`, `mesh`), one (color [3,H,W], depth [H,W], silhouette [H,W] or None, pose [7]) per frame with
         `idx % every == 0` that has an estimated pose: `source` "render": the map rendered at that pose with its rendered silhouette;
-        "sensor": the frame's own colour and sensor depth."""
+        "sensor": the frame's own colour and sensor depth.  `poses` (one per frame, None: the estimated ones) replaces the pose of every
+        view -- the geometry evaluation's reference places the same frames at their ground-truth poses."""
         for idx in range(len(self.seq)):
             pose = self.estimate_pose_list[idx]
             if pose is None or idx % every != 0:
                 continue
+            if poses is not None:
+                pose = poses[idx]
             if source == "render":
                 result = self.renderer.render(self.gaussians, camera_pose=pose)
                 yield result["render"], result["depth"][0], result["depth"][1], pose
@@ -339,6 +345,20 @@ class SLAM:
                 if depth is None:
                     raise ValueError(f'{block}.source "sensor": frame {idx} has no sensor depth')
                 yield color, depth, None, pose
+
+    def _cloud_geometry(self, every, source, voxel, opt, poses=None):
+        """The views of an export lifted and thinned (what `export_pointcloud` writes and `evaluate_geometry` scores): the finished builder
+        (its `rows()`: device tensor on a GPU) and its counters.  `opt` is the merged `pointcloud` block; `poses` as in `_export_views`."""
+        from . import pointcloud as pc
+        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
+        on_device = str(self.cfg["device"]).startswith("cuda")
+        Builder = pc.PointCloudBuilder if on_device else pc.HostPointCloudBuilder
+        builder = Builder(H, W, self.cfg["cam"], voxel=voxel, max_points=int(opt["max_points"]), sil_min=float(opt["sil_min"]),
+                          depth_max=float(opt["max_depth"]), device=self.cfg["device"])
+        with torch.no_grad():
+            for view in self._export_views(every, source, "pointcloud", poses):
+                builder.add(*view)
+        return builder, builder.finish()
 
     def export_pointcloud(self, path=None, every=None, voxel=None, source=None):
         """The reconstruction as a fused coloured point cloud (pointcloud.py; the core of the reference's scripts/visualizer.py): for every
@@ -359,16 +379,8 @@ class SLAM:
         if every < 1:
             raise ValueError(f"pointcloud.every = {every} (must be positive)")
         path = os.path.join(self.cfg["outputdir"], "pointcloud") if path is None else path
-        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
-        on_device = str(self.cfg["device"]).startswith("cuda")
-        Builder = pc.PointCloudBuilder if on_device else pc.HostPointCloudBuilder
-        builder = Builder(H, W, self.cfg["cam"], voxel=voxel, max_points=int(opt["max_points"]), sil_min=float(opt["sil_min"]),
-                          depth_max=float(opt["max_depth"]), device=self.cfg["device"])
+        builder, counters = self._cloud_geometry(every, source, voxel, opt)
         poses = [pose.detach() for pose in self.estimate_pose_list[:len(self.seq)] if pose is not None]
-        with torch.no_grad():
-            for view in self._export_views(every, source, "pointcloud"):
-                builder.add(*view)
-        counters = builder.finish()
         os.makedirs(path, exist_ok=True)
         out = {"cloud": pc.write_ply(os.path.join(path, "cloud.ply"), builder.rows()),
                "trajectory": pc.write_trajectory_ply(os.path.join(path, "trajectory.ply"), torch.stack(poses) if poses else np.zeros((0, 7))),
@@ -377,12 +389,12 @@ class SLAM:
         print(f"Point cloud: {counters['rows']} points from {counters['views']} views ({counters['valid']} valid pixels, voxel {voxel} m) in {out['cloud']}")
         return out
 
-    def _mesh_bounds(self, every, source, sil_min, depth_max):
+    def _mesh_bounds(self, every, source, sil_min, depth_max, poses=None):
         """The box [xmin, ymin, zmin, xmax, ymax, zmax] of the lifted valid points of an export's views (the point cloud's validity test and
         back-projection, here with torch operators in float64); its six numbers are read back once, after the last view."""
         cam = self.cfg["cam"]
         lo = hi = None
-        for color, depth, sil, pose in self._export_views(every, source, "mesh"):
+        for color, depth, sil, pose in self._export_views(every, source, "mesh", poses):
             d = depth.detach().float()
             ok = (d > 0) & torch.isfinite(d)
             if depth_max > 0:
@@ -411,6 +423,34 @@ class SLAM:
             raise ValueError("mesh export: no view has a valid pixel (mesh.sil_min, mesh.max_depth)")
         return box
 
+    def _mesh_geometry(self, every, source, voxel, trunc, opt, poses=None):
+        """The views of an export fused and meshed (what `export_mesh` writes and `evaluate_geometry` scores): (rows, triangles, counters,
+        lattice sizes, origin); device tensors on a GPU.  `opt` is the merged `mesh` block; `poses` as in `_export_views`."""
+        from . import mesh as ms
+        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
+        sil_min, depth_max = float(opt["sil_min"]), float(opt["max_depth"])
+        with torch.no_grad():
+            if opt["bounds"] is None:
+                box = self._mesh_bounds(every, source, sil_min, depth_max, poses)
+                box[:3] -= trunc + voxel
+                box[3:] += trunc + voxel
+            else:
+                box = np.asarray(opt["bounds"], dtype=np.float64).reshape(6)
+            origin = np.floor(box[:3] / voxel) * voxel
+            dims = [max(int(np.ceil((box[3 + a] - origin[a]) / voxel)) + 1, 2) for a in range(3)]
+            if dims[0] * dims[1] * dims[2] > min(int(opt["max_voxels"]), ms.MAX_SAMPLES):
+                raise ValueError(f"mesh export: the box {box[:3].tolist()} .. {box[3:].tolist()} at mesh.voxel = {voxel} m is a lattice of "
+                                 f"{dims[0]} x {dims[1]} x {dims[2]} samples, more than mesh.max_voxels = {int(opt['max_voxels'])} (at most 2^30); raise "
+                                 f"mesh.voxel or mesh.max_voxels, or set mesh.bounds")
+            on_device = str(self.cfg["device"]).startswith("cuda")
+            Volume = ms.TsdfVolume if on_device else ms.HostTsdfVolume
+            volume = Volume(dims, origin, voxel, trunc, H, W, self.cfg["cam"], sil_min=sil_min, depth_max=depth_max, min_weight=float(opt["min_weight"]),
+                            device=self.cfg["device"])
+            for view in self._export_views(every, source, "mesh", poses):
+                volume.add(*view)
+            rows, triangles, counters = volume.extract()
+        return rows, triangles, counters, dims, origin
+
     def export_mesh(self, path=None, every=None, voxel=None, source=None):
         """The reconstruction as a coloured triangle mesh (mesh.py): the views of `export_pointcloud` (`every`, `source`) fused into a dense
         truncated signed distance volume of `mesh.voxel`-sized cells (`mesh.trunc`, 0: 4 voxel) over `mesh.bounds` -- None: a first pass
@@ -433,28 +473,7 @@ class SLAM:
         if not (np.isfinite(voxel) and voxel > 0):
             raise ValueError(f"mesh.voxel = {voxel} (must be positive)")
         path = os.path.join(self.cfg["outputdir"], "mesh") if path is None else path
-        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
-        sil_min, depth_max = float(opt["sil_min"]), float(opt["max_depth"])
-        with torch.no_grad():
-            if opt["bounds"] is None:
-                box = self._mesh_bounds(every, source, sil_min, depth_max)
-                box[:3] -= trunc + voxel
-                box[3:] += trunc + voxel
-            else:
-                box = np.asarray(opt["bounds"], dtype=np.float64).reshape(6)
-            origin = np.floor(box[:3] / voxel) * voxel
-            dims = [max(int(np.ceil((box[3 + a] - origin[a]) / voxel)) + 1, 2) for a in range(3)]
-            if dims[0] * dims[1] * dims[2] > min(int(opt["max_voxels"]), ms.MAX_SAMPLES):
-                raise ValueError(f"mesh export: the box {box[:3].tolist()} .. {box[3:].tolist()} at mesh.voxel = {voxel} m is a lattice of "
-                                 f"{dims[0]} x {dims[1]} x {dims[2]} samples, more than mesh.max_voxels = {int(opt['max_voxels'])} (at most 2^30); raise "
-                                 f"mesh.voxel or mesh.max_voxels, or set mesh.bounds")
-            on_device = str(self.cfg["device"]).startswith("cuda")
-            Volume = ms.TsdfVolume if on_device else ms.HostTsdfVolume
-            volume = Volume(dims, origin, voxel, trunc, H, W, self.cfg["cam"], sil_min=sil_min, depth_max=depth_max, min_weight=float(opt["min_weight"]),
-                            device=self.cfg["device"])
-            for view in self._export_views(every, source, "mesh"):
-                volume.add(*view)
-            rows, triangles, counters = volume.extract()
+        rows, triangles, counters, dims, origin = self._mesh_geometry(every, source, voxel, trunc, opt)
         os.makedirs(path, exist_ok=True)
         out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles), "counters": counters, "lattice": tuple(dims),
                "origin": origin.tolist(), "voxel": voxel, "trunc": trunc}
@@ -462,6 +481,94 @@ class SLAM:
         print(f"Mesh: {counters['vertices']} vertices, {counters['triangles']} triangles from {counters['views']} views "
               f"(lattice {dims[0]} x {dims[1]} x {dims[2]}, voxel {voxel} m) in {out['mesh']}")
         return out
+
+    def _gt_poses(self):
+        """One ground-truth pose per frame for the geometry evaluation's reference: `gt_pose_list` as the run filled it, else (a resumed
+        checkpoint, which ran no frame) `pose_gt` of `outputdir/results.npz`."""
+        poses = list(self.gt_pose_list)
+        if any(p is None for p, e in zip(poses, self.estimate_pose_list) if e is not None) and "outputdir" in self.cfg:
+            stored = os.path.join(self.cfg["outputdir"], "results.npz")
+            if os.path.exists(stored):
+                for i, p in enumerate(np.load(stored, allow_pickle=True)["pose_gt"][:len(poses)]):
+                    if poses[i] is None:
+                        poses[i] = torch.tensor(p, device=self.cfg["device"])
+        missing = [i for i, (p, e) in enumerate(zip(poses, self.estimate_pose_list)) if e is not None and p is None]
+        if missing:
+            raise ValueError(f'geometry.reference "sensor": no ground-truth pose for frame(s) {missing[:8]} (neither from the run nor in results.npz)')
+        return poses
+
+    def _align_rows(self, rows, method):
+        """The rows with their positions moved by the trajectory alignment estimate -> ground truth (eval_utils.align_horn / align_umeyama
+        of the camera centres), applied in torch float64 and rounded once to float32."""
+        from .eval_utils import align_horn, align_umeyama, camera_centers
+        idx = [i for i, p in enumerate(self.estimate_pose_list[:len(self.seq)]) if p is not None]
+        gt = self._gt_poses()
+        est_c = camera_centers(torch.stack([self.estimate_pose_list[i].detach() for i in idx]))[:, 4:].numpy()
+        gt_c = camera_centers(torch.stack([gt[i].detach() for i in idx]))[:, 4:].numpy()
+        if method == "horn":
+            R, t, _ = align_horn(est_c.T, gt_c.T)
+            s = 1.0
+        else:
+            s, R, t = align_umeyama(gt_c, est_c)
+        rows = torch.as_tensor(rows).to(torch.int32).reshape(-1, 4)
+        A = torch.tensor(s * np.asarray(R), dtype=torch.float64, device=rows.device)
+        b = torch.tensor(np.asarray(t).reshape(3), dtype=torch.float64, device=rows.device)
+        xyz = rows[:, :3].contiguous().view(torch.float32).double() @ A.T + b
+        return torch.cat([xyz.float().view(torch.int32), rows[:, 3:]], 1).contiguous()
+
+    def evaluate_geometry(self, path=None, estimate=None, reference=None):
+        """The exported geometry scored against a reference surface (geometry.py): accuracy, completion, completion ratio, precision, recall,
+        F-score and Chamfer distance from exact truncated nearest-neighbour distances in both directions.  `estimate` "mesh" / "pointcloud":
+        what `export_mesh` / `export_pointcloud` produce (their blocks' `every`, `source` and sizes), from their rows in memory.
+        `reference` "sensor": the same frames' own colour and sensor depth fused by the same builder at the GROUND-TRUTH poses -- what a
+        perfect tracker and map would have exported (ValueError without sensor depth) --, or the path of a PLY file: a point cloud
+        (`pointcloud.read_ply`) or, with a face element, a mesh (`mesh.read_mesh_ply`).  Meshes on either side are sampled at
+        `geometry.density` samples per m^2; `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first.
+        Writes `path/metrics.json`, `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); arguments left None come from the
+        `geometry` config block.  HIP kernels and one read-back of the [2,8] table on a GPU, the host statement on `device: cpu`.  Touches
+        no pose and no other output.  Returns the comparison with the paths."""
+        from . import geometry as geo, mesh as ms, pointcloud as pc
+        from .config import _TUM
+        opt = dict(_TUM["geometry"], **(self.cfg.get("geometry") or {}))
+        estimate = str(opt["estimate"] if estimate is None else estimate)
+        reference = str(opt["reference"] if reference is None else reference)
+        align = str(opt["align"] or "none").lower()
+        if estimate not in ("mesh", "pointcloud"):
+            raise ValueError(f"geometry.estimate = {estimate!r} (mesh / pointcloud)")
+        if align not in ("none", "horn", "umeyama"):
+            raise ValueError(f"geometry.align = {align!r} (none / horn / umeyama)")
+        block = dict(_TUM[estimate], **(self.cfg.get(estimate) or {}))
+        every = int(block["every"] or self.cfg["mapping"]["kf_every"])
+        voxel = float(block["voxel"])
+        trunc = float(block["trunc"]) if estimate == "mesh" and float(block["trunc"] or 0) > 0 else 4.0 * voxel
+
+        def build(source, poses):
+            if estimate == "mesh":
+                rows, triangles = self._mesh_geometry(every, source, voxel, trunc, block, poses)[:2]
+                return rows, triangles
+            return self._cloud_geometry(every, source, voxel, block, poses)[0].rows()
+
+        est = build(str(block["source"]), None)
+        if align != "none":
+            est = (self._align_rows(est[0], align), est[1]) if estimate == "mesh" else self._align_rows(est, align)
+        if reference == "sensor":
+            ref = build("sensor", self._gt_poses())
+        else:
+            with open(reference, "rb") as fh:
+                has_faces = any(e[0] == "face" for e in pc._read_header(fh))
+            ref = ms.read_mesh_ply(reference) if has_faces else pc.read_ply(reference)
+        result = geo.compare(est, ref, device=self.cfg["device"], threshold=float(opt["threshold"]), max_dist=float(opt["max_dist"]),
+                             cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]))
+        path = os.path.join(self.cfg["outputdir"], "geometry") if path is None else path
+        result["files"] = geo.write_outputs(path, result, {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]),
+                                                           "seed": int(opt["seed"])})
+        self.geometry_eval = result      # what the last evaluation found (run() calls this without a caller to hand it to)
+        t = result["table"]
+        print(f"Geometry ({estimate} against {reference}): accuracy {result['accuracy'] * 100:.3f} cm, completion {result['completion'] * 100:.3f} cm, "
+              f"completion ratio {result['completion_ratio'] * 100:.2f} % at {float(opt['threshold']) * 100:g} cm, F-score {result['fscore']:.4f}, Chamfer "
+              f"{result['chamfer'] * 100:.3f} cm ({result['n_estimate']} / {result['n_reference']} points, clamped {int(t[0, 5])} / {int(t[1, 5])}) in "
+              f"{result['files']['metrics']}")
+        return result
 
     def run(self, progress=None, reraise=True):
         """slam/SLAM.py:375-503: every frame; `save_iterations` checkpoints on the way; with an `outputdir` the final map (as
@@ -510,6 +617,11 @@ class SLAM:
                         self.export_mesh()
                     except Exception as e5:      # noqa: BLE001
                         print(f"(mesh export: {e5!r})")
+                if (self.cfg.get("geometry") or {}).get("eval", False):          # likewise; after the mesh export
+                    try:
+                        self.evaluate_geometry()
+                    except Exception as e6:      # noqa: BLE001
+                        print(f"(geometry evaluation: {e6!r})")
         if self.failure is not None and reraise:
             raise self.failure
 

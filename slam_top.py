@@ -29,7 +29,9 @@ point cloud (the map rendered at every `pointcloud.every`-th estimated pose, lif
 uchar red green blue alpha`), and `pointcloud/trajectory.ply`, the camera path -- the computational core of the reference's scripts/visualizer.py, for MeshLab or
 CloudCompare; `--pointcloud --eval` writes the two files from the checkpoint without running a frame.  `--mesh` (or `mesh.export: true`) adds `mesh/mesh.ply`,
 the same views fused into a truncated signed distance volume and meshed by marching tetrahedra (a coloured triangle mesh, binary PLY); `--mesh --eval` likewise
-from the checkpoint.
+from the checkpoint.  `--geometry` (or `geometry.eval: true`) adds `geometry/metrics.json`, `accuracy.ply` and `completion.ply`: the exported mesh or cloud scored
+against a reference surface (the same frames' sensor depth at the ground-truth poses, or a PLY file) -- accuracy, completion, completion ratio, F-score, Chamfer
+distance; `--geometry --eval` likewise from the checkpoint.
 
 `--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
 `outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
@@ -133,6 +135,17 @@ def export_mesh_checkpoint(cfg, seq, iteration=None):
     return out
 
 
+def evaluate_geometry_checkpoint(cfg, seq, iteration=None):
+    """`--geometry --eval`: the geometry scores of a finished run from its checkpoint, without running a frame: resumes like
+    `evaluate_checkpoint` and calls `SLAM.evaluate_geometry` with the config's `geometry` block (the ground-truth poses of a "sensor"
+    reference come from results.npz).  Adds `outputdir/geometry/` (metrics.json, accuracy.ply, completion.ply) and touches nothing else.
+    Returns what the evaluation returns."""
+    slam, iteration = resume_checkpoint(cfg, seq, iteration)
+    out = slam.evaluate_geometry()
+    out["iteration"] = iteration
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=None, help="YAML config in the reference's schema")
@@ -142,6 +155,7 @@ def main():
     ap.add_argument("--eval", action="store_true", help="run no frame: score the finished run in outputdir from its checkpoint (PSNR, SSIM, depth L1 with eval_on_device, ATE RMSE)")
     ap.add_argument("--pointcloud", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the fused coloured point cloud and the camera path to outputdir/pointcloud (the config's `pointcloud` block)")
     ap.add_argument("--mesh", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the reconstruction as a coloured triangle mesh to outputdir/mesh/mesh.ply (the config's `mesh` block)")
+    ap.add_argument("--geometry", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) score the exported geometry against a reference surface into outputdir/geometry (the config's `geometry` block)")
     ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
@@ -167,9 +181,13 @@ def main():
             export_pointcloud_checkpoint(cfg, seq, args.iteration)
         if args.mesh:
             export_mesh_checkpoint(cfg, seq, args.iteration)
-        if not (args.pointcloud or args.mesh):
+        if args.geometry:
+            evaluate_geometry_checkpoint(cfg, seq, args.iteration)
+        if not (args.pointcloud or args.mesh or args.geometry):
             evaluate_checkpoint(cfg, seq, args.iteration)
         return
+    if args.geometry:
+        cfg["geometry"] = dict(cfg.get("geometry") or {}, eval=True)
     if args.pointcloud:
         cfg["pointcloud"] = dict(cfg.get("pointcloud") or {}, export=True)
     if args.mesh:
