@@ -338,7 +338,8 @@ int mm3dgs_slam_adam_project(const Mm3dgsCamera* cam, int P, const Mm3dgsSlamInp
  * initialisation of the new rows).  All asynchronous; the counts land in device words the caller reads when it chooses to.
  * ===================================================================================================== */
 /* keep[i] = 0 where  sigmoid(opacity[i]) < min_opacity  ||  max_k exp(log_scales[i,k]) > max_scale  ||
- * (max_radii2D != NULL && max_radii2D[i] > max_screen_size)   (slam/gaussian_model.py:574-588), else 1;
+ * (max_radii2D != NULL && max_radii2D[i] > max_screen_size)   (slam/gaussian_model.py:574-588), else 1; a NaN makes its clause
+ * false as in torch -- the maximum propagates a NaN scale component (torch.max), so such a row is not pruned for its size;
  * *n_pruned_accum += number of zeros written (a sticky counter: never reset by the library). */
 int mm3dgs_prune_mask(int P, const float* opacity_logits, const float* log_scales, const float* max_radii2D_or_null, float min_opacity,
                       float max_scale, float max_screen_size, uint8_t* keep, uint32_t* n_pruned_accum, void* stream);

@@ -16,6 +16,8 @@
 
 #define CB 256
 
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || a > b) ? a : b; }      // torch.max: NaN wins
+
 // keep[i] = !pruned; *n_pruned += number of pruned elements (sticky device counter: the host may read it much later)
 __global__ void __launch_bounds__(CB)
 prune_mask_kernel(int P, const float* __restrict__ opacity, const float* __restrict__ scaling, const float* __restrict__ max_radii2D,
@@ -25,7 +27,8 @@ prune_mask_kernel(int P, const float* __restrict__ opacity, const float* __restr
   bool pr = false;
   if (i < P) {
     const float o = 1.f / (1.f + expf(-opacity[i]));      // (accurate exp: the decisions must match torch.sigmoid / torch.exp)
-    const float s = fmaxf(fmaxf(scaling[(size_t)i * 3], scaling[(size_t)i * 3 + 1]), scaling[(size_t)i * 3 + 2]);
+    // (max_nan, not fmaxf: a NaN component makes the scale clause false, as get_scaling.max(dim=1).values > 0.1 extent does)
+    const float s = max_nan(max_nan(scaling[(size_t)i * 3], scaling[(size_t)i * 3 + 1]), scaling[(size_t)i * 3 + 2]);
     pr = (o < min_opacity) || (expf(s) > max_scale) || (use_screen && max_radii2D[i] > max_screen_size);
     keep[i] = pr ? 0 : 1;
   }
@@ -112,8 +115,6 @@ seed_gaussians_kernel(int H, int W, const float* __restrict__ color, const float
 #define DENSIFY_KEEP 0
 #define DENSIFY_CLONE 1
 #define DENSIFY_SPLIT 2
-
-__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || a > b) ? a : b; }      // torch.max: NaN wins
 
 __global__ void __launch_bounds__(CB)
 densify_classify_kernel(int P, int nb, const float* __restrict__ grad_accum, const float* __restrict__ denom, const float* __restrict__ scaling,

@@ -1145,7 +1145,8 @@ def eng_grads(eng, g):
 
 def test_device_prune_compaction_matches_the_torch_surgery():
     """GaussianModel.prune on the device (predicate kernel + order-preserving compaction of parameters, Adam moments and statistics,
-    csrc/compact.hip) against the torch path (slam/gaussian_model.py:380-451,574-588 mirrored in prune_points): same rows, same order."""
+    csrc/compact.hip) against the torch path (slam/gaussian_model.py:380-451,574-588 mirrored in prune_points): same rows, same order.
+    The edge sizes (one row .. 1025 workgroups), the NaN rows and the guard words are in tests/test_gpu_surgery.py."""
     import copy
     from mm3dgs_slam_amd.gaussian_model import GaussianModel
     from tests import densify_util as du
@@ -1186,7 +1187,8 @@ def test_device_prune_compaction_matches_the_torch_surgery():
 
 def test_device_seeding_matches_the_reference_fixture_g7_and_the_torch_mirror():
     """mm3dgs_seed_gaussians against G7 (the reference's get_pointcloud + initialisation on a 32x24 RGB-D, tests/golden) and, at
-    640x480 with a sparse mask, against the torch mirror Mapper.initialize_new_gaussians (same rows in the same raster order)."""
+    640x480 with a sparse mask, against the torch mirror Mapper.initialize_new_gaussians (same rows in the same raster order).
+    The edge shapes (1x1 .. 513x512, 1026 workgroups), row0 and n_rest against the float64 statement are in tests/test_gpu_surgery.py."""
     import os
     from mm3dgs_slam_amd.config import default_config
     from mm3dgs_slam_amd.gaussian_model import GaussianModel
