@@ -206,6 +206,11 @@ def profile_read():
     return out
 
 
+def ptr(t):
+    """The device (or host) address of a tensor's first element as the C ABI takes it; None is NULL."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def check(rc: int):
     if rc != 0:
         msg = load().mm3dgs_last_error()

@@ -41,7 +41,6 @@ raw array travels in the frame's staging slot: decoded by the same prefetch job,
 returns a fresh tensor on every call (keyframes keep the estimate), the same in any access order.  Neither path has been timed."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -171,9 +170,8 @@ def ingest_device(rgb_dev, depth_dev, png_depth_scale, H, W):
         raise ValueError(f"ingest_device: depth must be a contiguous 16-bit [{Hs},{Ws}] tensor on the GPU, got {depth_dev.dtype} {tuple(depth_dev.shape)}")
     color = torch.empty(3, H, W, dtype=torch.float32, device=rgb_dev.device)
     d = None if depth_dev is None else torch.empty(H, W, dtype=torch.float32, device=rgb_dev.device)
-    _lib.check(_lib.load().mm3dgs_ingest_frame(Hs, Ws, C.c_void_p(rgb_dev.data_ptr()), None if depth_dev is None else C.c_void_p(depth_dev.data_ptr()),
-                                               float(png_depth_scale), int(H), int(W), C.c_void_p(color.data_ptr()),
-                                               None if d is None else C.c_void_p(d.data_ptr()), _stream()))
+    P = _lib.ptr
+    _lib.check(_lib.load().mm3dgs_ingest_frame(Hs, Ws, P(rgb_dev), P(depth_dev), float(png_depth_scale), int(H), int(W), P(color), P(d), _stream()))
     return color, d
 
 
@@ -214,8 +212,8 @@ def ingest_est_device(raw_dev, scale, H, W):
         raise ValueError(f"ingest_est_device: a contiguous float32 / float16 / 16-bit integer [Hs,Ws] tensor on the GPU is needed, got "
                          f"{raw_dev.dtype} {tuple(raw_dev.shape)} on {raw_dev.device}")
     out = torch.empty(H, W, dtype=torch.float32, device=raw_dev.device)
-    _lib.check(_lib.load().mm3dgs_ingest_est(int(raw_dev.shape[0]), int(raw_dev.shape[1]), C.c_void_p(raw_dev.data_ptr()), code, float(scale),
-                                             int(H), int(W), C.c_void_p(out.data_ptr()), _stream()))
+    _lib.check(_lib.load().mm3dgs_ingest_est(int(raw_dev.shape[0]), int(raw_dev.shape[1]), _lib.ptr(raw_dev), code, float(scale), int(H), int(W),
+                                             _lib.ptr(out), _stream()))
     return out
 
 

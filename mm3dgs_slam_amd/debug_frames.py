@@ -122,9 +122,8 @@ def mosaic_call(H, W, rows, cols, kinds, a_ptrs, b_ptrs, lut_ptr, quant, bgr, wo
     kind_arr = (C.c_int32 * n)(*[int(k) for k in kinds])
     a_arr = (C.c_void_p * n)(*[p or None for p in a_ptrs])
     b_arr = (C.c_void_p * n)(*[p or None for p in b_ptrs])
-    vp = lambda p: C.c_void_p(p) if p else None
-    return _lib.load().mm3dgs_mosaic(int(H), int(W), int(rows), int(cols), kind_arr, a_arr, b_arr, vp(lut_ptr), int(quant), int(bool(bgr)),
-                                     vp(work_ptr), vp(out_ptr), _stream())
+    return _lib.load().mm3dgs_mosaic(int(H), int(W), int(rows), int(cols), kind_arr, a_arr, b_arr, lut_ptr or None, int(quant), int(bool(bgr)),
+                                     work_ptr or None, out_ptr or None, _stream())      # (a c_void_p parameter takes the address as it is)
 
 
 def compose_device(panels, rows, cols, quant=0, bgr=False):

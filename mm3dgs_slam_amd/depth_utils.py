@@ -56,7 +56,6 @@ def align_depth_device(est, depth, sil=None, sil_min=0.99, est_min=1e-6):
     (0 / 1), the number of valid pixels, a00, a01, b0, b1, zeros; not ok (fewer than two valid pixels, an estimate constant over them) is
     the identity fit.  One difference from ``get_scale_shift_LS``: a pixel whose depth is so small that ``1 / depth`` overflows is left
     out here and makes the host path return NaN.  The scaled estimate is a fresh tensor on every call (keyframes keep it)."""
-    import ctypes as C
     from . import _lib
     from .rasterizer import _stream
     if not (est.is_cuda and depth.is_cuda and (sil is None or sil.is_cuda)):
@@ -74,9 +73,8 @@ def align_depth_device(est, depth, sil=None, sil_min=0.99, est_min=1e-6):
         work = _WORK[key] = torch.empty(int(lib.mm3dgs_align_depth_work_bytes(H, W)) // 8, dtype=torch.float64, device=est_c.device)
     fit = torch.empty(16, dtype=torch.float64, device=est_c.device)
     out = torch.empty_like(est_c)
-    _lib.check(lib.mm3dgs_align_depth(H, W, C.c_void_p(est_c.data_ptr()), C.c_void_p(depth_c.data_ptr()),
-                                      C.c_void_p(sil_c.data_ptr() if sil_c is not None else None), float(sil_min), float(est_min),
-                                      C.c_void_p(work.data_ptr()), C.c_void_p(fit.data_ptr()), C.c_void_p(out.data_ptr()), _stream()))
+    P = _lib.ptr
+    _lib.check(lib.mm3dgs_align_depth(H, W, P(est_c), P(depth_c), P(sil_c), float(sil_min), float(est_min), P(work), P(fit), P(out), _stream()))
     return out, fit
 
 

@@ -175,7 +175,7 @@ def image_metrics_device(image, gt, depth, gt_depth, row_out):
         work = _EVAL_WORK[key] = torch.empty(int(lib.mm3dgs_eval_image_work_bytes(H, W)) // 8, dtype=torch.float64, device=image_c.device)
     if _EVAL_WINDOW is None:
         _EVAL_WINDOW = (C.c_float * 11)(*window_1d().tolist())
-    ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+    ptr = _lib.ptr
     _lib.check(lib.mm3dgs_eval_image(H, W, ptr(image_c), ptr(gt_c), ptr(depth_c), ptr(gt_depth_c), _EVAL_WINDOW, ptr(work), ptr(row_out),
                                      _stream()))
     return row_out

@@ -1,0 +1,218 @@
+"""The post-run stage of a SLAM object: what is made of the finished map and trajectory, after ``results.npz``, which it does not touch --
+``pointcloud.export`` / ``export_pointcloud`` (``pointcloud.py``), ``mesh.export`` / ``export_mesh`` (``mesh.py``) and ``geometry.eval`` /
+``evaluate_geometry`` (``geometry.py``).  Plain functions of the ``SLAM`` object, which keeps the three drivers as methods; ``options`` is
+the one place a config block is resolved, ``run_post`` what ``SLAM.run`` ends in."""
+import os
+
+import numpy as np
+import torch
+
+from . import geometry as geo, mesh as ms, pointcloud as pc
+from .config import _TUM
+
+
+def options(cfg, block, **overrides):
+    """The `pointcloud`, `mesh` or `geometry` block of `cfg` merged over the defaults, an override that is not None over both, resolved
+    and validated: `every` (None: `mapping.kf_every`), `voxel`, `source` and the mesh's `trunc` (0: 4 voxel) of an export;
+    `estimate`, `reference` and `align` of the evaluation."""
+    opt = dict(_TUM[block], **(cfg.get(block) or {}))
+    if block == "geometry":
+        opt.update((k, v) for k, v in overrides.items() if v is not None)
+        opt.update(estimate=str(opt["estimate"]), reference=str(opt["reference"]), align=str(opt["align"] or "none").lower())
+        if opt["estimate"] not in ("mesh", "pointcloud"):
+            raise ValueError(f"geometry.estimate = {opt['estimate']!r} (mesh / pointcloud)")
+        if opt["align"] not in ("none", "horn", "umeyama"):
+            raise ValueError(f"geometry.align = {opt['align']!r} (none / horn / umeyama)")
+        return opt
+    opt["every"] = opt["every"] or cfg["mapping"]["kf_every"]
+    opt.update((k, v) for k, v in overrides.items() if v is not None)
+    every, voxel, source = int(opt["every"]), float(opt["voxel"]), str(opt["source"])
+    opt.update(every=every, voxel=voxel, source=source)
+    if source not in ("render", "sensor"):
+        raise ValueError(f"{block}.source = {source!r} (render / sensor)")
+    if every < 1:
+        raise ValueError(f"{block}.every = {every} (must be positive)")
+    if block == "mesh":
+        if not (np.isfinite(voxel) and voxel > 0):
+            raise ValueError(f"{block}.voxel = {voxel} (must be positive)")
+        opt["trunc"] = float(opt["trunc"]) if float(opt["trunc"] or 0) > 0 else 4.0 * voxel
+    return opt
+
+
+def views(slam, every, source, block, poses=None):
+    """The views of an export (`pointcloud`, `mesh`), one (color [3,H,W], depth [H,W], silhouette [H,W] or None, pose [7]) per frame with
+    `idx % every == 0` that has an estimated pose: `source` "render": the map rendered at that pose with its rendered silhouette;
+    "sensor": the frame's own colour and sensor depth.  `poses` (one per frame, None: the estimated ones) replaces the pose of every
+    view -- the geometry evaluation's reference places the same frames at their ground-truth poses."""
+    for idx in range(len(slam.seq)):
+        pose = slam.estimate_pose_list[idx]
+        if pose is None or idx % every != 0:
+            continue
+        if poses is not None:
+            pose = poses[idx]
+        if source == "render":
+            result = slam.renderer.render(slam.gaussians, camera_pose=pose)
+            yield result["render"], result["depth"][0], result["depth"][1], pose
+        else:
+            color, depth, _ = slam.seq[idx]
+            if depth is None:
+                raise ValueError(f'{block}.source "sensor": frame {idx} has no sensor depth')
+            yield color, depth, None, pose
+
+
+def gt_poses(slam):
+    """One ground-truth pose per frame for the geometry evaluation's reference: `gt_pose_list` as the run filled it, else (a resumed
+    checkpoint, which ran no frame) `pose_gt` of `outputdir/results.npz`."""
+    poses = list(slam.gt_pose_list)
+    if any(p is None for p, e in zip(poses, slam.estimate_pose_list) if e is not None) and "outputdir" in slam.cfg:
+        stored = os.path.join(slam.cfg["outputdir"], "results.npz")
+        if os.path.exists(stored):
+            for i, p in enumerate(np.load(stored, allow_pickle=True)["pose_gt"][:len(poses)]):
+                if poses[i] is None:
+                    poses[i] = torch.tensor(p, device=slam.cfg["device"])
+    missing = [i for i, (p, e) in enumerate(zip(poses, slam.estimate_pose_list)) if e is not None and p is None]
+    if missing:
+        raise ValueError(f'geometry.reference "sensor": no ground-truth pose for frame(s) {missing[:8]} (neither from the run nor in results.npz)')
+    return poses
+
+
+def cloud_geometry(slam, opt, poses=None):
+    """The views of an export lifted and thinned (what `export_pointcloud` writes and `evaluate_geometry` scores): the finished builder
+    (its `rows()`: device tensor on a GPU) and its counters.  `opt`: `options` of the `pointcloud` block; `poses` as in `views`."""
+    Builder = pc.PointCloudBuilder if str(slam.cfg["device"]).startswith("cuda") else pc.HostPointCloudBuilder
+    builder = Builder(int(slam.cfg["desired_height"]), int(slam.cfg["desired_width"]), slam.cfg["cam"], voxel=opt["voxel"], max_points=int(opt["max_points"]), sil_min=float(opt["sil_min"]),
+                      depth_max=float(opt["max_depth"]), device=slam.cfg["device"])
+    with torch.no_grad():
+        for view in views(slam, opt["every"], opt["source"], "pointcloud", poses):
+            builder.add(*view)
+    return builder, builder.finish()
+
+
+def mesh_bounds(slam, opt, poses=None):
+    """The box [xmin, ymin, zmin, xmax, ymax, zmax] of the lifted valid points of an export's views (`mesh.view_bounds`, view by view); its
+    six numbers are read back once, after the last view."""
+    lo = hi = None
+    for color, depth, sil, pose in views(slam, opt["every"], opt["source"], "mesh", poses):
+        a, b = ms.view_bounds(depth, sil, pose, slam.cfg["cam"], float(opt["sil_min"]), float(opt["max_depth"]))
+        lo, hi = (a, b) if lo is None else (torch.minimum(lo, a), torch.maximum(hi, b))
+    if lo is None:
+        raise ValueError("mesh export: no frame has an estimated pose")
+    box = torch.cat([lo, hi]).cpu().numpy()          # the one read-back
+    if not np.isfinite(box).all():
+        raise ValueError("mesh export: no view has a valid pixel (mesh.sil_min, mesh.max_depth)")
+    return box
+
+
+def mesh_geometry(slam, opt, poses=None):
+    """The views of an export fused and meshed (what `export_mesh` writes and `evaluate_geometry` scores): (rows, triangles, counters,
+    lattice sizes, origin); device tensors on a GPU.  `opt`: `options` of the `mesh` block; `poses` as in `views`."""
+    voxel, trunc, cfg = opt["voxel"], opt["trunc"], slam.cfg
+    with torch.no_grad():
+        if opt["bounds"] is None:
+            box = mesh_bounds(slam, opt, poses)
+            box[:3] -= trunc + voxel
+            box[3:] += trunc + voxel
+        else:
+            box = np.asarray(opt["bounds"], dtype=np.float64).reshape(6)
+        origin, dims = ms.lattice_for(box, voxel, opt["max_voxels"])
+        Volume = ms.TsdfVolume if str(cfg["device"]).startswith("cuda") else ms.HostTsdfVolume
+        volume = Volume(dims, origin, voxel, trunc, int(cfg["desired_height"]), int(cfg["desired_width"]), cfg["cam"], sil_min=float(opt["sil_min"]),
+                        depth_max=float(opt["max_depth"]), min_weight=float(opt["min_weight"]), device=cfg["device"])
+        for view in views(slam, opt["every"], opt["source"], "mesh", poses):
+            volume.add(*view)
+        rows, triangles, counters = volume.extract()
+    return rows, triangles, counters, dims, origin
+
+
+def export_pointcloud(slam, path=None, every=None, voxel=None, source=None):
+    """The reconstruction as a fused coloured point cloud (pointcloud.py; the core of the reference's scripts/visualizer.py): for every
+    frame with `idx % every == 0` that has an estimated pose one view at that pose -- `source` "render": the map rendered there, with
+    the rendered silhouette as the surface test (> `pointcloud.sil_min`, the reference's 0.99); "sensor": the frame's own colour and
+    sensor depth -- is lifted to world points, and the first point of every `voxel`-sized cell is kept.  Writes `path/cloud.ply` and
+    `path/trajectory.ply` (default `outputdir/pointcloud`); arguments left None come from the `pointcloud` config block.  One
+    mm3dgs_pointcloud_add_view call per view on a GPU, the host statement on `device: cpu`.  Returns the two paths and the counters;
+    raises RuntimeError when points were dropped for lack of room (`pointcloud.max_points`)."""
+    opt = options(slam.cfg, "pointcloud", every=every, voxel=voxel, source=source)
+    path = os.path.join(slam.cfg["outputdir"], "pointcloud") if path is None else path
+    builder, counters = cloud_geometry(slam, opt)
+    poses = [pose.detach() for pose in slam.estimate_pose_list[:len(slam.seq)] if pose is not None]
+    os.makedirs(path, exist_ok=True)
+    out = {"cloud": pc.write_ply(os.path.join(path, "cloud.ply"), builder.rows()),
+           "trajectory": pc.write_trajectory_ply(os.path.join(path, "trajectory.ply"), torch.stack(poses) if poses else np.zeros((0, 7))),
+           "counters": counters}
+    slam.pointcloud_export = out      # what the last export wrote (run_post calls this without a caller to hand it to)
+    print(f"Point cloud: {counters['rows']} points from {counters['views']} views ({counters['valid']} valid pixels, voxel {opt['voxel']} m) in {out['cloud']}")
+    return out
+
+
+def export_mesh(slam, path=None, every=None, voxel=None, source=None):
+    """The reconstruction as a coloured triangle mesh (mesh.py): the views of `export_pointcloud` (`every`, `source`) fused into a dense
+    truncated signed distance volume of `mesh.voxel`-sized cells (`mesh.trunc`, 0: 4 voxel) over `mesh.bounds` -- None: a first pass
+    over the same views takes the box of their lifted valid points, which is grown by trunc + voxel, the origin snapped down to a
+    multiple of voxel --, then marching tetrahedra over the samples seen at least `mesh.min_weight` times.  Writes `path/mesh.ply`
+    (default `outputdir/mesh`; the format: `mesh.write_mesh_ply`).  One mm3dgs_tsdf_integrate call per view and one mm3dgs_tsdf_mesh_plan /
+    _emit pair on a GPU, the host statement on `device: cpu`.  Returns the path, the counters and the lattice; raises ValueError when the
+    lattice exceeds `mesh.max_voxels`."""
+    opt = options(slam.cfg, "mesh", every=every, voxel=voxel, source=source)
+    path = os.path.join(slam.cfg["outputdir"], "mesh") if path is None else path
+    rows, triangles, counters, dims, origin = mesh_geometry(slam, opt)
+    os.makedirs(path, exist_ok=True)
+    out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles), "counters": counters, "lattice": tuple(dims),
+           "origin": origin.tolist(), "voxel": opt["voxel"], "trunc": opt["trunc"]}
+    slam.mesh_export = out      # what the last export wrote
+    print(f"Mesh: {counters['vertices']} vertices, {counters['triangles']} triangles from {counters['views']} views "
+          f"(lattice {dims[0]} x {dims[1]} x {dims[2]}, voxel {opt['voxel']} m) in {out['mesh']}")
+    return out
+
+
+def evaluate_geometry(slam, path=None, estimate=None, reference=None):
+    """The exported geometry scored against a reference surface (the figures of geometry.py).  `estimate` "mesh" / "pointcloud": what `export_mesh` / `export_pointcloud` produce (their blocks' `every`, `source` and sizes), from their rows in memory.
+    `reference` "sensor": the same frames' own colour and sensor depth fused by the same builder at the GROUND-TRUTH poses -- what a
+    perfect tracker and map would have exported (ValueError without sensor depth) --, or the path of a PLY file: a point cloud or, with a
+    face element, a mesh (`mesh.read_surface_ply`).  Meshes on either side are sampled at `geometry.density` samples per m^2;
+    `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first.  Writes `path/metrics.json`,
+    `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); arguments left None come from the `geometry` config block.  HIP
+    kernels and one read-back of the [2,8] table on a GPU, the host statement on `device: cpu`.  Touches no pose and no other output.
+    Returns the comparison with the paths."""
+    opt = options(slam.cfg, "geometry", estimate=estimate, reference=reference)
+    estimate, reference, align = opt["estimate"], opt["reference"], opt["align"]
+    block = options(slam.cfg, estimate)
+
+    def build(block, poses):
+        if estimate == "mesh":
+            return mesh_geometry(slam, block, poses)[:2]
+        return cloud_geometry(slam, block, poses)[0].rows()
+
+    est = build(block, None)
+    if align != "none":
+        move = lambda rows: geo.align_rows(rows, slam.estimate_pose_list[:len(slam.seq)], gt_poses(slam), align)
+        est = (move(est[0]), est[1]) if estimate == "mesh" else move(est)
+    ref = build(dict(block, source="sensor"), gt_poses(slam)) if reference == "sensor" else ms.read_surface_ply(reference)
+    result = geo.compare(est, ref, device=slam.cfg["device"], threshold=float(opt["threshold"]), max_dist=float(opt["max_dist"]),
+                         cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]))
+    path = os.path.join(slam.cfg["outputdir"], "geometry") if path is None else path
+    result["files"] = geo.write_outputs(path, result, {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]),
+                                                       "seed": int(opt["seed"])})
+    slam.geometry_eval = result      # what the last evaluation found
+    t = result["table"]
+    print(f"Geometry ({estimate} against {reference}): accuracy {result['accuracy'] * 100:.3f} cm, completion {result['completion'] * 100:.3f} cm, "
+          f"completion ratio {result['completion_ratio'] * 100:.2f} % at {float(opt['threshold']) * 100:g} cm, F-score {result['fscore']:.4f}, Chamfer "
+          f"{result['chamfer'] * 100:.3f} cm ({result['n_estimate']} / {result['n_reference']} points, clamped {int(t[0, 5])} / {int(t[1, 5])}) in "
+          f"{result['files']['metrics']}")
+    return result
+
+
+# (config block, its switch, the stage, how a failure is reported), in the order they run
+POST = (("pointcloud", "export", export_pointcloud, "point cloud export"),
+        ("mesh", "export", export_mesh, "mesh export"),
+        ("geometry", "eval", evaluate_geometry, "geometry evaluation"))
+
+
+def run_post(slam):
+    """The stages whose block is switched on, each reported and never raised: one that fails takes neither the run nor the next one down."""
+    for block, switch, stage, label in POST:
+        if (slam.cfg.get(block) or {}).get(switch, False):
+            try:
+                stage(slam)
+            except Exception as e:      # noqa: BLE001
+                print(f"({label}: {e!r})")

@@ -24,6 +24,7 @@ import warnings
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 from .general_utils import densify_frame, densify_seed
 from .mapper import Mapper
 from .rasterizer import _camera, _stream
@@ -36,10 +37,6 @@ def _gauss_window():
 
 
 _WINDOW = _gauss_window()
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class FusedEngine:

@@ -221,7 +221,7 @@ class GaussianModel:
         radii = self.max_radii2D if max_screen_size is not None else None
         _lib.check(_library().mm3dgs_prune_mask(P, _ptr(self._opacity), _ptr(self._scaling), _ptr(radii), float(min_opacity),
                                                 float(0.1 * extent), float(max_screen_size if max_screen_size is not None else 0.0),
-                                                _ptr(keep), C.c_void_p(counter_ptr), _stream()))
+                                                _ptr(keep), counter_ptr, _stream()))      # (a c_void_p parameter takes the address as it is)
         return keep
 
     def compact_device(self, keep):

@@ -43,7 +43,7 @@ import os
 import numpy as np
 import torch
 
-from .pointcloud import _np, rows_xyz
+from .pointcloud import as_np, rows_xyz
 
 ROW_NAMES = ("n", "mean", "rms", "max", "within_ratio", "clamped", "skipped", "reserved")
 SAMPLE_COUNTERS = ("samples", "degenerate", "written", "dropped", "triangles", "reserved5", "overflow", "reserved7")
@@ -207,7 +207,7 @@ def derived_figures(table):
 # ---- surface sampling ---------------------------------------------------------------------------------------------------------------
 def _triangle_counts(vrows, triangles, density, seed):
     xyz = rows_xyz(vrows).astype(np.float64)
-    tri = _np(triangles, np.int32).reshape(-1, 3).astype(np.int64)
+    tri = as_np(triangles, np.int32).reshape(-1, 3).astype(np.int64)
     m, nv = len(tri), len(xyz)
     ok = ((tri >= 0) & (tri < nv)).all(1)
     ti = np.where(ok[:, None], tri, 0)
@@ -232,7 +232,7 @@ def sample_mesh_host(vrows, triangles, density, seed=0, cap=None, full=False):
     density = float(density)
     if not (np.isfinite(density) and density > 0):
         raise ValueError(f"density = {density} (must be finite and positive)")
-    vr = _np(vrows, np.int32).reshape(-1, 4)
+    vr = as_np(vrows, np.int32).reshape(-1, 4)
     nt, ok, (a, e1, e2, ti), area = _triangle_counts(vr, triangles, density, seed)
     m = len(nt)
     total = int(nt.sum())
@@ -264,9 +264,8 @@ def sample_mesh_device(vrows, triangles, density, seed=0, max_samples=1 << 24, d
     """The device sampler: (rows tensor [n,4] int32 on the device, counters dict) -- one mm3dgs_mesh_sample_plan, one read-back of the
     counter block, the exact allocation, one mm3dgs_mesh_sample_emit.  Raises when the samples exceed `max_samples`."""
     from . import _lib
-    from .pointcloud import PointCloudBuilder
     from .rasterizer import _stream
-    lib, P = _lib.load(), PointCloudBuilder._ptr
+    lib, P = _lib.load(), _lib.ptr
     vr = torch.as_tensor(vrows, device=device).to(torch.int32).reshape(-1, 4).contiguous()
     tr = torch.as_tensor(triangles, device=device).to(torch.int32).reshape(-1, 3).contiguous()
     m, nv = int(tr.shape[0]), int(vr.shape[0])
@@ -296,7 +295,6 @@ class GeometryScorer:
 
     def __init__(self, reference, cell, max_dist, threshold, device="cuda:0"):
         from . import _lib
-        from .pointcloud import PointCloudBuilder
         from .rasterizer import _stream
         import ctypes as C
         if not str(device).startswith("cuda"):
@@ -325,7 +323,7 @@ class GeometryScorer:
         nbytes = int(self.lib.mm3dgs_nn_grid_work_bytes(self.n_ref, gx, gy, gz))
         if nbytes == 0:
             raise ValueError(f"reference of {self.n_ref} rows over {gx} x {gy} x {gz} cells: at most 2^30 rows and 2^26 cells")
-        P = PointCloudBuilder._ptr
+        P = _lib.ptr
         self._origin = (C.c_int64 * 3)(*[int(v) for v in self.origin_cell])
         self.cell_start = torch.empty(gx * gy * gz + 1, dtype=torch.int32, device=device)
         self.sorted = torch.empty(self.n_ref, 4, dtype=torch.int32, device=device)
@@ -338,7 +336,6 @@ class GeometryScorer:
     def query(self, rows, dist=None, row=None):
         """(dist [n_q] float32, row [8] float64) on the device for the query rows [n_q,4] int32."""
         from . import _lib
-        from .pointcloud import PointCloudBuilder
         from .rasterizer import _stream
         q = torch.as_tensor(rows, device=self.device).to(torch.int32).reshape(-1, 4).contiguous()
         nq = int(q.shape[0])
@@ -355,7 +352,7 @@ class GeometryScorer:
             has = (n > 0).double()
             row.copy_(torch.stack([n, has * md, has * md, has * md, has * float(np.float32(md) <= np.float32(self.threshold)), n, nq - n, n * 0]))
             return dist, row
-        P = PointCloudBuilder._ptr
+        P = _lib.ptr
         gx, gy, gz = self.dims
         work = torch.empty(int(self.lib.mm3dgs_nn_query_work_bytes(nq)) // 8, dtype=torch.int64, device=self.device)
         _lib.check(self.lib.mm3dgs_nn_query(nq, P(q), self.n_ref, self.cell, self._origin, gx, gy, gz, P(self.cell_start), P(self.sorted), self.max_dist,
@@ -381,7 +378,7 @@ def compare_host(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, dens
                 raise ValueError(f"{c['samples']} surface samples at density {density} per m^2: more than max_samples = {int(max_samples)}")
             counters[name + "_sampler"] = c
         else:
-            rows = _np(side, np.int32).reshape(-1, 4)
+            rows = as_np(side, np.int32).reshape(-1, 4)
         sets.append(rows)
     d_er, i_er = nn_distances_host(sets[0], sets[1], cell, max_dist)
     d_re, i_re = nn_distances_host(sets[1], sets[0], cell, max_dist)
@@ -425,13 +422,33 @@ def compare(estimate, reference, device="cpu", **kw):
     return compare_host(estimate, reference, **kw)
 
 
+def align_rows(rows, est_poses, gt_poses, method):
+    """The rows with their positions moved by the trajectory alignment estimate -> ground truth (eval_utils.align_horn / align_umeyama
+    of the camera centres of every frame that has an estimated pose; the two lists run frame by frame), applied in torch float64 and
+    rounded once to float32."""
+    from .eval_utils import align_horn, align_umeyama, camera_centers
+    pairs = [(e.detach(), g.detach()) for e, g in zip(est_poses, gt_poses) if e is not None]
+    est_c = camera_centers(torch.stack([e for e, _ in pairs]))[:, 4:].numpy()
+    gt_c = camera_centers(torch.stack([g for _, g in pairs]))[:, 4:].numpy()
+    if method == "horn":
+        R, t, _ = align_horn(est_c.T, gt_c.T)
+        s = 1.0
+    else:
+        s, R, t = align_umeyama(gt_c, est_c)
+    rows = torch.as_tensor(rows).to(torch.int32).reshape(-1, 4)
+    A = torch.tensor(s * np.asarray(R), dtype=torch.float64, device=rows.device)
+    b = torch.tensor(np.asarray(t).reshape(3), dtype=torch.float64, device=rows.device)
+    xyz = rows[:, :3].contiguous().view(torch.float32).double() @ A.T + b
+    return torch.cat([xyz.float().view(torch.int32), rows[:, 3:]], 1).contiguous()
+
+
 # ---- outputs --------------------------------------------------------------------------------------------------------------------------
 def colour_by_distance(rows, dist, threshold):
     """The rows with their colour replaced by viridis(d / (2 threshold)) (debug_frames' table and lookup, bytes rounded; a NaN is black),
     encoded on the host."""
     from .debug_frames import viridis
-    rows = _np(rows, np.int32).reshape(-1, 4).copy()
-    d = _np(dist, np.float32).reshape(-1).astype(np.float64)
+    rows = as_np(rows, np.int32).reshape(-1, 4).copy()
+    d = as_np(dist, np.float32).reshape(-1).astype(np.float64)
     lut = np.floor(viridis().numpy() * 255.0 + 0.5).astype(np.uint32)
     with np.errstate(invalid="ignore"):
         t = np.clip(d / (2.0 * float(threshold)), 0.0, 1.0)

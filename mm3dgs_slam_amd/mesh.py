@@ -21,7 +21,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .pointcloud import CLOUD_PROPERTIES, _np, _read_header, pose_rotation, quantise_colour, valid_mask
+from .pointcloud import CLOUD_PROPERTIES, as_np, device_view, pose_rotation, quantise_colour, read_header, read_ply, valid_mask
 
 INTEGRATE_COUNTERS = ("views", "dist_updates", "colour_updates")
 MESH_COUNTERS = ("vertices", "triangles", "vertices_written", "triangles_written", "vertices_dropped", "triangles_dropped")
@@ -86,6 +86,43 @@ def check_lattice(nx, ny, nz):
         raise ValueError(f"lattice {nx} x {ny} x {nz}: every size must be at least 2 and the product at most 2^30")
 
 
+def view_bounds(depth, sil, pose, cam, sil_min, depth_max):
+    """(lo [3], hi [3]) float64 on the input's device: the box of one view's lifted valid pixels -- the rules of ``pointcloud.valid_mask``,
+    ``pose_rotation`` and ``backproject_host`` with torch operators, nothing read back.  No valid pixel: (+inf, -inf)."""
+    d = depth.detach().float()
+    ok = (d > 0) & torch.isfinite(d)
+    if depth_max > 0:
+        ok &= d <= depth_max
+    if sil is not None:
+        ok &= sil.detach().float() > sil_min
+    H, W = d.shape
+    v, u = torch.meshgrid(torch.arange(H, device=d.device, dtype=torch.float64), torch.arange(W, device=d.device, dtype=torch.float64), indexing="ij")
+    z = d.double()
+    p = pose.detach().double().reshape(7)
+    q = p[:4] / p[:4].norm()
+    w, x, y, zz = q[0], q[1], q[2], q[3]
+    R = torch.stack([torch.stack([1 - 2 * (y * y + zz * zz), 2 * (x * y - w * zz), 2 * (x * zz + w * y)]),
+                     torch.stack([2 * (x * y + w * zz), 1 - 2 * (x * x + zz * zz), 2 * (y * zz - w * x)]),
+                     torch.stack([2 * (x * zz - w * y), 2 * (y * zz + w * x), 1 - 2 * (x * x + y * y)])])
+    pc = torch.stack([(u - float(cam["cx"])) / float(cam["fx"]) * z, (v - float(cam["cy"])) / float(cam["fy"]) * z, z], -1).reshape(-1, 3)
+    pw = (pc - p[4:]) @ R                      # rows: R^T (p_c - t)
+    m = ok.reshape(-1, 1)
+    inf = torch.tensor(float("inf"), device=d.device, dtype=torch.float64)
+    return torch.where(m, pw, inf).amin(0), torch.where(m, pw, -inf).amax(0)
+
+
+def lattice_for(box, voxel, max_voxels):
+    """(origin float64 [3], dims [3]) of the lattice over the box [xmin, ymin, zmin, xmax, ymax, zmax]: the origin snapped down to a
+    multiple of voxel, per axis ceil(extent / voxel) + 1 samples and at least 2; more than `max_voxels` (at most 2^30) is an error."""
+    origin = np.floor(box[:3] / voxel) * voxel
+    dims = [max(int(np.ceil((box[3 + a] - origin[a]) / voxel)) + 1, 2) for a in range(3)]
+    if dims[0] * dims[1] * dims[2] > min(int(max_voxels), MAX_SAMPLES):
+        raise ValueError(f"mesh export: the box {box[:3].tolist()} .. {box[3:].tolist()} at mesh.voxel = {voxel} m is a lattice of "
+                         f"{dims[0]} x {dims[1]} x {dims[2]} samples, more than mesh.max_voxels = {int(max_voxels)} (at most 2^30); raise "
+                         f"mesh.voxel or mesh.max_voxels, or set mesh.bounds")
+    return origin, dims
+
+
 # ---- integration ----------------------------------------------------------------------------------------------------------------
 def integrate_host(tsdf_w, rgb_w, color, depth, sil, pose, fx, fy, cx, cy, origin, voxel, trunc, sil_min=0.0, depth_max=0.0, full=False):
     """One view into the volume, in place, in float64 from the float32 inputs.  Per sample: p_c = R p_w + t, skipped if z <= 0; pixel u =
@@ -93,8 +130,8 @@ def integrate_host(tsdf_w, rgb_w, color, depth, sil, pose, fx, fy, cx, cy, origi
     point cloud's validity test; sdf = depth - z, skipped if sdf < -trunc; s = min(1, sdf / trunc); T <- (T W + s) / (W + 1), W <- W + 1,
     rounded to float32 once; the colour mean and its weight likewise, only if sdf <= trunc.  Returns (distance updates, colour updates);
     with ``full`` also dict(upd, col: the masks [nz,ny,nx]; fu, fv: the pixel coordinates before the floor; sdf; z)."""
-    col = _np(color, np.float32)
-    d = _np(depth, np.float32)
+    col = as_np(color, np.float32)
+    d = as_np(depth, np.float32)
     H, W = d.shape
     nz, ny, nx = tsdf_w.shape[:3]
     ok = valid_mask(d, sil, sil_min, depth_max)
@@ -303,17 +340,9 @@ class TsdfVolume:
 
     def add(self, color, depth, sil, pose):
         from . import _lib
-        from .pointcloud import PointCloudBuilder
         from .rasterizer import _stream
-        tensors = [color, depth, pose] + ([] if sil is None else [sil])
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
-            raise RuntimeError("TsdfVolume.add needs device tensors (the host path is HostTsdfVolume)")
-        if tuple(color.shape) != (3, self.H, self.W) or tuple(depth.shape) != (self.H, self.W) or (sil is not None and tuple(sil.shape) != (self.H, self.W)):
-            raise ValueError(f"TsdfVolume.add: color [3,{self.H},{self.W}], depth and sil [{self.H},{self.W}]; got {tuple(color.shape)}, "
-                             f"{tuple(depth.shape)}, {None if sil is None else tuple(sil.shape)}")
-        prep = lambda t: None if t is None else t.detach().float().contiguous()
-        color_c, depth_c, sil_c, pose_c = prep(color), prep(depth), prep(sil), prep(pose).reshape(7)
-        c, P = self.cam, PointCloudBuilder._ptr
+        color_c, depth_c, sil_c, pose_c = device_view("TsdfVolume", self.H, self.W, color, depth, sil, pose)
+        c, P = self.cam, _lib.ptr
         _lib.check(self.lib.mm3dgs_tsdf_integrate(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c), P(color_c),
                                                   P(depth_c), P(sil_c), self.sil_min, self.depth_max, self._origin(), self.voxel, self.trunc,
                                                   self.nx, self.ny, self.nz, P(self.tsdf_w), P(self.rgb_w), P(self.counters), _stream()))
@@ -321,9 +350,8 @@ class TsdfVolume:
     def extract(self):
         """(rows [V,4] int32, triangles [T,3] int32, counters): tensors on the device."""
         from . import _lib
-        from .pointcloud import PointCloudBuilder
         from .rasterizer import _stream
-        P = PointCloudBuilder._ptr
+        P = _lib.ptr
         nbytes = int(self.lib.mm3dgs_tsdf_mesh_work_bytes(self.nx, self.ny, self.nz))
         work = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
         mc = torch.empty(8, dtype=torch.int64, device=self.device)
@@ -352,8 +380,8 @@ def mesh_header(n_vertices, n_faces):
 def write_mesh_ply(path, rows, triangles):
     """Binary little-endian PLY: ``float x y z; uchar red green blue alpha`` per vertex (the row bytes as they are), ``list uchar int
     vertex_indices`` per face (the byte 3, then three int32)."""
-    rows = _np(rows, np.int32).reshape(-1, 4)
-    tri = _np(triangles, np.int32).reshape(-1, 3)
+    rows = as_np(rows, np.int32).reshape(-1, 4)
+    tri = as_np(triangles, np.int32).reshape(-1, 3)
     faces = np.empty(len(tri), dtype=_FACE)
     faces["n"] = 3
     faces["v"] = tri
@@ -367,7 +395,7 @@ def write_mesh_ply(path, rows, triangles):
 def read_mesh_ply(path):
     """(rows [V,4] int32, triangles [T,3] int32) of a file written by ``write_mesh_ply``."""
     with open(path, "rb") as fh:
-        elements = _read_header(fh)
+        elements = read_header(fh)
         if ([e[0] for e in elements] != ["vertex", "face"] or [p for _, p in elements[0][2]] != ["x", "y", "z", "red", "green", "blue", "alpha"]
                 or elements[1][2] != [("list", "uchar")]):
             raise ValueError(f"{path}: not a mesh of write_mesh_ply")
@@ -379,3 +407,10 @@ def read_mesh_ply(path):
     if not bool((f["n"] == 3).all()):
         raise ValueError(f"{path}: a face that is not a triangle")
     return np.frombuffer(body, dtype="<i4").reshape(nv, 4).copy(), f["v"].astype(np.int32).copy()
+
+
+def read_surface_ply(path):
+    """A surface file of either writer: ``read_mesh_ply`` (rows, triangles) when the header has a face element, else ``read_ply`` rows."""
+    with open(path, "rb") as fh:
+        has_faces = any(e[0] == "face" for e in read_header(fh))
+    return read_mesh_ply(path) if has_faces else read_ply(path)

@@ -17,7 +17,8 @@ COUNTER_NAMES = ("rows", "valid", "merged", "out_of_range", "probe_fail", "capac
 CELL_LIMIT = 1 << 20      # cells on either side of the origin per axis
 
 
-def _np(t, dtype):
+def as_np(t, dtype):
+    """A tensor (any device) or array as a contiguous numpy array of `dtype`; None stays None."""
     if t is None:
         return None
     return np.ascontiguousarray((t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dtype, copy=False))
@@ -25,7 +26,7 @@ def _np(t, dtype):
 
 def pose_rotation(pose):
     """(R, t) of the world->camera 7-vector (qw,qx,qy,qz,tx,ty,tz) in float64; the quaternion is normalised here."""
-    p = _np(pose, np.float32).astype(np.float64).reshape(7)
+    p = as_np(pose, np.float32).astype(np.float64).reshape(7)
     w, x, y, z = p[:4] / np.sqrt((p[:4] * p[:4]).sum())
     R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
                   [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
@@ -43,13 +44,13 @@ def quantise_colour(c):
 
 def valid_mask(depth, sil, sil_min, depth_max):
     """The valid pixels [H,W]: strict float32 comparisons on the inputs, a NaN fails."""
-    d = _np(depth, np.float32)
+    d = as_np(depth, np.float32)
     with np.errstate(invalid="ignore"):
         ok = (d > 0) & (d < np.float32(np.inf))
         if float(np.float32(depth_max)) > 0:
             ok &= d <= np.float32(depth_max)
         if sil is not None:
-            ok &= _np(sil, np.float32) > np.float32(sil_min)
+            ok &= as_np(sil, np.float32) > np.float32(sil_min)
     return ok
 
 
@@ -59,8 +60,8 @@ def backproject_host(color, depth, sil, pose, fx, fy, cx, cy, sil_min=0.0, depth
     p_w = R^T (p_c - t), rounded once to float32; the colour rule of ``quantise_colour``, alpha 255.  With ``full`` also the float64
     positions [n,3], scale = |R|^T (|p_c| + |t|) componentwise (what a float32 evaluation's error is measured against) and the pixel
     indices [n]."""
-    col = _np(color, np.float32)
-    d = _np(depth, np.float32)
+    col = as_np(color, np.float32)
+    d = as_np(depth, np.float32)
     H, W = d.shape
     idx = np.flatnonzero(valid_mask(d, sil, sil_min, depth_max).reshape(-1))
     z = d.reshape(-1)[idx].astype(np.float64)
@@ -153,6 +154,19 @@ class HostPointCloudBuilder:
         return np.concatenate(self.parts) if self.parts else np.empty((0, 4), dtype=np.int32)
 
 
+def device_view(who, H, W, color, depth, sil, pose):
+    """One view as the device builders (`who`: PointCloudBuilder, TsdfVolume) take it: device tensors color [3,H,W], depth and sil (or None)
+    [H,W], pose 7 values, returned as contiguous float32 (color, depth, sil, pose [7]); such a tensor is not copied."""
+    tensors = [color, depth, pose] + ([] if sil is None else [sil])
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
+        raise RuntimeError(f"{who}.add needs device tensors (the host path is Host{who})")
+    if tuple(color.shape) != (3, H, W) or tuple(depth.shape) != (H, W) or (sil is not None and tuple(sil.shape) != (H, W)):
+        raise ValueError(f"{who}.add: color [3,{H},{W}], depth and sil [{H},{W}]; got {tuple(color.shape)}, "
+                         f"{tuple(depth.shape)}, {None if sil is None else tuple(sil.shape)}")
+    prep = lambda t: None if t is None else t.detach().float().contiguous()
+    return prep(color), prep(depth), prep(sil), prep(pose).reshape(7)
+
+
 class PointCloudBuilder:
     """The device builder: owns the rows [max_points,4] int32, the voxel table (slots = the power of two >= 2 max_points, 16 bytes each;
     none with voxel == 0), the eight counters and the work buffer; ``add`` is one mm3dgs_pointcloud_add_view call on the current stream."""
@@ -182,29 +196,16 @@ class PointCloudBuilder:
         self.work = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
         self.view = 0
         self._read = None
-        _lib.check(self.lib.mm3dgs_pointcloud_reset(self._ptr(self.table), self.slots, self._ptr(self.counters), _stream()))
-
-    @staticmethod
-    def _ptr(t):
-        import ctypes as C
-        return C.c_void_p(None if t is None else t.data_ptr())
+        _lib.check(self.lib.mm3dgs_pointcloud_reset(_lib.ptr(self.table), self.slots, _lib.ptr(self.counters), _stream()))
 
     def add(self, color, depth, sil, pose):
         from . import _lib
         from .rasterizer import _stream
-        tensors = [color, depth, pose] + ([] if sil is None else [sil])
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
-            raise RuntimeError("PointCloudBuilder.add needs device tensors (the host path is HostPointCloudBuilder)")
-        if tuple(color.shape) != (3, self.H, self.W) or tuple(depth.shape) != (self.H, self.W) or (sil is not None and tuple(sil.shape) != (self.H, self.W)):
-            raise ValueError(f"PointCloudBuilder.add: color [3,{self.H},{self.W}], depth and sil [{self.H},{self.W}]; got {tuple(color.shape)}, "
-                             f"{tuple(depth.shape)}, {None if sil is None else tuple(sil.shape)}")
-        prep = lambda t: None if t is None else t.detach().float().contiguous()      # (no copy for a float32 tensor with contiguous elements)
-        color_c, depth_c, sil_c, pose_c = prep(color), prep(depth), prep(sil), prep(pose).reshape(7)
-        c = self.cam
-        _lib.check(self.lib.mm3dgs_pointcloud_add_view(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), self._ptr(pose_c),
-                                                       self._ptr(color_c), self._ptr(depth_c), self._ptr(sil_c), self.sil_min, self.depth_max,
-                                                       self.voxel, self.view, self._ptr(self.buf), self.cap, self._ptr(self.table), self.slots,
-                                                       self._ptr(self.counters), self._ptr(self.work), _stream()))
+        color_c, depth_c, sil_c, pose_c = device_view("PointCloudBuilder", self.H, self.W, color, depth, sil, pose)
+        c, P = self.cam, _lib.ptr
+        _lib.check(self.lib.mm3dgs_pointcloud_add_view(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c),
+                                                       P(color_c), P(depth_c), P(sil_c), self.sil_min, self.depth_max, self.voxel, self.view,
+                                                       P(self.buf), self.cap, P(self.table), self.slots, P(self.counters), P(self.work), _stream()))
         self.view += 1
         self._read = None
 
@@ -234,14 +235,14 @@ def cloud_header(n):
 
 def write_ply(path, rows):
     """Binary little-endian PLY, ``float x y z; uchar red green blue alpha``: the body is the row buffer's bytes as they are."""
-    rows = _np(rows, np.int32).reshape(-1, 4)
+    rows = as_np(rows, np.int32).reshape(-1, 4)
     with open(path, "wb") as fh:
         fh.write(cloud_header(len(rows)).encode("ascii"))
         fh.write(rows.astype("<i4", copy=False).tobytes())
     return path
 
 
-def _read_header(fh):
+def read_header(fh):
     """[(element name, count, [(type, property name)])] of a PLY header, the stream left at the body."""
     elements = []
     if fh.readline().strip() != b"ply":
@@ -264,7 +265,7 @@ def _read_header(fh):
 def read_ply(path):
     """The rows [n,4] int32 of a file written by ``write_ply``."""
     with open(path, "rb") as fh:
-        elements = _read_header(fh)
+        elements = read_header(fh)
         if len(elements) != 1 or [p for _, p in elements[0][2]] != ["x", "y", "z", "red", "green", "blue", "alpha"]:
             raise ValueError(f"{path}: not a point cloud of write_ply")
         n = elements[0][1]
@@ -307,7 +308,7 @@ def write_trajectory_ply(path, poses):
 def read_trajectory_ply(path):
     """(xyz float32 [n,3], rgb uint8 [n,3], edges int32 [m,2]) of a file written by ``write_trajectory_ply``."""
     with open(path, "rb") as fh:
-        elements = _read_header(fh)
+        elements = read_header(fh)
         if [e[0] for e in elements] != ["vertex", "edge"]:
             raise ValueError(f"{path}: not a trajectory of write_trajectory_ply")
         vert = np.frombuffer(fh.read(_TRAJ_VERTEX.itemsize * elements[0][1]), dtype=_TRAJ_VERTEX)

@@ -27,6 +27,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 MAX_CHANNELS = 6
 
@@ -101,10 +102,6 @@ def set_binning_policy(mode: str = "exact", headroom: float = 2.0):
 
 def get_binning_policy():
     return dict(_policy)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _f32c(t: Optional[torch.Tensor], name: str):

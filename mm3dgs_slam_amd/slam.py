@@ -11,11 +11,8 @@ configuration carries ``iteration`` (``:90-104`` map + poses, ``slam/mapper.py:6
 sources: ``SyntheticSequence`` here, recorded TUM / UT-MM directories in ``dataset.RecordedSequence``.  The Replica and other loaders, the
 monocular depth network and LPIPS (a downloaded network; its list stays empty) are out of scope.  Debug outputs
 (``debug_frames.py``): ``debug.create_video`` writes the reference's per-frame 2 x 3 mosaic (``:233-276,450-485``) as numbered PNG files under
-``outputdir/debug_video/``, ``debug.save_keyframes`` one PNG per keyframe (mapper.py), ``render()`` the image-over-depth pairs of ``:148-195``.  ``pointcloud.export`` / ``export_pointcloud()``
-(``pointcloud.py``): the reconstruction as a fused coloured point cloud and the camera path, ``outputdir/pointcloud/cloud.ply`` + ``trajectory.ply``;
-``mesh.export`` / ``export_mesh()`` (``mesh.py``): the same views fused into a truncated signed distance volume and meshed, ``outputdir/mesh/mesh.ply``; ``geometry.eval`` / ``evaluate_geometry()``
-(``geometry.py``): that mesh or cloud scored against a reference surface (accuracy, completion, completion ratio, F-score, Chamfer distance),
-``outputdir/geometry/metrics.json`` + ``accuracy.ply`` + ``completion.ply``."""
+``outputdir/debug_video/``, ``debug.save_keyframes`` one PNG per keyframe (mapper.py), ``render()`` the image-over-depth pairs of ``:148-195``.  What
+is made of the finished run -- point cloud, mesh, geometry scores -- is ``export.py``; ``run()`` ends in its ``run_post``."""
 from __future__ import annotations
 
 import math
@@ -24,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import synthetic
+from . import export, synthetic
 from .gaussian_model import GaussianModel
 from .mapper import Mapper
 from .pose_utils import get_camera_from_tensor, get_tensor_from_camera
@@ -326,249 +323,8 @@ class SLAM:
                     df.save_png(df.compose([(df.COLOR, color, None), (df.DEPTH, depth, None)], 2, 1, quant=1, bgr=False), written[-1])
         return written
 
-    def _export_views(self, every, source, block, poses=None):
-        """The views of an export (`pointcloud`, `mesh`), one (color [3,H,W], depth [H,W], silhouette [H,W] or None, pose [7]) per frame with
-        `idx % every == 0` that has an estimated pose: `source` "render": the map rendered at that pose with its rendered silhouette;
-        "sensor": the frame's own colour and sensor depth.  `poses` (one per frame, None: the estimated ones) replaces the pose of every
-        view -- the geometry evaluation's reference places the same frames at their ground-truth poses."""
-        for idx in range(len(self.seq)):
-            pose = self.estimate_pose_list[idx]
-            if pose is None or idx % every != 0:
-                continue
-            if poses is not None:
-                pose = poses[idx]
-            if source == "render":
-                result = self.renderer.render(self.gaussians, camera_pose=pose)
-                yield result["render"], result["depth"][0], result["depth"][1], pose
-            else:
-                color, depth, _ = self.seq[idx]
-                if depth is None:
-                    raise ValueError(f'{block}.source "sensor": frame {idx} has no sensor depth')
-                yield color, depth, None, pose
-
-    def _cloud_geometry(self, every, source, voxel, opt, poses=None):
-        """The views of an export lifted and thinned (what `export_pointcloud` writes and `evaluate_geometry` scores): the finished builder
-        (its `rows()`: device tensor on a GPU) and its counters.  `opt` is the merged `pointcloud` block; `poses` as in `_export_views`."""
-        from . import pointcloud as pc
-        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
-        on_device = str(self.cfg["device"]).startswith("cuda")
-        Builder = pc.PointCloudBuilder if on_device else pc.HostPointCloudBuilder
-        builder = Builder(H, W, self.cfg["cam"], voxel=voxel, max_points=int(opt["max_points"]), sil_min=float(opt["sil_min"]),
-                          depth_max=float(opt["max_depth"]), device=self.cfg["device"])
-        with torch.no_grad():
-            for view in self._export_views(every, source, "pointcloud", poses):
-                builder.add(*view)
-        return builder, builder.finish()
-
-    def export_pointcloud(self, path=None, every=None, voxel=None, source=None):
-        """The reconstruction as a fused coloured point cloud (pointcloud.py; the core of the reference's scripts/visualizer.py): for every
-        frame with `idx % every == 0` that has an estimated pose one view at that pose -- `source` "render": the map rendered there, with
-        the rendered silhouette as the surface test (> `pointcloud.sil_min`, the reference's 0.99); "sensor": the frame's own colour and
-        sensor depth -- is lifted to world points, and the first point of every `voxel`-sized cell is kept.  Writes `path/cloud.ply` and
-        `path/trajectory.ply` (default `outputdir/pointcloud`); arguments left None come from the `pointcloud` config block.  One
-        mm3dgs_pointcloud_add_view call per view on a GPU, the host statement on `device: cpu`.  Returns the two paths and the counters;
-        raises RuntimeError when points were dropped for lack of room (`pointcloud.max_points`)."""
-        from . import pointcloud as pc
-        from .config import _TUM
-        opt = dict(_TUM["pointcloud"], **(self.cfg.get("pointcloud") or {}))
-        every = int(every if every is not None else (opt["every"] or self.cfg["mapping"]["kf_every"]))
-        voxel = float(opt["voxel"] if voxel is None else voxel)
-        source = str(opt["source"] if source is None else source)
-        if source not in ("render", "sensor"):
-            raise ValueError(f"pointcloud.source = {source!r} (render / sensor)")
-        if every < 1:
-            raise ValueError(f"pointcloud.every = {every} (must be positive)")
-        path = os.path.join(self.cfg["outputdir"], "pointcloud") if path is None else path
-        builder, counters = self._cloud_geometry(every, source, voxel, opt)
-        poses = [pose.detach() for pose in self.estimate_pose_list[:len(self.seq)] if pose is not None]
-        os.makedirs(path, exist_ok=True)
-        out = {"cloud": pc.write_ply(os.path.join(path, "cloud.ply"), builder.rows()),
-               "trajectory": pc.write_trajectory_ply(os.path.join(path, "trajectory.ply"), torch.stack(poses) if poses else np.zeros((0, 7))),
-               "counters": counters}
-        self.pointcloud_export = out      # what the last export wrote (run() calls this without a caller to hand it to)
-        print(f"Point cloud: {counters['rows']} points from {counters['views']} views ({counters['valid']} valid pixels, voxel {voxel} m) in {out['cloud']}")
-        return out
-
-    def _mesh_bounds(self, every, source, sil_min, depth_max, poses=None):
-        """The box [xmin, ymin, zmin, xmax, ymax, zmax] of the lifted valid points of an export's views (the point cloud's validity test and
-        back-projection, here with torch operators in float64); its six numbers are read back once, after the last view."""
-        cam = self.cfg["cam"]
-        lo = hi = None
-        for color, depth, sil, pose in self._export_views(every, source, "mesh", poses):
-            d = depth.detach().float()
-            ok = (d > 0) & torch.isfinite(d)
-            if depth_max > 0:
-                ok &= d <= depth_max
-            if sil is not None:
-                ok &= sil.detach().float() > sil_min
-            H, W = d.shape
-            v, u = torch.meshgrid(torch.arange(H, device=d.device, dtype=torch.float64), torch.arange(W, device=d.device, dtype=torch.float64), indexing="ij")
-            z = d.double()
-            p = pose.detach().double().reshape(7)
-            q = p[:4] / p[:4].norm()
-            w, x, y, zz = q[0], q[1], q[2], q[3]
-            R = torch.stack([torch.stack([1 - 2 * (y * y + zz * zz), 2 * (x * y - w * zz), 2 * (x * zz + w * y)]),
-                             torch.stack([2 * (x * y + w * zz), 1 - 2 * (x * x + zz * zz), 2 * (y * zz - w * x)]),
-                             torch.stack([2 * (x * zz - w * y), 2 * (y * zz + w * x), 1 - 2 * (x * x + y * y)])])
-            pc_ = torch.stack([(u - float(cam["cx"])) / float(cam["fx"]) * z, (v - float(cam["cy"])) / float(cam["fy"]) * z, z], -1).reshape(-1, 3)
-            pw = (pc_ - p[4:]) @ R                      # rows: R^T (p_c - t)
-            m = ok.reshape(-1, 1)
-            inf = torch.tensor(float("inf"), device=d.device, dtype=torch.float64)
-            a, b = torch.where(m, pw, inf).amin(0), torch.where(m, pw, -inf).amax(0)
-            lo, hi = (a, b) if lo is None else (torch.minimum(lo, a), torch.maximum(hi, b))
-        if lo is None:
-            raise ValueError("mesh export: no frame has an estimated pose")
-        box = torch.cat([lo, hi]).cpu().numpy()          # the one read-back
-        if not np.isfinite(box).all():
-            raise ValueError("mesh export: no view has a valid pixel (mesh.sil_min, mesh.max_depth)")
-        return box
-
-    def _mesh_geometry(self, every, source, voxel, trunc, opt, poses=None):
-        """The views of an export fused and meshed (what `export_mesh` writes and `evaluate_geometry` scores): (rows, triangles, counters,
-        lattice sizes, origin); device tensors on a GPU.  `opt` is the merged `mesh` block; `poses` as in `_export_views`."""
-        from . import mesh as ms
-        H, W = int(self.cfg["desired_height"]), int(self.cfg["desired_width"])
-        sil_min, depth_max = float(opt["sil_min"]), float(opt["max_depth"])
-        with torch.no_grad():
-            if opt["bounds"] is None:
-                box = self._mesh_bounds(every, source, sil_min, depth_max, poses)
-                box[:3] -= trunc + voxel
-                box[3:] += trunc + voxel
-            else:
-                box = np.asarray(opt["bounds"], dtype=np.float64).reshape(6)
-            origin = np.floor(box[:3] / voxel) * voxel
-            dims = [max(int(np.ceil((box[3 + a] - origin[a]) / voxel)) + 1, 2) for a in range(3)]
-            if dims[0] * dims[1] * dims[2] > min(int(opt["max_voxels"]), ms.MAX_SAMPLES):
-                raise ValueError(f"mesh export: the box {box[:3].tolist()} .. {box[3:].tolist()} at mesh.voxel = {voxel} m is a lattice of "
-                                 f"{dims[0]} x {dims[1]} x {dims[2]} samples, more than mesh.max_voxels = {int(opt['max_voxels'])} (at most 2^30); raise "
-                                 f"mesh.voxel or mesh.max_voxels, or set mesh.bounds")
-            on_device = str(self.cfg["device"]).startswith("cuda")
-            Volume = ms.TsdfVolume if on_device else ms.HostTsdfVolume
-            volume = Volume(dims, origin, voxel, trunc, H, W, self.cfg["cam"], sil_min=sil_min, depth_max=depth_max, min_weight=float(opt["min_weight"]),
-                            device=self.cfg["device"])
-            for view in self._export_views(every, source, "mesh", poses):
-                volume.add(*view)
-            rows, triangles, counters = volume.extract()
-        return rows, triangles, counters, dims, origin
-
-    def export_mesh(self, path=None, every=None, voxel=None, source=None):
-        """The reconstruction as a coloured triangle mesh (mesh.py): the views of `export_pointcloud` (`every`, `source`) fused into a dense
-        truncated signed distance volume of `mesh.voxel`-sized cells (`mesh.trunc`, 0: 4 voxel) over `mesh.bounds` -- None: a first pass
-        over the same views takes the box of their lifted valid points, which is grown by trunc + voxel, the origin snapped down to a
-        multiple of voxel --, then marching tetrahedra over the samples seen at least `mesh.min_weight` times.  Writes `path/mesh.ply`
-        (default `outputdir/mesh`): binary PLY, `float x y z; uchar red green blue alpha` per vertex, `list uchar int vertex_indices` per
-        face.  One mm3dgs_tsdf_integrate call per view and one mm3dgs_tsdf_mesh_plan / _emit pair on a GPU, the host statement on `device:
-        cpu`.  Returns the path, the counters and the lattice; raises ValueError when the lattice exceeds `mesh.max_voxels`."""
-        from . import mesh as ms
-        from .config import _TUM
-        opt = dict(_TUM["mesh"], **(self.cfg.get("mesh") or {}))
-        every = int(every if every is not None else (opt["every"] or self.cfg["mapping"]["kf_every"]))
-        voxel = float(opt["voxel"] if voxel is None else voxel)
-        source = str(opt["source"] if source is None else source)
-        trunc = float(opt["trunc"]) if float(opt["trunc"] or 0) > 0 else 4.0 * voxel
-        if source not in ("render", "sensor"):
-            raise ValueError(f"mesh.source = {source!r} (render / sensor)")
-        if every < 1:
-            raise ValueError(f"mesh.every = {every} (must be positive)")
-        if not (np.isfinite(voxel) and voxel > 0):
-            raise ValueError(f"mesh.voxel = {voxel} (must be positive)")
-        path = os.path.join(self.cfg["outputdir"], "mesh") if path is None else path
-        rows, triangles, counters, dims, origin = self._mesh_geometry(every, source, voxel, trunc, opt)
-        os.makedirs(path, exist_ok=True)
-        out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles), "counters": counters, "lattice": tuple(dims),
-               "origin": origin.tolist(), "voxel": voxel, "trunc": trunc}
-        self.mesh_export = out      # what the last export wrote (run() calls this without a caller to hand it to)
-        print(f"Mesh: {counters['vertices']} vertices, {counters['triangles']} triangles from {counters['views']} views "
-              f"(lattice {dims[0]} x {dims[1]} x {dims[2]}, voxel {voxel} m) in {out['mesh']}")
-        return out
-
-    def _gt_poses(self):
-        """One ground-truth pose per frame for the geometry evaluation's reference: `gt_pose_list` as the run filled it, else (a resumed
-        checkpoint, which ran no frame) `pose_gt` of `outputdir/results.npz`."""
-        poses = list(self.gt_pose_list)
-        if any(p is None for p, e in zip(poses, self.estimate_pose_list) if e is not None) and "outputdir" in self.cfg:
-            stored = os.path.join(self.cfg["outputdir"], "results.npz")
-            if os.path.exists(stored):
-                for i, p in enumerate(np.load(stored, allow_pickle=True)["pose_gt"][:len(poses)]):
-                    if poses[i] is None:
-                        poses[i] = torch.tensor(p, device=self.cfg["device"])
-        missing = [i for i, (p, e) in enumerate(zip(poses, self.estimate_pose_list)) if e is not None and p is None]
-        if missing:
-            raise ValueError(f'geometry.reference "sensor": no ground-truth pose for frame(s) {missing[:8]} (neither from the run nor in results.npz)')
-        return poses
-
-    def _align_rows(self, rows, method):
-        """The rows with their positions moved by the trajectory alignment estimate -> ground truth (eval_utils.align_horn / align_umeyama
-        of the camera centres), applied in torch float64 and rounded once to float32."""
-        from .eval_utils import align_horn, align_umeyama, camera_centers
-        idx = [i for i, p in enumerate(self.estimate_pose_list[:len(self.seq)]) if p is not None]
-        gt = self._gt_poses()
-        est_c = camera_centers(torch.stack([self.estimate_pose_list[i].detach() for i in idx]))[:, 4:].numpy()
-        gt_c = camera_centers(torch.stack([gt[i].detach() for i in idx]))[:, 4:].numpy()
-        if method == "horn":
-            R, t, _ = align_horn(est_c.T, gt_c.T)
-            s = 1.0
-        else:
-            s, R, t = align_umeyama(gt_c, est_c)
-        rows = torch.as_tensor(rows).to(torch.int32).reshape(-1, 4)
-        A = torch.tensor(s * np.asarray(R), dtype=torch.float64, device=rows.device)
-        b = torch.tensor(np.asarray(t).reshape(3), dtype=torch.float64, device=rows.device)
-        xyz = rows[:, :3].contiguous().view(torch.float32).double() @ A.T + b
-        return torch.cat([xyz.float().view(torch.int32), rows[:, 3:]], 1).contiguous()
-
-    def evaluate_geometry(self, path=None, estimate=None, reference=None):
-        """The exported geometry scored against a reference surface (geometry.py): accuracy, completion, completion ratio, precision, recall,
-        F-score and Chamfer distance from exact truncated nearest-neighbour distances in both directions.  `estimate` "mesh" / "pointcloud":
-        what `export_mesh` / `export_pointcloud` produce (their blocks' `every`, `source` and sizes), from their rows in memory.
-        `reference` "sensor": the same frames' own colour and sensor depth fused by the same builder at the GROUND-TRUTH poses -- what a
-        perfect tracker and map would have exported (ValueError without sensor depth) --, or the path of a PLY file: a point cloud
-        (`pointcloud.read_ply`) or, with a face element, a mesh (`mesh.read_mesh_ply`).  Meshes on either side are sampled at
-        `geometry.density` samples per m^2; `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first.
-        Writes `path/metrics.json`, `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); arguments left None come from the
-        `geometry` config block.  HIP kernels and one read-back of the [2,8] table on a GPU, the host statement on `device: cpu`.  Touches
-        no pose and no other output.  Returns the comparison with the paths."""
-        from . import geometry as geo, mesh as ms, pointcloud as pc
-        from .config import _TUM
-        opt = dict(_TUM["geometry"], **(self.cfg.get("geometry") or {}))
-        estimate = str(opt["estimate"] if estimate is None else estimate)
-        reference = str(opt["reference"] if reference is None else reference)
-        align = str(opt["align"] or "none").lower()
-        if estimate not in ("mesh", "pointcloud"):
-            raise ValueError(f"geometry.estimate = {estimate!r} (mesh / pointcloud)")
-        if align not in ("none", "horn", "umeyama"):
-            raise ValueError(f"geometry.align = {align!r} (none / horn / umeyama)")
-        block = dict(_TUM[estimate], **(self.cfg.get(estimate) or {}))
-        every = int(block["every"] or self.cfg["mapping"]["kf_every"])
-        voxel = float(block["voxel"])
-        trunc = float(block["trunc"]) if estimate == "mesh" and float(block["trunc"] or 0) > 0 else 4.0 * voxel
-
-        def build(source, poses):
-            if estimate == "mesh":
-                rows, triangles = self._mesh_geometry(every, source, voxel, trunc, block, poses)[:2]
-                return rows, triangles
-            return self._cloud_geometry(every, source, voxel, block, poses)[0].rows()
-
-        est = build(str(block["source"]), None)
-        if align != "none":
-            est = (self._align_rows(est[0], align), est[1]) if estimate == "mesh" else self._align_rows(est, align)
-        if reference == "sensor":
-            ref = build("sensor", self._gt_poses())
-        else:
-            with open(reference, "rb") as fh:
-                has_faces = any(e[0] == "face" for e in pc._read_header(fh))
-            ref = ms.read_mesh_ply(reference) if has_faces else pc.read_ply(reference)
-        result = geo.compare(est, ref, device=self.cfg["device"], threshold=float(opt["threshold"]), max_dist=float(opt["max_dist"]),
-                             cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]))
-        path = os.path.join(self.cfg["outputdir"], "geometry") if path is None else path
-        result["files"] = geo.write_outputs(path, result, {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]),
-                                                           "seed": int(opt["seed"])})
-        self.geometry_eval = result      # what the last evaluation found (run() calls this without a caller to hand it to)
-        t = result["table"]
-        print(f"Geometry ({estimate} against {reference}): accuracy {result['accuracy'] * 100:.3f} cm, completion {result['completion'] * 100:.3f} cm, "
-              f"completion ratio {result['completion_ratio'] * 100:.2f} % at {float(opt['threshold']) * 100:g} cm, F-score {result['fscore']:.4f}, Chamfer "
-              f"{result['chamfer'] * 100:.3f} cm ({result['n_estimate']} / {result['n_reference']} points, clamped {int(t[0, 5])} / {int(t[1, 5])}) in "
-              f"{result['files']['metrics']}")
-        return result
+    # the post-run stage (export.py): export_pointcloud(path, every, voxel, source), export_mesh(likewise), evaluate_geometry(path, estimate, reference)
+    export_pointcloud, export_mesh, evaluate_geometry = export.export_pointcloud, export.export_mesh, export.evaluate_geometry
 
     def run(self, progress=None, reraise=True):
         """slam/SLAM.py:375-503: every frame; `save_iterations` checkpoints on the way; with an `outputdir` the final map (as
@@ -607,21 +363,7 @@ class SLAM:
                     if self.failure is None:
                         raise
                     print(f"(while saving after the failure above: {e2!r})")
-                if (self.cfg.get("pointcloud") or {}).get("export", False):      # after results.npz, which it does not touch; reported, never raised
-                    try:
-                        self.export_pointcloud()
-                    except Exception as e4:      # noqa: BLE001
-                        print(f"(point cloud export: {e4!r})")
-                if (self.cfg.get("mesh") or {}).get("export", False):            # likewise
-                    try:
-                        self.export_mesh()
-                    except Exception as e5:      # noqa: BLE001
-                        print(f"(mesh export: {e5!r})")
-                if (self.cfg.get("geometry") or {}).get("eval", False):          # likewise; after the mesh export
-                    try:
-                        self.evaluate_geometry()
-                    except Exception as e6:      # noqa: BLE001
-                        print(f"(geometry evaluation: {e6!r})")
+                export.run_post(self)      # the exports and the geometry evaluation that are switched on; reported, never raised
         if self.failure is not None and reraise:
             raise self.failure
 
@@ -647,12 +389,9 @@ class SLAM:
             return self._evaluate_images_device(last_idx)
         from .eval_utils import psnr
         from .loss_utils import ssim
-        every = int(self.cfg.get("eval_every", 1))
         psnr_list, ssim_list = [], []
         with torch.no_grad():
-            for idx in range(last_idx):
-                if idx != 0 and (idx + 1) % every != 0:
-                    continue
+            for idx in self._eval_frames(last_idx):
                 color = self.seq[idx][0]
                 image = self.renderer.render(self.gaussians, camera_pose=self.estimate_pose_list[idx])["render"]
                 psnr_list.append(psnr(image, color).mean().detach().cpu().numpy())

@@ -144,12 +144,11 @@ class Tracker:
     @staticmethod
     def _predict_const_vel_device(pm1, pm2):
         """mm3dgs_propagate_const_vel: utils/pose_utils.py:203-216 on the device (same algebra as propagate_const_vel_np, float64)."""
-        import ctypes as C
         from . import _lib
         from .rasterizer import _stream
         a, b = pm1.detach().float().contiguous(), pm2.detach().float().contiguous()
         out = torch.empty(7, dtype=torch.float32, device=a.device)
-        _lib.check(_lib.load().mm3dgs_propagate_const_vel(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr()), _stream()))
+        _lib.check(_lib.load().mm3dgs_propagate_const_vel(_lib.ptr(a), _lib.ptr(b), _lib.ptr(out), _stream()))
         return out
 
     def _predict_imu_device(self, pm1, pm2, imu_meas, dt_cam, dt_imu):
@@ -182,7 +181,6 @@ def propagate_imu_device(pm1, pm2, imu6, c2i, dt_cam, dt_imu, gravity=GRAVITY):
     """mm3dgs_propagate_imu: utils/pose_utils.py:148-200 on the device (same algebra as pose_utils.propagate_imu_np, float64).  All four
     tensors on the device: two 7-vectors, the [n,6] float32 sample block (angular velocity, linear acceleration; read only) and the 4x4
     camera->IMU extrinsic.  One launch on the current stream, no synchronisation; returns the device 7-vector."""
-    import ctypes as C
     from . import _lib
     from .rasterizer import _stream
     a, b = pm1.detach().float().contiguous(), pm2.detach().float().contiguous()
@@ -194,6 +192,6 @@ def propagate_imu_device(pm1, pm2, imu6, c2i, dt_cam, dt_imu, gravity=GRAVITY):
         raise RuntimeError("propagate_imu_device needs device tensors (the host path is pose_utils.propagate_imu)")
     out = torch.empty(7, dtype=torch.float32, device=a.device)
     gx, gy, gz = (float(v) for v in gravity)
-    _lib.check(_lib.load().mm3dgs_propagate_imu(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(imu6.data_ptr() if n > 0 else None), n,
-                                                C.c_void_p(c2i.data_ptr()), float(dt_cam), float(dt_imu), gx, gy, gz, C.c_void_p(out.data_ptr()), _stream()))
+    P = _lib.ptr
+    _lib.check(_lib.load().mm3dgs_propagate_imu(P(a), P(b), P(imu6 if n > 0 else None), n, P(c2i), float(dt_cam), float(dt_imu), gx, gy, gz, P(out), _stream()))
     return out

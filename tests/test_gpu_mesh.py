@@ -402,3 +402,25 @@ def test_native_run_exports_its_mesh_and_the_checkpoint_reproduces_it(tmp_path):
     cfg_on["mesh"]["max_voxels"] = 1000
     with pytest.raises(ValueError, match=r"mesh\.max_voxels = 1000"):
         on.export_mesh()
+
+
+def test_both_device_builders_reject_a_wrong_shaped_view_before_any_launch():
+    """`pointcloud.device_view`, the view contract of PointCloudBuilder.add and TsdfVolume.add: a colour or silhouette tensor of the wrong
+    shape is a ValueError that names the caller's class, raised before a launch -- both builders' counters read the same afterwards."""
+    H, W = 2, 3
+    cam = {"fx": 4.0, "fy": 4.0, "cx": 1.0, "cy": 0.5}
+    color, depth, sil = torch.rand(3, H, W, device=DEV), torch.full((H, W), 1.5, device=DEV), torch.ones(H, W, device=DEV)
+    pose = torch.tensor([1.0, 0, 0, 0, 0, 0, 0], device=DEV)
+    cloud = pc.PointCloudBuilder(H, W, cam, voxel=0.01, max_points=64, device=DEV)
+    volume = ms.TsdfVolume((4, 4, 4), [-1.0, -1.0, 0.5], 0.5, 2.0, H, W, cam, device=DEV)
+    for builder, name in ((cloud, "PointCloudBuilder"), (volume, "TsdfVolume")):
+        builder.add(color, depth, sil, pose)      # a good view first: the counters are not all zero
+        before = builder.counters.cpu().clone()
+        assert int(before[6 if builder is cloud else 0]) == 1, before
+        for bad in ((torch.rand(3, W, H, device=DEV), depth, sil, pose), (color, depth, torch.ones(H, W + 1, device=DEV), pose),
+                    (torch.rand(4, H, W, device=DEV), depth, None, pose)):
+            with pytest.raises(ValueError, match=name + r"\.add: color \[3,2,3\]"):
+                builder.add(*bad)
+        torch.cuda.synchronize()
+        assert torch.equal(builder.counters.cpu(), before), (name, before, builder.counters.cpu())
+    assert cloud.view == 1

@@ -82,9 +82,8 @@ class Direction:
 
     def build(self):
         from mm3dgs_slam_amd import _lib
-        from mm3dgs_slam_amd.pointcloud import PointCloudBuilder
         from mm3dgs_slam_amd.rasterizer import _stream
-        s, P = self.scorer, PointCloudBuilder._ptr
+        s, P = self.scorer, _lib.ptr
         _lib.check(s.lib.mm3dgs_nn_grid_build(s.n_ref, P(s.rows), s.cell, s._origin, *s.dims, P(s.cell_start), P(s.sorted), P(s.counters), P(self.gwork), _stream()))
 
     def query(self, rows=None):
@@ -159,9 +158,8 @@ def torch_sampler(v, tris, n):
 
 def sampler_line(emit, args):
     from mm3dgs_slam_amd import _lib, geometry as geo
-    from mm3dgs_slam_amd.pointcloud import PointCloudBuilder
     from mm3dgs_slam_amd.rasterizer import _stream
-    lib, P = _lib.load(), PointCloudBuilder._ptr
+    lib, P = _lib.load(), _lib.ptr
     v, tris = room_mesh()
     density = 1e6 / 108.0
     rows, c = geo.sample_mesh_device(v, tris, density, seed=0, device=DEV)
@@ -181,8 +179,8 @@ def sampler_line(emit, args):
 
 def export_sets(args, H, W, outdir):
     """The two sets of a 30-view export: the rendered map's mesh and the sensor mesh at the ground-truth poses, sampled."""
-    from mm3dgs_slam_amd import geometry as geo
-    from mm3dgs_slam_amd.config import _TUM, default_config
+    from mm3dgs_slam_amd import export, geometry as geo
+    from mm3dgs_slam_amd.config import default_config
     from mm3dgs_slam_amd.slam import SLAM, SyntheticSequence
     torch.manual_seed(0); random.seed(0); np.random.seed(0)
     frac = min(1.0, args.gaussians / (0.95 * H * W))
@@ -194,18 +192,18 @@ def export_sets(args, H, W, outdir):
         slam.estimate_pose_list[i] = seq[i][2].clone()
         slam.gt_pose_list[i] = seq[i][2].clone()
     with torch.no_grad():
-        box = slam._mesh_bounds(1, "sensor", 0.99, 0.0)
+        box = export.mesh_bounds(slam, export.options(slam.cfg, "mesh", every=1, source="sensor"))
     voxel = float((box[3:] - box[:3]).max()) / 246.0
-    opt = dict(_TUM["mesh"], voxel=voxel)
+    opt = export.options(slam.cfg, "mesh", every=1, source="sensor", voxel=voxel)
     # the estimate: the sensor frames fused at poses 1 cm off the true ones (a map after one mapped frame renders too few surface pixels
     # to be a set worth timing: 2 484 samples at 640x480, none at 1200x680); the reference: the same frames at the true poses
-    gt = slam._gt_poses()
+    gt = export.gt_poses(slam)
     off = [p.clone() for p in gt]
     for p in off:
         p[4:] += 0.01
     sets = []
     for poses in (off, gt):
-        rows, tris = slam._mesh_geometry(1, "sensor", voxel, 4.0 * voxel, opt, poses)[:2]
+        rows, tris = export.mesh_geometry(slam, opt, poses)[:2]
         sets.append(geo.sample_mesh_device(rows, tris, args.density, seed=0, max_samples=1 << 26, device=DEV)[0])
     del slam, seq
     torch.cuda.empty_cache()

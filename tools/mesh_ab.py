@@ -101,8 +101,9 @@ class TorchVolume:
 
 def lattice(slam, every, source):
     """The export's box at SIDE samples along its longest side: (origin, voxel, trunc, bounds)."""
+    from mm3dgs_slam_amd import export
     with torch.no_grad():
-        box = slam._mesh_bounds(every, source, 0.99, 0.0)
+        box = export.mesh_bounds(slam, export.options(slam.cfg, "mesh", every=every, source=source, sil_min=0.99, max_depth=0.0))
     voxel = float((box[3:] - box[:3]).max()) / (SIDE - 10)      # room for trunc + voxel on both sides
     trunc = 4.0 * voxel
     origin = np.floor((box[:3] - trunc - voxel) / voxel) * voxel
@@ -111,11 +112,11 @@ def lattice(slam, every, source):
 
 def integrate_times(slam, args, emit, H, W, source, origin, voxel, trunc):
     """(a): us per integrated view"""
-    from mm3dgs_slam_amd import mesh as ms
+    from mm3dgs_slam_amd import export, mesh as ms
     cam, sil_min = slam.cfg["cam"], 0.99
     i = min(5, args.frames - 1)
     with torch.no_grad():
-        view = [v for k, v in enumerate(slam._export_views(1, source, "mesh")) if k == i][0]
+        view = [v for k, v in enumerate(export.views(slam, 1, source, "mesh")) if k == i][0]
     view = tuple(None if t is None else t.detach().float().contiguous() for t in view)
     dims = (SIDE, SIDE, SIDE)
     dev = ms.TsdfVolume(dims, origin, voxel, trunc, H, W, cam, sil_min=sil_min, device=DEV)
@@ -146,13 +147,12 @@ def integrate_times(slam, args, emit, H, W, source, origin, voxel, trunc):
 
 def mesh_times(slam, args, emit, H, W, source, origin, voxel, trunc):
     """(b): us per plan + emit on the volume of all views"""
-    from mm3dgs_slam_amd import _lib, mesh as ms
-    from mm3dgs_slam_amd.pointcloud import PointCloudBuilder
+    from mm3dgs_slam_amd import _lib, export, mesh as ms
     from mm3dgs_slam_amd.rasterizer import _stream
-    P = PointCloudBuilder._ptr
+    P = _lib.ptr
     vol = ms.TsdfVolume((SIDE, SIDE, SIDE), origin, voxel, trunc, H, W, slam.cfg["cam"], sil_min=0.99, device=DEV)
     with torch.no_grad():
-        for view in slam._export_views(1, source, "mesh"):
+        for view in export.views(slam, 1, source, "mesh"):
             vol.add(*view)
     rows, tris, c = vol.extract()
     V, T = c["vertices"], c["triangles"]

@@ -96,7 +96,7 @@ def call_times(slam, args, emit, H, W, voxel):
     def prepare():      # untimed: a cloud that holds the first view
         from mm3dgs_slam_amd import _lib
         from mm3dgs_slam_amd.rasterizer import _stream
-        _lib.check(builder.lib.mm3dgs_pointcloud_reset(builder._ptr(builder.table), builder.slots, builder._ptr(builder.counters), _stream()))
+        _lib.check(builder.lib.mm3dgs_pointcloud_reset(_lib.ptr(builder.table), builder.slots, _lib.ptr(builder.counters), _stream()))
         builder.view, builder._read = 0, None
         if voxel > 0:
             builder.add(*va)
