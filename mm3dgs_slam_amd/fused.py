@@ -744,6 +744,26 @@ def _adam_state(opt, name):
     return group, p, st
 
 
+def shard_table(ranges, lo, hi, grad_ptr):
+    """The mm3dgs_adam group table of one rank's slice [lo, hi) of a flat array whose groups lie at `ranges` = [(a, b, param, exp_avg,
+    exp_avg_sq, lr)]: [a, b) the group's elements in the flat layout, the three device addresses of ITS first element, its learning rate.
+    One entry per group the slice touches, over the elements [max(lo, a), min(hi, b)) of that group's three arrays; the gradient of flat
+    element i is the float at grad_ptr + 4 (i - lo) (a reduce-scatter's output).  Returns (table, entries used); nothing here touches the
+    device.  A group's slice starts at element max(lo, a) - a of arrays that begin at a multiple of P: it is 16-byte aligned only by chance,
+    and an entry that is not takes mm3dgs_adam's scalar body (tests/test_gpu_adam.py runs every rank's table on one device)."""
+    table, k = (_lib.Mm3dgsAdamGroup * 8)(), 0
+    for a, b, param, exp_avg, exp_avg_sq, lr in ranges:
+        i0, i1 = max(lo, a), min(hi, b)
+        if i0 >= i1:
+            continue
+        e = table[k]; k += 1
+        e.param = param + 4 * (i0 - a)
+        e.grad = grad_ptr + 4 * (i0 - lo)
+        e.exp_avg, e.exp_avg_sq = exp_avg + 4 * (i0 - a), exp_avg_sq + 4 * (i0 - a)
+        e.n, e.lr = i1 - i0, float(lr)
+    return table, k
+
+
 class _PoseState:
     """Bundle-adjustment state of one window pose: the buffer its views render from and Adam steps, the two moments, the step counter,
     the pose it was copied from (written back after the loop) and either
@@ -1083,22 +1103,17 @@ class _MapLoop:
         this rank's S = ceil(W P / world) summed elements in shard_g; mm3dgs_adam on exactly those elements of the parameters and of both
         moments (the slice cuts through the groups: one table entry per group it touches); all-gather of the stepped PARAMETERS.  The
         moments of elements another rank owns go stale here and are gathered when somebody needs them (sync_moments: before map surgery
-        and at the end of the loop).  Same arithmetic per element as the all-reduce path's mm3dgs_adam: bit-identical parameters (tested
-        over gloo)."""
+        and at the end of the loop).  Same arithmetic per element as the all-reduce path's mm3dgs_adam: bit-identical parameters and
+        moments.  The plumbing around the step is tested over gloo with the CPU stand-in; the kernel itself in
+        tests/test_gpu_adam.py::test_sharded_step_of_every_rank_equals_the_whole_group_step, which makes every rank's call -- shard_table
+        from that rank's shard_bounds -- on one device and compares with one whole-group call bit for bit."""
         opt = self.g.optimizer
         lo, hi = self.window.shard_bounds(self.width() * P)[1:]
         groups = self._flat_groups(P)
-        table, k = (_lib.Mm3dgsAdamGroup * 8)(), 0
         for group, p, st, a, b in groups:
             st["step"] += 1                                     # (every replica counts every step of every group, as the replicated path does)
-            i0, i1 = max(lo, a), min(hi, b)
-            if i0 >= i1:
-                continue
-            e = table[k]; k += 1
-            e.param = p.data_ptr() + 4 * (i0 - a)
-            e.grad = self.shard_g.data_ptr() + 4 * (i0 - lo)
-            e.exp_avg, e.exp_avg_sq = st["exp_avg"].data_ptr() + 4 * (i0 - a), st["exp_avg_sq"].data_ptr() + 4 * (i0 - a)
-            e.n, e.lr = i1 - i0, float(group["lr"])
+        table, k = shard_table([(a, b, p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), group["lr"])
+                                for group, p, st, a, b in groups], lo, hi, self.shard_g.data_ptr())
         b1, b2 = opt.param_groups[0]["betas"]
         if k:
             _lib.check(self.eng.lib.mm3dgs_adam(table, k, int(groups[0][2]["step"].item()), float(b1), float(b2),
