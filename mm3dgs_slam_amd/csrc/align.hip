@@ -25,6 +25,7 @@
 #include <math.h>
 #include "mm3dgs_common.h"
 #include "fused_api.h"
+#include "block_ops.h"
 
 // The solve restates the host path literally (det = a00 n - a01^2 from two rounded products) and the apply is float32 with an unfused
 // multiply and add.  hipcc contracts a * b + c to an FMA by default, and the header's __fmul_rn / __fadd_rn do not stop it: they are the
@@ -41,19 +42,6 @@ static int align_rows(size_t HW) {
   return (int)(r < ALIGN_MAX_ROWS ? r : ALIGN_MAX_ROWS);
 }
 size_t align_depth_work_bytes(int H, int W) { return align_up((size_t)align_rows((size_t)H * (size_t)W) * ALIGN_ROW * sizeof(double), 256); }
-
-// sum of five per-lane doubles over the 256-lane workgroup, in a fixed order; the totals are returned to EVERY lane
-__device__ __forceinline__ void align_block_sums(double (&v)[5], double (*sh)[5]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 5; k++) {
-    const double t = wave_sum_to_lane63_f64(v[k]);
-    if (lane == 63) sh[wv][k] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 5; k++) v[k] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
-}
 
 __global__ void __launch_bounds__(ALIGN_WG)
 align_sums_kernel(size_t HW, const float* __restrict__ est, const float* __restrict__ depth, const float* __restrict__ sil, float sil_min,
@@ -73,7 +61,7 @@ align_sums_kernel(size_t HW, const float* __restrict__ est, const float* __restr
     acc[3] += valid ? h * z : 0.0;
     acc[4] += valid ? z : 0.0;
   }
-  align_block_sums(acc, sh);
+  block_sums_f64<5, true>(acc, sh);      // fixed order; the totals in every lane
   if (threadIdx.x < ALIGN_ROW) {
     double r = 0.0;
 #pragma unroll
@@ -90,7 +78,7 @@ align_finish_apply_kernel(size_t HW, const float* __restrict__ est, const double
   const bool has = (int)threadIdx.x < nrows;
 #pragma unroll
   for (int k = 0; k < 5; k++) tot[k] = has ? rows[(size_t)threadIdx.x * ALIGN_ROW + k] : 0.0;
-  align_block_sums(tot, sh);
+  block_sums_f64<5, true>(tot, sh);
   // get_scale_shift_LS, literally: a singular system (fewer than two valid pixels, or an estimate that is constant over them to its own
   // float32 rounding) has no fit and returns the identity
   const double a00 = tot[0], a01 = tot[1], n = tot[2], b0 = tot[3], b1 = tot[4];

@@ -57,6 +57,10 @@ struct ProfScope {
 
 __global__ void profile_null_kernel() {}
 
+// compact.hip states its two work-buffer layouts beside the kernels that read them: the launchers' pointers and, from a null base, the size
+uint32_t* compact_work(const void* work, size_t n, size_t* bytes = nullptr);
+uint32_t* densify_work(const void* work, size_t P, uint8_t*& cls, size_t* bytes = nullptr);
+
 extern "C" {
 
 void mm3dgs_profile_enable(int on) { g_prof_on = on; }
@@ -1017,11 +1021,11 @@ int mm3dgs_prune_mask(int P, const float* opacity, const float* log_scales, cons
                     (hipStream_t)stream);
   return check_launch("prune_mask");
 }
-size_t mm3dgs_compact_work_bytes(size_t n) { return align_up(((n + 255) / 256 + 1) * 4, 256); }
+size_t mm3dgs_compact_work_bytes(size_t n) { size_t b; compact_work(nullptr, n, &b); return b; }
 int mm3dgs_compact_plan(size_t n, const uint8_t* keep, void* work, uint32_t* n_keep, void* stream) {
   if (n > 0x7fffffffull) return fail(-1, "n too large");
   if (!work || !n_keep || (n > 0 && !keep)) return fail(-1, "NULL argument");
-  launch_compact_plan((int)n, keep, (uint32_t*)work, n_keep, (hipStream_t)stream);
+  launch_compact_plan((int)n, keep, compact_work(work, n), n_keep, (hipStream_t)stream);
   return check_launch("compact_plan");
 }
 int mm3dgs_compact_rows(size_t n, const uint8_t* keep, const void* work, const Mm3dgsCompactArray* arrays, int n_arrays, void* stream) {
@@ -1036,7 +1040,7 @@ int mm3dgs_compact_rows(size_t n, const uint8_t* keep, const void* work, const M
     if (!arrays[a].src || !arrays[a].dst) return fail(-1, "array %d: NULL pointer", a);
     t.src[t.n_arrays] = arrays[a].src; t.dst[t.n_arrays] = arrays[a].dst; t.width[t.n_arrays] = arrays[a].width; t.n_arrays++;
   }
-  launch_compact_rows((int)n, keep, (const uint32_t*)work, t, (hipStream_t)stream);
+  launch_compact_rows((int)n, keep, compact_work(work, n), t, (hipStream_t)stream);
   return check_launch("compact_rows");
 }
 int mm3dgs_seed_gaussians(int H, int W, const float* color, const float* depth, const uint8_t* keep, const void* work, const float* pose, float fx,
@@ -1046,19 +1050,19 @@ int mm3dgs_seed_gaussians(int H, int W, const float* color, const float* depth, 
   if (!out->xyz || !out->f_dc || !out->opacity || !out->scaling || !out->rotation || !out->rgb || (n_rest > 0 && !out->f_rest))
     return fail(-1, "NULL output array");
   SeedOut o = {out->xyz, out->f_dc, out->f_rest, out->opacity, out->scaling, out->rotation, out->rgb, n_rest > 0 ? n_rest : 0};
-  launch_seed_gaussians(H, W, color, depth, keep, (const uint32_t*)work, pose, fx, fy, cx, cy, row0, o, (hipStream_t)stream);
+  launch_seed_gaussians(H, W, color, depth, keep, compact_work(work, (size_t)H * (size_t)W), pose, fx, fy, cx, cy, row0, o, (hipStream_t)stream);
   return check_launch("seed_gaussians");
 }
 
-// densification (slam/gaussian_model.py:490-592).  work = [class bytes, P rounded up to 256][3 x nb block counts]
-static size_t densify_cls_bytes(size_t P) { return align_up(P, 256); }
-size_t mm3dgs_densify_work_bytes(size_t P) { return densify_cls_bytes(P) + align_up((3 * ((P + 255) / 256) + 1) * 4, 256); }
+// densification (slam/gaussian_model.py:490-592)
+size_t mm3dgs_densify_work_bytes(size_t P) { uint8_t* cls; size_t b; densify_work(nullptr, P, cls, &b); return b; }
 int mm3dgs_densify_plan(size_t P, const float* grad_accum, const float* denom, const float* log_scales, float max_grad, float max_clone_scale,
                         void* work, uint32_t* counts, void* stream) {
   if (P > 0x7fffffffull) return fail(-1, "P too large");
   if (!work || !counts || (P > 0 && (!grad_accum || !denom || !log_scales))) return fail(-1, "NULL argument");
-  launch_densify_plan((int)P, grad_accum, denom, log_scales, max_grad, max_clone_scale, (uint8_t*)work,
-                      (uint32_t*)((char*)work + densify_cls_bytes(P)), counts, (hipStream_t)stream);
+  uint8_t* cls;
+  uint32_t* block_counts = densify_work(work, P, cls);
+  launch_densify_plan((int)P, grad_accum, denom, log_scales, max_grad, max_clone_scale, cls, block_counts, counts, (hipStream_t)stream);
   return check_launch("densify_plan");
 }
 int mm3dgs_densify_rows(size_t P, const void* work, uint32_t n_keep, uint32_t n_clone, uint32_t n_split, int N, uint32_t seed,
@@ -1080,8 +1084,9 @@ int mm3dgs_densify_rows(size_t P, const void* work, uint32_t n_keep, uint32_t n_
   }
   if (n_split > 0 && (t.width[0] != 3 || t.width[4] != 3 || t.width[5] != 4)) return fail(-1, "split needs xyz[3], scaling[3], rotation[4]");
   t.grad_accum = st->grad_accum; t.denom = st->denom; t.max_radii2D = st->max_radii2D; t.parent = st->parent;
-  launch_densify_rows((int)P, (const uint8_t*)work, (const uint32_t*)((const char*)work + densify_cls_bytes(P)), n_keep, n_clone, n_split, N, seed,
-                      (float)(0.8 * (double)N), t, (hipStream_t)stream);
+  uint8_t* cls;
+  uint32_t* block_counts = densify_work(work, P, cls);
+  launch_densify_rows((int)P, cls, block_counts, n_keep, n_clone, n_split, N, seed, (float)(0.8 * (double)N), t, (hipStream_t)stream);
   return check_launch("densify_rows");
 }
 

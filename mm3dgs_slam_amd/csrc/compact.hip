@@ -12,7 +12,9 @@
 #include "mm3dgs_common.h"
 #include <algorithm>
 #include "fused_api.h"
-#include "compact_scan.h"      // scan_block_counts, block_rank (shared with pointcloud.hip)
+#include "mm3dgs_math.h"       // quat_to_R
+#include "block_ops.h"         // scan_block_counts, block_rank, block_flag_counts, block_sums_u32, Carve
+#include "view_pixel.h"        // Rigid, rigid_from_pose (shared with pointcloud.hip and tsdf.hip)
 
 #define CB 256
 
@@ -37,31 +39,23 @@ prune_mask_kernel(int P, const float* __restrict__ opacity, const float* __restr
 }
 
 __global__ void __launch_bounds__(CB) compact_count_kernel(int n, const uint8_t* __restrict__ keep, uint32_t* __restrict__ block_counts) {
-  __shared__ uint32_t wsum[CB / 64];
+  __shared__ uint32_t wsum[1][CB / 64];
   const int i = blockIdx.x * CB + threadIdx.x;
-  const unsigned long long m = __ballot(i < n && keep[i] != 0);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  const bool kept[1] = {i < n && keep[i] != 0};
+  const uint32_t t = block_flag_counts(kept, wsum);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = t;
 }
 
 __global__ void __launch_bounds__(1024) compact_scan_kernel(int nb, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ n_keep) {
   scan_block_counts(nb, block_counts, n_keep);
 }
 
-// rank[i] = position of element i among the kept ones (only meaningful where keep[i])
-__device__ __forceinline__ uint32_t compact_rank(int i, int n, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ block_pre,
-                                                 bool& kept, uint32_t* wsum) {
-  kept = i < n && keep[i] != 0;
-  return block_rank(kept, block_pre[blockIdx.x], wsum);
-}
-
 __global__ void __launch_bounds__(CB)
 compact_rows_kernel(int n, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ block_pre, CompactTable t) {
   __shared__ uint32_t wsum[CB / 64];
   const int i = blockIdx.x * CB + threadIdx.x;
-  bool kept;
-  const uint32_t r = compact_rank(i, n, keep, block_pre, kept, wsum);
+  const bool kept = i < n && keep[i] != 0;
+  const uint32_t r = block_rank(kept, block_pre[blockIdx.x], wsum);      // its position among the kept ones
   if (!kept) return;
   for (int a = 0; a < t.n_arrays; a++) {
     const int w = t.width[a];
@@ -69,6 +63,14 @@ compact_rows_kernel(int n, const uint8_t* __restrict__ keep, const uint32_t* __r
     float* d = t.dst[a] + (size_t)r * w;
     for (int c = 0; c < w; c++) d[c] = s[c];
   }
+}
+
+// world->camera 7-vector (qw,qx,qy,qz,tx,ty,tz) -> (R, t) in float32; the quaternion is normalised by its reciprocal norm
+__device__ __forceinline__ void pose_to_Rt(const float* __restrict__ pose, float R[3][3], float t[3]) {
+  const float n = 1.f / sqrtf(pose[0] * pose[0] + pose[1] * pose[1] + pose[2] * pose[2] + pose[3] * pose[3]);
+  const float q[4] = {pose[0] * n, pose[1] * n, pose[2] * n, pose[3] * n};
+  quat_to_R(q, R);
+  t[0] = pose[4]; t[1] = pose[5]; t[2] = pose[6];
 }
 
 // pixel i (raster order) with keep[i] seeds Gaussian row0 + rank(i)
@@ -79,19 +81,15 @@ seed_gaussians_kernel(int H, int W, const float* __restrict__ color, const float
   __shared__ uint32_t wsum[CB / 64];
   const int n = H * W;
   const int i = blockIdx.x * CB + threadIdx.x;
-  bool kept;
-  const uint32_t r = row0 + compact_rank(i, n, keep, block_pre, kept, wsum);
+  const bool kept = i < n && keep[i] != 0;
+  const uint32_t r = row0 + block_rank(kept, block_pre[blockIdx.x], wsum);
   if (!kept) return;
   // camera-to-world of the world-to-camera pose (qw,qx,qy,qz,tx,ty,tz): x_w = R^T (x_c - t)
-  float qw = pose[0], qx = pose[1], qy = pose[2], qz = pose[3];
-  const float qn = 1.f / sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-  qw *= qn; qx *= qn; qy *= qn; qz *= qn;
-  const float R[3][3] = {{1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qw * qz), 2.f * (qx * qz + qw * qy)},
-                         {2.f * (qx * qy + qw * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qw * qx)},
-                         {2.f * (qx * qz - qw * qy), 2.f * (qy * qz + qw * qx), 1.f - 2.f * (qx * qx + qy * qy)}};
+  float R[3][3], t[3];
+  pose_to_Rt(pose, R, t);
   const int u = i % W, v = i / W;
   const float z = depth[i];
-  const float c[3] = {((float)u - cx) / fx * z - pose[4], ((float)v - cy) / fy * z - pose[5], z - pose[6]};
+  const float c[3] = {((float)u - cx) / fx * z - t[0], ((float)v - cy) / fy * z - t[1], z - t[2]};
 #pragma unroll
   for (int a = 0; a < 3; a++) o.xyz[(size_t)r * 3 + a] = R[0][a] * c[0] + R[1][a] * c[1] + R[2][a] * c[2];
   const float ls = logf(z / ((fx + fy) * 0.5f));     // log sqrt((z / f)^2)
@@ -130,11 +128,9 @@ densify_classify_kernel(int P, int nb, const float* __restrict__ grad_accum, con
     c = g >= max_grad ? (s > max_clone_scale ? DENSIFY_SPLIT : (s <= max_clone_scale ? DENSIFY_CLONE : DENSIFY_KEEP)) : DENSIFY_KEEP;
     cls[i] = (uint8_t)c;
   }
-  const unsigned long long m[3] = {__ballot(c < 2), __ballot(c == DENSIFY_CLONE), __ballot(c == DENSIFY_SPLIT)};
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < 3; k++) wsum[k][threadIdx.x >> 6] = (uint32_t)__popcll(m[k]);
-  __syncthreads();
-  if (threadIdx.x < 3) block_counts[threadIdx.x * nb + blockIdx.x] = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
+  const bool is[3] = {c < 2, c == DENSIFY_CLONE, c == DENSIFY_SPLIT};
+  const uint32_t t = block_flag_counts(is, wsum);
+  if (threadIdx.x < 3) block_counts[threadIdx.x * nb + blockIdx.x] = t;
 }
 
 // workgroup k scans class k's block counts; counts[k] = its total
@@ -180,6 +176,8 @@ densify_rows_kernel(int P, int nb, const uint8_t* __restrict__ cls, const uint32
     return;
   }
   // split: N children with xyz = R(normalize(q)) (exp(s) * z) + xyz, scaling = log(exp(s) / (0.8 N)) (gaussian_model.py:490-515)
+  // (R written out, not quat_to_R: through the helper the compiler contracts the children's xyz differently -- 23 of the 55 densification
+  // runs of tests/surgery_cases.py changed bytes on an MI355X; the quaternion is divided by its norm, as the reference normalises)
   const float* q = t.src[5] + (size_t)i * 4;
   float w = q[0], x = q[1], y = q[2], z = q[3];
   const float qn = sqrtf(w * w + x * x + y * y + z * z);
@@ -215,15 +213,6 @@ densify_rows_kernel(int P, int nb, const uint8_t* __restrict__ cls, const uint32
 // that round to the world origin at 4 decimals) back-projected to the world and projected into the current view;
 // counts[0] = points that land inside the image in front of the camera, counts[1] = points tested.  One pass over the rendered
 // depth / silhouette planes instead of ~30 element-wise torch launches; a fixed small grid, so only a handful of atomics per counter.
-__device__ __forceinline__ void pose_to_Rt(const float* __restrict__ pose, float R[3][3], float t[3]) {
-  float w = pose[0], x = pose[1], y = pose[2], z = pose[3];
-  const float n = 1.f / sqrtf(w * w + x * x + y * y + z * z);
-  w *= n; x *= n; y *= n; z *= n;
-  R[0][0] = 1.f - 2.f * (y * y + z * z); R[0][1] = 2.f * (x * y - w * z); R[0][2] = 2.f * (x * z + w * y);
-  R[1][0] = 2.f * (x * y + w * z); R[1][1] = 1.f - 2.f * (x * x + z * z); R[1][2] = 2.f * (y * z - w * x);
-  R[2][0] = 2.f * (x * z - w * y); R[2][1] = 2.f * (y * z + w * x); R[2][2] = 1.f - 2.f * (x * x + y * y);
-  t[0] = pose[4]; t[1] = pose[5]; t[2] = pose[6];
-}
 __global__ void __launch_bounds__(CB)
 covisibility_ratio_kernel(int H, int W, const float* __restrict__ depth, const float* __restrict__ sil, const float* __restrict__ kf_pose,
                           const float* __restrict__ cur_pose, float fx, float fy, float cx, float cy, uint32_t* __restrict__ counts) {
@@ -252,15 +241,25 @@ covisibility_ratio_kernel(int H, int W, const float* __restrict__ depth, const f
     n_in += inside ? 1u : 0u; n_sel += sel ? 1u : 0u;
   }
   __shared__ uint32_t red[2][CB / 64];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { n_in += __shfl_down(n_in, off, 64); n_sel += __shfl_down(n_sel, off, 64); }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = n_in; red[1][threadIdx.x >> 6] = n_sel; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    uint32_t t = 0;
-    for (int w = 0; w < CB / 64; w++) t += red[threadIdx.x][w];
-    if (t) atomicAdd(&counts[threadIdx.x], t);
-  }
+  const uint32_t nn[2] = {n_in, n_sel};
+  const uint32_t t = block_sums_u32(nn, red);
+  if (threadIdx.x < 2 && t) atomicAdd(&counts[threadIdx.x], t);
+}
+
+// ---- work buffers, carved for api.hip: it hands the launchers these pointers, and sizes a buffer by the walk from a null base -----------
+// compaction = [uint32 per 256 elements, + 1]; densification = [class byte per row][3 x uint32 per 256 rows, + 1]
+uint32_t* compact_work(const void* work, size_t n, size_t* bytes) {
+  Carve c = {(uintptr_t)work};
+  uint32_t* block_pre = c.take<uint32_t>((n + 255) / 256 + 1);
+  if (bytes) *bytes = c.at;
+  return block_pre;
+}
+uint32_t* densify_work(const void* work, size_t P, uint8_t*& cls, size_t* bytes) {
+  Carve c = {(uintptr_t)work};
+  cls = c.take<uint8_t>(P);
+  uint32_t* block_counts = c.take<uint32_t>(3 * ((P + 255) / 256) + 1);
+  if (bytes) *bytes = c.at;
+  return block_counts;
 }
 
 // ---- launchers (called from api.hip) ------------------------------------------------------------------------------------------
@@ -312,20 +311,7 @@ void launch_covisibility_ratio(int H, int W, const float* depth, const float* si
   hipLaunchKernelGGL(covisibility_ratio_kernel, dim3(nb), dim3(CB), 0, s, H, W, depth, sil, kf_pose, cur_pose, fx, fy, cx, cy, counts);
 }
 
-// ---- rigid 4x4 algebra of the one-lane pose kernels below, in double: [R | t; 0 1] as (R, t) --------------------------------------------
-struct Rigid { double R[3][3], t[3]; };
-// world->camera 7-vector (qw,qx,qy,qz,tx,ty,tz): normalised quaternion -> R (utils/pose_utils.py:240-271,352-368)
-__device__ inline Rigid rigid_from_pose(const float* __restrict__ p) {
-  Rigid o;
-  double w = p[0], x = p[1], y = p[2], z = p[3];
-  const double n = sqrt(w * w + x * x + y * y + z * z);
-  w /= n; x /= n; y /= n; z /= n;
-  o.R[0][0] = 1.0 - 2.0 * (y * y + z * z); o.R[0][1] = 2.0 * (x * y - w * z); o.R[0][2] = 2.0 * (x * z + w * y);
-  o.R[1][0] = 2.0 * (x * y + w * z); o.R[1][1] = 1.0 - 2.0 * (x * x + z * z); o.R[1][2] = 2.0 * (y * z - w * x);
-  o.R[2][0] = 2.0 * (x * z - w * y); o.R[2][1] = 2.0 * (y * z + w * x); o.R[2][2] = 1.0 - 2.0 * (x * x + y * y);
-  o.t[0] = p[4]; o.t[1] = p[5]; o.t[2] = p[6];
-  return o;
-}
+// ---- rigid 4x4 algebra of the one-lane pose kernels below, in double: Rigid = (R, t), rigid_from_pose (view_pixel.h) ------------------
 // closed-form inverse [R^T | -R^T t]
 __device__ inline Rigid rigid_inverse(const Rigid& a) {
   Rigid o;

@@ -14,6 +14,7 @@
 // one dword load per lane.
 #include <math.h>
 #include "loss_tile.h"
+#include "block_ops.h"
 
 #define EVAL_ROW 12     // doubles per tile row (the row width reduce_rows_256 reads): sse[3], ssim_sum[3], n, sum |d|, sum d^2, three zeros
 
@@ -22,20 +23,6 @@ struct EvalCfg { int H, W; float window[11]; };
 static int eval_tiles_x(int W) { return (W + LT - 1) / LT; }
 static int eval_tiles(int H, int W) { return eval_tiles_x(W) * ((H + LT - 1) / LT); }
 size_t eval_image_work_bytes(int H, int W) { return align_up((size_t)eval_tiles(H, W) * EVAL_ROW * sizeof(double), 256); }
-
-// sum of nine per-lane doubles over the 256-lane workgroup, in a fixed order (valid in lane 0 only)
-__device__ __forceinline__ void eval_block_sums(double (&v)[9], double (*sh)[9]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const double t = wave_sum_to_lane63_f64(v[k]);
-    if (lane == 63) sh[wv][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < 9; k++) v[k] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
-}
 
 __global__ void __launch_bounds__(256)
 eval_tile_kernel(EvalCfg cfg, const float* __restrict__ image, const float* __restrict__ gt, const float* __restrict__ depth,
@@ -95,7 +82,7 @@ eval_tile_kernel(EvalCfg cfg, const float* __restrict__ image, const float* __re
       acc[3 + ch] = (double)((p.A1 * p.A2) / (p.B1 * p.B2));      // the correctly rounded float32 division, as the host chain's map
     }
   }
-  eval_block_sums(acc, red);
+  block_sums_f64<9, false>(acc, red);      // fixed order; valid in lane 0
   if (tid == 0) {
     double* row = partial + (size_t)tile * EVAL_ROW;
 #pragma unroll

@@ -7,7 +7,7 @@
 //   ng_count_kernel    one lane per reference row: its cell (NN_NO_CELL for a row that is not finite or lies outside the box), one integer
 //                      atomicAdd on the cell's count -- a count does not depend on the order of its adds.
 //   ng_cellscan_kernel per 256 cells: the exclusive prefix inside the block and the block's total.
-//   ng_scan_kernel     one workgroup of 1024: scan_block_counts over the block totals (compact_scan.h), the total.
+//   ng_scan_kernel     one workgroup of 1024: scan_block_counts over the block totals (block_ops.h), the total.
 //   ng_base_kernel     cell_start = block prefix + local prefix; the same value into the cell's fill cursor.
 //   ng_scatter_kernel  every row takes a slot of its cell (integer atomicAdd on the cursor) and stores one 16-byte record {x, y, z, row index}.
 //                      The order inside a cell depends on the atomics; a minimum over the cell does not.
@@ -23,7 +23,7 @@
 //   ms_base_kernel     prefix[t] += block prefix.
 //   ms_emit_kernel     one lane per SAMPLE: binary search of its triangle in the exclusive prefix, then the sample's row.
 #include <math.h>
-#include "compact_scan.h"
+#include "block_ops.h"
 #include "fused_api.h"
 
 #define GB 256
@@ -35,18 +35,16 @@ static size_t ng_nb(size_t n) { return (n + GB - 1) / GB; }
 // ---- grid build -------------------------------------------------------------------------------------------------------------------
 // work = [uint32 cell per reference row][uint32 count, then fill cursor, per cell][uint32 per 256 cells]
 struct NgWork { uint32_t* cellidx; uint32_t* cursor; uint32_t* bcounts; };
-size_t nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz) {
-  const size_t nc = (size_t)gx * (size_t)gy * (size_t)gz;
-  return align_up((size_t)n_ref * 4, 256) + align_up(nc * 4, 256) + align_up(ng_nb(nc) * 4, 256);
-}
-static NgWork ng_work(void* base, size_t n_ref, size_t nc) {
-  char* c = (char*)base;
+static NgWork ng_work(void* base, size_t n_ref, size_t nc, size_t* bytes = nullptr) {
+  Carve c = {(uintptr_t)base};
   NgWork w;
-  w.cellidx = (uint32_t*)c;  c += align_up(n_ref * 4, 256);
-  w.cursor = (uint32_t*)c;   c += align_up(nc * 4, 256);
-  w.bcounts = (uint32_t*)c;
+  w.cellidx = c.take<uint32_t>(n_ref);
+  w.cursor = c.take<uint32_t>(nc);
+  w.bcounts = c.take<uint32_t>(ng_nb(nc));
+  if (bytes) *bytes = c.at;
   return w;
 }
+size_t nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz) { size_t b; ng_work(nullptr, (size_t)n_ref, (size_t)gx * (size_t)gy * (size_t)gz, &b); return b; }
 
 __device__ __forceinline__ bool ng_finite(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }
 
@@ -93,23 +91,12 @@ ng_count_kernel(NnGrid g, const uint4* __restrict__ rows, uint32_t n, uint32_t* 
   }
 }
 
-// inclusive scan of v over the workgroup of GB lanes (every lane calls); wtot: GB / 64 words of LDS
-__device__ __forceinline__ uint32_t ng_block_scan(uint32_t v, uint32_t* wtot) {
-  const uint32_t x = wave_scan_incl(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 63) wtot[wv] = x;
-  __syncthreads();
-  uint32_t pre = 0;
-  for (int w = 0; w < wv; w++) pre += wtot[w];
-  return pre + x;
-}
-
 __global__ void __launch_bounds__(GB)
 ng_cellscan_kernel(const uint32_t* __restrict__ counts, size_t nc, uint32_t* __restrict__ cell_start, uint32_t* __restrict__ bcounts) {
   __shared__ uint32_t wtot[GB / 64];
   const size_t i = (size_t)blockIdx.x * GB + threadIdx.x;
   const uint32_t v = i < nc ? counts[i] : 0u;
-  const uint32_t incl = ng_block_scan(v, wtot);
+  const uint32_t incl = block_scan_incl(v, wtot);
   if (i < nc) cell_start[i] = incl - v;
   if (threadIdx.x == GB - 1) bcounts[blockIdx.x] = incl;
 }
@@ -214,7 +201,7 @@ __global__ void __launch_bounds__(GB)
 ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted,
                 uint32_t n_ref, double max_dist, float threshold, int rmax, float* __restrict__ dist_out, double* __restrict__ partial) {
 #pragma clang fp contract(off)
-  __shared__ double wsum[2][GB / 64];
+  __shared__ double wsum[GB / 64][2];
   __shared__ uint32_t wcnt[4][GB / 64];
   __shared__ uint32_t smax;
   const uint32_t i = blockIdx.x * GB + threadIdx.x;
@@ -265,19 +252,16 @@ ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const u
     }
     dist_out[i] = out;
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const double s1 = wave_sum_to_lane63_f64(dd), s2 = wave_sum_to_lane63_f64(dd * dd);
-  const unsigned long long m[4] = {__ballot(scored), __ballot(within), __ballot(clamped), __ballot(skipped)};
-  if (lane == 63) { wsum[0][wv] = s1; wsum[1][wv] = s2; }
-  if (lane == 0)
-    for (int k = 0; k < 4; k++) wcnt[k][wv] = (uint32_t)__popcll(m[k]);
-  __syncthreads();
+  double sums[2] = {dd, dd * dd};
+  block_sums_f64<2, false>(sums, wsum);
+  const bool is[4] = {scored, within, clamped, skipped};
+  const uint32_t cnt = block_flag_counts(is, wcnt);
+  double* row = partial + (size_t)blockIdx.x * NN_ROW;
+  if (threadIdx.x < 4) row[3 + threadIdx.x] = (double)cnt;
   if (threadIdx.x == 0) {
-    double* row = partial + (size_t)blockIdx.x * NN_ROW;
-    row[0] = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
-    row[1] = (wsum[1][0] + wsum[1][1]) + (wsum[1][2] + wsum[1][3]);
+    row[0] = sums[0];
+    row[1] = sums[1];
     row[2] = (double)__uint_as_float(smax);
-    for (int k = 0; k < 4; k++) row[3 + k] = (double)(wcnt[k][0] + wcnt[k][1] + wcnt[k][2] + wcnt[k][3]);
     row[7] = 0.0;
   }
 }
@@ -325,16 +309,17 @@ void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t 
 // ---- surface sampler --------------------------------------------------------------------------------------------------------------
 // work = [256 B header: uint64 samples (0 when they exceed 32 bits)][uint32 exclusive prefix per triangle][2 x uint32 per 256 triangles: samples, degenerate]
 struct MsWork { unsigned long long* hdr; uint32_t* prefix; uint32_t* bcounts; uint32_t* dcounts; };
-size_t mesh_sample_work_bytes(uint64_t m) { return 256 + align_up((size_t)m * 4, 256) + 2 * align_up(ng_nb((size_t)m) * 4, 256); }
-static MsWork ms_work(void* base, size_t m) {
-  char* c = (char*)base;
+static MsWork ms_work(void* base, size_t m, size_t* bytes = nullptr) {
+  Carve c = {(uintptr_t)base};
   MsWork w;
-  w.hdr = (unsigned long long*)c;  c += 256;
-  w.prefix = (uint32_t*)c;         c += align_up(m * 4, 256);
-  w.bcounts = (uint32_t*)c;        c += align_up(ng_nb(m) * 4, 256);
-  w.dcounts = (uint32_t*)c;
+  w.hdr = c.take<unsigned long long>(1);
+  w.prefix = c.take<uint32_t>(m);
+  w.bcounts = c.take<uint32_t>(ng_nb(m));
+  w.dcounts = c.take<uint32_t>(ng_nb(m));
+  if (bytes) *bytes = c.at;
   return w;
 }
+size_t mesh_sample_work_bytes(uint64_t m) { size_t b; ms_work(nullptr, (size_t)m, &b); return b; }
 
 // the 32-bit mixer (geometry.py: mix32 / sample_hash state the same one)
 __device__ __forceinline__ uint32_t ms_mix(uint32_t x) {
@@ -384,34 +369,27 @@ __device__ __forceinline__ uint32_t ms_count(const MeshSample& ms, uint32_t t, b
 __global__ void __launch_bounds__(GB)
 ms_plan_kernel(MeshSample ms, uint32_t* __restrict__ prefix, uint32_t* __restrict__ bcounts, uint32_t* __restrict__ dcounts) {
   __shared__ uint32_t wtot[GB / 64];
-  __shared__ uint32_t wdeg[GB / 64];
+  __shared__ uint32_t wdeg[1][GB / 64];
   const uint32_t t = blockIdx.x * GB + threadIdx.x;
   bool deg = false;
   const uint32_t nt = t < ms.m ? ms_count(ms, t, deg) : 0u;
-  const uint32_t incl = ng_block_scan(nt, wtot);
+  const uint32_t incl = block_scan_incl(nt, wtot);
   if (t < ms.m) prefix[t] = incl - nt;
   if (threadIdx.x == GB - 1) bcounts[blockIdx.x] = incl;
-  const unsigned long long md = __ballot(deg);
-  if ((threadIdx.x & 63) == 0) wdeg[threadIdx.x >> 6] = (uint32_t)__popcll(md);
-  __syncthreads();
-  if (threadIdx.x == 0) dcounts[blockIdx.x] = wdeg[0] + wdeg[1] + wdeg[2] + wdeg[3];
+  const bool is[1] = {deg};
+  const uint32_t nd = block_flag_counts(is, wdeg);
+  if (threadIdx.x == 0) dcounts[blockIdx.x] = nd;
 }
 
 __global__ void __launch_bounds__(1024)
 ms_scan_kernel(int nb, uint32_t* __restrict__ bcounts, const uint32_t* __restrict__ dcounts, unsigned long long m, unsigned long long* __restrict__ hdr,
                unsigned long long* __restrict__ counters) {
-  __shared__ unsigned long long sh[2][16];
+  __shared__ unsigned long long sh[16];
   __shared__ uint32_t total32;
   // the 64-bit sums first: the scan overwrites the block totals with their prefix
-  unsigned long long s = 0ull, d = 0ull;
-  for (int i = threadIdx.x; i < nb; i += 1024) { s += bcounts[i]; d += dcounts[i]; }
-  for (int off = 32; off > 0; off >>= 1) { s += __shfl_down(s, off); d += __shfl_down(d, off); }      // integer sums: any order
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = d; }
-  __syncthreads();
+  const unsigned long long total = block_array_sum(nb, bcounts, sh), deg = block_array_sum(nb, dcounts, sh);
   scan_block_counts(nb, bcounts, &total32);
   if (threadIdx.x == 0) {
-    unsigned long long total = 0ull, deg = 0ull;
-    for (int w = 0; w < 16; w++) { total += sh[0][w]; deg += sh[1][w]; }
     const bool over = total > 0xffffffffull;      // the prefix is 32 bits wide: nothing can be emitted
     hdr[0] = over ? 0ull : total;
     counters[0] = total;

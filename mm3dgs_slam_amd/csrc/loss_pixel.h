@@ -12,6 +12,7 @@
 // 1 / (ref + 200) branch, so a 1e-7 relative rounding of the sums would become 1e-2 on the correlation) stay in double -- only
 // the columns the configuration uses (workgroup-uniform mask): none without a Pearson term, 4..8 for the mapping loss, 4..11 with
 // the two-target tracking form.
+// (Not block_ops.h's block_sums_f64: float and double columns, the order ((w0 + w1) + w2) + w3, and this one sits in the mapping loop.)
 __device__ __forceinline__ unsigned pearson_double_cols(const LossCfg& cfg) {
   return cfg.w_pearson == 0.f ? 0u : (cfg.pearson_invert ? 0xff0u : 0x1f0u);
 }

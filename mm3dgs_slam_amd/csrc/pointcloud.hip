@@ -17,9 +17,9 @@
 // A position is evaluated in double from the float32 inputs and rounded once to float32; the three kernels that need it call one function
 // compiled without contraction, so they agree on the float32 value and hence on the key.
 #include <math.h>
-#include "compact_scan.h"
+#include "block_ops.h"
 #include "fused_api.h"
-#include "view_pixel.h"      // PcRigid / pc_rigid, view_pixel_valid, pc_quant (shared with tsdf.hip)
+#include "view_pixel.h"      // Rigid / rigid_from_pose, view_pixel_valid, pc_quant (shared with tsdf.hip)
 
 #define PB 256
 #define PC_MAX_PROBE 128                 // slots a point may inspect; the table is sized for a load of at most 1/2
@@ -27,18 +27,23 @@
 #define PC_CELL_LIMIT 1048576.0          // 2^20 cells on either side of the origin per axis
 
 // work = [256 B header: uint64 base of this view][flag byte per pixel][4 x per-workgroup counts: representatives, valid, out of range, probe failures]
+struct PcWork { unsigned long long* hdr; uint8_t* flag; uint32_t* counts[4]; };
 static size_t pc_nb(size_t n) { return (n + PB - 1) / PB; }
-static size_t pc_flag_bytes(size_t n) { return align_up(n, 256); }
-static size_t pc_count_bytes(size_t n) { return align_up(pc_nb(n) * 4, 256); }
-size_t pointcloud_work_bytes(int H, int W) {
-  const size_t n = (size_t)H * (size_t)W;
-  return 256 + pc_flag_bytes(n) + 4 * pc_count_bytes(n);
+static PcWork pc_work(void* base, size_t n, size_t* bytes = nullptr) {
+  Carve c = {(uintptr_t)base};
+  PcWork w;
+  w.hdr = c.take<unsigned long long>(1);
+  w.flag = c.take<uint8_t>(n);
+  for (int k = 0; k < 4; k++) w.counts[k] = c.take<uint32_t>(pc_nb(n));
+  if (bytes) *bytes = c.at;
+  return w;
 }
+size_t pointcloud_work_bytes(int H, int W) { size_t b; pc_work(nullptr, (size_t)H * (size_t)W, &b); return b; }
 
 struct PcPoint { float x, y, z; };
 
 // the world point of pixel i at depth z: p_c = ((u - cx) / fx z, (v - cy) / fy z, z), p_w = R^T (p_c - t); no half-pixel offset
-__device__ __forceinline__ PcPoint pc_backproject(const PointCloudView& v, const PcRigid& g, int i, float zf) {
+__device__ __forceinline__ PcPoint pc_backproject(const PointCloudView& v, const Rigid& g, int i, float zf) {
 #pragma clang fp contract(off)
   const double z = (double)zf;
   const double c0 = ((double)(i % v.W) - v.cx) / v.fx * z - g.t[0];
@@ -72,7 +77,7 @@ __global__ void __launch_bounds__(PB) pc_claim_kernel(PointCloudView v) {
   if (i >= n) return;
   float z;
   if (!pc_valid(v, i, z)) return;
-  const PcRigid g = pc_rigid(v.pose);
+  const Rigid g = rigid_from_pose(v.pose);
   uint64_t key;
   if (!pc_key(pc_backproject(v, g, i, z), v.voxel, key)) return;
   const uint64_t mask = v.slots - 1, ticket = ((uint64_t)v.view << 32) | (uint64_t)(uint32_t)i;
@@ -99,7 +104,7 @@ pc_select_kernel(PointCloudView v, uint8_t* __restrict__ flag, uint32_t* __restr
   const bool valid = i < n && pc_valid(v, i, z);
   bool rep = valid, oor = false, fail = false;
   if (valid && v.table) {
-    const PcRigid g = pc_rigid(v.pose);
+    const Rigid g = rigid_from_pose(v.pose);
     uint64_t key;
     rep = false;
     if (!pc_key(pc_backproject(v, g, i, z), v.voxel, key)) {
@@ -118,25 +123,9 @@ pc_select_kernel(PointCloudView v, uint8_t* __restrict__ flag, uint32_t* __restr
     }
   }
   if (i < n) flag[i] = rep ? 1 : 0;
-  const unsigned long long m[4] = {__ballot(rep), __ballot(valid), __ballot(oor), __ballot(fail)};
-  if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < 4; k++) wsum[k][threadIdx.x >> 6] = (uint32_t)__popcll(m[k]);
-  __syncthreads();
-  if (threadIdx.x < 4) counts[threadIdx.x * stride + blockIdx.x] =wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
-}
-
-// sum of a[0..nb) over a workgroup of 1024 (valid in lane 0)
-__device__ __forceinline__ uint32_t pc_block_sum(int nb, const uint32_t* __restrict__ a, uint32_t* sh) {
-  uint32_t s = 0;
-  for (int i = threadIdx.x; i < nb; i += 1024) s += a[i];
-  s = wave_scan_incl(s);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 63) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  uint32_t t = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < 16; w++) t += sh[w];
-  return t;
+  const bool is[4] = {rep, valid, oor, fail};
+  const uint32_t t = block_flag_counts(is, wsum);
+  if (threadIdx.x < 4) counts[threadIdx.x * stride + blockIdx.x] = t;
 }
 
 __global__ void __launch_bounds__(1024)
@@ -145,9 +134,9 @@ pc_scan_kernel(int nb, size_t stride, uint32_t* __restrict__ counts, unsigned lo
   __shared__ uint32_t sh[16];
   __shared__ uint32_t total;
   scan_block_counts(nb, counts, &total);
-  const uint32_t valid = pc_block_sum(nb, counts + stride, sh);
-  const uint32_t oor = pc_block_sum(nb, counts + 2 * stride, sh);
-  const uint32_t fail = pc_block_sum(nb, counts + 3 * stride, sh);
+  const uint32_t valid = block_array_sum(nb, counts + stride, sh);
+  const uint32_t oor = block_array_sum(nb, counts + 2 * stride, sh);
+  const uint32_t fail = block_array_sum(nb, counts + 3 * stride, sh);
   if (threadIdx.x == 0) {      // (lane 0 wrote `total` itself)
     const unsigned long long reps = total, base = counters[0];
     const unsigned long long room = base < cap ? cap - base : 0ull;
@@ -172,7 +161,7 @@ pc_scatter_kernel(PointCloudView v, const uint8_t* __restrict__ flag, const uint
   const bool rep = i < n && flag[i] != 0;
   const unsigned long long r = hdr[0] + (unsigned long long)block_rank(rep, block_pre[blockIdx.x], wsum);
   if (!rep || r >= cap) return;
-  const PcRigid g = pc_rigid(v.pose);
+  const Rigid g = rigid_from_pose(v.pose);
   const PcPoint p = pc_backproject(v, g, i, v.depth[i]);
   const uint32_t rgba = pc_quant(v.color[i]) | (pc_quant(v.color[(size_t)n + i]) << 8) | (pc_quant(v.color[2 * (size_t)n + i]) << 16) | 0xff000000u;
   rows[r] = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(p.z), rgba);      // one 16-byte store
@@ -195,12 +184,10 @@ void launch_pointcloud_reset(void* table, uint64_t slots, uint64_t* counters, hi
 void launch_pointcloud_add_view(const PointCloudView& v, void* rows, uint64_t cap, uint64_t* counters, void* work, hipStream_t s) {
   const size_t n = (size_t)v.H * (size_t)v.W;
   const int nb = (int)pc_nb(n);
-  unsigned long long* hdr = (unsigned long long*)work;
-  uint8_t* flag = (uint8_t*)work + 256;
-  uint32_t* counts = (uint32_t*)(flag + pc_flag_bytes(n));
-  const size_t stride = pc_count_bytes(n) / 4;
+  const PcWork w = pc_work(work, n);
+  const size_t stride = (size_t)(w.counts[1] - w.counts[0]);      // the four count arrays are equally spaced
   if (v.table) hipLaunchKernelGGL(pc_claim_kernel, dim3(nb), dim3(PB), 0, s, v);
-  hipLaunchKernelGGL(pc_select_kernel, dim3(nb), dim3(PB), 0, s, v, flag, counts, stride);
-  hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(1024), 0, s, nb, stride, counts, (unsigned long long)cap, (unsigned long long*)counters, hdr);
-  hipLaunchKernelGGL(pc_scatter_kernel, dim3(nb), dim3(PB), 0, s, v, flag, counts, hdr, (unsigned long long)cap, (uint4*)rows);
+  hipLaunchKernelGGL(pc_select_kernel, dim3(nb), dim3(PB), 0, s, v, w.flag, w.counts[0], stride);
+  hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(1024), 0, s, nb, stride, w.counts[0], (unsigned long long)cap, (unsigned long long*)counters, w.hdr);
+  hipLaunchKernelGGL(pc_scatter_kernel, dim3(nb), dim3(PB), 0, s, v, w.flag, w.counts[0], w.hdr, (unsigned long long)cap, (uint4*)rows);
 }

@@ -17,7 +17,7 @@
 //                           and per-cube triangle base).  Emit: tm_vertex (one 16-byte row per vertex at base[q] + popcount(mask[q] below d)),
 //                           tm_triangle (int32[3] per triangle, by tetrahedron then case order).  No atomic decides a position or an index.
 #include <math.h>
-#include "compact_scan.h"
+#include "block_ops.h"
 #include "fused_api.h"
 #include "view_pixel.h"
 
@@ -30,13 +30,13 @@ __global__ void __launch_bounds__(TB)
 tsdf_integrate_kernel(TsdfView v, float2* __restrict__ tsdf_w, float4* __restrict__ rgb_w, unsigned long long* __restrict__ counters, unsigned xb,
                       unsigned yb) {
 #pragma clang fp contract(off)
-  __shared__ PcRigid g;      // the pose is the same for every sample: one lane normalises the quaternion for its workgroup
+  __shared__ Rigid g;      // the pose is the same for every sample: one lane normalises the quaternion for its workgroup
   __shared__ uint32_t wsum[2][TB / 64];
   const unsigned b = blockIdx.x;
   const int i = (int)(b % xb) * 64 + (int)(threadIdx.x & 63);
   const int j = (int)((b / xb) % yb) * 4 + (int)(threadIdx.x >> 6);
   const int k0 = (int)(b / (xb * yb)) * TZ;
-  if (threadIdx.x == 0) g = pc_rigid(v.pose);
+  if (threadIdx.x == 0) g = rigid_from_pose(v.pose);
   __syncthreads();
   uint32_t nupd = 0, ncup = 0;
   if (i < v.nx && j < v.ny) {
@@ -72,15 +72,10 @@ tsdf_integrate_kernel(TsdfView v, float2* __restrict__ tsdf_w, float4* __restric
       }
     }
   }
-  const uint32_t su = wave_scan_incl(nupd), sc = wave_scan_incl(ncup);      // (every lane is here)
-  if ((threadIdx.x & 63) == 63) { wsum[0][threadIdx.x >> 6] = su; wsum[1][threadIdx.x >> 6] = sc; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t tu = wsum[0][0] + wsum[0][1] + wsum[0][2] + wsum[0][3], tc = wsum[1][0] + wsum[1][1] + wsum[1][2] + wsum[1][3];
-    if (tu) atomicAdd(counters + 1, (unsigned long long)tu);
-    if (tc) atomicAdd(counters + 2, (unsigned long long)tc);
-    if (b == 0) atomicAdd(counters, 1ull);
-  }
+  const uint32_t nn[2] = {nupd, ncup};
+  const uint32_t t = block_sums_u32(nn, wsum);      // (every lane is here)
+  if (threadIdx.x < 2 && t) atomicAdd(counters + 1 + threadIdx.x, (unsigned long long)t);
+  if (threadIdx.x == 0 && b == 0) atomicAdd(counters, 1ull);
 }
 
 void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_t* counters, hipStream_t s) {
@@ -94,23 +89,21 @@ void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_
 //        [edge mask byte per sample: bit d][uint32 vertex base per sample][uint32 triangle base per cube][per-256 vertex counts][per-256 triangle counts]
 struct TmWork { unsigned long long* hdr; uint8_t* state; uint8_t* cube; uint8_t* vmask; uint32_t* vbase; uint32_t* tbase; uint32_t* vcounts; uint32_t* tcounts; };
 static size_t tm_nb(size_t n) { return (n + TB - 1) / TB; }
-size_t tsdf_mesh_work_bytes(int nx, int ny, int nz) {
-  const size_t n = (size_t)nx * (size_t)ny * (size_t)nz;
-  return 256 + 3 * align_up(n, 256) + 2 * align_up(n * 4, 256) + 2 * align_up(tm_nb(n) * 4, 256);
-}
-static TmWork tm_work(void* base, size_t n) {
-  char* c = (char*)base;
+static TmWork tm_work(void* base, size_t n, size_t* bytes = nullptr) {
+  Carve c = {(uintptr_t)base};
   TmWork w;
-  w.hdr = (unsigned long long*)c;  c += 256;
-  w.state = (uint8_t*)c;           c += align_up(n, 256);
-  w.cube = (uint8_t*)c;            c += align_up(n, 256);
-  w.vmask = (uint8_t*)c;           c += align_up(n, 256);
-  w.vbase = (uint32_t*)c;          c += align_up(n * 4, 256);
-  w.tbase = (uint32_t*)c;          c += align_up(n * 4, 256);
-  w.vcounts = (uint32_t*)c;        c += align_up(tm_nb(n) * 4, 256);
-  w.tcounts = (uint32_t*)c;
+  w.hdr = c.take<unsigned long long>(2);
+  w.state = c.take<uint8_t>(n);
+  w.cube = c.take<uint8_t>(n);
+  w.vmask = c.take<uint8_t>(n);
+  w.vbase = c.take<uint32_t>(n);
+  w.tbase = c.take<uint32_t>(n);
+  w.vcounts = c.take<uint32_t>(tm_nb(n));
+  w.tcounts = c.take<uint32_t>(tm_nb(n));
+  if (bytes) *bytes = c.at;
   return w;
 }
+size_t tsdf_mesh_work_bytes(int nx, int ny, int nz) { size_t b; tm_work(nullptr, (size_t)nx * (size_t)ny * (size_t)nz, &b); return b; }
 
 struct TmGrid { int nx, ny, nz; size_t n; };
 
@@ -139,17 +132,6 @@ __device__ __forceinline__ void tm_coords(const TmGrid& g, size_t i, int& x, int
   x = (int)(i % (size_t)g.nx);
   y = (int)((i / (size_t)g.nx) % (size_t)g.ny);
   z = (int)(i / ((size_t)g.nx * (size_t)g.ny));
-}
-
-// inclusive scan of v over the workgroup of TB lanes (every lane calls); wtot: TB / 64 words of LDS
-__device__ __forceinline__ uint32_t tm_block_scan(uint32_t v, uint32_t* wtot) {
-  const uint32_t x = wave_scan_incl(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 63) wtot[wv] = x;
-  __syncthreads();
-  uint32_t pre = 0;
-  for (int w = 0; w < wv; w++) pre += wtot[w];
-  return pre + x;
 }
 
 __global__ void __launch_bounds__(TB) tm_state_kernel(TmGrid g, const float2* __restrict__ tsdf_w, float min_weight, uint8_t* __restrict__ state) {
@@ -190,7 +172,7 @@ __global__ void __launch_bounds__(TB) tm_cube_kernel(TmGrid g, const uint8_t* __
     }
     cube[i] = out;
   }
-  const uint32_t incl = tm_block_scan(ntri, wtot);
+  const uint32_t incl = block_scan_incl(ntri, wtot);
   if (threadIdx.x == TB - 1) tcounts[blockIdx.x] = incl;
 }
 
@@ -220,7 +202,7 @@ tm_edge_kernel(TmGrid g, const uint8_t* __restrict__ state, const uint8_t* __res
     }
     vmask[i] = (uint8_t)mask;
   }
-  const uint32_t incl = tm_block_scan((uint32_t)__popc(mask), wtot);
+  const uint32_t incl = block_scan_incl((uint32_t)__popc(mask), wtot);
   if (threadIdx.x == TB - 1) vcounts[blockIdx.x] = incl;
 }
 
@@ -245,7 +227,7 @@ tm_base_kernel(TmGrid g, const uint8_t* __restrict__ cube, const uint8_t* __rest
   __shared__ uint32_t wv[TB / 64], wt[TB / 64];
   const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
   const uint32_t nv = i < g.n ? (uint32_t)__popc((unsigned)vmask[i]) : 0u, nt = i < g.n ? (uint32_t)(cube[i] & 0x7fu) : 0u;
-  const uint32_t iv = tm_block_scan(nv, wv), it = tm_block_scan(nt, wt);
+  const uint32_t iv = block_scan_incl(nv, wv), it = block_scan_incl(nt, wt);
   if (i < g.n) {
     vbase[i] = vpre[blockIdx.x] + iv - nv;
     tbase[i] = tpre[blockIdx.x] + it - nt;

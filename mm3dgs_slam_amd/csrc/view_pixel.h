@@ -1,14 +1,15 @@
-// What pointcloud.hip and tsdf.hip share about one posed RGB-D view: the pixel validity test, the world->camera pose in double, and the
-// colour byte of a float32 channel.  One statement each, so the point cloud and the mesh agree on which pixels are surface.
+// What pointcloud.hip and tsdf.hip share about one posed RGB-D view: the pixel validity test, the world->camera pose in double (also
+// compact.hip's, for pose prediction), and the colour byte of a float32 channel.  One statement each, so cloud and mesh agree on which pixels are surface.
 #pragma once
 #include <math.h>
 #include "mm3dgs_common.h"
 
-struct PcRigid { double R[3][3], t[3]; };
+struct Rigid { double R[3][3], t[3]; };      // [R | t; 0 1]
 
-__device__ __forceinline__ PcRigid pc_rigid(const float* __restrict__ pose) {
+// world->camera 7-vector (qw,qx,qy,qz,tx,ty,tz): normalised quaternion -> R (utils/pose_utils.py:240-271,352-368), no contraction
+__device__ __forceinline__ Rigid rigid_from_pose(const float* __restrict__ pose) {
 #pragma clang fp contract(off)
-  PcRigid o;
+  Rigid o;
   double w = pose[0], x = pose[1], y = pose[2], z = pose[3];
   const double n = sqrt(w * w + x * x + y * y + z * z);
   w /= n; x /= n; y /= n; z /= n;

@@ -1,0 +1,201 @@
+#!/usr/bin/env python
+"""sha256 of every output the kernels outside the tracking and mapping loops write (compact, align, eval, pointcloud, tsdf, geometry),
+over the case lists the GPU tests define, as one JSON file -- to compare two builds of the library bit for bit:
+
+    MM3DGS_LIB=$PWD/mm3dgs_slam_amd/csrc/variants/libmm3dgs_hip_parent.so python tools/offloop_digest.py parent.json
+    python tools/offloop_digest.py new.json          # each in a fresh process; then compare the two files
+
+The drivers are the tests' own (tests/test_gpu_*.py: caller-owned buffers between guard words, the statement's checks included), so a
+digest exists only for a call the tests accept.  The one output whose order the kernels leave to atomics, the within-cell order of
+mm3dgs_nn_grid_build's records, is sorted by row index inside each cell before it is hashed, as test_gpu_geometry.py compares it."""
+import hashlib
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np      # noqa: E402
+import torch            # noqa: E402
+
+DEV = "cuda:0"
+OUT = {}
+
+
+def put(key, *arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(a if isinstance(a, bytes) else np.ascontiguousarray(a.cpu().numpy() if torch.is_tensor(a) else a).tobytes())
+    assert key not in OUT, key
+    OUT[key] = h.hexdigest()
+
+
+def surgery():
+    import ctypes as C
+    from tests import surgery_cases as cases, surgery_ref as ref, test_gpu_surgery as t
+    lib, th = t._lib(), (cases.MIN_OPACITY, cases.MAX_SCALE, cases.MAX_SCREEN)
+    for n in cases.SIZES:
+        for use_radii in (True, False):
+            opacity, scales, radii, placed = cases.prune_rows(n)
+            r = radii if use_radii else None
+            ref.move_prune_rows(opacity, scales, r, ref.prune_keep(opacity, scales, r, *th)[1], placed, *th)
+            src = [t.Source(opacity), t.Source(scales), t.Source(radii)]
+            k, counter = t.Guarded(n, 0xCD), t.Guarded(4, np.array([1000], np.uint32))
+            assert t._prune_call(n, src[0], src[1], src[2] if use_radii else None, k, counter) == 0
+            t._sync()
+            put(f"prune {n} radii {use_radii}", k.read(np.uint8), counter.read(np.uint32))
+        for pattern in cases.KEEP_PATTERNS:
+            widths = (1, 3, 0, 4) if n >= cases.LARGE else (1, 3, 0, 4, 45)
+            arrays = [a if a.shape[1] else None for a in cases.row_arrays(n, widths)]
+            out, total = t._compact(n, cases.keep_bytes(n, pattern), arrays, 0xCD)      # (the plan's words are checked exactly in there)
+            put(f"compact {n} {pattern}", np.uint32(total), *out)
+    for H, W in cases.SEED_SHAPES:
+        for row0, n_rest in ((0, 0), (5, 15)):
+            c = cases.seed_case(H, W)
+            src = {k: t.Source(c[k]) for k in ("color", "depth", "keep", "pose")}
+            work, n = t._checked_plan(H * W, src["keep"], c["keep"])
+            out, so = {}, t.lib_mod().Mm3dgsSeedOutputs()
+            for name, w in dict(t.SEED_WIDTHS, f_rest=3 * n_rest).items():
+                out[name] = t.Guarded((row0 + n) * w * 4, 0xCD)
+                setattr(so, name, out[name].ptr)
+            assert lib.mm3dgs_seed_gaussians(H, W, t._ptr(src["color"]), t._ptr(src["depth"]), t._ptr(src["keep"]), t._ptr(work), t._ptr(src["pose"]), c["fx"],
+                                             c["fy"], c["cx"], c["cy"], row0, C.byref(so), n_rest, t._stream()) == 0
+            t._sync()
+            put(f"seed {H}x{W} row0 {row0} n_rest {n_rest}", *[g.read(np.uint8) for g in out.values()])
+    for P, mix, N in cases.DENSIFY_RUNS:
+        run = cases.densify_run(P, mix)
+        arrays, grad_accum, denom, placed = cases.densify_rows(P, mix, n_rest=run["n_rest"])
+        cls, _ = t._settled_classes(P, grad_accum, denom, arrays["scaling"], placed)
+        moments = cases.densify_moments(arrays, [k for k in run["moment_groups"] if arrays[k].shape[1]])
+        got = t._densify(P, arrays, moments, grad_accum, denom, cls, N, run["with_parent"], 0xCD)[0]      # (class bytes and plan words checked in there)
+        put(f"densify {P} {mix} N {N}", *[got[k] for k in sorted(got)])
+    for H, W in cases.COVIS_SHAPES:
+        for view in cases.COVIS_VIEWS:
+            for plain in (False, True):
+                c = cases.covis_case(H, W, view, plain=plain)
+                a = [c[k] for k in ("depth", "sil", "kf_pose", "cur_pose", "fx", "fy", "cx", "cy")]
+                ref.move_covisibility_pixels(c["sil"], ref.covisibility(*a)[1], c["placed"])
+                src, counts = [t.Source(c[k]) for k in ("depth", "sil", "kf_pose", "cur_pose")], t.Guarded(8, 0xCD)
+                assert t._covis_call(H, W, *src, c, counts) == 0
+                t._sync()
+                put(f"covisibility {H}x{W} {view} plain {plain}", counts.read(np.uint32))
+
+
+def pointcloud():
+    from tests import pointcloud_cases as cases, test_gpu_pointcloud as t
+
+    def run(key, H, W, views, voxel=0.0):
+        cloud = t.Cloud(H, W, len(views) * H * W, voxel=voxel, work_fill=0xFF)
+        for v in views:
+            cloud.add(t.to_dev(v))
+        put(key, *cloud.read())
+
+    for H, W in cases.SHAPES:
+        for pattern in cases.PATTERNS:
+            run(f"cloud {H}x{W} {pattern}", H, W, [cases.view(H, W, pattern)])
+    for H, W in ((17, 33), (520, 520)):
+        v = cases.plane_view(H, W)
+        for voxel in (1000.0, 2.0 ** -16, 3.3 * cases.footprint(v)):
+            run(f"cloud thinned {H}x{W} voxel {voxel:.6g}", H, W, [v], voxel)
+    for H, W in ((17, 33), (48, 64)):
+        vs = t._stream_views(H, W)
+        run(f"cloud stream {H}x{W}", H, W, vs, 3.3 * cases.footprint(vs[0]))
+
+
+def mesh():
+    from tests import mesh_cases as cases, test_gpu_mesh as t
+    for dims, hw, pattern, n_views in t.INTEGRATE_CASES:
+        case = cases.integrate_case(dims, hw[0], hw[1], pattern, n_views)
+        vol = t.Volume(dims)
+        for v in case["views"]:
+            assert vol.integrate(t.to_dev(v), case) == 0
+        put(f"integrate {dims} {hw} {pattern} x{n_views}", *vol.read())
+    for dims in cases.MESH_SHAPES:
+        for kind in cases.KINDS:
+            vol = cases.analytic_volume(kind, dims)
+            dv = t.Volume(dims, vol["tsdf_w"], vol["rgb_w"])
+            m = t.Mesher(dv, vol["origin"], vol["voxel"], 0, 0)
+            assert m.plan() == 0
+            V, T = (int(x) for x in m.counters.cpu()[:2])
+            m = t.Mesher(dv, vol["origin"], vol["voxel"], V, T, work_fill=0xFF)
+            assert m.plan() == 0 and m.emit() == 0
+            rows, tris, c = m.read()
+            put(f"mesh {dims} {kind}", rows[:V], tris[:T], c)
+
+
+def geometry():
+    from tests import geometry_cases as cases, test_gpu_geometry as t
+
+    def nn(key, case):
+        g = t.NN(case, 0xFF)
+        assert g.build() == 0 and g.query() == 0
+        dist, row, counters, cell_start, srt = g.read()
+        cell = np.searchsorted(cell_start, np.arange(len(srt)), "right")      # the within-cell order is the atomics': by row index instead
+        put(key, dist, row, counters, cell_start, srt[np.lexsort((srt[:, 3], cell))])
+
+    for n_ref in cases.SIZES:
+        for n_q in cases.SIZES:
+            nn(f"nn sized {n_ref} x {n_q}", cases.sized_case(n_ref, n_q))
+    for name, case in cases.nn_cases().items():
+        nn(f"nn {name}", case)
+
+    def sample(key, v, tris, density, seed):
+        s = t.Sampler(v, tris, density, seed, 0)
+        assert s.plan() == 0
+        s = t.Sampler(v, tris, density, seed, int(s.counters.cpu()[0]), 0xFF)
+        assert s.plan() == 0 and s.emit() == 0
+        put(key, *s.read())
+
+    for m in (1, 255, 256, 257):
+        sample(f"sampler random {m}", *cases.random_mesh(m, seed=m), 150.0, m)
+    sample("sampler 262400 tiny triangles", *cases.tiny_mesh(), 1e4, 4)
+    for where in ("first", "last"):
+        sample(f"sampler wall {where}", *cases.wall_mesh(where), 100.0, 6)
+    sample("sampler degenerate", *cases.degenerate_mesh()[:2], 100.0, 2)
+
+
+def evaluation():
+    from tests import eval_cases as ec, test_gpu_eval as t
+    for case in ec.CASES:
+        put("eval %s %dx%d" % case, t.score(*(x.to(DEV) for x in ec.inputs(*case)), fill=float("nan")))
+
+
+def depth_align():
+    from tests import depth_align_ref as R, test_gpu_depth_align as t
+    for shape in R.SHAPES:
+        est, depth, sil = R.make_inputs(*shape)
+        put("align %dx%d" % shape, *t._run(est, depth, sil, planes=shape in R.ODD_SHAPES))
+    est, depth, _ = R.make_inputs(17, 23)
+    put("align 17x23 without a silhouette", *t._run(est, depth, None))
+
+
+def pose_prediction():
+    from mm3dgs_slam_amd.tracker import Tracker
+    from tests import imu_cases, test_gpu_imu_predict as t
+    cs = imu_cases.random_cases()
+    for k, c in enumerate(cs):
+        put(f"imu case {k}", t._kernel(c["p1"], c["p2"], c["imu6"], c["c2i"], c["dt_cam"], c["dt_imu"]))
+        put(f"const vel case {k}", Tracker._predict_const_vel_device(t._dev(c["p1"]), t._dev(c["p2"])))
+    for k, c in enumerate(cs[:8]):
+        put(f"imu n = 0, case {k}", t._kernel(c["p1"], c["p2"], np.zeros((0, 6)), c["c2i"], c["dt_cam"], c["dt_imu"]))
+        put(f"imu pose_m2 == pose_m1, case {k}", t._kernel(c["p1"], c["p1"], c["imu6"], c["c2i"], 1.0, c["dt_imu"]))
+        put(f"imu identity c2i, case {k}", t._kernel(c["p1"], c["p2"], c["imu6"], np.eye(4), c["dt_cam"], c["dt_imu"]))
+
+
+def main():
+    from mm3dgs_slam_amd import _lib
+    for stage in (surgery, pointcloud, mesh, geometry, evaluation, depth_align, pose_prediction):
+        t0 = time.time()
+        before = len(OUT)
+        stage()
+        torch.cuda.synchronize()
+        print(f"{stage.__name__}: {len(OUT) - before} digests, {time.time() - t0:.1f} s", flush=True)
+    with open(sys.argv[1], "w") as f:
+        json.dump(OUT, f, indent=0, sort_keys=True)
+    print(f"{len(OUT)} digests of {_lib.LIB_PATH} -> {sys.argv[1]}")
+
+
+if __name__ == "__main__":
+    main()
