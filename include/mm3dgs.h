@@ -642,6 +642,40 @@ int mm3dgs_mesh_sample_plan(uint64_t n_vertices, const void* vrows /*[n_vertices
 int mm3dgs_mesh_sample_emit(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed,
                             const void* work, void* rows /*[cap] x 16 bytes*/, uint64_t cap, uint64_t* counters /*[8], device*/, void* stream);
 
+/* ---- visibility culling: the rows of a point set that the views of a run could have seen ------------------------------------------------
+ * Host statement: mm3dgs_slam_amd/cull.py (cull_host).  rows: [n] x 16 bytes {float x, y, z; uint32 rgba} on the device, 16-byte aligned;
+ * seen: uint32 [n] and counters: uint64 [8] on the device, both zeroed by the caller before the first view.
+ *
+ * mm3dgs_cull_mark_view: one launch per view, one lane per row.  pose: world->camera (qw,qx,qy,qz,tx,ty,tz) on the device, normalised by
+ * the kernel; depth_or_null: float32 [H,W] on the device.  A row is seen by the view when, every operation in double from the widened
+ * float32 inputs, no fused multiply-add, p_c[k] = R[k][0] x + R[k][1] y + R[k][2] z + t[k] summed left to right:
+ *   1. its three coordinates are finite (else it is skipped: seen by no view);
+ *   2. z_c > z_near (a NaN fails);  3. z_far == 0 or z_c <= z_far;
+ *   4. fu = floor(fx x_c / z_c + cx + 0.5) and fv likewise lie in [0, W) x [0, H);
+ *   5. with a depth image: d = depth[fv][fu] satisfies d > 0, d < inf, and d <= depth_max when depth_max > 0 (strict float32 tests, a
+ *      NaN fails: a hole sees nothing), and z_c <= (double)d + eps.
+ * Then seen[i] += 1 (plain load and store: each row belongs to one lane, views are ordered on the stream); a row that is not seen touches
+ * neither the depth image nor seen.  counters[0] += 1 (views), counters[1] += the rows this view sees, one integer atomic per workgroup.
+ * Nothing else is written.  n = 0 counts the view.
+ *
+ * mm3dgs_cull_select: a row is kept when it is finite and seen[i] >= min_views (min_views >= 1).  Kept rows go to out_rows in their
+ * original order, index_or_null[k] (uint32) = the original row of kept row k; a kept row at or beyond cap is not written.  Per-256 counts,
+ * one 1024-wide scan, a scatter by rank: no atomic decides a position, the same inputs give the same bytes on every call.  counters [2]
+ * kept, [3] written = min(kept, cap), [4] dropped for lack of room, [5] skipped rows (not finite), [6] [7] 0; [0] [1] are left as they are.
+ * work: mm3dgs_cull_work_bytes(n) bytes, 8-byte aligned, contents irrelevant before and after.  Nothing outside out_rows[0:written],
+ * index[0:written], counters[0:8] and work is written.  n = 0 launches nothing but the counter update.  No host synchronisation.
+ *
+ * -1 (nothing is launched, nothing is written): H or W not positive or H W above 2^28; n above 2^30; fx, fy not finite or 0; cx, cy not
+ * finite; z_near, z_far or eps negative or not finite; depth_max NaN; min_views 0; cap above 2^31; a NULL pose, counters or work; NULL
+ * rows or seen with n > 0; NULL out_rows with n > 0 and cap > 0; rows or out_rows not 16-byte aligned, counters or work not 8-byte
+ * aligned, seen, index, depth or pose not 4-byte aligned.  mm3dgs_cull_work_bytes returns 0 for n above 2^30. */
+int mm3dgs_cull_mark_view(int H, int W, double fx, double fy, double cx, double cy, const float* pose /*[7], device*/, const float* depth_or_null /*[H,W]*/,
+                          float depth_max, double z_near, double z_far, double eps, uint64_t n, const void* rows /*[n] x 16 bytes*/, uint32_t* seen /*[n]*/,
+                          uint64_t* counters /*[8], device*/, void* stream);
+size_t mm3dgs_cull_work_bytes(uint64_t n);
+int mm3dgs_cull_select(uint64_t n, const void* rows /*[n] x 16 bytes*/, const uint32_t* seen /*[n]*/, uint32_t min_views, void* out_rows /*[cap] x 16 bytes*/,
+                       uint64_t cap, uint32_t* index_or_null /*[cap]*/, void* work, uint64_t* counters /*[8], device*/, void* stream);
+
 /* ---- frame ingest: raw sensor bytes -> the two images the SLAM loops consume, in one launch ------------------------------------------
  * rgb: uint8 interleaved [Hs,Ws,3] on the device, any byte alignment; depth_or_null: uint16 [Hs,Ws], 2-byte aligned.  out_color [3,H,W]
  * float32 in [0,1]; out_depth_or_null [H,W] float32 in metres, required iff depth is given (a colour-only call passes NULL for both).
@@ -779,7 +813,8 @@ const char* mm3dgs_last_error(void);
         a truncated signed distance volume, marching tetrahedra over it); mm3dgs_nn_grid_work_bytes / mm3dgs_nn_grid_build /
         mm3dgs_nn_query_work_bytes / mm3dgs_nn_query / mm3dgs_mesh_sample_work_bytes / mm3dgs_mesh_sample_plan / mm3dgs_mesh_sample_emit
         (geometry scores of an export against a reference: exact truncated nearest-neighbour distances through a uniform grid, and
-        area-uniform samples of a triangle mesh); a caller that needs them looks the symbols up */
+        area-uniform samples of a triangle mesh); mm3dgs_cull_mark_view / mm3dgs_cull_work_bytes / mm3dgs_cull_select (the rows of a
+        point set that the views of a run could have seen, for the geometry scores); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

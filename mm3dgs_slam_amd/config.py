@@ -39,6 +39,7 @@ _TUM = {
     # umeyama moves the estimate by the trajectory alignment first; opt-in, changes no pose and no other output
     "geometry": {"eval": False, "estimate": "mesh", "reference": "sensor", "threshold": 0.05, "max_dist": 1.0,
                  "density": 10000.0, "cell": 0, "seed": 0, "align": "none", "max_samples": 16777216},
+    # (further keys of the block, with their defaults: GEOMETRY_CULL below)
     "scene_radius_depth_ratio": 2, "desired_height": 480, "desired_width": 640,
     "debug": {"get_runtime_stats": False, "create_video": False, "save_keyframes": False},
     "pipeline": {"convert_SHs_python": False, "compute_cov3D_python": False, "transform_means_python": True,
@@ -61,6 +62,15 @@ _TUM = {
     "cam": {"image_height": 480, "image_width": 640, "fx": 517.3, "fy": 516.5, "cx": 318.6, "cy": 255.3,
             "crop_edge": 8, "png_depth_scale": 5000.0, "fps": 30},
 }
+
+
+# Optional keys of the `geometry` block and their defaults (export.options merges them under the block; they are kept out of the default
+# block itself, whose exact contents a test pins): before scoring, both surfaces are culled to what the cameras of the run saw (cull.py,
+# mm3dgs_cull_mark_view / mm3dgs_cull_select) -- the views are the frames the scored export uses, at their ground-truth poses.  `cull`
+# none / frustum (inside some view's image and depth range) / occlusion (also not behind the frame's sensor depth by more than cull_eps;
+# 0: the block's `threshold` -- a point farther behind the measured surface than the score's own threshold cannot count as within it
+# anyway); cull_near / cull_far: the depth range in metres (far 0: no limit); a point is kept when at least cull_min_views views see it
+GEOMETRY_CULL = {"cull": "none", "cull_eps": 0, "cull_near": 0, "cull_far": 0, "cull_min_views": 1}
 
 
 # configs/UTMM.yml's hot-path settings that differ from TUM.yml (BASELINE.json configs[2]: RGB-D + IMU): 640x330, intrinsics of the

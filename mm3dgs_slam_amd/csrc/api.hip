@@ -956,6 +956,45 @@ int mm3dgs_mesh_sample_emit(uint64_t n_vertices, const void* vrows, uint64_t m, 
   return check_launch("mesh_sample_emit");
 }
 
+// ---- visibility culling (cull.hip) -------------------------------------------------------------------------------------------------
+size_t mm3dgs_cull_work_bytes(uint64_t n) { return n <= NN_MAX_ROWS ? cull_work_bytes(n) : 0; }
+
+int mm3dgs_cull_mark_view(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* depth_or_null, float depth_max,
+                          double z_near, double z_far, double eps, uint64_t n, const void* rows, uint32_t* seen, uint64_t* counters, void* stream) {
+  if (H <= 0 || W <= 0) return fail(-1, "cull_mark_view: H = %d, W = %d (both must be positive)", H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "cull_mark_view: %d x %d has more than 2^28 pixels", H, W);
+  if (n > NN_MAX_ROWS) return fail(-1, "cull_mark_view: n = %llu (at most 2^30)", (unsigned long long)n);
+  if (!pose || !counters || (n && (!rows || !seen))) return fail(-1, "cull_mark_view: NULL argument (pose and counters are required; rows and seen unless n is 0)");
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "cull_mark_view: fx = %g, fy = %g (finite, not 0)", fx, fy);
+  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "cull_mark_view: cx = %g, cy = %g (must be finite)", cx, cy);
+  if (!(z_near >= 0.0) || !isfinite(z_near) || !(z_far >= 0.0) || !isfinite(z_far) || !(eps >= 0.0) || !isfinite(eps))
+    return fail(-1, "cull_mark_view: near = %g, far = %g, eps = %g (each must be finite and not negative)", z_near, z_far, eps);
+  if (!(depth_max == depth_max)) return fail(-1, "cull_mark_view: depth_max is not a number");
+  if ((uintptr_t)rows & 15) return fail(-1, "cull_mark_view: rows must be 16-byte aligned");
+  if ((uintptr_t)counters & 7) return fail(-1, "cull_mark_view: counters must be 8-byte aligned");
+  if (((uintptr_t)seen | (uintptr_t)depth_or_null | (uintptr_t)pose) & 3) return fail(-1, "cull_mark_view: seen, the depth image and the pose must be 4-byte aligned");
+  CullView v;
+  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
+  v.pose = pose; v.depth = depth_or_null; v.depth_max = depth_max;
+  v.z_near = z_near; v.z_far = z_far; v.eps = eps;
+  launch_cull_mark_view(v, n, rows, seen, counters, (hipStream_t)stream);
+  return check_launch("cull_mark_view");
+}
+
+int mm3dgs_cull_select(uint64_t n, const void* rows, const uint32_t* seen, uint32_t min_views, void* out_rows, uint64_t cap, uint32_t* index_or_null,
+                       void* work, uint64_t* counters, void* stream) {
+  if (n > NN_MAX_ROWS) return fail(-1, "cull_select: n = %llu (at most 2^30)", (unsigned long long)n);
+  if (min_views < 1) return fail(-1, "cull_select: min_views = 0 (at least 1)");
+  if (cap > ((uint64_t)1 << 31)) return fail(-1, "cull_select: cap = %llu (at most 2^31)", (unsigned long long)cap);
+  if (!work || !counters || (n && (!rows || !seen)) || (n && cap && !out_rows))
+    return fail(-1, "cull_select: NULL argument (work and counters are required; rows and seen unless n is 0; out_rows unless n or cap is 0)");
+  if (((uintptr_t)rows | (uintptr_t)out_rows) & 15) return fail(-1, "cull_select: rows and out_rows must be 16-byte aligned");
+  if (((uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "cull_select: work and counters must be 8-byte aligned");
+  if (((uintptr_t)seen | (uintptr_t)index_or_null) & 3) return fail(-1, "cull_select: seen and index must be 4-byte aligned");
+  launch_cull_select(n, rows, seen, min_views, out_rows, cap, index_or_null, work, counters, (hipStream_t)stream);
+  return check_launch("cull_select");
+}
+
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
                         float* out_color, float* out_depth_or_null, void* stream) {
   if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);

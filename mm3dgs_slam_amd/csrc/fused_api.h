@@ -168,6 +168,20 @@ void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t 
 size_t mesh_sample_work_bytes(uint64_t m);
 void launch_mesh_sample_plan(const MeshSample& ms, void* work, uint64_t* counters, hipStream_t s);
 void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint64_t cap, uint64_t* counters, hipStream_t s);
+// visibility culling (cull.hip): one view marks the rows (16 bytes each) it sees in seen (uint32 per row, += 1), select keeps the rows with
+// seen >= min_views in order; depth NULL = frustum only; work = the buffer of cull_work_bytes(n); n <= 2^30, near / far / eps >= 0 and
+// finite, H W <= 2^28, as the entry points have checked
+struct CullView {
+  int H, W;
+  double fx, fy, cx, cy;
+  const float* pose; const float* depth;
+  float depth_max;
+  double z_near, z_far, eps;
+};
+size_t cull_work_bytes(uint64_t n);
+void launch_cull_mark_view(const CullView& v, uint64_t n, const void* rows, uint32_t* seen, uint64_t* counters, hipStream_t s);
+void launch_cull_select(uint64_t n, const void* rows, const uint32_t* seen, uint32_t min_views, void* out_rows, uint64_t cap, uint32_t* index, void* work,
+                        uint64_t* counters, hipStream_t s);
 // frame ingest (ingest.hip): raw uint8 RGB [Hs,Ws,3] + uint16 depth [Hs,Ws] -> colour [3,H,W] in [0,1] + depth [H,W] in metres, one
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,

@@ -7,8 +7,8 @@ import os
 import numpy as np
 import torch
 
-from . import geometry as geo, mesh as ms, pointcloud as pc
-from .config import _TUM
+from . import cull as cl, geometry as geo, mesh as ms, pointcloud as pc
+from .config import _TUM, GEOMETRY_CULL
 
 
 def options(cfg, block, **overrides):
@@ -17,12 +17,21 @@ def options(cfg, block, **overrides):
     `estimate`, `reference` and `align` of the evaluation."""
     opt = dict(_TUM[block], **(cfg.get(block) or {}))
     if block == "geometry":
+        opt = dict(GEOMETRY_CULL, **opt)
         opt.update((k, v) for k, v in overrides.items() if v is not None)
-        opt.update(estimate=str(opt["estimate"]), reference=str(opt["reference"]), align=str(opt["align"] or "none").lower())
+        opt.update(estimate=str(opt["estimate"]), reference=str(opt["reference"]), align=str(opt["align"] or "none").lower(),
+                   cull=str(opt["cull"] or "none").lower())
         if opt["estimate"] not in ("mesh", "pointcloud"):
             raise ValueError(f"geometry.estimate = {opt['estimate']!r} (mesh / pointcloud)")
         if opt["align"] not in ("none", "horn", "umeyama"):
             raise ValueError(f"geometry.align = {opt['align']!r} (none / horn / umeyama)")
+        if opt["cull"] not in cl.MODES:
+            raise ValueError(f"geometry.cull = {opt['cull']!r} (none / frustum / occlusion)")
+        try:
+            near, far, eps, min_views = cl.check_options(opt["cull_near"] or 0, opt["cull_far"] or 0, opt["cull_eps"] or 0, opt["cull_min_views"])
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"geometry.cull_near / cull_far / cull_eps / cull_min_views: {e}") from None
+        opt.update(cull_near=near, cull_far=far, cull_eps=eps if eps > 0 else float(opt["threshold"]), cull_min_views=min_views)
         return opt
     opt["every"] = opt["every"] or cfg["mapping"]["kf_every"]
     opt.update((k, v) for k, v in overrides.items() if v is not None)
@@ -74,6 +83,28 @@ def gt_poses(slam):
     if missing:
         raise ValueError(f'geometry.reference "sensor": no ground-truth pose for frame(s) {missing[:8]} (neither from the run nor in results.npz)')
     return poses
+
+
+def cull_views(slam, opt, block):
+    """The ``cull=`` argument of the geometry evaluation (None with `cull: none`): one view per frame the scored export uses (`idx % every
+    == 0` with an estimated pose), placed at its ground-truth pose -- the reference lives in the ground-truth frame, and the estimate has
+    been moved there by `geometry.align`.  "occlusion": each view carries the frame's sensor depth (ValueError naming the frame without
+    one; depths beyond the export block's `max_depth` see nothing); "frustum": no frame is read.  `opt`, `block`: `options` of the
+    `geometry` block and of the estimate's."""
+    if opt["cull"] == "none":
+        return None
+    poses, out = gt_poses(slam), []
+    for idx in range(len(slam.seq)):
+        if slam.estimate_pose_list[idx] is None or idx % block["every"] != 0:
+            continue
+        depth = None
+        if opt["cull"] == "occlusion":
+            depth = slam.seq[idx][1]
+            if depth is None:
+                raise ValueError(f'geometry.cull "occlusion": frame {idx} has no sensor depth')
+        out.append((depth, poses[idx].detach()))
+    return cl.spec(out, int(slam.cfg["desired_height"]), int(slam.cfg["desired_width"]), slam.cfg["cam"], near=opt["cull_near"], far=opt["cull_far"],
+                   eps=opt["cull_eps"], min_views=opt["cull_min_views"], depth_max=float(block["max_depth"]))
 
 
 def cloud_geometry(slam, opt, poses=None):
@@ -170,7 +201,8 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     `reference` "sensor": the same frames' own colour and sensor depth fused by the same builder at the GROUND-TRUTH poses -- what a
     perfect tracker and map would have exported (ValueError without sensor depth) --, or the path of a PLY file: a point cloud or, with a
     face element, a mesh (`mesh.read_surface_ply`).  Meshes on either side are sampled at `geometry.density` samples per m^2;
-    `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first.  Writes `path/metrics.json`,
+    `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first; `geometry.cull` frustum / occlusion then
+    removes from both point sets what no camera of the run could have seen (`cull_views`, cull.py; metrics.json gains a `cull` block).  Writes `path/metrics.json`,
     `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); arguments left None come from the `geometry` config block.  HIP
     kernels and one read-back of the [2,8] table on a GPU, the host statement on `device: cpu`.  Touches no pose and no other output.
     Returns the comparison with the paths."""
@@ -188,8 +220,9 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
         move = lambda rows: geo.align_rows(rows, slam.estimate_pose_list[:len(slam.seq)], gt_poses(slam), align)
         est = (move(est[0]), est[1]) if estimate == "mesh" else move(est)
     ref = build(dict(block, source="sensor"), gt_poses(slam)) if reference == "sensor" else ms.read_surface_ply(reference)
+    culled = {} if opt["cull"] == "none" else {"cull": cull_views(slam, opt, block)}
     result = geo.compare(est, ref, device=slam.cfg["device"], threshold=float(opt["threshold"]), max_dist=float(opt["max_dist"]),
-                         cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]))
+                         cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]), **culled)
     path = os.path.join(slam.cfg["outputdir"], "geometry") if path is None else path
     result["files"] = geo.write_outputs(path, result, {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]),
                                                        "seed": int(opt["seed"])})

@@ -34,7 +34,12 @@ corner is not finite, or A is 0 or not finite.  Sample j of triangle t: ``r1 = h
 corner with the largest weight among ``(1 - r1 - r2, r1, r2)``, lowest index on a tie (exact comparisons: the weights are multiples of
 2^-32).  Samples are ordered by triangle, then j.  ``h(seed, t, k) = mix32(mix32(mix32(seed ^ 0x9e3779b9) + t) + k)`` in uint32
 arithmetic, ``mix32(x)``: ``x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16`` (``ms_mix`` / ``ms_hash`` in the
-kernel file state the same one)."""
+kernel file state the same one).
+
+**Culling** (``cull=``, off by default; ``cull.py`` states the rule).  A reference file covers the whole scene, a run sees part of it: with
+the run's views given, both point sets are reduced -- after sampling, before the search -- to the rows at least ``min_views`` views could
+have seen (inside a view's frustum; with depth images also not behind the surface the view measured), and every figure, array and file is
+about the kept rows."""
 from __future__ import annotations
 
 import json
@@ -180,8 +185,30 @@ def nn_brute_host(query, reference, max_dist):
     return out, cl, d
 
 
-def direction_row(dist, clamped, threshold):
-    """The eight figures of one direction from the stored float32 distances (NaN = skipped) and the clamped mask."""
+def kernel_order_sum(values):
+    """The float64 sum of one value per query (0 for a skipped one) in mm3dgs_nn_query's fixed order: a balanced binary tree over the 256
+    lanes of a workgroup (the wave's DPP sum, then (w0 + w1) + (w2 + w3)); then ng_finish_kernel: lane t adds the workgroups t, t + 256,
+    ... in order, and the 256 lanes are added in order.  Padding lanes add 0.0, which changes no sum."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    nb = max((len(v) + 255) // 256, 1)
+    a = np.zeros(nb * 256, dtype=np.float64)
+    a[:len(v)] = v
+    a = a.reshape(nb, 256)
+    while a.shape[1] > 1:
+        a = a[:, 0::2] + a[:, 1::2]
+    rounds = np.zeros(((nb + 255) // 256) * 256, dtype=np.float64)
+    rounds[:nb] = a[:, 0]
+    lanes = np.zeros(256, dtype=np.float64)
+    for chunk in rounds.reshape(-1, 256):
+        lanes = lanes + chunk
+    return float(np.add.accumulate(lanes)[-1])
+
+
+def direction_row(dist, clamped, threshold, sum_order="numpy"):
+    """The eight figures of one direction from the stored float32 distances (NaN = skipped) and the clamped mask.  `sum_order` "kernel"
+    adds the distances and their squares in the kernels' order (``kernel_order_sum``): the mean and the rms then carry the device's
+    roundings, and a device table can be held to this one bit for bit; "numpy" (the default, what every output of the host path uses)
+    differs from it in the last bits."""
     dist = np.asarray(dist, dtype=np.float32)
     scored = ~np.isnan(dist)
     d = dist[scored].astype(np.float64)
@@ -190,6 +217,9 @@ def direction_row(dist, clamped, threshold):
     row[0] = n
     if n:
         row[1], row[2], row[3] = d.sum() / n, np.sqrt((d * d).sum() / n), d.max()
+        if sum_order == "kernel":
+            z = np.where(scored, dist, np.float32(0)).astype(np.float64)
+            row[1], row[2] = kernel_order_sum(z) / n, np.sqrt(kernel_order_sum(z * z) / n)
         row[4] = float((dist[scored] <= np.float32(threshold)).sum()) / n
     row[5] = float(np.asarray(clamped, dtype=bool)[scored].sum())
     row[6] = float((~scored).sum())
@@ -365,10 +395,12 @@ def _is_mesh(side):
     return isinstance(side, (tuple, list)) and len(side) == 2
 
 
-def compare_host(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24):
-    """The comparison of the module docstring on the host.  Each side is rows [n,4] int32 or (vertex rows, triangles).  Returns a dict:
+def compare_host(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24, cull=None, sum_order="numpy"):
+    """The comparison of the module docstring on the host (`sum_order`: ``direction_row``).  Each side is rows [n,4] int32 or (vertex rows, triangles).  Returns a dict:
     the derived figures, table [2,8], cells (the cell each grid used), counters, n_estimate, n_reference, and the arrays estimate_rows,
-    reference_rows, dist_estimate, dist_reference."""
+    reference_rows, dist_estimate, dist_reference.  `cull` (``cull.spec``: the run's views plus the options; None: off) removes from both
+    point sets, after sampling and before the search, what no view could have seen: everything returned is then about the kept points,
+    and the result gains `cull` (``cull.summary``) and estimate_index / reference_index (the original row of every kept row)."""
     cell = float(cell) if cell and float(cell) > 0 else float(threshold)
     sets, counters = [], {}
     for name, side in (("estimate", estimate), ("reference", reference)):
@@ -380,16 +412,22 @@ def compare_host(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, dens
         else:
             rows = as_np(side, np.int32).reshape(-1, 4)
         sets.append(rows)
+    culled = None
+    if cull is not None:
+        from . import cull as cl
+        (sets[0], ie, ce), (sets[1], ir, cr) = cl.apply_host(sets[0], cull), cl.apply_host(sets[1], cull)
+        culled = (cl.summary(cull, ce, cr), ie, ir)
     d_er, i_er = nn_distances_host(sets[0], sets[1], cell, max_dist)
     d_re, i_re = nn_distances_host(sets[1], sets[0], cell, max_dist)
-    table = np.stack([direction_row(d_er, i_er["clamped"], threshold), direction_row(d_re, i_re["clamped"], threshold)])
+    table = np.stack([direction_row(d_er, i_er["clamped"], threshold, sum_order), direction_row(d_re, i_re["clamped"], threshold, sum_order)])
     counters.update(reference_skipped=i_er["ref_skipped"], estimate_skipped=i_re["ref_skipped"])
-    return _result(table, (i_er["cell"], i_re["cell"]), counters, sets, (d_er, d_re), threshold, max_dist)
+    return _result(table, (i_er["cell"], i_re["cell"]), counters, sets, (d_er, d_re), threshold, max_dist, culled)
 
 
-def compare_device(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24, device="cuda:0"):
+def compare_device(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24, device="cuda:0", cull=None):
     """The same comparison on the device: meshes sampled by the kernels, one GeometryScorer per direction, the [2,8] table read back once;
-    the rows and distances stay device tensors."""
+    the rows and distances stay device tensors.  `cull` as in ``compare_host``: one ``cull.Culler`` per side (one mm3dgs_cull_mark_view
+    per view, one mm3dgs_cull_select and one read-back of its counters)."""
     cell = float(cell) if cell and float(cell) > 0 else float(threshold)
     sets, counters = [], {}
     for name, side in (("estimate", estimate), ("reference", reference)):
@@ -398,17 +436,25 @@ def compare_device(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, de
         else:
             rows = torch.as_tensor(side, device=device).to(torch.int32).reshape(-1, 4).contiguous()
         sets.append(rows)
+    culled = None
+    if cull is not None:
+        from . import cull as cl
+        views = cl.device_views(cull, device)
+        (sets[0], ie, ce), (sets[1], ir, cr) = cl.apply_device(sets[0], cull, views, device), cl.apply_device(sets[1], cull, views, device)
+        culled = (cl.summary(cull, ce, cr), ie, ir)
     on_ref = GeometryScorer(sets[1], cell, max_dist, threshold, device)
     on_est = GeometryScorer(sets[0], cell, max_dist, threshold, device)
     table = torch.zeros(2, 8, dtype=torch.float64, device=device)
     d_er, _ = on_ref.query(sets[0], row=table[0])
     d_re, _ = on_est.query(sets[1], row=table[1])
     counters.update(reference_skipped=on_ref.ref_skipped, estimate_skipped=on_est.ref_skipped)
-    return _result(table.cpu().numpy(), (on_ref.cell, on_est.cell), counters, sets, (d_er, d_re), threshold, max_dist)      # the one read-back
+    return _result(table.cpu().numpy(), (on_ref.cell, on_est.cell), counters, sets, (d_er, d_re), threshold, max_dist, culled)      # the one read-back
 
 
-def _result(table, cells, counters, sets, dists, threshold, max_dist):
+def _result(table, cells, counters, sets, dists, threshold, max_dist, culled=None):
     out = derived_figures(table)
+    if culled is not None:
+        out.update(cull=culled[0], estimate_index=culled[1], reference_index=culled[2])
     out.update(table=np.asarray(table, dtype=np.float64), cells=[float(c) for c in cells], counters=counters, threshold=float(threshold),
                max_dist=float(max_dist), n_estimate=int(sets[0].shape[0]), n_reference=int(sets[1].shape[0]),
                estimate_rows=sets[0], reference_rows=sets[1], dist_estimate=dists[0], dist_reference=dists[1])
@@ -466,6 +512,8 @@ def metrics_dict(result, extra=None):
     t = result["table"]
     out["estimate_to_reference"] = {name: float(t[0, k]) for k, name in enumerate(ROW_NAMES[:7])}
     out["reference_to_estimate"] = {name: float(t[1, k]) for k, name in enumerate(ROW_NAMES[:7])}
+    if result.get("cull") is not None:
+        out["cull"] = result["cull"]
     out.update(extra or {})
     return out
 

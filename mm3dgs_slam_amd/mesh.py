@@ -409,8 +409,117 @@ def read_mesh_ply(path):
     return np.frombuffer(body, dtype="<i4").reshape(nv, 4).copy(), f["v"].astype(np.int32).copy()
 
 
-def read_surface_ply(path):
-    """A surface file of either writer: ``read_mesh_ply`` (rows, triangles) when the header has a face element, else ``read_ply`` rows."""
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4",
+              "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def _foreign_header(fh, path):
+    """[(element name, count, [(property name, scalar type) or (property name, count type, item type)])] of a binary little-endian header."""
+    if fh.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a PLY file")
+    elements, fmt = [], None
+    while True:
+        line = fh.readline()
+        if not line:
+            raise ValueError(f"{path}: PLY header without end_header")
+        try:
+            words = line.decode("ascii").split()
+        except UnicodeDecodeError:
+            raise ValueError(f"{path}: PLY header is not ASCII") from None
+        if not words or words[0] in ("comment", "obj_info"):
+            continue
+        if words[0] == "format":
+            fmt = words[1] if len(words) > 1 else None
+        elif words[0] == "element" and len(words) == 3 and words[2].isdigit():
+            elements.append((words[1], int(words[2]), []))
+        elif words[0] == "property" and elements and len(words) == 3 and words[1] in _PLY_TYPES:
+            elements[-1][2].append((words[2], words[1]))
+        elif words[0] == "property" and elements and len(words) == 5 and words[1] == "list" and words[2] in _PLY_TYPES and words[3] in _PLY_TYPES:
+            elements[-1][2].append((words[4], words[2], words[3]))
+        elif words[0] == "end_header":
+            break
+        else:
+            raise ValueError(f"{path}: PLY header line {line!r}")
+    if fmt != "binary_little_endian":
+        raise ValueError(f"{path}: PLY format {fmt} (binary_little_endian only)")
+    return elements
+
+
+def read_foreign_ply(path):
+    """A binary little-endian PLY file of another writer (a dataset's ground-truth mesh): rows [V,4] int32, or (rows, triangles [T,3] int32)
+    when the file has a `face` element.  The `vertex` element: fixed-size scalar properties that include float x, y, z; the colour from
+    uchar red, green, blue where present, else 255; alpha from uchar alpha where present, else 255; every other property (normals, ...) is
+    skipped.  The optional `face` element, right behind it: one list property, a uchar count with int or uint indices; a polygon of more
+    than three corners is fanned from corner 0, one of fewer is dropped.  Anything else -- ASCII or big-endian files, other elements, an
+    index beyond the vertices, a short body -- raises ValueError."""
     with open(path, "rb") as fh:
-        has_faces = any(e[0] == "face" for e in read_header(fh))
-    return read_mesh_ply(path) if has_faces else read_ply(path)
+        elements = _foreign_header(fh, path)
+        names = [e[0] for e in elements]
+        if names not in (["vertex"], ["vertex", "face"]):
+            raise ValueError(f"{path}: elements {names} (vertex, then optionally face)")
+        _, nv, props = elements[0]
+        if any(len(p) != 2 for p in props) or len({p[0] for p in props}) != len(props):
+            raise ValueError(f"{path}: the vertex element must have distinct scalar properties")
+        vtype = np.dtype([(name, _PLY_TYPES[t]) for name, t in props])
+        if any(k not in vtype.names or vtype[k] != np.dtype("<f4") for k in "xyz"):
+            raise ValueError(f"{path}: the vertex element needs float x, y, z")
+        body = fh.read(vtype.itemsize * nv)
+        if len(body) != vtype.itemsize * nv:
+            raise ValueError(f"{path}: {len(body)} body bytes for {nv} vertices of {vtype.itemsize} bytes")
+        vert = np.frombuffer(body, dtype=vtype)
+        faces = None
+        if len(elements) == 2:
+            _, nf, fprops = elements[1]
+            if len(fprops) != 1 or len(fprops[0]) != 3 or _PLY_TYPES[fprops[0][1]] != "u1" or _PLY_TYPES[fprops[0][2]] not in ("<i4", "<u4"):
+                raise ValueError(f"{path}: the face element must be one list property of uchar counts and int / uint indices")
+            faces = (nf, fh.read())
+    rows = np.empty((nv, 4), dtype=np.int32)
+    for k, name in enumerate("xyz"):
+        rows[:, k] = vert[name].view(np.int32)
+    rgba = np.full((nv, 4), 255, dtype=np.uint32)
+    for k, name in enumerate(("red", "green", "blue", "alpha")):
+        if name in vtype.names and vtype[name] == np.dtype("u1"):
+            rgba[:, k] = vert[name]
+    rows[:, 3] = (rgba[:, 0] | (rgba[:, 1] << 8) | (rgba[:, 2] << 16) | (rgba[:, 3] << 24)).astype(np.uint32).view(np.int32)
+    if faces is None:
+        return rows
+    nf, data = faces
+    raw = np.frombuffer(data, dtype=np.uint8)
+    # the start of every face record: a uniform corner count is one strided view, anything else is walked
+    k0 = int(raw[0]) if nf and len(raw) else 0
+    if nf and len(raw) >= nf * (1 + 4 * k0) and bool((raw[:nf * (1 + 4 * k0):1 + 4 * k0] == k0).all()):
+        starts, counts = np.arange(nf, dtype=np.int64) * (1 + 4 * k0), np.full(nf, k0, dtype=np.int64)
+    else:
+        starts, counts, at = np.empty(nf, dtype=np.int64), np.empty(nf, dtype=np.int64), 0
+        for f in range(nf):
+            if at >= len(raw):
+                raise ValueError(f"{path}: the body ends inside face {f}")
+            starts[f], counts[f] = at, int(raw[at])
+            at += 1 + 4 * int(raw[at])
+    if nf and int(starts[-1] + 1 + 4 * counts[-1]) > len(raw):
+        raise ValueError(f"{path}: the body ends inside the faces")
+    tris = []
+    for k in np.unique(counts):
+        if k < 3:
+            continue
+        s = starts[counts == k]
+        idx = raw[(s[:, None] + 1 + np.arange(4 * k)[None, :])].reshape(-1, 4 * int(k)).copy().view("<u4").astype(np.int64)      # [faces, k]
+        if idx.size and (idx.max() >= nv):
+            raise ValueError(f"{path}: a face index beyond the {nv} vertices")
+        fan = np.stack([np.stack([idx[:, 0], idx[:, j], idx[:, j + 1]], 1) for j in range(1, int(k) - 1)], 1)      # [faces, k - 2, 3]
+        tris.append((np.repeat(s, int(k) - 2), fan.reshape(-1, 3)))
+    if not tris:
+        return rows, np.zeros((0, 3), dtype=np.int32)
+    order = np.argsort(np.concatenate([t[0] for t in tris]), kind="stable")      # file order, a polygon's fan in corner order
+    return rows, np.concatenate([t[1] for t in tris])[order].astype(np.int32)
+
+
+def read_surface_ply(path):
+    """A surface file: one of this package's two writers -- ``read_mesh_ply`` (rows, triangles) when the header has a face element, else
+    ``read_ply`` rows --, and when those strict readers reject it, ``read_foreign_ply`` (a dataset's mesh: normals, no alpha, uint indices)."""
+    try:
+        with open(path, "rb") as fh:
+            has_faces = any(e[0] == "face" for e in read_header(fh))
+        return read_mesh_ply(path) if has_faces else read_ply(path)
+    except (ValueError, IndexError):
+        return read_foreign_ply(path)
