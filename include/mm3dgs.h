@@ -676,6 +676,65 @@ size_t mm3dgs_cull_work_bytes(uint64_t n);
 int mm3dgs_cull_select(uint64_t n, const void* rows /*[n] x 16 bytes*/, const uint32_t* seen /*[n]*/, uint32_t min_views, void* out_rows /*[cap] x 16 bytes*/,
                        uint64_t cap, uint32_t* index_or_null /*[cap]*/, void* work, uint64_t* counters /*[8], device*/, void* stream);
 
+/* ---- mesh cleaning: the connected components of an indexed triangle mesh, and the mesh without its small pieces ------------------------
+ * Host statement: mm3dgs_slam_amd/mesh_clean.py (components_host, clean_host).  rows: [V] x 16 bytes {float x, y, z; uint32 rgba} on the
+ * device, 16-byte aligned (only moved, never read as numbers); triangles: int32 [T][3], 4-byte aligned -- what mm3dgs_tsdf_mesh_emit writes.
+ * The rule, in integers only:
+ *   valid        a triangle whose three indices lie in [0, V).  An invalid one joins nothing, is counted nowhere but in `skipped`, and is
+ *                never written.  A triangle with a repeated index is valid and counts as one triangle.
+ *   connected    two vertices that a valid triangle both uses; components are the transitive closure.  This is connectivity through shared
+ *                VERTICES (Open3D's cluster_connected_triangles and trimesh use shared edges: the two differ where surfaces touch in a point).
+ *   label[v]     the smallest vertex index of v's component; v itself for a vertex no valid triangle uses.
+ *   tri_count[r] the valid triangles whose vertices carry label r; 0 at every index that is not a label.
+ *   kept         mode MM3DGS_MESH_CLEAN_SMALL: the components with tri_count >= min_triangles (min_triangles >= 1);
+ *                mode MM3DGS_MESH_CLEAN_LARGEST: the one component with the greatest tri_count, on a tie the one with the smallest label;
+ *                without a valid triangle nothing is kept.
+ *   output       the vertices of kept components (which all have a triangle: a vertex that no valid triangle uses is dropped) in their
+ *                original order, the 16 row bytes untouched; the valid triangles of kept components in their original order, re-indexed to
+ *                the new vertex positions; index_or_null[k] (uint32) = the original vertex of kept vertex k.
+ * counters: uint64 [8] on the device, 8-byte aligned, not cumulative, shared by the three calls:
+ *   mm3dgs_mesh_components  [0] components with a triangle, [1] the largest: (tri_count << 32) | (~label & 0xffffffff), 0 without a valid
+ *                           triangle, [2] skipped (invalid) triangles, [3] vertices no valid triangle uses, [4..7] 0
+ *   mm3dgs_mesh_clean_plan  [4] components kept, [5] vertices kept, [6] triangles kept, [7] 0; [0..3] are READ ([1] names mode largest's
+ *                           winner) and left as they are
+ *   mm3dgs_mesh_clean_emit  [7] (kept triangles not written << 32) | kept vertices not written; the rest is left as it is
+ *
+ * mm3dgs_mesh_components writes label [V] and tri_count [V] (both uint32) and counters.  label serves as the parent array of a union-find:
+ * one lane per triangle joins (a, b) and (b, c) by hooking the larger of two roots under the smaller with one compare-and-swap, and goes on
+ * from the value the swap returned when it fails; a second launch replaces every parent by its root, a third adds one per valid triangle to
+ * tri_count[label] (integer atomic adds: order-free), and one workgroup reduces tri_count to the counters.  Parents only ever point to lower
+ * vertices of the same component, so every walk is bounded by V; a compare-and-swap fails only because another lane's succeeded; no lane
+ * waits for another (no flag, no spin, no cooperative launch); the smallest vertex of a component can never be hooked, so it is the root
+ * whatever the order of arrival: the same input gives the same bytes on every call.  V = 0 launches only the counter update ([2] = T);
+ * T = 0 the initialisation (label[v] = v, tri_count[v] = 0) and the counter update.  Nothing outside label[0:V], tri_count[0:V] and
+ * counters[0:8] is written; triangles is read only and every index is range-checked before it addresses anything.
+ *
+ * mm3dgs_mesh_clean_plan (label, tri_count and counters as mm3dgs_mesh_components left them; any label array with label[v] < V is safe):
+ * per-256 counts of kept vertices, kept roots and kept triangles, one 1024-wide scan of each, and the remap of every vertex to its new
+ * index, all into work.  mm3dgs_mesh_clean_emit (same V, T, triangles and work): kept rows to out_rows [vcap] x 16 bytes and index_or_null
+ * [vcap] at their remap, kept triangles through the remap to out_triangles [tcap][3] at block prefix + rank.  A kept row at or beyond vcap
+ * and a kept triangle at or beyond tcap is not written and is counted in [7]; a written triangle may then name a vertex that was not
+ * written -- with caps of [5] and [6], read back after the plan, nothing is dropped.  No atomic decides a position.  work:
+ * mm3dgs_mesh_clean_work_bytes(V, T) bytes, 8-byte aligned, contents irrelevant before the plan.  V = 0 or T = 0 launches only the counter
+ * updates.  Four launches at most for the plan, three for emit, no host synchronisation.  Nothing outside work, counters[0:8],
+ * out_rows[0:min([5], vcap)], index[0:min([5], vcap)] and out_triangles[0:min([6], tcap)] is written; rows, triangles, label and tri_count
+ * are read only.
+ *
+ * -1 (nothing is launched, nothing is written): V or T above 2^30; a mode other than the two; min_triangles 0 in mode small; vcap or tcap
+ * above 2^31; a NULL counters or work; NULL label or tri_count with V > 0, NULL rows (emit) with V > 0, NULL triangles with T > 0; NULL
+ * out_rows / out_triangles with V > 0, T > 0 and a cap above 0; rows or out_rows not 16-byte aligned, counters or work not 8-byte aligned,
+ * triangles, out_triangles, label, tri_count or index not 4-byte aligned.  mm3dgs_mesh_clean_work_bytes returns 0 for V or T above 2^30. */
+#define MM3DGS_MESH_CLEAN_SMALL 1
+#define MM3DGS_MESH_CLEAN_LARGEST 2
+size_t mm3dgs_mesh_clean_work_bytes(uint64_t V, uint64_t T);
+int mm3dgs_mesh_components(uint64_t V, uint64_t T, const int32_t* triangles /*[T][3]*/, uint32_t* label /*[V]*/, uint32_t* tri_count /*[V]*/,
+                           uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_mesh_clean_plan(uint64_t V, uint64_t T, const int32_t* triangles /*[T][3]*/, const uint32_t* label /*[V]*/, const uint32_t* tri_count /*[V]*/,
+                           int mode, uint32_t min_triangles, void* work, uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_mesh_clean_emit(uint64_t V, uint64_t T, const void* rows /*[V] x 16 bytes*/, const int32_t* triangles /*[T][3]*/, const void* work,
+                           void* out_rows /*[vcap] x 16 bytes*/, uint64_t vcap, int32_t* out_triangles /*[tcap][3]*/, uint64_t tcap,
+                           uint32_t* index_or_null /*[vcap]*/, uint64_t* counters /*[8], device*/, void* stream);
+
 /* ---- frame ingest: raw sensor bytes -> the two images the SLAM loops consume, in one launch ------------------------------------------
  * rgb: uint8 interleaved [Hs,Ws,3] on the device, any byte alignment; depth_or_null: uint16 [Hs,Ws], 2-byte aligned.  out_color [3,H,W]
  * float32 in [0,1]; out_depth_or_null [H,W] float32 in metres, required iff depth is given (a colour-only call passes NULL for both).
@@ -814,7 +873,9 @@ const char* mm3dgs_last_error(void);
         mm3dgs_nn_query_work_bytes / mm3dgs_nn_query / mm3dgs_mesh_sample_work_bytes / mm3dgs_mesh_sample_plan / mm3dgs_mesh_sample_emit
         (geometry scores of an export against a reference: exact truncated nearest-neighbour distances through a uniform grid, and
         area-uniform samples of a triangle mesh); mm3dgs_cull_mark_view / mm3dgs_cull_work_bytes / mm3dgs_cull_select (the rows of a
-        point set that the views of a run could have seen, for the geometry scores); a caller that needs them looks the symbols up */
+        point set that the views of a run could have seen, for the geometry scores); mm3dgs_mesh_clean_work_bytes / mm3dgs_mesh_components /
+        mm3dgs_mesh_clean_plan / mm3dgs_mesh_clean_emit (the connected components of a triangle mesh and the mesh without its small
+        pieces); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

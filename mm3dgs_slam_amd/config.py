@@ -27,7 +27,7 @@ _TUM = {
     # mm3dgs_tsdf_mesh_plan / _emit): the same views as the point cloud fused into a dense truncated signed distance volume of `voxel`-sized
     # cells (trunc 0: 4 voxel) over `bounds` ([xmin, ymin, zmin, xmax, ymax, zmax]; None: the box of the views' lifted valid points, grown by
     # trunc + voxel), then marching tetrahedra over the samples seen at least min_weight times; a lattice above max_voxels samples is an
-    # error; opt-in, changes no pose
+    # error; opt-in, changes no pose (further keys of the block, with their defaults: MESH_CLEAN below)
     "mesh": {"export": False, "every": None, "voxel": 0.02, "trunc": 0, "source": "render", "sil_min": 0.99, "max_depth": 0, "min_weight": 1,
              "bounds": None, "max_voxels": 1 << 28},
     # after the run, the exported geometry scored against a reference surface (outputdir/geometry/metrics.json + accuracy.ply +
@@ -72,6 +72,14 @@ _TUM = {
 # anyway); cull_near / cull_far: the depth range in metres (far 0: no limit); a point is kept when at least cull_min_views views see it
 GEOMETRY_CULL = {"cull": "none", "cull_eps": 0, "cull_near": 0, "cull_far": 0, "cull_min_views": 1}
 
+
+# Optional keys of the `mesh` block and their defaults (export.options merges them under the block; kept out of the default block for the
+# same reason): after the extraction, the mesh's small disconnected pieces are removed (mesh_clean.py, mm3dgs_mesh_components /
+# mm3dgs_mesh_clean_plan / _emit) -- from mesh.ply and from both meshes of the geometry evaluation, which share the block.  `clean` none /
+# small (drop the components -- vertices joined through triangles -- of fewer than clean_min_triangles triangles) / largest (keep the one
+# component with the most triangles).  clean_min_triangles: 100 is a placeholder, not a measured default: the right value depends on
+# mesh.voxel (a piece of a given size has more triangles at a finer voxel)
+MESH_CLEAN = {"clean": "none", "clean_min_triangles": 100}
 
 # configs/UTMM.yml's hot-path settings that differ from TUM.yml (BASELINE.json configs[2]: RGB-D + IMU): 640x330, intrinsics of the
 # 1280x660 sensor scaled by 1/2 (gradslam_datasets/datautils.py:73-118), isotropic Gaussians, IMU dead-reckoning for the pose

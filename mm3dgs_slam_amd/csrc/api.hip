@@ -995,6 +995,49 @@ int mm3dgs_cull_select(uint64_t n, const void* rows, const uint32_t* seen, uint3
   return check_launch("cull_select");
 }
 
+// ---- mesh cleaning (meshclean.hip) ------------------------------------------------------------------------------------------------------
+static bool mesh_clean_sizes_ok(uint64_t V, uint64_t T) { return V <= NN_MAX_ROWS && T <= NN_MAX_ROWS; }
+size_t mm3dgs_mesh_clean_work_bytes(uint64_t V, uint64_t T) { return mesh_clean_sizes_ok(V, T) ? mesh_clean_work_bytes(V, T) : 0; }
+
+int mm3dgs_mesh_components(uint64_t V, uint64_t T, const int32_t* triangles, uint32_t* label, uint32_t* tri_count, uint64_t* counters, void* stream) {
+  if (!mesh_clean_sizes_ok(V, T)) return fail(-1, "mesh_components: V = %llu, T = %llu (each at most 2^30)", (unsigned long long)V, (unsigned long long)T);
+  if (!counters || (V && (!label || !tri_count)) || (T && !triangles))
+    return fail(-1, "mesh_components: NULL argument (counters is required; label and tri_count unless V is 0; triangles unless T is 0)");
+  if ((uintptr_t)counters & 7) return fail(-1, "mesh_components: counters must be 8-byte aligned");
+  if (((uintptr_t)triangles | (uintptr_t)label | (uintptr_t)tri_count) & 3) return fail(-1, "mesh_components: triangles, label and tri_count must be 4-byte aligned");
+  launch_mesh_components(V, T, triangles, label, tri_count, counters, (hipStream_t)stream);
+  return check_launch("mesh_components");
+}
+
+int mm3dgs_mesh_clean_plan(uint64_t V, uint64_t T, const int32_t* triangles, const uint32_t* label, const uint32_t* tri_count, int mode, uint32_t min_triangles,
+                           void* work, uint64_t* counters, void* stream) {
+  if (!mesh_clean_sizes_ok(V, T)) return fail(-1, "mesh_clean_plan: V = %llu, T = %llu (each at most 2^30)", (unsigned long long)V, (unsigned long long)T);
+  if (mode != MM3DGS_MESH_CLEAN_SMALL && mode != MM3DGS_MESH_CLEAN_LARGEST) return fail(-1, "mesh_clean_plan: mode = %d (1 small, 2 largest)", mode);
+  if (mode == MM3DGS_MESH_CLEAN_SMALL && min_triangles < 1) return fail(-1, "mesh_clean_plan: min_triangles = 0 in mode small (at least 1)");
+  if (!work || !counters || (V && (!label || !tri_count)) || (T && !triangles))
+    return fail(-1, "mesh_clean_plan: NULL argument (work and counters are required; label and tri_count unless V is 0; triangles unless T is 0)");
+  if (((uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "mesh_clean_plan: work and counters must be 8-byte aligned");
+  if (((uintptr_t)triangles | (uintptr_t)label | (uintptr_t)tri_count) & 3) return fail(-1, "mesh_clean_plan: triangles, label and tri_count must be 4-byte aligned");
+  launch_mesh_clean_plan(V, T, triangles, label, tri_count, mode, min_triangles, work, counters, (hipStream_t)stream);
+  return check_launch("mesh_clean_plan");
+}
+
+int mm3dgs_mesh_clean_emit(uint64_t V, uint64_t T, const void* rows, const int32_t* triangles, const void* work, void* out_rows, uint64_t vcap,
+                           int32_t* out_triangles, uint64_t tcap, uint32_t* index_or_null, uint64_t* counters, void* stream) {
+  if (!mesh_clean_sizes_ok(V, T)) return fail(-1, "mesh_clean_emit: V = %llu, T = %llu (each at most 2^30)", (unsigned long long)V, (unsigned long long)T);
+  if (vcap > ((uint64_t)1 << 31) || tcap > ((uint64_t)1 << 31))
+    return fail(-1, "mesh_clean_emit: vcap = %llu, tcap = %llu (each at most 2^31)", (unsigned long long)vcap, (unsigned long long)tcap);
+  if (!work || !counters || (V && !rows) || (T && !triangles) || (V && T && vcap && !out_rows) || (V && T && tcap && !out_triangles))
+    return fail(-1, "mesh_clean_emit: NULL argument (work and counters are required; rows unless V is 0; triangles unless T is 0; out_rows and "
+                    "out_triangles unless V, T or their cap is 0)");
+  if (((uintptr_t)rows | (uintptr_t)out_rows) & 15) return fail(-1, "mesh_clean_emit: rows and out_rows must be 16-byte aligned");
+  if (((uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "mesh_clean_emit: work and counters must be 8-byte aligned");
+  if (((uintptr_t)triangles | (uintptr_t)out_triangles | (uintptr_t)index_or_null) & 3)
+    return fail(-1, "mesh_clean_emit: triangles, out_triangles and index must be 4-byte aligned");
+  launch_mesh_clean_emit(V, T, rows, triangles, work, out_rows, vcap, out_triangles, tcap, index_or_null, counters, (hipStream_t)stream);
+  return check_launch("mesh_clean_emit");
+}
+
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
                         float* out_color, float* out_depth_or_null, void* stream) {
   if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);

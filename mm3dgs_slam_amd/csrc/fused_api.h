@@ -182,6 +182,16 @@ size_t cull_work_bytes(uint64_t n);
 void launch_cull_mark_view(const CullView& v, uint64_t n, const void* rows, uint32_t* seen, uint64_t* counters, hipStream_t s);
 void launch_cull_select(uint64_t n, const void* rows, const uint32_t* seen, uint32_t min_views, void* out_rows, uint64_t cap, uint32_t* index, void* work,
                         uint64_t* counters, hipStream_t s);
+// mesh cleaning (meshclean.hip): label = the smallest vertex of a vertex's component (through valid triangles: three indices in [0, V)),
+// tri_count = the valid triangles per label, counters [0..3]; plan: which components the mode keeps, the per-256 counts, their scan and
+// the vertex remap into work = the buffer of mesh_clean_work_bytes(V, T), counters [4..7]; emit: kept rows and re-indexed triangles in
+// their order below the caps; V, T <= 2^30, mode 1 / 2, min_triangles >= 1 in mode 1, as the entry points have checked
+size_t mesh_clean_work_bytes(uint64_t V, uint64_t T);
+void launch_mesh_components(uint64_t V, uint64_t T, const int* tris, uint32_t* label, uint32_t* tri_count, uint64_t* counters, hipStream_t s);
+void launch_mesh_clean_plan(uint64_t V, uint64_t T, const int* tris, const uint32_t* label, const uint32_t* tri_count, int mode, uint32_t min_triangles,
+                            void* work, uint64_t* counters, hipStream_t s);
+void launch_mesh_clean_emit(uint64_t V, uint64_t T, const void* rows, const int* tris, const void* work, void* out_rows, uint64_t vcap, int* out_tris,
+                            uint64_t tcap, uint32_t* index, uint64_t* counters, hipStream_t s);
 // frame ingest (ingest.hip): raw uint8 RGB [Hs,Ws,3] + uint16 depth [Hs,Ws] -> colour [3,H,W] in [0,1] + depth [H,W] in metres, one
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,

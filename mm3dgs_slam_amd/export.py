@@ -7,14 +7,14 @@ import os
 import numpy as np
 import torch
 
-from . import cull as cl, geometry as geo, mesh as ms, pointcloud as pc
-from .config import _TUM, GEOMETRY_CULL
+from . import cull as cl, geometry as geo, mesh as ms, mesh_clean as mc, pointcloud as pc
+from .config import _TUM, GEOMETRY_CULL, MESH_CLEAN
 
 
 def options(cfg, block, **overrides):
     """The `pointcloud`, `mesh` or `geometry` block of `cfg` merged over the defaults, an override that is not None over both, resolved
-    and validated: `every` (None: `mapping.kf_every`), `voxel`, `source` and the mesh's `trunc` (0: 4 voxel) of an export;
-    `estimate`, `reference` and `align` of the evaluation."""
+    and validated: `every` (None: `mapping.kf_every`), `voxel`, `source` and the mesh's `trunc` (0: 4 voxel), `clean` and
+    `clean_min_triangles` of an export; `estimate`, `reference` and `align` of the evaluation."""
     opt = dict(_TUM[block], **(cfg.get(block) or {}))
     if block == "geometry":
         opt = dict(GEOMETRY_CULL, **opt)
@@ -33,6 +33,8 @@ def options(cfg, block, **overrides):
             raise ValueError(f"geometry.cull_near / cull_far / cull_eps / cull_min_views: {e}") from None
         opt.update(cull_near=near, cull_far=far, cull_eps=eps if eps > 0 else float(opt["threshold"]), cull_min_views=min_views)
         return opt
+    if block == "mesh":
+        opt = dict(MESH_CLEAN, **opt)
     opt["every"] = opt["every"] or cfg["mapping"]["kf_every"]
     opt.update((k, v) for k, v in overrides.items() if v is not None)
     every, voxel, source = int(opt["every"]), float(opt["voxel"]), str(opt["source"])
@@ -45,6 +47,13 @@ def options(cfg, block, **overrides):
         if not (np.isfinite(voxel) and voxel > 0):
             raise ValueError(f"{block}.voxel = {voxel} (must be positive)")
         opt["trunc"] = float(opt["trunc"]) if float(opt["trunc"] or 0) > 0 else 4.0 * voxel
+        opt["clean"] = str(opt["clean"] or "none").lower()
+        if opt["clean"] not in mc.MODES:
+            raise ValueError(f"mesh.clean = {opt['clean']!r} (none / small / largest)")
+        try:
+            opt["clean_min_triangles"] = mc.check_options("small", opt["clean_min_triangles"])[1]
+        except (TypeError, ValueError):
+            raise ValueError(f"mesh.clean_min_triangles = {opt['clean_min_triangles']!r} (an integer, at least 1)") from None
     return opt
 
 
@@ -136,7 +145,9 @@ def mesh_bounds(slam, opt, poses=None):
 
 def mesh_geometry(slam, opt, poses=None):
     """The views of an export fused and meshed (what `export_mesh` writes and `evaluate_geometry` scores): (rows, triangles, counters,
-    lattice sizes, origin); device tensors on a GPU.  `opt`: `options` of the `mesh` block; `poses` as in `views`."""
+    lattice sizes, origin); device tensors on a GPU.  `opt`: `options` of the `mesh` block; `poses` as in `views`.  With `mesh.clean`
+    small / largest the mesh is cleaned behind the extraction (mesh_clean.py) and the counters -- which stay those of the extraction --
+    carry the cleaning's figures under `clean`."""
     voxel, trunc, cfg = opt["voxel"], opt["trunc"], slam.cfg
     with torch.no_grad():
         if opt["bounds"] is None:
@@ -152,6 +163,10 @@ def mesh_geometry(slam, opt, poses=None):
         for view in views(slam, opt["every"], opt["source"], "mesh", poses):
             volume.add(*view)
         rows, triangles, counters = volume.extract()
+        if opt.get("clean", "none") != "none":
+            rows, triangles, _, info = mc.clean(rows, triangles, opt["clean"], opt["clean_min_triangles"], device=cfg["device"])
+            counters = dict(counters, clean=dict(info, mode=opt["clean"], min_triangles=opt["clean_min_triangles"], vertices=int(rows.shape[0]),
+                                                 triangles=int(triangles.shape[0])))
     return rows, triangles, counters, dims, origin
 
 
@@ -180,7 +195,8 @@ def export_mesh(slam, path=None, every=None, voxel=None, source=None):
     """The reconstruction as a coloured triangle mesh (mesh.py): the views of `export_pointcloud` (`every`, `source`) fused into a dense
     truncated signed distance volume of `mesh.voxel`-sized cells (`mesh.trunc`, 0: 4 voxel) over `mesh.bounds` -- None: a first pass
     over the same views takes the box of their lifted valid points, which is grown by trunc + voxel, the origin snapped down to a
-    multiple of voxel --, then marching tetrahedra over the samples seen at least `mesh.min_weight` times.  Writes `path/mesh.ply`
+    multiple of voxel --, then marching tetrahedra over the samples seen at least `mesh.min_weight` times, and with `mesh.clean` small /
+    largest the removal of the small disconnected pieces (mesh_clean.py; the returned dict gains `clean`).  Writes `path/mesh.ply`
     (default `outputdir/mesh`; the format: `mesh.write_mesh_ply`).  One mm3dgs_tsdf_integrate call per view and one mm3dgs_tsdf_mesh_plan /
     _emit pair on a GPU, the host statement on `device: cpu`.  Returns the path, the counters and the lattice; raises ValueError when the
     lattice exceeds `mesh.max_voxels`."""
@@ -190,9 +206,13 @@ def export_mesh(slam, path=None, every=None, voxel=None, source=None):
     os.makedirs(path, exist_ok=True)
     out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles), "counters": counters, "lattice": tuple(dims),
            "origin": origin.tolist(), "voxel": opt["voxel"], "trunc": opt["trunc"]}
+    cleaned = ""
+    if "clean" in counters:
+        out["clean"] = counters["clean"]
+        cleaned = f"; {mc.summary(opt['clean'], opt['clean_min_triangles'], counters['clean'])}"
     slam.mesh_export = out      # what the last export wrote
     print(f"Mesh: {counters['vertices']} vertices, {counters['triangles']} triangles from {counters['views']} views "
-          f"(lattice {dims[0]} x {dims[1]} x {dims[2]}, voxel {opt['voxel']} m) in {out['mesh']}")
+          f"(lattice {dims[0]} x {dims[1]} x {dims[2]}, voxel {opt['voxel']} m){cleaned} in {out['mesh']}")
     return out
 
 
@@ -202,7 +222,9 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     perfect tracker and map would have exported (ValueError without sensor depth) --, or the path of a PLY file: a point cloud or, with a
     face element, a mesh (`mesh.read_surface_ply`).  Meshes on either side are sampled at `geometry.density` samples per m^2;
     `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first; `geometry.cull` frustum / occlusion then
-    removes from both point sets what no camera of the run could have seen (`cull_views`, cull.py; metrics.json gains a `cull` block).  Writes `path/metrics.json`,
+    removes from both point sets what no camera of the run could have seen (`cull_views`, cull.py; metrics.json gains a `cull` block).
+    With `mesh.clean` small / largest the estimate mesh and the `reference: sensor` mesh come cleaned from their builder (a reference
+    file is left as it is) and metrics.json gains a `mesh_clean` block.  Writes `path/metrics.json`,
     `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); arguments left None come from the `geometry` config block.  HIP
     kernels and one read-back of the [2,8] table on a GPU, the host statement on `device: cpu`.  Touches no pose and no other output.
     Returns the comparison with the paths."""
@@ -210,22 +232,29 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     estimate, reference, align = opt["estimate"], opt["reference"], opt["align"]
     block = options(slam.cfg, estimate)
 
-    def build(block, poses):
+    cleaned = {}
+
+    def build(block, poses, side):
         if estimate == "mesh":
-            return mesh_geometry(slam, block, poses)[:2]
+            rows, triangles, counters = mesh_geometry(slam, block, poses)[:3]
+            if "clean" in counters:
+                cleaned[side] = counters["clean"]
+            return rows, triangles
         return cloud_geometry(slam, block, poses)[0].rows()
 
-    est = build(block, None)
+    est = build(block, None, "estimate")
     if align != "none":
         move = lambda rows: geo.align_rows(rows, slam.estimate_pose_list[:len(slam.seq)], gt_poses(slam), align)
         est = (move(est[0]), est[1]) if estimate == "mesh" else move(est)
-    ref = build(dict(block, source="sensor"), gt_poses(slam)) if reference == "sensor" else ms.read_surface_ply(reference)
+    ref = build(dict(block, source="sensor"), gt_poses(slam), "reference") if reference == "sensor" else ms.read_surface_ply(reference)
     culled = {} if opt["cull"] == "none" else {"cull": cull_views(slam, opt, block)}
     result = geo.compare(est, ref, device=slam.cfg["device"], threshold=float(opt["threshold"]), max_dist=float(opt["max_dist"]),
                          cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]), **culled)
     path = os.path.join(slam.cfg["outputdir"], "geometry") if path is None else path
-    result["files"] = geo.write_outputs(path, result, {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]),
-                                                       "seed": int(opt["seed"])})
+    extra = {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]), "seed": int(opt["seed"])}
+    if cleaned:
+        result["mesh_clean"] = extra["mesh_clean"] = dict(cleaned, mode=block["clean"], min_triangles=block["clean_min_triangles"])
+    result["files"] = geo.write_outputs(path, result, extra)
     slam.geometry_eval = result      # what the last evaluation found
     t = result["table"]
     print(f"Geometry ({estimate} against {reference}): accuracy {result['accuracy'] * 100:.3f} cm, completion {result['completion'] * 100:.3f} cm, "

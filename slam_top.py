@@ -31,7 +31,8 @@ CloudCompare; `--pointcloud --eval` writes the two files from the checkpoint wit
 the same views fused into a truncated signed distance volume and meshed by marching tetrahedra (a coloured triangle mesh, binary PLY); `--mesh --eval` likewise
 from the checkpoint.  `--geometry` (or `geometry.eval: true`) adds `geometry/metrics.json`, `accuracy.ply` and `completion.ply`: the exported mesh or cloud scored
 against a reference surface (the same frames' sensor depth at the ground-truth poses, or a PLY file) -- accuracy, completion, completion ratio, F-score, Chamfer
-distance; `--geometry --eval` likewise from the checkpoint.
+distance; `--geometry --eval` likewise from the checkpoint.  `--mesh-clean small|largest` (or `mesh.clean`) removes the mesh's small disconnected pieces behind
+the extraction, for `--mesh` and for the meshes `--geometry` scores (`mesh.clean_min_triangles`; mesh_clean.py).
 
 `--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
 `outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
@@ -156,6 +157,7 @@ def main():
     ap.add_argument("--pointcloud", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the fused coloured point cloud and the camera path to outputdir/pointcloud (the config's `pointcloud` block)")
     ap.add_argument("--mesh", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the reconstruction as a coloured triangle mesh to outputdir/mesh/mesh.ply (the config's `mesh` block)")
     ap.add_argument("--geometry", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) score the exported geometry against a reference surface into outputdir/geometry (the config's `geometry` block)")
+    ap.add_argument("--mesh-clean", choices=("small", "largest"), default=None, help="with --mesh / --geometry: remove the mesh's small disconnected pieces (overrides the `mesh` block's `clean`; small: components below mesh.clean_min_triangles triangles, largest: all but the largest component)")
     ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
@@ -175,6 +177,8 @@ def main():
                     "save_keyframes": bool(dbg.get("save_keyframes", False))}
     cfg.setdefault("outputdir", "output/" + (str(cfg.get("scene") or "recorded") if sequence_source(cfg) == "recorded" else "synthetic"))
     outdir = cfg["outputdir"]
+    if args.mesh_clean:
+        cfg["mesh"] = dict(cfg.get("mesh") or {}, clean=args.mesh_clean)
     if args.eval:
         seq = build_sequence(cfg, args.frames, args.gaussians)
         if args.pointcloud:
