@@ -676,6 +676,49 @@ size_t mm3dgs_cull_work_bytes(uint64_t n);
 int mm3dgs_cull_select(uint64_t n, const void* rows /*[n] x 16 bytes*/, const uint32_t* seen /*[n]*/, uint32_t min_views, void* out_rows /*[cap] x 16 bytes*/,
                        uint64_t cap, uint32_t* index_or_null /*[cap]*/, void* work, uint64_t* counters /*[8], device*/, void* stream);
 
+/* ---- mesh depth: a triangle mesh rendered to a depth image from a camera, and the comparison of two depth images -------------------------
+ * Host statement: mm3dgs_slam_amd/mesh_depth.py (render_host, compare_rows_host).  vrows: [V] x 16 bytes {float x, y, z; uint32 rgba} on the
+ * device, 16-byte aligned; triangles: int32 [T][3]; pose: world->camera (qw,qx,qy,qz,tx,ty,tz) on the device, normalised by the kernel;
+ * counters: uint64 [8] on the device, zeroed by the caller before the first view, accumulating over the calls.
+ *
+ * mm3dgs_mesh_depth_render: one view.  Every operation in double from the widened float32 inputs, no fused multiply-add, in this order:
+ *   corner    p_c[k] = R[k][0] x + R[k][1] y + R[k][2] z + t[k], summed left to right.
+ *   triangle  first match wins: invalid -- an index outside [0, V) or a corner whose p_c has a component that is not finite; behind -- no
+ *             corner has z_c > z_near; otherwise drawn.
+ *   setup     with corners a, b, c: n0 = b x c, n1 = c x a, n2 = a x b, each component p q - r s (two products, one subtraction), and
+ *             det = a.x n0.x + a.y n0.y + a.z n0.z, summed left to right.
+ *   pixel     with integer centre (u, v): dx = (u - cx) / fx, dy = (v - cy) / fy; E_i = n_i.x dx + n_i.y dy + n_i.z and S = E0 + E1 + E2,
+ *             summed left to right; inside when E0, E1, E2 >= 0 and S > 0, or E0, E1, E2 <= 0 and S < 0 (two-sided); a hit when inside and
+ *             z = det / S is finite, z > z_near, and z <= z_far when z_far > 0.
+ *   result    the hit with the smallest double z, on an exact tie the lowest triangle index: depth_out[v][u] = (float)z, rounded once,
+ *             tri_out_or_null[v][u] = that index; no hit gives 0.0f and -1.  Every pixel of both images is written on every call.
+ * A drawn triangle is binned into the 16 x 16-pixel tiles its rectangle touches -- floor(min) - 1 .. ceil(max) + 1 of the projections
+ * fx x / z + cx, fy y / z + cy, clamped to the image in double, when all three z_c > 0 and the projections are finite, else the whole
+ * image: only ever a superset of the hits -- with room for max_pairs (tile, triangle) pairs; the pairs beyond it are dropped and counted,
+ * and the images of a call that dropped pairs are void.  The order inside a tile's list depends on the order atomics arrive in; the images
+ * do not (a minimum over (z, index)), so the same inputs give the same bytes on every call.  counters: [0] += 1 (views), [1] += drawn,
+ * [2] += invalid, [3] += behind triangles, [4] += pairs kept, [5] += pairs dropped, [6] += hit pixels, [7] is left as it is.
+ * work: mm3dgs_mesh_depth_work_bytes(V, T, H, W, max_pairs) bytes, 8-byte aligned, contents irrelevant before and after.  Nothing outside
+ * depth_out, tri_out, counters[0:7] and work is written.  V = 0 or T = 0: all zeros and -1, the view is counted.  No host synchronisation.
+ *
+ * mm3dgs_depth_compare: a (estimate), b (reference): float32 [H,W] on the device.  A pixel is valid in an image when d > 0 && d < inf
+ * (strict float32 tests, a NaN fails).  row: double [8] on the device, 8-byte aligned -- one row of the caller's table: [0] n, the pixels
+ * valid in both, [1] mean |a - b|, [2] rms, [3] max, [4] pixels valid only in b, [5] only in a, [6] in neither, [7] 0; differences in
+ * double from the widened values; [1..3] are 0 when n is 0.  The sums have one fixed order: per 256 consecutive pixels a balanced binary
+ * tree over the lanes, then lane t of one workgroup adds the partial rows t, t + 256, ... in order and the 256 lanes are added in order.
+ * work: mm3dgs_depth_compare_work_bytes(H, W) bytes, 8-byte aligned.  Nothing outside row[0:8] and work is written.
+ *
+ * -1 (nothing is launched, nothing is written): H or W not positive or H W above 2^28; V or T above 2^30; max_pairs above 2^31; fx, fy
+ * not finite or 0; cx, cy not finite; z_near or z_far negative or not finite; a NULL pose, depth_out, a, b, row, work or counters; NULL
+ * vrows with V > 0 or triangles with T > 0; vrows not 16-byte aligned, work, counters or row not 8-byte aligned, triangles, an image or the
+ * pose not 4-byte aligned.  The two _work_bytes return 0 for sizes the calls reject. */
+size_t mm3dgs_mesh_depth_work_bytes(uint64_t V, uint64_t T, int H, int W, uint64_t max_pairs);
+int mm3dgs_mesh_depth_render(int H, int W, double fx, double fy, double cx, double cy, const float* pose /*[7], device*/, double z_near, double z_far,
+                             uint64_t V, const void* vrows /*[V] x 16 bytes*/, uint64_t T, const int32_t* triangles /*[T][3]*/, uint64_t max_pairs,
+                             float* depth_out /*[H,W]*/, int32_t* tri_out_or_null /*[H,W]*/, void* work, uint64_t* counters /*[8], device*/, void* stream);
+size_t mm3dgs_depth_compare_work_bytes(int H, int W);
+int mm3dgs_depth_compare(int H, int W, const float* a /*[H,W]*/, const float* b /*[H,W]*/, void* work, double* row /*[8], device*/, void* stream);
+
 /* ---- mesh cleaning: the connected components of an indexed triangle mesh, and the mesh without its small pieces ------------------------
  * Host statement: mm3dgs_slam_amd/mesh_clean.py (components_host, clean_host).  rows: [V] x 16 bytes {float x, y, z; uint32 rgba} on the
  * device, 16-byte aligned (only moved, never read as numbers); triangles: int32 [T][3], 4-byte aligned -- what mm3dgs_tsdf_mesh_emit writes.
@@ -875,7 +918,9 @@ const char* mm3dgs_last_error(void);
         area-uniform samples of a triangle mesh); mm3dgs_cull_mark_view / mm3dgs_cull_work_bytes / mm3dgs_cull_select (the rows of a
         point set that the views of a run could have seen, for the geometry scores); mm3dgs_mesh_clean_work_bytes / mm3dgs_mesh_components /
         mm3dgs_mesh_clean_plan / mm3dgs_mesh_clean_emit (the connected components of a triangle mesh and the mesh without its small
-        pieces); a caller that needs them looks the symbols up */
+        pieces); mm3dgs_mesh_depth_work_bytes / mm3dgs_mesh_depth_render / mm3dgs_depth_compare_work_bytes / mm3dgs_depth_compare (a
+        triangle mesh rendered to a depth image from a camera, and the depth L1 of two such images); a caller that needs them looks the
+        symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

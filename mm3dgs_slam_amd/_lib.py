@@ -124,6 +124,11 @@ _SIGS = {
     "mm3dgs_mesh_components": (C.c_int, [C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
     "mm3dgs_mesh_clean_plan": (C.c_int, [C.c_uint64, C.c_uint64, _P, _P, _P, C.c_int, C.c_uint32, _P, _P, _P]),
     "mm3dgs_mesh_clean_emit": (C.c_int, [C.c_uint64, C.c_uint64, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, _P]),
+    "mm3dgs_mesh_depth_work_bytes": (C.c_size_t, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64]),
+    "mm3dgs_mesh_depth_render": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _P, C.c_double, C.c_double, C.c_uint64, _P, C.c_uint64,
+                                           _P, C.c_uint64, _P, _P, _P, _P, _P]),
+    "mm3dgs_depth_compare_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mm3dgs_depth_compare": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "mm3dgs_ingest_frame": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_double, C.c_int, C.c_int, _P, _P, _P]),
     "mm3dgs_ingest_est": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P]),
     "mm3dgs_mosaic_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

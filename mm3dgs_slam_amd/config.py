@@ -39,7 +39,7 @@ _TUM = {
     # umeyama moves the estimate by the trajectory alignment first; opt-in, changes no pose and no other output
     "geometry": {"eval": False, "estimate": "mesh", "reference": "sensor", "threshold": 0.05, "max_dist": 1.0,
                  "density": 10000.0, "cell": 0, "seed": 0, "align": "none", "max_samples": 16777216},
-    # (further keys of the block, with their defaults: GEOMETRY_CULL below)
+    # (further keys of the block, with their defaults: GEOMETRY_CULL and GEOMETRY_DEPTH below)
     "scene_radius_depth_ratio": 2, "desired_height": 480, "desired_width": 640,
     "debug": {"get_runtime_stats": False, "create_video": False, "save_keyframes": False},
     "pipeline": {"convert_SHs_python": False, "compute_cov3D_python": False, "transform_means_python": True,
@@ -71,6 +71,17 @@ _TUM = {
 # 0: the block's `threshold` -- a point farther behind the measured surface than the score's own threshold cannot count as within it
 # anyway); cull_near / cull_far: the depth range in metres (far 0: no limit); a point is kept when at least cull_min_views views see it
 GEOMETRY_CULL = {"cull": "none", "cull_eps": 0, "cull_near": 0, "cull_far": 0, "cull_min_views": 1}
+
+
+# Further optional keys of the `geometry` block (merged the same way, kept apart for the same reason): what needs a mesh rendered to a depth
+# image from a camera (mesh_depth.py, mm3dgs_mesh_depth_render / mm3dgs_depth_compare).  `depth_l1`: after the 3D scores, the estimate
+# mesh and the reference mesh are rendered at the views the culling uses (the frames the scored export takes, at their ground-truth poses;
+# cull_near / cull_far are the depth range) and the mean absolute depth difference goes to metrics.json (`depth_l1`) and
+# outputdir/geometry/depth_l1.npz -- needs `estimate: mesh` and a mesh as the reference.  `cull_depth` sensor / reference: what
+# `cull: occlusion` tests against, the frame's sensor depth or the reference mesh rendered at the view (no frame needs sensor depth then).
+# depth_max_pairs: the room of one view's tile lists in (tile, triangle) pairs; 2^25 (128 MB of uint32 pairs) is a placeholder, not a
+# measured default: the need grows with the triangles and with the image, and a view that exceeds it raises
+GEOMETRY_DEPTH = {"depth_l1": False, "cull_depth": "sensor", "depth_max_pairs": 1 << 25}
 
 
 # Optional keys of the `mesh` block and their defaults (export.options merges them under the block; kept out of the default block for the

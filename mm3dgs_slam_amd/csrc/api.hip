@@ -1038,6 +1038,50 @@ int mm3dgs_mesh_clean_emit(uint64_t V, uint64_t T, const void* rows, const int32
   return check_launch("mesh_clean_emit");
 }
 
+// ---- mesh depth (meshdepth.hip) -----------------------------------------------------------------------------------------------------------
+#define MD_MAX_PAIRS ((uint64_t)1 << 31)
+static bool mesh_depth_sizes_ok(uint64_t V, uint64_t T, int H, int W, uint64_t max_pairs) {
+  return V <= NN_MAX_ROWS && T <= NN_MAX_ROWS && H > 0 && W > 0 && eval_shape_ok(H, W) && max_pairs <= MD_MAX_PAIRS;
+}
+size_t mm3dgs_mesh_depth_work_bytes(uint64_t V, uint64_t T, int H, int W, uint64_t max_pairs) {
+  return mesh_depth_sizes_ok(V, T, H, W, max_pairs) ? mesh_depth_work_bytes(V, T, H, W, max_pairs) : 0;
+}
+
+int mm3dgs_mesh_depth_render(int H, int W, double fx, double fy, double cx, double cy, const float* pose, double z_near, double z_far, uint64_t V,
+                             const void* vrows, uint64_t T, const int32_t* triangles, uint64_t max_pairs, float* depth_out, int32_t* tri_out_or_null, void* work,
+                             uint64_t* counters, void* stream) {
+  if (H <= 0 || W <= 0) return fail(-1, "mesh_depth_render: H = %d, W = %d (both must be positive)", H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "mesh_depth_render: %d x %d has more than 2^28 pixels", H, W);
+  if (V > NN_MAX_ROWS || T > NN_MAX_ROWS) return fail(-1, "mesh_depth_render: V = %llu, T = %llu (each at most 2^30)", (unsigned long long)V, (unsigned long long)T);
+  if (max_pairs > MD_MAX_PAIRS) return fail(-1, "mesh_depth_render: max_pairs = %llu (at most 2^31)", (unsigned long long)max_pairs);
+  if (!pose || !depth_out || !work || !counters || (V && !vrows) || (T && !triangles))
+    return fail(-1, "mesh_depth_render: NULL argument (pose, depth_out, work and counters are required; vrows unless V is 0; triangles unless T is 0)");
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "mesh_depth_render: fx = %g, fy = %g (finite, not 0)", fx, fy);
+  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "mesh_depth_render: cx = %g, cy = %g (must be finite)", cx, cy);
+  if (!(z_near >= 0.0) || !isfinite(z_near) || !(z_far >= 0.0) || !isfinite(z_far))
+    return fail(-1, "mesh_depth_render: near = %g, far = %g (each must be finite and not negative)", z_near, z_far);
+  if ((uintptr_t)vrows & 15) return fail(-1, "mesh_depth_render: vrows must be 16-byte aligned");
+  if (((uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "mesh_depth_render: work and counters must be 8-byte aligned");
+  if (((uintptr_t)triangles | (uintptr_t)depth_out | (uintptr_t)tri_out_or_null | (uintptr_t)pose) & 3)
+    return fail(-1, "mesh_depth_render: triangles, depth_out, tri_out and the pose must be 4-byte aligned");
+  MeshDepthView v;
+  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy; v.pose = pose; v.z_near = z_near; v.z_far = z_far;
+  launch_mesh_depth_render(v, V, vrows, T, triangles, max_pairs, depth_out, tri_out_or_null, work, counters, (hipStream_t)stream);
+  return check_launch("mesh_depth_render");
+}
+
+size_t mm3dgs_depth_compare_work_bytes(int H, int W) { return (H > 0 && W > 0 && eval_shape_ok(H, W)) ? depth_compare_work_bytes(H, W) : 0; }
+
+int mm3dgs_depth_compare(int H, int W, const float* a, const float* b, void* work, double* row, void* stream) {
+  if (H <= 0 || W <= 0) return fail(-1, "depth_compare: H = %d, W = %d (both must be positive)", H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "depth_compare: %d x %d has more than 2^28 pixels", H, W);
+  if (!a || !b || !work || !row) return fail(-1, "depth_compare: NULL argument (a, b, work and row are required)");
+  if (((uintptr_t)work | (uintptr_t)row) & 7) return fail(-1, "depth_compare: work and row must be 8-byte aligned");
+  if (((uintptr_t)a | (uintptr_t)b) & 3) return fail(-1, "depth_compare: the images must be 4-byte aligned");
+  launch_depth_compare(H, W, a, b, work, row, (hipStream_t)stream);
+  return check_launch("depth_compare");
+}
+
 int mm3dgs_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth_or_null, double png_depth_scale, int H, int W,
                         float* out_color, float* out_depth_or_null, void* stream) {
   if (Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0) return fail(-1, "ingest_frame: source %d x %d, output %d x %d (all must be positive)", Hs, Ws, H, W);

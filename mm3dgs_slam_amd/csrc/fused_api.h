@@ -192,6 +192,21 @@ void launch_mesh_clean_plan(uint64_t V, uint64_t T, const int* tris, const uint3
                             void* work, uint64_t* counters, hipStream_t s);
 void launch_mesh_clean_emit(uint64_t V, uint64_t T, const void* rows, const int* tris, const void* work, void* out_rows, uint64_t vcap, int* out_tris,
                             uint64_t tcap, uint32_t* index, uint64_t* counters, hipStream_t s);
+// mesh depth (meshdepth.hip): a triangle mesh (16-byte vertex rows, int32 [T][3] triangles) rendered to a depth image [H,W] float32 and the
+// winning triangle [H,W] int32 (tri NULL: not written) from one posed camera, through per-tile lists of at most max_pairs (tile, triangle)
+// pairs in work = the buffer of mesh_depth_work_bytes; and one row [8] of the comparison of two depth images, work = the buffer of
+// depth_compare_work_bytes; V, T <= 2^30, max_pairs <= 2^31, H W <= 2^28, near / far >= 0 and finite, as the entry points have checked
+struct MeshDepthView {
+  int H, W;
+  double fx, fy, cx, cy;
+  const float* pose;
+  double z_near, z_far;
+};
+size_t mesh_depth_work_bytes(uint64_t V, uint64_t T, int H, int W, uint64_t max_pairs);
+void launch_mesh_depth_render(const MeshDepthView& v, uint64_t V, const void* vrows, uint64_t T, const int* tris, uint64_t max_pairs, float* depth, int* tri,
+                              void* work, uint64_t* counters, hipStream_t s);
+size_t depth_compare_work_bytes(int H, int W);
+void launch_depth_compare(int H, int W, const float* a, const float* b, void* work, double* row, hipStream_t s);
 // frame ingest (ingest.hip): raw uint8 RGB [Hs,Ws,3] + uint16 depth [Hs,Ws] -> colour [3,H,W] in [0,1] + depth [H,W] in metres, one
 // launch; depth and out_depth are both NULL or both given; H W and Hs Ws are at most 2^30 (the entry point checks)
 void launch_ingest_frame(int Hs, int Ws, const uint8_t* rgb, const uint16_t* depth, double depth_scale, int H, int W, float* out_color,

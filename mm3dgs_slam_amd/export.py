@@ -7,8 +7,8 @@ import os
 import numpy as np
 import torch
 
-from . import cull as cl, geometry as geo, mesh as ms, mesh_clean as mc, pointcloud as pc
-from .config import _TUM, GEOMETRY_CULL, MESH_CLEAN
+from . import cull as cl, geometry as geo, mesh as ms, mesh_clean as mc, mesh_depth as md, pointcloud as pc
+from .config import _TUM, GEOMETRY_CULL, GEOMETRY_DEPTH, MESH_CLEAN
 
 
 def options(cfg, block, **overrides):
@@ -17,7 +17,7 @@ def options(cfg, block, **overrides):
     `clean_min_triangles` of an export; `estimate`, `reference` and `align` of the evaluation."""
     opt = dict(_TUM[block], **(cfg.get(block) or {}))
     if block == "geometry":
-        opt = dict(GEOMETRY_CULL, **opt)
+        opt = dict(GEOMETRY_DEPTH, **dict(GEOMETRY_CULL, **opt))
         opt.update((k, v) for k, v in overrides.items() if v is not None)
         opt.update(estimate=str(opt["estimate"]), reference=str(opt["reference"]), align=str(opt["align"] or "none").lower(),
                    cull=str(opt["cull"] or "none").lower())
@@ -32,6 +32,13 @@ def options(cfg, block, **overrides):
         except (TypeError, ValueError) as e:
             raise ValueError(f"geometry.cull_near / cull_far / cull_eps / cull_min_views: {e}") from None
         opt.update(cull_near=near, cull_far=far, cull_eps=eps if eps > 0 else float(opt["threshold"]), cull_min_views=min_views)
+        opt.update(depth_l1=bool(opt["depth_l1"]), cull_depth=str(opt["cull_depth"] or "sensor").lower())
+        if opt["cull_depth"] not in ("sensor", "reference"):
+            raise ValueError(f"geometry.cull_depth = {opt['cull_depth']!r} (sensor / reference)")
+        pairs = opt["depth_max_pairs"]
+        if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or not 1 <= int(pairs) <= md.MAX_PAIRS:
+            raise ValueError(f"geometry.depth_max_pairs = {pairs!r} (an integer, 1 .. 2^31)")
+        opt["depth_max_pairs"] = int(pairs)
         return opt
     if block == "mesh":
         opt = dict(MESH_CLEAN, **opt)
@@ -94,24 +101,50 @@ def gt_poses(slam):
     return poses
 
 
-def cull_views(slam, opt, block):
+def scored_frames(slam, block):
+    """The frames the scored export uses: `idx % every == 0` with an estimated pose."""
+    return [idx for idx in range(len(slam.seq)) if slam.estimate_pose_list[idx] is not None and idx % block["every"] == 0]
+
+
+def mesh_renderer(slam, opt, mesh):
+    """pose -> the depth image [H,W] of the mesh (rows, triangles) at that pose over cull_near .. cull_far (mesh_depth.py): a device tensor
+    from one mm3dgs_mesh_depth_render call on a GPU, the host statement on `device: cpu`; and `finish()`, which raises when a view's
+    tile lists lacked room (`geometry.depth_max_pairs`)."""
+    cfg, cam = slam.cfg, slam.cfg["cam"]
+    H, W = int(cfg["desired_height"]), int(cfg["desired_width"])
+    if str(cfg["device"]).startswith("cuda"):
+        r = md.MeshDepth(mesh[0], mesh[1], H, W, cam["fx"], cam["fy"], cam["cx"], cam["cy"], opt["cull_near"], opt["cull_far"], opt["depth_max_pairs"], cfg["device"])
+        return (lambda pose: r.render(pose, want_tri=False)[0]), r.finish
+    rows, tris = pc.as_np(mesh[0], np.int32), pc.as_np(mesh[1], np.int32)
+    return (lambda pose: md.render_host(rows, tris, pose, H, W, cam["fx"], cam["fy"], cam["cx"], cam["cy"], opt["cull_near"], opt["cull_far"])[0]), (lambda: None)
+
+
+def cull_views(slam, opt, block, reference=None):
     """The ``cull=`` argument of the geometry evaluation (None with `cull: none`): one view per frame the scored export uses (`idx % every
     == 0` with an estimated pose), placed at its ground-truth pose -- the reference lives in the ground-truth frame, and the estimate has
     been moved there by `geometry.align`.  "occlusion": each view carries the frame's sensor depth (ValueError naming the frame without
-    one; depths beyond the export block's `max_depth` see nothing); "frustum": no frame is read.  `opt`, `block`: `options` of the
-    `geometry` block and of the estimate's."""
+    one; depths beyond the export block's `max_depth` see nothing), or with `cull_depth: reference` the depth of the `reference` mesh
+    (rows, triangles) rendered at the view (ValueError when the reference is not a mesh; no frame is read); "frustum": no frame is read.
+    `opt`, `block`: `options` of the `geometry` block and of the estimate's."""
     if opt["cull"] == "none":
         return None
     poses, out = gt_poses(slam), []
-    for idx in range(len(slam.seq)):
-        if slam.estimate_pose_list[idx] is None or idx % block["every"] != 0:
-            continue
+    render = finish = None
+    if opt["cull"] == "occlusion" and opt["cull_depth"] == "reference":
+        if not geo._is_mesh(reference):
+            raise ValueError('geometry.cull_depth "reference": the reference is not a mesh (`reference: sensor` with `estimate: mesh`, or a PLY file with faces)')
+        render, finish = mesh_renderer(slam, opt, reference)
+    for idx in scored_frames(slam, block):
         depth = None
-        if opt["cull"] == "occlusion":
+        if render is not None:
+            depth = render(poses[idx].detach())
+        elif opt["cull"] == "occlusion":
             depth = slam.seq[idx][1]
             if depth is None:
                 raise ValueError(f'geometry.cull "occlusion": frame {idx} has no sensor depth')
         out.append((depth, poses[idx].detach()))
+    if finish is not None:
+        finish()
     return cl.spec(out, int(slam.cfg["desired_height"]), int(slam.cfg["desired_width"]), slam.cfg["cam"], near=opt["cull_near"], far=opt["cull_far"],
                    eps=opt["cull_eps"], min_views=opt["cull_min_views"], depth_max=float(block["max_depth"]))
 
@@ -222,7 +255,11 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     perfect tracker and map would have exported (ValueError without sensor depth) --, or the path of a PLY file: a point cloud or, with a
     face element, a mesh (`mesh.read_surface_ply`).  Meshes on either side are sampled at `geometry.density` samples per m^2;
     `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first; `geometry.cull` frustum / occlusion then
-    removes from both point sets what no camera of the run could have seen (`cull_views`, cull.py; metrics.json gains a `cull` block).
+    removes from both point sets what no camera of the run could have seen (`cull_views`, cull.py; metrics.json gains a `cull` block;
+    `geometry.cull_depth: reference` tests occlusion against the reference mesh rendered at each view instead of the sensor depth).
+    `geometry.depth_l1: true` (needs `estimate: mesh` and a mesh as the reference) also renders both meshes -- the unculled ones, the
+    estimate after `geometry.align` -- to depth images at the same views over `cull_near` .. `cull_far` (mesh_depth.py) and writes their
+    depth L1 as the `depth_l1` block of metrics.json and the per-view table and frame indices to `path/depth_l1.npz`.
     With `mesh.clean` small / largest the estimate mesh and the `reference: sensor` mesh come cleaned from their builder (a reference
     file is left as it is) and metrics.json gains a `mesh_clean` block.  Writes `path/metrics.json`,
     `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); arguments left None come from the `geometry` config block.  HIP
@@ -247,20 +284,37 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
         move = lambda rows: geo.align_rows(rows, slam.estimate_pose_list[:len(slam.seq)], gt_poses(slam), align)
         est = (move(est[0]), est[1]) if estimate == "mesh" else move(est)
     ref = build(dict(block, source="sensor"), gt_poses(slam), "reference") if reference == "sensor" else ms.read_surface_ply(reference)
-    culled = {} if opt["cull"] == "none" else {"cull": cull_views(slam, opt, block)}
+    if opt["depth_l1"] and not (estimate == "mesh" and geo._is_mesh(ref)):
+        raise ValueError("geometry.depth_l1 needs `estimate: mesh` and a mesh as the reference (`reference: sensor`, or a PLY file with faces)")
+    culled = {} if opt["cull"] == "none" else {"cull": cull_views(slam, opt, block, ref)}
     result = geo.compare(est, ref, device=slam.cfg["device"], threshold=float(opt["threshold"]), max_dist=float(opt["max_dist"]),
                          cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]), **culled)
+    if "cull" in culled and culled["cull"]["mode"] == "occlusion" and opt["cull_depth"] == "reference":
+        result["cull"] = dict(result["cull"], depth="reference")
     path = os.path.join(slam.cfg["outputdir"], "geometry") if path is None else path
     extra = {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]), "seed": int(opt["seed"])}
     if cleaned:
         result["mesh_clean"] = extra["mesh_clean"] = dict(cleaned, mode=block["clean"], min_triangles=block["clean_min_triangles"])
+    if opt["depth_l1"]:
+        frames, poses = scored_frames(slam, block), gt_poses(slam)
+        table, summary = md.depth_l1(est, ref, [poses[i].detach() for i in frames], int(slam.cfg["desired_height"]), int(slam.cfg["desired_width"]), slam.cfg["cam"],
+                                     near=opt["cull_near"], far=opt["cull_far"], device=slam.cfg["device"], max_pairs=opt["depth_max_pairs"])
+        result["depth_l1"] = extra["depth_l1"] = dict(summary, near=opt["cull_near"], far=opt["cull_far"])
+        result["depth_l1_table"] = table
     result["files"] = geo.write_outputs(path, result, extra)
+    if opt["depth_l1"]:
+        result["files"]["depth_l1"] = os.path.join(path, "depth_l1.npz")
+        np.savez(result["files"]["depth_l1"], table=table, frames=np.asarray(frames, dtype=np.int64))
     slam.geometry_eval = result      # what the last evaluation found
     t = result["table"]
     print(f"Geometry ({estimate} against {reference}): accuracy {result['accuracy'] * 100:.3f} cm, completion {result['completion'] * 100:.3f} cm, "
           f"completion ratio {result['completion_ratio'] * 100:.2f} % at {float(opt['threshold']) * 100:g} cm, F-score {result['fscore']:.4f}, Chamfer "
           f"{result['chamfer'] * 100:.3f} cm ({result['n_estimate']} / {result['n_reference']} points, clamped {int(t[0, 5])} / {int(t[1, 5])}) in "
           f"{result['files']['metrics']}")
+    if opt["depth_l1"]:
+        d = result["depth_l1"]
+        print(f"Depth L1 ({d['views']} views, {d['empty_views']} empty): {d['mean'] * 100:.3f} cm (pooled {d['pooled'] * 100:.3f} cm, rmse {d['rmse'] * 100:.3f} cm, max "
+              f"{d['max'] * 100:.3f} cm, coverage {d['coverage'] * 100:.2f} %) in {result['files']['depth_l1']}")
     return result
 
 
