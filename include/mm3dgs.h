@@ -576,6 +576,74 @@ int mm3dgs_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void
                           const void* work, void* rows /*[vcap] x 16 bytes*/, uint64_t vcap, void* triangles /*[tcap] x int32[3]*/,
                           uint64_t tcap, uint64_t* counters /*[8], device*/, void* stream);
 
+/* ---- the same volume as voxel blocks: storage only where a depth pixel puts the truncation band --------------------------------------
+ * The dense volume pays for the whole box; a surface occupies O(area / voxel^2) of its O(volume / voxel^3) samples.  Here sample (i, j, k)
+ * in Z^3 (signed) sits at anchor + voxel (i, j, k), evaluated in double in exactly that form (anchor: host double[3]); storage is allocated
+ * in blocks of 8 x 8 x 8 samples, block b = floor(index / 8) per axis with |b| < 2^20, named by the key (bz + 2^20) << 42 | (by + 2^20) <<
+ * 21 | (bx + 2^20): ascending keys are blocks in z-major raster order; all ones is the empty key.  Two passes: every view is reserved, the
+ * block set is frozen (list, the caller's sort, index), then every view is integrated; a sample outside the frozen set is never touched,
+ * and every sample of a reserved block carries exactly the value the dense volume holds at that position (one shared device function).
+ * All calls need trunc <= 16 voxel; max_blocks and n are 1 .. 2^21 (2^30 samples: 32-bit bases, int32 indices).
+ *
+ * table: mm3dgs_tsdf_blocks_table_bytes(max_blocks) bytes of device memory, 8-byte aligned, the caller's: a power of two >= 2 max_blocks
+ * slots of 64-bit keys, a 32-bit rank per slot, and per-256-slot counts; 0 for a max_blocks the calls reject.
+ * counters: uint64[8] on the device, cumulative since the reset: [0] views reserved, [1] valid pixels, [2] (pixel, block) pairs, [3]
+ * distinct blocks claimed, [4] dropped: pairs whose probe window (128 slots) held no room plus blocks claimed beyond max_blocks, [5]
+ * pixels out of range, [6] errors of the last mm3dgs_tsdf_blocks_index, [7] 0.  [4] != 0 means the block set is incomplete.
+ * mm3dgs_tsdf_blocks_reset: every key empty, every rank none, the counters 0.
+ * mm3dgs_tsdf_blocks_reserve: one launch per view, one lane per pixel; the only thing that decides which blocks exist.  A pixel (u, v) that
+ * passes the point cloud's validity test with depth d is lifted to its world point P (the point cloud's rule, in double, not rounded); with
+ *   ax = (|u - cx| trunc + (d + trunc) / 2) / |fx|,  ay = (|v - cy| trunc + (d + trunc) / 2) / |fy|,  R = sqrt(ax^2 + ay^2 + trunc^2)
+ * every block from floor(floor((P - R - anchor) / voxel) / 8) to floor(ceil((P + R - anchor) / voxel) / 8) per axis is claimed (64-bit
+ * atomicCAS where an agent-scope load read empty, linear probing, at most 128 probes).  A sample the integration updates through that
+ * pixel with |sdf| <= trunc lies within R of P: |z - d| <= trunc, the nearest-pixel projection is at most half a pixel off, and the ray's
+ * slope; floor and ceil leave a whole sample of slack.  A box that leaves |b| < 2^20 or spans more than 8 blocks on an axis skips the
+ * pixel ([5]).  clip_or_null: host int[6] = the lowest and the highest block coordinate per axis a reservation may touch (mesh.bounds).
+ * Nothing outside the table and the counters is written.
+ * mm3dgs_tsdf_blocks_list: the table's keys into keys[0:cap] by count, scan and scatter, in slot order (unspecified: the caller sorts); a
+ * key whose place is at or beyond cap is not written.  Three launches.
+ * mm3dgs_tsdf_blocks_index: keys = the n sorted keys.  Writes each key's rank into its slot and neighbours int32 [n][27] (entry (dz + 1)
+ * 9 + (dy + 1) 3 + (dx + 1): the rank of the block at that offset, -1 for none; entry 13 is the block itself).  Keys that are not
+ * strictly ascending, an empty key or a key that is not in the table are counted in counters[6] (set by this call) and then nothing is
+ * indexed: neither a rank nor a neighbour is written.  Four launches.
+ * mm3dgs_tsdf_blocks_integrate: one launch per view, one workgroup per block, a wave of 64 lanes is one 8 x 8 z slice.  The pool is tsdf_w
+ * float2 [n][512] and rgb_w float4 [n][512], block r = the r-th sorted key, x fastest inside a block, zeros = empty.  The per-sample rule
+ * and the counters ([0] views, [1] distance updates, [2] colour updates; an array of its own, not the reservation's) are
+ * mm3dgs_tsdf_integrate's.  A block whose bounding sphere lies behind the camera or projects outside the image leaves early
+ * (conservatively).
+ * mm3dgs_tsdf_blocks_mesh_plan / _emit: the dense rule (known / inside / valid cube, Kuhn tetrahedra, vertex on edge (q, d), case table,
+ * winding) applied to the lattice that holds the pool's values in the reserved blocks and is unknown everywhere else: a cube or an edge at a
+ * block face reads the neighbour block, or unknown where there is none.  Vertices by block in ascending key, then by sample in raster
+ * order inside the block, then by d; triangles by block, then cube, then tetrahedron, then case.  Positions anchor + voxel (q + t d) with
+ * q the global sample index, in double, rounded once.  work (mm3dgs_tsdf_blocks_mesh_work_bytes(n)), counters, caps and what is written:
+ * as for mm3dgs_tsdf_mesh_plan / _emit over n 512 samples.  No atomic decides a position or an index.
+ * Every loop in every kernel is bounded (128 probes, 8^3 blocks of a pixel, 27 neighbours); no host synchronisation.
+ * -1 (nothing is launched): max_blocks or n of 0 or above 2^21; a NULL required pointer (silhouette and clip may be NULL; rows / triangles
+ * / keys with a cap of 0); H or W <= 0 or more than 2^28 pixels; voxel or trunc not finite or not positive, trunc > 16 voxel; an anchor
+ * that is not finite; fx or fy zero or not finite, cx or cy not finite; min_weight not a number; table, keys, tsdf_w, work or counters not
+ * 8-byte aligned, rgb_w or rows not 16-byte aligned, an image, the pose, neighbours or triangles not 4-byte aligned. */
+size_t mm3dgs_tsdf_blocks_table_bytes(uint64_t max_blocks);
+int mm3dgs_tsdf_blocks_reset(void* table, uint64_t max_blocks, uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_tsdf_blocks_reserve(int H, int W, double fx, double fy, double cx, double cy, const float* pose /*[7], device*/,
+                               const float* depth /*[H,W]*/, const float* silhouette_or_null /*[H,W]*/, float sil_min, float depth_max,
+                               const double* anchor /*host [3]*/, double voxel, double trunc, const int* clip_or_null /*host [6]*/, void* table,
+                               uint64_t max_blocks, uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_tsdf_blocks_list(void* table, uint64_t max_blocks, uint64_t* keys /*[cap], device*/, uint64_t cap, void* stream);
+int mm3dgs_tsdf_blocks_index(void* table, uint64_t max_blocks, const uint64_t* keys /*[n], sorted*/, uint64_t n, int32_t* neighbours /*[n][27]*/,
+                             uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_tsdf_blocks_integrate(int H, int W, double fx, double fy, double cx, double cy, const float* pose /*[7], device*/,
+                                 const float* color /*[3,H,W]*/, const float* depth /*[H,W]*/, const float* silhouette_or_null /*[H,W]*/,
+                                 float sil_min, float depth_max, const double* anchor /*host [3]*/, double voxel, double trunc,
+                                 const uint64_t* keys /*[n], sorted*/, uint64_t n, void* tsdf_w /*[n][512] float2*/, void* rgb_w /*[n][512] float4*/,
+                                 uint64_t* counters /*[8], device*/, void* stream);
+size_t mm3dgs_tsdf_blocks_mesh_work_bytes(uint64_t n);
+int mm3dgs_tsdf_blocks_mesh_plan(uint64_t n, const int32_t* neighbours /*[n][27]*/, const void* tsdf_w, float min_weight, void* work,
+                                 uint64_t* counters /*[8], device*/, void* stream);
+int mm3dgs_tsdf_blocks_mesh_emit(uint64_t n, const uint64_t* keys /*[n], sorted*/, const int32_t* neighbours /*[n][27]*/, const void* tsdf_w,
+                                 const void* rgb_w, const double* anchor /*host [3]*/, double voxel, const void* work,
+                                 void* rows /*[vcap] x 16 bytes*/, uint64_t vcap, void* triangles /*[tcap] x int32[3]*/, uint64_t tcap,
+                                 uint64_t* counters /*[8], device*/, void* stream);
+
 /* ---- geometry scores: exact truncated nearest-neighbour distances between two point sets, and area-uniform samples of a mesh --------
  * Host statement: mm3dgs_slam_amd/geometry.py (nn_distances_host, direction_row, sample_mesh_host).  A point set is [n] x 16 bytes
  * {float x, y, z; uint32 rgba} on the device, 16-byte aligned (the point cloud's rows); only the position is read.
@@ -919,8 +987,9 @@ const char* mm3dgs_last_error(void);
         point set that the views of a run could have seen, for the geometry scores); mm3dgs_mesh_clean_work_bytes / mm3dgs_mesh_components /
         mm3dgs_mesh_clean_plan / mm3dgs_mesh_clean_emit (the connected components of a triangle mesh and the mesh without its small
         pieces); mm3dgs_mesh_depth_work_bytes / mm3dgs_mesh_depth_render / mm3dgs_depth_compare_work_bytes / mm3dgs_depth_compare (a
-        triangle mesh rendered to a depth image from a camera, and the depth L1 of two such images); a caller that needs them looks the
-        symbols up */
+        triangle mesh rendered to a depth image from a camera, and the depth L1 of two such images); mm3dgs_tsdf_blocks_table_bytes /
+        mm3dgs_tsdf_blocks_reset / _reserve / _list / _index / _integrate / mm3dgs_tsdf_blocks_mesh_work_bytes / _mesh_plan / _mesh_emit
+        (the mesh export's volume as hashed 8 x 8 x 8 voxel blocks, mesh.volume: sparse); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

@@ -108,6 +108,17 @@ _SIGS = {
     "mm3dgs_tsdf_mesh_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mm3dgs_tsdf_mesh_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, _P]),
     "mm3dgs_tsdf_mesh_emit": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_double), C.c_double, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
+    "mm3dgs_tsdf_blocks_table_bytes": (C.c_size_t, [C.c_uint64]),
+    "mm3dgs_tsdf_blocks_reset": (C.c_int, [_P, C.c_uint64, _P, _P]),
+    "mm3dgs_tsdf_blocks_reserve": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, C.c_float, C.c_float,
+                                             C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_int), _P, C.c_uint64, _P, _P]),
+    "mm3dgs_tsdf_blocks_list": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _P]),
+    "mm3dgs_tsdf_blocks_index": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, _P, _P, _P]),
+    "mm3dgs_tsdf_blocks_integrate": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.c_float, C.c_float,
+                                               C.POINTER(C.c_double), C.c_double, C.c_double, _P, C.c_uint64, _P, _P, _P, _P]),
+    "mm3dgs_tsdf_blocks_mesh_work_bytes": (C.c_size_t, [C.c_uint64]),
+    "mm3dgs_tsdf_blocks_mesh_plan": (C.c_int, [C.c_uint64, _P, _P, C.c_float, _P, _P, _P]),
+    "mm3dgs_tsdf_blocks_mesh_emit": (C.c_int, [C.c_uint64, _P, _P, _P, _P, C.POINTER(C.c_double), C.c_double, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
     "mm3dgs_nn_grid_work_bytes": (C.c_size_t, [C.c_uint64, C.c_int, C.c_int, C.c_int]),
     "mm3dgs_nn_grid_build": (C.c_int, [C.c_uint64, _P, C.c_double, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "mm3dgs_nn_query_work_bytes": (C.c_size_t, [C.c_uint64]),

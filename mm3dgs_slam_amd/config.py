@@ -92,6 +92,14 @@ GEOMETRY_DEPTH = {"depth_l1": False, "cull_depth": "sensor", "depth_max_pairs": 
 # mesh.voxel (a piece of a given size has more triangles at a finer voxel)
 MESH_CLEAN = {"clean": "none", "clean_min_triangles": 100}
 
+# Further optional keys of the `mesh` block (merged the same way): `volume` dense / sparse.  dense (the default) is the lattice over the
+# box of everything the cameras saw, 24 bytes per sample, capped by max_voxels.  sparse allocates 8 x 8 x 8-sample blocks only where a depth
+# pixel puts the truncation band (mesh.SparseTsdfVolume, mm3dgs_tsdf_blocks_*): a reservation pass over the views replaces the bounds
+# pass, max_voxels is not consulted, the lattice is anchored at the world origin, trunc may be at most 16 voxel, and at most max_blocks
+# blocks (1 .. 2^21; 12 KiB each) are held -- more is an error that names the key.  max_blocks: 2^18 (3 GiB of pool when all are used) is a
+# placeholder, not a measured default
+MESH_VOLUME = {"volume": "dense", "max_blocks": 1 << 18}
+
 # configs/UTMM.yml's hot-path settings that differ from TUM.yml (BASELINE.json configs[2]: RGB-D + IMU): 640x330, intrinsics of the
 # 1280x660 sensor scaled by 1/2 (gradslam_datasets/datautils.py:73-118), isotropic Gaussians, IMU dead-reckoning for the pose
 # prediction, Pearson term in tracking, 0.002 pose learning rates, size threshold 200.

@@ -859,6 +859,113 @@ int mm3dgs_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void
   return check_launch("tsdf_mesh_emit");
 }
 
+// ---- the same as a voxel-block volume (tsdf_sparse.hip) ----------------------------------------------------------------------------
+#define TSDF_MAX_BLOCKS ((uint64_t)1 << 21)      // 2^30 samples: 32-bit bases, int32 indices
+static bool tsdf_blocks_ok(uint64_t n) { return n >= 1 && n <= TSDF_MAX_BLOCKS; }
+// the checks every call with a view shares; `who` names the call
+static int tsdf_blocks_view(const char* who, int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
+                            const float* sil, float sil_min, float depth_max, const double* anchor, double voxel, double trunc, TsdfView& v) {
+  if (H <= 0 || W <= 0) return fail(-1, "%s: H = %d, W = %d (both must be positive)", who, H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "%s: %d x %d has more than 2^28 pixels", who, H, W);
+  if (!depth || !pose || !anchor) return fail(-1, "%s: NULL argument (depth, pose and anchor are required)", who);
+  if (!(voxel > 0.0) || !isfinite(voxel) || !(trunc > 0.0) || !isfinite(trunc)) return fail(-1, "%s: voxel = %g, trunc = %g (both must be finite and positive)", who, voxel, trunc);
+  if (!(trunc <= 16.0 * voxel)) return fail(-1, "%s: trunc = %g is more than 16 voxel = %g", who, trunc, 16.0 * voxel);
+  if (!tsdf_origin_ok(anchor)) return fail(-1, "%s: the anchor must be finite", who);
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "%s: fx = %g, fy = %g (finite, not 0)", who, fx, fy);
+  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "%s: cx = %g, cy = %g (must be finite)", who, cx, cy);
+  if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)sil | (uintptr_t)pose) & 3) return fail(-1, "%s: the images and the pose must be 4-byte aligned", who);
+  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
+  v.pose = pose; v.color = color; v.depth = depth; v.sil = sil;
+  v.sil_min = sil_min; v.depth_max = depth_max;
+  v.o[0] = anchor[0]; v.o[1] = anchor[1]; v.o[2] = anchor[2]; v.voxel = voxel; v.trunc = trunc;
+  v.nx = v.ny = v.nz = 0;
+  return 0;
+}
+
+size_t mm3dgs_tsdf_blocks_table_bytes(uint64_t max_blocks) { return tsdf_blocks_ok(max_blocks) ? tsdf_blocks_table_bytes(max_blocks, nullptr) : 0; }
+
+int mm3dgs_tsdf_blocks_reset(void* table, uint64_t max_blocks, uint64_t* counters, void* stream) {
+  if (!tsdf_blocks_ok(max_blocks)) return fail(-1, "tsdf_blocks_reset: max_blocks = %llu (1 .. 2^21)", (unsigned long long)max_blocks);
+  if (!table || !counters) return fail(-1, "tsdf_blocks_reset: NULL argument (table and counters are required)");
+  if (((uintptr_t)table | (uintptr_t)counters) & 7) return fail(-1, "tsdf_blocks_reset: table and counters must be 8-byte aligned");
+  launch_tsdf_blocks_reset(table, max_blocks, counters, (hipStream_t)stream);
+  return check_launch("tsdf_blocks_reset");
+}
+
+int mm3dgs_tsdf_blocks_reserve(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* depth, const float* silhouette_or_null,
+                               float sil_min, float depth_max, const double* anchor, double voxel, double trunc, const int* clip_or_null, void* table,
+                               uint64_t max_blocks, uint64_t* counters, void* stream) {
+  TsdfView v;
+  if (int rc = tsdf_blocks_view("tsdf_blocks_reserve", H, W, fx, fy, cx, cy, pose, nullptr, depth, silhouette_or_null, sil_min, depth_max, anchor, voxel, trunc, v)) return rc;
+  if (!tsdf_blocks_ok(max_blocks)) return fail(-1, "tsdf_blocks_reserve: max_blocks = %llu (1 .. 2^21)", (unsigned long long)max_blocks);
+  if (!table || !counters) return fail(-1, "tsdf_blocks_reserve: NULL argument (table and counters are required)");
+  if (((uintptr_t)table | (uintptr_t)counters) & 7) return fail(-1, "tsdf_blocks_reserve: table and counters must be 8-byte aligned");
+  TsdfBlockClip clip;
+  for (int a = 0; a < 3; a++) {
+    clip.lo[a] = clip_or_null ? clip_or_null[a] : -(1 << 20);
+    clip.hi[a] = clip_or_null ? clip_or_null[3 + a] : (1 << 20);
+  }
+  launch_tsdf_blocks_reserve(v, clip, table, max_blocks, counters, (hipStream_t)stream);
+  return check_launch("tsdf_blocks_reserve");
+}
+
+int mm3dgs_tsdf_blocks_list(void* table, uint64_t max_blocks, uint64_t* keys, uint64_t cap, void* stream) {
+  if (!tsdf_blocks_ok(max_blocks)) return fail(-1, "tsdf_blocks_list: max_blocks = %llu (1 .. 2^21)", (unsigned long long)max_blocks);
+  if (!table || (!keys && cap)) return fail(-1, "tsdf_blocks_list: NULL argument (table is required; keys unless cap is 0)");
+  if (((uintptr_t)table | (uintptr_t)keys) & 7) return fail(-1, "tsdf_blocks_list: table and keys must be 8-byte aligned");
+  launch_tsdf_blocks_list(table, max_blocks, keys, cap, (hipStream_t)stream);
+  return check_launch("tsdf_blocks_list");
+}
+
+int mm3dgs_tsdf_blocks_index(void* table, uint64_t max_blocks, const uint64_t* keys, uint64_t n, int32_t* neighbours, uint64_t* counters, void* stream) {
+  if (!tsdf_blocks_ok(max_blocks) || !tsdf_blocks_ok(n))
+    return fail(-1, "tsdf_blocks_index: max_blocks = %llu, n = %llu (both 1 .. 2^21)", (unsigned long long)max_blocks, (unsigned long long)n);
+  if (!table || !keys || !neighbours || !counters) return fail(-1, "tsdf_blocks_index: NULL argument (table, keys, neighbours and counters are required)");
+  if (((uintptr_t)table | (uintptr_t)keys | (uintptr_t)counters) & 7) return fail(-1, "tsdf_blocks_index: table, keys and counters must be 8-byte aligned");
+  if ((uintptr_t)neighbours & 3) return fail(-1, "tsdf_blocks_index: neighbours must be 4-byte aligned");
+  launch_tsdf_blocks_index(table, max_blocks, keys, n, neighbours, counters, (hipStream_t)stream);
+  return check_launch("tsdf_blocks_index");
+}
+
+int mm3dgs_tsdf_blocks_integrate(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
+                                 const float* silhouette_or_null, float sil_min, float depth_max, const double* anchor, double voxel, double trunc,
+                                 const uint64_t* keys, uint64_t n, void* tsdf_w, void* rgb_w, uint64_t* counters, void* stream) {
+  TsdfView v;
+  if (int rc = tsdf_blocks_view("tsdf_blocks_integrate", H, W, fx, fy, cx, cy, pose, color, depth, silhouette_or_null, sil_min, depth_max, anchor, voxel, trunc, v)) return rc;
+  if (!tsdf_blocks_ok(n)) return fail(-1, "tsdf_blocks_integrate: n = %llu blocks (1 .. 2^21)", (unsigned long long)n);
+  if (!color || !keys || !tsdf_w || !rgb_w || !counters) return fail(-1, "tsdf_blocks_integrate: NULL argument (color, keys, tsdf_w, rgb_w and counters are required)");
+  if ((uintptr_t)rgb_w & 15) return fail(-1, "tsdf_blocks_integrate: rgb_w must be 16-byte aligned");
+  if (((uintptr_t)tsdf_w | (uintptr_t)keys | (uintptr_t)counters) & 7) return fail(-1, "tsdf_blocks_integrate: tsdf_w, keys and counters must be 8-byte aligned");
+  launch_tsdf_blocks_integrate(v, keys, n, tsdf_w, rgb_w, counters, (hipStream_t)stream);
+  return check_launch("tsdf_blocks_integrate");
+}
+
+size_t mm3dgs_tsdf_blocks_mesh_work_bytes(uint64_t n) { return tsdf_blocks_ok(n) ? tsdf_blocks_mesh_work_bytes(n) : 0; }
+
+int mm3dgs_tsdf_blocks_mesh_plan(uint64_t n, const int32_t* neighbours, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, void* stream) {
+  if (!tsdf_blocks_ok(n)) return fail(-1, "tsdf_blocks_mesh_plan: n = %llu blocks (1 .. 2^21)", (unsigned long long)n);
+  if (!neighbours || !tsdf_w || !work || !counters) return fail(-1, "tsdf_blocks_mesh_plan: NULL argument (neighbours, tsdf_w, work and counters are required)");
+  if (!(min_weight == min_weight)) return fail(-1, "tsdf_blocks_mesh_plan: min_weight is not a number");
+  if (((uintptr_t)tsdf_w | (uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "tsdf_blocks_mesh_plan: tsdf_w, work and counters must be 8-byte aligned");
+  if ((uintptr_t)neighbours & 3) return fail(-1, "tsdf_blocks_mesh_plan: neighbours must be 4-byte aligned");
+  launch_tsdf_blocks_mesh_plan(n, neighbours, tsdf_w, min_weight, work, counters, (hipStream_t)stream);
+  return check_launch("tsdf_blocks_mesh_plan");
+}
+
+int mm3dgs_tsdf_blocks_mesh_emit(uint64_t n, const uint64_t* keys, const int32_t* neighbours, const void* tsdf_w, const void* rgb_w, const double* anchor,
+                                 double voxel, const void* work, void* rows, uint64_t vcap, void* triangles, uint64_t tcap, uint64_t* counters, void* stream) {
+  if (!tsdf_blocks_ok(n)) return fail(-1, "tsdf_blocks_mesh_emit: n = %llu blocks (1 .. 2^21)", (unsigned long long)n);
+  if (!keys || !neighbours || !tsdf_w || !rgb_w || !anchor || !work || !counters || (!rows && vcap) || (!triangles && tcap))
+    return fail(-1, "tsdf_blocks_mesh_emit: NULL argument (keys, neighbours, tsdf_w, rgb_w, anchor, work and counters are required; rows and triangles unless their cap is 0)");
+  if (!(voxel > 0.0) || !isfinite(voxel)) return fail(-1, "tsdf_blocks_mesh_emit: voxel = %g (must be finite and positive)", voxel);
+  if (!tsdf_origin_ok(anchor)) return fail(-1, "tsdf_blocks_mesh_emit: the anchor must be finite");
+  if (((uintptr_t)rgb_w | (uintptr_t)rows) & 15) return fail(-1, "tsdf_blocks_mesh_emit: rgb_w and rows must be 16-byte aligned");
+  if (((uintptr_t)tsdf_w | (uintptr_t)keys | (uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "tsdf_blocks_mesh_emit: tsdf_w, keys, work and counters must be 8-byte aligned");
+  if (((uintptr_t)triangles | (uintptr_t)neighbours) & 3) return fail(-1, "tsdf_blocks_mesh_emit: triangles and neighbours must be 4-byte aligned");
+  launch_tsdf_blocks_mesh_emit(n, keys, neighbours, tsdf_w, rgb_w, anchor, voxel, work, rows, vcap, triangles, tcap, counters, (hipStream_t)stream);
+  return check_launch("tsdf_blocks_mesh_emit");
+}
+
 // ---- geometry scores (geometry.hip) ----------------------------------------------------------------------------------------------
 #define NN_MAX_ROWS ((uint64_t)1 << 30)
 #define NN_MAX_CELLS ((size_t)1 << 26)

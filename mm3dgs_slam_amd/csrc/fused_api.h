@@ -155,6 +155,21 @@ void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_
 void launch_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s);
 void launch_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void* rgb_w, const double* origin, double voxel, const void* work, void* rows,
                            uint64_t vcap, void* tris, uint64_t tcap, uint64_t* counters, hipStream_t s);
+// the same as a voxel-block volume (tsdf_sparse.hip): 8 x 8 x 8-sample blocks named by 63-bit keys in the caller's open-addressing table
+// ({uint64 key} x slots, {uint32 rank} x slots, per-256 counts), reserved per view, listed, and -- once the caller has sorted the keys --
+// indexed; the pool is tsdf_w float2 [n][512], rgb_w float4 [n][512] in the order of the sorted keys.  TsdfView: o = the anchor, nx / ny /
+// nz unused.  Sizes, pointers, trunc <= 16 voxel, max_blocks and n <= 2^21: as the entry points have checked
+struct TsdfBlockClip { int lo[3], hi[3]; };      // the block coordinates a reservation may touch, inclusive
+size_t tsdf_blocks_table_bytes(uint64_t max_blocks, uint64_t* slots);
+void launch_tsdf_blocks_reset(void* table, uint64_t max_blocks, uint64_t* counters, hipStream_t s);
+void launch_tsdf_blocks_reserve(const TsdfView& v, const TsdfBlockClip& clip, void* table, uint64_t max_blocks, uint64_t* counters, hipStream_t s);
+void launch_tsdf_blocks_list(void* table, uint64_t max_blocks, uint64_t* keys, uint64_t cap, hipStream_t s);
+void launch_tsdf_blocks_index(void* table, uint64_t max_blocks, const uint64_t* keys, uint64_t n, int* neighbours, uint64_t* counters, hipStream_t s);
+void launch_tsdf_blocks_integrate(const TsdfView& v, const uint64_t* keys, uint64_t n, void* tsdf_w, void* rgb_w, uint64_t* counters, hipStream_t s);
+size_t tsdf_blocks_mesh_work_bytes(uint64_t n);
+void launch_tsdf_blocks_mesh_plan(uint64_t n, const int* neighbours, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s);
+void launch_tsdf_blocks_mesh_emit(uint64_t n, const uint64_t* keys, const int* neighbours, const void* tsdf_w, const void* rgb_w, const double* anchor, double voxel,
+                                  const void* work, void* rows, uint64_t vcap, void* tris, uint64_t tcap, uint64_t* counters, hipStream_t s);
 // geometry scores (geometry.hip): a uniform grid over a reference point set (16-byte rows), the exact truncated nearest-neighbour distance
 // of every query row with one row of eight figures, and area-uniform samples of a triangle mesh; sizes, pointers, cell, max_dist, rmax =
 // ceil(max_dist / cell) and density as the entry points have checked them (gx gy gz <= 2^26, at most 2^30 rows, rmax <= 2^20)

@@ -17,11 +17,9 @@
 //                           and per-cube triangle base).  Emit: tm_vertex (one 16-byte row per vertex at base[q] + popcount(mask[q] below d)),
 //                           tm_triangle (int32[3] per triangle, by tetrahedron then case order).  No atomic decides a position or an index.
 #include <math.h>
-#include "block_ops.h"
-#include "fused_api.h"
-#include "view_pixel.h"
+#include "tsdf_sample.h"      // the per-sample update, the case tables and the work layout (shared with tsdf_sparse.hip)
 
-#define TB 256
+#define TB TM_TB
 
 // ---- integration ----------------------------------------------------------------------------------------------------------------
 #define TZ 8      // z slices per workgroup: one add per workgroup and counter instead of one per wave and slice (every add lands on the same word)
@@ -44,32 +42,8 @@ tsdf_integrate_kernel(TsdfView v, float2* __restrict__ tsdf_w, float4* __restric
     const double pw0 = v.o[0] + v.voxel * (double)i, pw1 = v.o[1] + v.voxel * (double)j;
     for (int k = k0; k < k0 + TZ && k < v.nz; k++) {
       const double pw2 = v.o[2] + v.voxel * (double)k;
-      const double z = g.R[2][0] * pw0 + g.R[2][1] * pw1 + g.R[2][2] * pw2 + g.t[2];
-      if (!(z > 0.0)) continue;
-      const double x = g.R[0][0] * pw0 + g.R[0][1] * pw1 + g.R[0][2] * pw2 + g.t[0];
-      const double y = g.R[1][0] * pw0 + g.R[1][1] * pw1 + g.R[1][2] * pw2 + g.t[1];
-      const double fu = floor(v.fx * x / z + v.cx + 0.5), fv = floor(v.fy * y / z + v.cy + 0.5);
-      if (!(fu >= 0.0 && fu < (double)v.W && fv >= 0.0 && fv < (double)v.H)) continue;      // (a NaN fails)
-      const size_t pix = (size_t)(int)fv * (size_t)v.W + (size_t)(int)fu;
-      float d;
-      if (!view_pixel_valid(v.depth, v.sil, v.sil_min, v.depth_max, pix, d)) continue;
-      const double sdf = (double)d - z;
-      if (sdf < -v.trunc) continue;
-      // the sample is seen: from here on the volume is read and written
-      double s = sdf / v.trunc;
-      s = s < 1.0 ? s : 1.0;
       const size_t q = ((size_t)k * (size_t)v.ny + (size_t)j) * (size_t)v.nx + (size_t)i;
-      const float2 tw = tsdf_w[q];
-      const double T = (double)tw.x, W = (double)tw.y;
-      tsdf_w[q] = make_float2((float)((T * W + s) / (W + 1.0)), (float)(W + 1.0));      // one 8-byte store
-      nupd++;
-      if (sdf <= v.trunc) {
-        const float4 c = rgb_w[q];
-        const double Cw = (double)c.w;
-        rgb_w[q] = make_float4((float)(((double)c.x * Cw + (double)v.color[pix]) / (Cw + 1.0)), (float)(((double)c.y * Cw + (double)v.color[hw + pix]) / (Cw + 1.0)),
-                               (float)(((double)c.z * Cw + (double)v.color[2 * hw + pix]) / (Cw + 1.0)), (float)(Cw + 1.0));      // one 16-byte store
-        ncup++;
-      }
+      tsdf_sample_update(v, g, hw, pw0, pw1, pw2, tsdf_w + q, rgb_w + q, nupd, ncup);
     }
   }
   const uint32_t nn[2] = {nupd, ncup};
@@ -85,44 +59,9 @@ void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_
 }
 
 // ---- marching tetrahedra --------------------------------------------------------------------------------------------------------
-// work = [256 B header: uint64 vertices, triangles][state byte per sample: bit 0 known, bit 1 inside][cube byte per sample: 0x80 valid | triangles]
-//        [edge mask byte per sample: bit d][uint32 vertex base per sample][uint32 triangle base per cube][per-256 vertex counts][per-256 triangle counts]
-struct TmWork { unsigned long long* hdr; uint8_t* state; uint8_t* cube; uint8_t* vmask; uint32_t* vbase; uint32_t* tbase; uint32_t* vcounts; uint32_t* tcounts; };
-static size_t tm_nb(size_t n) { return (n + TB - 1) / TB; }
-static TmWork tm_work(void* base, size_t n, size_t* bytes = nullptr) {
-  Carve c = {(uintptr_t)base};
-  TmWork w;
-  w.hdr = c.take<unsigned long long>(2);
-  w.state = c.take<uint8_t>(n);
-  w.cube = c.take<uint8_t>(n);
-  w.vmask = c.take<uint8_t>(n);
-  w.vbase = c.take<uint32_t>(n);
-  w.tbase = c.take<uint32_t>(n);
-  w.vcounts = c.take<uint32_t>(tm_nb(n));
-  w.tcounts = c.take<uint32_t>(tm_nb(n));
-  if (bytes) *bytes = c.at;
-  return w;
-}
 size_t tsdf_mesh_work_bytes(int nx, int ny, int nz) { size_t b; tm_work(nullptr, (size_t)nx * (size_t)ny * (size_t)nz, &b); return b; }
 
 struct TmGrid { int nx, ny, nz; size_t n; };
-
-// The triangles of a positively oriented tetrahedron by its 4-bit inside mask (bit v: vertex v of the path is inside), as
-// count | six 3-bit edge ids << 2; edges 0..5 = the vertex pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  One vertex apart: the triangle of its
-// three edges; two and two: the quadrilateral (a,c) (a,d) (b,d) (b,c) as two triangles; wound so that the normal points from the inside
-// vertices to the outside ones (mesh.py derives the same table by rule and checks the winding numerically).
-#define TM1(a, b, c) (1u | (a##u << 2) | (b##u << 5) | (c##u << 8))
-#define TM2(a, b, c, d, e, f) (2u | (a##u << 2) | (b##u << 5) | (c##u << 8) | (d##u << 11) | (e##u << 14) | (f##u << 17))
-__device__ const uint32_t TM_CASES[16] = {0u, TM1(0, 1, 2), TM1(0, 4, 3), TM2(1, 2, 4, 1, 4, 3), TM1(1, 3, 5), TM2(0, 5, 2, 0, 3, 5), TM2(0, 4, 5, 0, 5, 1),
-                                          TM1(2, 4, 5), TM1(2, 5, 4), TM2(0, 1, 5, 0, 5, 4), TM2(0, 5, 3, 0, 2, 5), TM1(1, 5, 3), TM2(1, 3, 4, 1, 4, 2),
-                                          TM1(0, 3, 4), TM1(0, 2, 1), 0u};
-// cube corners (bit 0 x, bit 1 y, bit 2 z) of the path's two middle vertices, by tetrahedron = axis permutation in lexicographic order:
-// (x,y,z) (x,z,y) (y,x,z) (y,z,x) (z,x,y) (z,y,x); the odd permutations (1, 2, 5) mirror the tetrahedron: their triangles swap two corners
-__device__ const uint8_t TM_MID1[6] = {1, 1, 2, 2, 4, 4};
-__device__ const uint8_t TM_MID2[6] = {3, 5, 3, 6, 5, 6};
-#define TM_ODD 0x26u
-__device__ const uint8_t TM_EDGE_LO[6] = {0, 0, 0, 1, 1, 2};
-__device__ const uint8_t TM_EDGE_HI[6] = {1, 2, 3, 2, 3, 3};
 
 __device__ __forceinline__ size_t tm_corner(const TmGrid& g, unsigned c) {
   return (size_t)(c & 1u) + (size_t)((c >> 1) & 1u) * (size_t)g.nx + (size_t)((c >> 2) & 1u) * (size_t)g.nx * (size_t)g.ny;
@@ -134,9 +73,9 @@ __device__ __forceinline__ void tm_coords(const TmGrid& g, size_t i, int& x, int
   z = (int)(i / ((size_t)g.nx * (size_t)g.ny));
 }
 
-__global__ void __launch_bounds__(TB) tm_state_kernel(TmGrid g, const float2* __restrict__ tsdf_w, float min_weight, uint8_t* __restrict__ state) {
+__global__ void __launch_bounds__(TB) tm_state_kernel(size_t n, const float2* __restrict__ tsdf_w, float min_weight, uint8_t* __restrict__ state) {
   const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-  if (i >= g.n) return;
+  if (i >= n) return;
   const float2 tw = tsdf_w[i];
   state[i] = (uint8_t)((tw.y >= min_weight ? 1 : 0) | (tw.x < 0.f ? 2 : 0));      // (a NaN weight is not known)
 }
@@ -151,10 +90,6 @@ __device__ __forceinline__ bool tm_cube_corners(const TmGrid& g, const uint8_t* 
     inside |= ((s >> 1) & 1u) << c;
   }
   return (known & 1u) != 0;
-}
-
-__device__ __forceinline__ unsigned tm_tet_mask(unsigned inside, int k) {
-  return (inside & 1u) | (((inside >> TM_MID1[k]) & 1u) << 1) | (((inside >> TM_MID2[k]) & 1u) << 2) | (((inside >> 7) & 1u) << 3);
 }
 
 __global__ void __launch_bounds__(TB) tm_cube_kernel(TmGrid g, const uint8_t* __restrict__ state, uint8_t* __restrict__ cube, uint32_t* __restrict__ tcounts) {
@@ -222,16 +157,26 @@ tm_scan_kernel(int nb, uint32_t* __restrict__ vcounts, uint32_t* __restrict__ tc
 }
 
 __global__ void __launch_bounds__(TB)
-tm_base_kernel(TmGrid g, const uint8_t* __restrict__ cube, const uint8_t* __restrict__ vmask, const uint32_t* __restrict__ vpre, const uint32_t* __restrict__ tpre,
+tm_base_kernel(size_t n, const uint8_t* __restrict__ cube, const uint8_t* __restrict__ vmask, const uint32_t* __restrict__ vpre, const uint32_t* __restrict__ tpre,
                uint32_t* __restrict__ vbase, uint32_t* __restrict__ tbase) {
   __shared__ uint32_t wv[TB / 64], wt[TB / 64];
   const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-  const uint32_t nv = i < g.n ? (uint32_t)__popc((unsigned)vmask[i]) : 0u, nt = i < g.n ? (uint32_t)(cube[i] & 0x7fu) : 0u;
+  const uint32_t nv = i < n ? (uint32_t)__popc((unsigned)vmask[i]) : 0u, nt = i < n ? (uint32_t)(cube[i] & 0x7fu) : 0u;
   const uint32_t iv = block_scan_incl(nv, wv), it = block_scan_incl(nt, wt);
-  if (i < g.n) {
+  if (i < n) {
     vbase[i] = vpre[blockIdx.x] + iv - nv;
     tbase[i] = tpre[blockIdx.x] + it - nt;
   }
+}
+
+void launch_tm_state(size_t n, const void* tsdf_w, float min_weight, const TmWork& w, hipStream_t s) {
+  hipLaunchKernelGGL(tm_state_kernel, dim3((unsigned)tm_nb(n)), dim3(TB), 0, s, n, (const float2*)tsdf_w, min_weight, w.state);
+}
+
+void launch_tm_scan_base(size_t n, const TmWork& w, uint64_t* counters, hipStream_t s) {
+  const unsigned nb = (unsigned)tm_nb(n);
+  hipLaunchKernelGGL(tm_scan_kernel, dim3(1), dim3(1024), 0, s, (int)nb, w.vcounts, w.tcounts, w.hdr, (unsigned long long*)counters);
+  hipLaunchKernelGGL(tm_base_kernel, dim3(nb), dim3(TB), 0, s, n, w.cube, w.vmask, w.vcounts, w.tcounts, w.vbase, w.tbase);
 }
 
 void launch_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s) {
@@ -239,14 +184,11 @@ void launch_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min
   g.nx = nx; g.ny = ny; g.nz = nz; g.n = (size_t)nx * (size_t)ny * (size_t)nz;
   const TmWork w = tm_work(work, g.n);
   const unsigned nb = (unsigned)tm_nb(g.n);
-  hipLaunchKernelGGL(tm_state_kernel, dim3(nb), dim3(TB), 0, s, g, (const float2*)tsdf_w, min_weight, w.state);
+  launch_tm_state(g.n, tsdf_w, min_weight, w, s);
   hipLaunchKernelGGL(tm_cube_kernel, dim3(nb), dim3(TB), 0, s, g, w.state, w.cube, w.tcounts);
   hipLaunchKernelGGL(tm_edge_kernel, dim3(nb), dim3(TB), 0, s, g, w.state, w.cube, w.vmask, w.vcounts);
-  hipLaunchKernelGGL(tm_scan_kernel, dim3(1), dim3(1024), 0, s, (int)nb, w.vcounts, w.tcounts, w.hdr, (unsigned long long*)counters);
-  hipLaunchKernelGGL(tm_base_kernel, dim3(nb), dim3(TB), 0, s, g, w.cube, w.vmask, w.vcounts, w.tcounts, w.vbase, w.tbase);
+  launch_tm_scan_base(g.n, w, counters, s);
 }
-
-struct TmEmit { double o[3], voxel; unsigned long long vcap, tcap; };
 
 __global__ void __launch_bounds__(TB)
 tm_vertex_kernel(TmGrid g, TmEmit e, const float2* __restrict__ tsdf_w, const float4* __restrict__ rgb_w, const uint8_t* __restrict__ vmask,

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import cull as cl, geometry as geo, mesh as ms, mesh_clean as mc, mesh_depth as md, pointcloud as pc
-from .config import _TUM, GEOMETRY_CULL, GEOMETRY_DEPTH, MESH_CLEAN
+from .config import _TUM, GEOMETRY_CULL, GEOMETRY_DEPTH, MESH_CLEAN, MESH_VOLUME
 
 
 def options(cfg, block, **overrides):
@@ -41,7 +41,7 @@ def options(cfg, block, **overrides):
         opt["depth_max_pairs"] = int(pairs)
         return opt
     if block == "mesh":
-        opt = dict(MESH_CLEAN, **opt)
+        opt = dict(MESH_VOLUME, **dict(MESH_CLEAN, **opt))
     opt["every"] = opt["every"] or cfg["mapping"]["kf_every"]
     opt.update((k, v) for k, v in overrides.items() if v is not None)
     every, voxel, source = int(opt["every"]), float(opt["voxel"]), str(opt["source"])
@@ -61,6 +61,15 @@ def options(cfg, block, **overrides):
             opt["clean_min_triangles"] = mc.check_options("small", opt["clean_min_triangles"])[1]
         except (TypeError, ValueError):
             raise ValueError(f"mesh.clean_min_triangles = {opt['clean_min_triangles']!r} (an integer, at least 1)") from None
+        opt["volume"] = str(opt["volume"] or "dense").lower()
+        if opt["volume"] not in ("dense", "sparse"):
+            raise ValueError(f"mesh.volume = {opt['volume']!r} (dense / sparse)")
+        blocks = opt["max_blocks"]
+        if isinstance(blocks, bool) or not isinstance(blocks, (int, np.integer)) or not 1 <= int(blocks) <= ms.MAX_BLOCKS:
+            raise ValueError(f"mesh.max_blocks = {blocks!r} (an integer, 1 .. 2^21)")
+        opt["max_blocks"] = int(blocks)
+        if opt["volume"] == "sparse" and not opt["trunc"] <= ms.MAX_TRUNC_VOXELS * voxel:
+            raise ValueError(f"mesh.trunc = {opt['trunc']} with mesh.volume: sparse (at most {ms.MAX_TRUNC_VOXELS} mesh.voxel = {ms.MAX_TRUNC_VOXELS * voxel})")
     return opt
 
 
@@ -182,6 +191,8 @@ def mesh_geometry(slam, opt, poses=None):
     small / largest the mesh is cleaned behind the extraction (mesh_clean.py) and the counters -- which stay those of the extraction --
     carry the cleaning's figures under `clean`."""
     voxel, trunc, cfg = opt["voxel"], opt["trunc"], slam.cfg
+    if opt.get("volume", "dense") == "sparse":
+        return sparse_mesh_geometry(slam, opt, poses)
     with torch.no_grad():
         if opt["bounds"] is None:
             box = mesh_bounds(slam, opt, poses)
@@ -201,6 +212,33 @@ def mesh_geometry(slam, opt, poses=None):
             counters = dict(counters, clean=dict(info, mode=opt["clean"], min_triangles=opt["clean_min_triangles"], vertices=int(rows.shape[0]),
                                                  triangles=int(triangles.shape[0])))
     return rows, triangles, counters, dims, origin
+
+
+def sparse_mesh_geometry(slam, opt, poses=None):
+    """`mesh_geometry` with `mesh.volume: sparse`: no bounds pass and no `mesh.max_voxels`; a reservation pass over the views decides which
+    8 x 8 x 8-sample blocks exist (`mesh.reserve_host`, mm3dgs_tsdf_blocks_reserve), the set is frozen, and a second pass over the same views
+    integrates them.  The same five values; the lattice sizes and the origin describe the block set's bounding lattice, and the counters
+    gain `blocks`, `pairs` and `volume_bytes`."""
+    cfg = slam.cfg
+    Volume = ms.SparseTsdfVolume if str(cfg["device"]).startswith("cuda") else ms.HostSparseTsdfVolume
+    with torch.no_grad():
+        volume = Volume(opt["voxel"], opt["trunc"], int(cfg["desired_height"]), int(cfg["desired_width"]), cfg["cam"], sil_min=float(opt["sil_min"]),
+                        depth_max=float(opt["max_depth"]), min_weight=float(opt["min_weight"]), max_blocks=opt["max_blocks"], bounds=opt["bounds"], device=cfg["device"])
+        n = 0
+        for _, depth, sil, pose in views(slam, opt["every"], opt["source"], "mesh", poses):
+            volume.reserve(depth, sil, pose)
+            n += 1
+        if n == 0:
+            raise ValueError("mesh export: no frame has an estimated pose")
+        volume.freeze()
+        for view in views(slam, opt["every"], opt["source"], "mesh", poses):
+            volume.add(*view)
+        rows, triangles, counters = volume.extract()
+        if opt.get("clean", "none") != "none":
+            rows, triangles, _, info = mc.clean(rows, triangles, opt["clean"], opt["clean_min_triangles"], device=cfg["device"])
+            counters = dict(counters, clean=dict(info, mode=opt["clean"], min_triangles=opt["clean_min_triangles"], vertices=int(rows.shape[0]),
+                                                 triangles=int(triangles.shape[0])))
+    return rows, triangles, counters, volume.dims, volume.origin
 
 
 def export_pointcloud(slam, path=None, every=None, voxel=None, source=None):
@@ -232,7 +270,9 @@ def export_mesh(slam, path=None, every=None, voxel=None, source=None):
     largest the removal of the small disconnected pieces (mesh_clean.py; the returned dict gains `clean`).  Writes `path/mesh.ply`
     (default `outputdir/mesh`; the format: `mesh.write_mesh_ply`).  One mm3dgs_tsdf_integrate call per view and one mm3dgs_tsdf_mesh_plan /
     _emit pair on a GPU, the host statement on `device: cpu`.  Returns the path, the counters and the lattice; raises ValueError when the
-    lattice exceeds `mesh.max_voxels`."""
+    lattice exceeds `mesh.max_voxels`.  With `mesh.volume: sparse` the volume is held in 8 x 8 x 8-sample blocks only where a view's
+    truncation band reaches (`sparse_mesh_geometry`): neither the bounds pass nor `mesh.max_voxels`; the returned dict gains `volume`,
+    `blocks`, `pairs` and `volume_bytes`; raises ValueError when more than `mesh.max_blocks` blocks are needed."""
     opt = options(slam.cfg, "mesh", every=every, voxel=voxel, source=source)
     path = os.path.join(slam.cfg["outputdir"], "mesh") if path is None else path
     rows, triangles, counters, dims, origin = mesh_geometry(slam, opt)
@@ -240,6 +280,9 @@ def export_mesh(slam, path=None, every=None, voxel=None, source=None):
     out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles), "counters": counters, "lattice": tuple(dims),
            "origin": origin.tolist(), "voxel": opt["voxel"], "trunc": opt["trunc"]}
     cleaned = ""
+    if opt["volume"] == "sparse":
+        out.update(volume="sparse", blocks=counters["blocks"], pairs=counters["pairs"], volume_bytes=counters["volume_bytes"])
+        cleaned = f"; sparse volume: {counters['blocks']} blocks from {counters['pairs']} (pixel, block) pairs, {counters['volume_bytes']} bytes"
     if "clean" in counters:
         out["clean"] = counters["clean"]
         cleaned = f"; {mc.summary(opt['clean'], opt['clean_min_triangles'], counters['clean'])}"

@@ -15,7 +15,10 @@ axis permutation, the same cut in every cube, so face diagonals agree between ne
 its weight is at least ``min_weight`` and *inside* if its distance is negative; a cube is *valid* if its 8 corners are known.  A surface
 vertex lies on a lattice edge that leaves a sample q in one of the 7 directions d in {0,1}^3 \\ {0} (d as a 3-bit number, x the low bit);
 the edge carries a vertex iff its endpoints differ in *inside* and at least one valid cube contains it.  Vertices are ordered by q in raster
-order, then by d; triangles by cube in raster order, then by tetrahedron, then by case order; the normal points from inside to outside."""
+order, then by d; triangles by cube in raster order, then by tetrahedron, then by case order; the normal points from inside to outside.
+
+With ``mesh.volume: sparse`` the volume is held in blocks of 8 x 8 x 8 samples, only where a view's truncation band reaches (``reserve_host``,
+``HostSparseTsdfVolume``, ``SparseTsdfVolume`` over ``csrc/tsdf_sparse.hip``): the statement stands above those classes."""
 from __future__ import annotations
 
 import numpy as np
@@ -124,12 +127,13 @@ def lattice_for(box, voxel, max_voxels):
 
 
 # ---- integration ----------------------------------------------------------------------------------------------------------------
-def integrate_host(tsdf_w, rgb_w, color, depth, sil, pose, fx, fy, cx, cy, origin, voxel, trunc, sil_min=0.0, depth_max=0.0, full=False):
+def integrate_host(tsdf_w, rgb_w, color, depth, sil, pose, fx, fy, cx, cy, origin, voxel, trunc, sil_min=0.0, depth_max=0.0, full=False, first=(0, 0, 0)):
     """One view into the volume, in place, in float64 from the float32 inputs.  Per sample: p_c = R p_w + t, skipped if z <= 0; pixel u =
     floor(fx x / z + cx + 0.5), v likewise (pixel centres at integer coordinates), skipped outside the image or where the pixel fails the
     point cloud's validity test; sdf = depth - z, skipped if sdf < -trunc; s = min(1, sdf / trunc); T <- (T W + s) / (W + 1), W <- W + 1,
     rounded to float32 once; the colour mean and its weight likewise, only if sdf <= trunc.  Returns (distance updates, colour updates);
-    with ``full`` also dict(upd, col: the masks [nz,ny,nx]; fu, fv: the pixel coordinates before the floor; sdf; z)."""
+    with ``full`` also dict(upd, col: the masks [nz,ny,nx]; fu, fv: the pixel coordinates before the floor; sdf; z).  ``first``: the
+    (signed) lattice index of the array's sample [0,0,0]: sample [k,j,i] sits at origin + voxel (first + (i, j, k))."""
     col = as_np(color, np.float32)
     d = as_np(depth, np.float32)
     H, W = d.shape
@@ -138,8 +142,10 @@ def integrate_host(tsdf_w, rgb_w, color, depth, sil, pose, fx, fy, cx, cy, origi
     R, t = pose_rotation(pose)
     o = np.asarray(origin, dtype=np.float64).reshape(3)
     voxel, trunc = float(voxel), float(trunc)
-    pw = [o[0] + voxel * np.arange(nx, dtype=np.float64)[None, None, :], o[1] + voxel * np.arange(ny, dtype=np.float64)[None, :, None],
-          o[2] + voxel * np.arange(nz, dtype=np.float64)[:, None, None]]
+    f = [int(a) for a in first]
+    pw = [o[0] + voxel * (f[0] + np.arange(nx, dtype=np.int64)).astype(np.float64)[None, None, :],
+          o[1] + voxel * (f[1] + np.arange(ny, dtype=np.int64)).astype(np.float64)[None, :, None],
+          o[2] + voxel * (f[2] + np.arange(nz, dtype=np.int64)).astype(np.float64)[:, None, None]]
     x, y, z = (R[a, 0] * pw[0] + R[a, 1] * pw[1] + R[a, 2] * pw[2] + t[a] for a in range(3))
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         fu = float(fx) * x / z + float(cx) + 0.5
@@ -178,11 +184,13 @@ def _shift(a, dz, dy, dx, fill):
     return b
 
 
-def mesh_host(tsdf_w, rgb_w, origin, voxel, min_weight=1.0, full=False):
+def mesh_host(tsdf_w, rgb_w, origin, voxel, min_weight=1.0, full=False, first=(0, 0, 0), where=False):
     """The mesh of a volume: (rows [V,4] int32 = {float32 x, y, z bits; rgba}, triangles [T,3] int32, counters int64 [8] = V, T, V, T, 0,
     0, 0, 0).  Vertex (q, d): t = T0 / (T0 - T1) of the distances at q and q + d, p = origin + voxel (q + t d), colour c0 + t (c1 - c0)
     of the endpoints' mean colours, all in float64, rounded once to float32; the colour bytes by ``quantise_colour``, alpha 255.  With
-    ``full`` also the float64 positions [V,3]."""
+    ``full`` also the float64 positions [V,3].  ``first``: the (signed) lattice index of the array's sample [0,0,0], so q = first + the
+    array index.  ``where``: also the flat array index of every vertex's sample q [V] and of every triangle's cube [T] (what a
+    reordering needs)."""
     tsdf_w, rgb_w = np.asarray(tsdf_w, dtype=np.float32), np.asarray(rgb_w, dtype=np.float32)
     nz, ny, nx = tsdf_w.shape[:3]
     check_lattice(nx, ny, nz)
@@ -222,11 +230,12 @@ def mesh_host(tsdf_w, rgb_w, origin, voxel, min_weight=1.0, full=False):
         q = np.flatnonzero((vm >> d) & 1)
         idx = vbase[q] + POPCOUNT[vm[q] & ((1 << d) - 1)]
         t = Tf[q] / (Tf[q] - Tf[q + stride(d)])
-        qi = np.stack([q % nx, (q // nx) % ny, q // (nx * ny)], 1).astype(np.float64)
+        qi = (np.stack([q % nx, (q // nx) % ny, q // (nx * ny)], 1) + np.array([int(a) for a in first], dtype=np.int64)[None, :]).astype(np.float64)
         dv = np.array([d & 1, (d >> 1) & 1, (d >> 2) & 1], dtype=np.float64)
         xyz[idx] = o[None, :] + voxel * (qi + t[:, None] * dv[None, :])
         with np.errstate(invalid="ignore"):
             rgb[idx] = Cf[q] + t[:, None] * (Cf[q + stride(d)] - Cf[q])
+    vq = np.repeat(np.arange(len(vm), dtype=np.int64), vcount)      # (a sample's vertices are consecutive, by d)
     rows = np.empty((V, 4), dtype=np.int32)
     rows[:, :3] = xyz.astype(np.float32).view(np.int32)
     with np.errstate(invalid="ignore"):
@@ -257,7 +266,11 @@ def mesh_host(tsdf_w, rgb_w, origin, voxel, min_weight=1.0, full=False):
             tris[tbase[q] + before[q] + s] = out
         before = before + per_tet[k]
     out = (rows, tris.astype(np.int32), np.array([V, Tn, V, Tn, 0, 0, 0, 0], dtype=np.int64))
-    return out + (xyz,) if full else out
+    if full:
+        out += (xyz,)
+    if where:
+        out += (vq, np.repeat(np.arange(len(tcount), dtype=np.int64), tcount))
+    return out
 
 
 # ---- checks on a mesh (tests, tools) ----------------------------------------------------------------------------------------------
@@ -368,8 +381,358 @@ class TsdfVolume:
         return rows[:V], tris[:T], _mesh_counters(totals[8:], m)
 
 
+# ---- the volume as voxel blocks (mesh.volume: sparse) ------------------------------------------------------------------------------------
+# One statement; the host path below and csrc/tsdf_sparse.hip both follow it.
+#   Lattice      sample (i, j, k) in Z^3 (signed) sits at anchor + voxel (i, j, k), in float64 exactly in that form; block b = floor(index /
+#                8) per axis, |b| < 2^20; key = (bz + 2^20) << 42 | (by + 2^20) << 21 | (bx + 2^20): ascending keys are blocks in z-major
+#                raster order.
+#   Reservation  per view, the only thing that decides which blocks exist.  A pixel (u, v) that passes ``valid_mask`` with depth d is lifted
+#                to its world point P (``backproject_host``'s rule, not rounded); ax = (|u - cx| trunc + (d + trunc) / 2) / |fx|, ay
+#                likewise, R = sqrt(ax^2 + ay^2 + trunc^2); per axis every block from floor(floor((P - R - anchor) / voxel) / 8) to
+#                floor(ceil((P + R - anchor) / voxel) / 8) is reserved (with ``mesh.bounds``: only the blocks that intersect the box).
+#                Why this R: a sample that the integration updates through (u, v) with |sdf| <= trunc has |z - d| <= trunc; its projection
+#                is at most half a pixel from (u, v), so |x - (u - cx) z / fx| <= z / (2 |fx|); with p_d the pixel's point at depth d,
+#                |x - x_d| <= |u - cx| |z - d| / |fx| + z / (2 |fx|) <= (|u - cx| trunc + (d + trunc) / 2) / |fx| = ax, likewise ay, and
+#                |z - d| <= trunc: the sample lies within R of P.  floor and ceil leave a whole sample of slack for roundoff.  A pixel
+#                whose box leaves |b| < 2^20 or spans more than 8 blocks on an axis is skipped and counted (trunc <= 16 voxel keeps a
+#                box of an ordinary view within 6).
+#   Two passes   all views are reserved, the set is frozen (keys sorted ascending; block r of the pool is the r-th key; the pool is tsdf_w
+#                [n,512,2] and rgb_w [n,512,4], x fastest inside a block), then all views are integrated: every sample of a reserved block
+#                carries exactly what the dense volume would hold there, every other sample is unknown (weight 0) and never touched.
+#   Mesh         the dense rule applied to that masked lattice; vertices by block in ascending key, then by sample in raster order inside
+#                the block, then by d; triangles by block, then cube, then tetrahedron, then case.
+# Consequence: the sparse mesh is the dense mesh minus the triangles of cubes that have a corner in an unreserved block -- a cube that
+# needs a negative sample next to a block no pixel's band reached.
+BLOCK = 8
+BLOCK_BIAS = 1 << 20
+MAX_BLOCKS = 1 << 21
+MAX_TRUNC_VOXELS = 16
+MAX_BOX = 8                      # blocks a pixel's box may span per axis
+BLOCK_BYTES = 512 * 24
+RESERVE_COUNTERS = ("views", "valid", "pairs", "blocks", "dropped", "out_of_range", "index_errors")
+
+
+def block_keys(blocks):
+    """int64 keys of block coordinates [n,3] = (bx, by, bz), each |b| < 2^20."""
+    b = np.asarray(blocks, dtype=np.int64).reshape(-1, 3) + BLOCK_BIAS
+    return (b[:, 2] << 42) | (b[:, 1] << 21) | b[:, 0]
+
+
+def key_blocks(keys):
+    """Block coordinates [n,3] = (bx, by, bz) of int64 keys."""
+    k = np.asarray(keys).astype(np.int64).reshape(-1)
+    return np.stack([k & 0x1fffff, (k >> 21) & 0x1fffff, (k >> 42) & 0x1fffff], 1) - BLOCK_BIAS
+
+
+def block_clip(bounds, anchor, voxel):
+    """None, or int [6] = the lowest and the highest block coordinate per axis that holds a sample inside the box `bounds` = [xmin, ymin,
+    zmin, xmax, ymax, zmax]."""
+    if bounds is None:
+        return None
+    box, o = np.asarray(bounds, dtype=np.float64).reshape(6), np.asarray(anchor, dtype=np.float64).reshape(3)
+    lo = np.floor(np.ceil((box[:3] - o) / float(voxel)) / BLOCK)
+    hi = np.floor(np.floor((box[3:] - o) / float(voxel)) / BLOCK)
+    return np.clip(np.concatenate([lo, hi]), -(BLOCK_BIAS - 1), BLOCK_BIAS - 1).astype(np.int64)
+
+
+def reserve_host(depth, sil, pose, fx, fy, cx, cy, voxel, trunc, anchor=(0.0, 0.0, 0.0), sil_min=0.0, depth_max=0.0, clip=None, full=False):
+    """The block set of one view in float64: (keys int64 [m] ascending, dict(valid, pairs, out_of_range)).  With ``full`` the dict also
+    holds `near`: the valid pixels whose box edge lies within 1e-9 sample of a sample boundary on some axis (there another evaluation
+    order may decide differently), and `keys_without_near`: the keys of all other pixels."""
+    d = as_np(depth, np.float32)
+    H, W = d.shape
+    voxel, trunc = float(voxel), float(trunc)
+    if not trunc <= MAX_TRUNC_VOXELS * voxel:
+        raise ValueError(f"trunc = {trunc} is more than {MAX_TRUNC_VOXELS} voxel = {MAX_TRUNC_VOXELS * voxel}")
+    idx = np.flatnonzero(valid_mask(d, sil, sil_min, depth_max).reshape(-1))
+    z = d.reshape(-1)[idx].astype(np.float64)
+    u, v = (idx % W).astype(np.float64), (idx // W).astype(np.float64)
+    R, t = pose_rotation(pose)
+    o = np.asarray(anchor, dtype=np.float64).reshape(3)
+    fx, fy, cx, cy = float(fx), float(fy), float(cx), float(cy)
+    c = [(u - cx) / fx * z - t[0], (v - cy) / fy * z - t[1], z - t[2]]
+    ax = (np.abs(u - cx) * trunc + 0.5 * (z + trunc)) / abs(fx)
+    ay = (np.abs(v - cy) * trunc + 0.5 * (z + trunc)) / abs(fy)
+    rad = np.sqrt(ax * ax + ay * ay + trunc * trunc)
+    ok = np.ones(len(idx), dtype=bool)
+    near = np.zeros(len(idx), dtype=bool)
+    lo, hi = np.zeros((len(idx), 3), dtype=np.int64), np.zeros((len(idx), 3), dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for a in range(3):
+            P = R[0, a] * c[0] + R[1, a] * c[1] + R[2, a] * c[2]
+            ql, qh = (P - rad - o[a]) / voxel, (P + rad - o[a]) / voxel
+            for q in (ql, qh):
+                frac = q - np.floor(q)
+                near |= (frac < 1e-9) | (frac > 1 - 1e-9)
+            bl, bh = np.floor(np.floor(ql) / BLOCK), np.floor(np.ceil(qh) / BLOCK)
+            fine = (np.abs(bl) < BLOCK_BIAS) & (np.abs(bh) < BLOCK_BIAS) & (bh - bl < MAX_BOX)      # (a NaN fails)
+            ok &= fine
+            lo[:, a], hi[:, a] = np.where(fine, bl, 0).astype(np.int64), np.where(fine, bh, 0).astype(np.int64)
+    if clip is not None:
+        cl = np.asarray(clip, dtype=np.int64).reshape(6)
+        lo, hi = np.maximum(lo, cl[None, :3]), np.minimum(hi, cl[None, 3:])
+    keys, clean, pairs = [], [], 0
+    span = (hi - lo)[ok].max(0) + 1 if ok.any() else np.zeros(3, dtype=np.int64)
+    for dz in range(int(max(span[2], 0))):
+        for dy in range(int(max(span[1], 0))):
+            for dx in range(int(max(span[0], 0))):
+                b = lo + np.array([dx, dy, dz], dtype=np.int64)[None, :]
+                m = ok & (b <= hi).all(1)
+                pairs += int(m.sum())
+                keys.append(block_keys(b[m]))
+                if full:
+                    clean.append(block_keys(b[m & ~near]))
+    cat = lambda parts: np.unique(np.concatenate(parts)) if parts else np.zeros(0, dtype=np.int64)
+    info = {"valid": len(idx), "pairs": pairs, "out_of_range": int((~ok).sum())}
+    if full:
+        info.update(near=int(near.sum()), keys_without_near=cat(clean))
+    return cat(keys), info
+
+
+def _frozen_lattice(keys, anchor, voxel):
+    """(blocks [n,3], first [3] = the lattice index of the bounding lattice's first sample, dims [3], origin float64 [3]) of sorted keys."""
+    blocks = key_blocks(keys)
+    bmin, bmax = blocks.min(0), blocks.max(0)
+    first = BLOCK * bmin
+    return blocks, first, [int(v) for v in BLOCK * (bmax - bmin + 1)], np.asarray(anchor, dtype=np.float64).reshape(3) + float(voxel) * first.astype(np.float64)
+
+
+def pool_index(blocks, first, dims, flat):
+    """The pool index rank 512 + local raster index of the bounding lattice's samples `flat` (flat array indices, x fastest) -- -1 where the
+    sample's block is not one of `blocks` [n,3] (ascending keys)."""
+    nx, ny, nz = dims
+    rank = np.full((nz // BLOCK, ny // BLOCK, nx // BLOCK), -1, dtype=np.int64)
+    rel = blocks - first[None, :] // BLOCK
+    rank[rel[:, 2], rel[:, 1], rel[:, 0]] = np.arange(len(blocks))
+    flat = np.asarray(flat, dtype=np.int64)
+    i, j, k = flat % nx, (flat // nx) % ny, flat // (nx * ny)
+    r = rank[k // BLOCK, j // BLOCK, i // BLOCK]
+    return np.where(r >= 0, r * 512 + (k % BLOCK) * 64 + (j % BLOCK) * BLOCK + i % BLOCK, -1)
+
+
+def reorder_to_blocks(rows, tris, vq, tq, blocks, first, dims):
+    """A mesh of ``mesh_host(..., where=True)`` over the bounding lattice in the voxel-block order: vertices by block in ascending key, then
+    by sample in raster order inside the block, then by d; triangles by block, then cube, then tetrahedron, then case."""
+    perm = np.argsort(pool_index(blocks, first, dims, vq), kind="stable")
+    inv = np.empty(len(perm), dtype=np.int64)
+    inv[perm] = np.arange(len(perm))
+    order = np.argsort(pool_index(blocks, first, dims, tq), kind="stable")
+    return rows[perm], inv[tris.astype(np.int64)][order].astype(np.int32).reshape(-1, 3), perm
+
+
+def mesh_blocks_host(keys, tsdf_w, rgb_w, anchor, voxel, min_weight=1.0, full=False):
+    """The mesh of a pool (tsdf_w [n,512,2], rgb_w [n,512,4], block r = the r-th of the ascending `keys`): ``mesh_host`` over the block
+    set's bounding lattice, unknown outside the blocks, in the voxel-block order.  Returns what ``mesh_host`` returns."""
+    keys = np.asarray(keys).astype(np.int64).reshape(-1)
+    if len(keys) == 0 or not bool((np.diff(keys) > 0).all()):
+        raise ValueError("mesh_blocks_host: the keys must be strictly ascending and at least one")
+    blocks, first, dims, _ = _frozen_lattice(keys, anchor, voxel)
+    nx, ny, nz = dims
+    check_lattice(nx, ny, nz)
+    s = pool_index(blocks, first, dims, np.arange(nx * ny * nz))
+    tw, rw = np.zeros((nx * ny * nz, 2), dtype=np.float32), np.zeros((nx * ny * nz, 4), dtype=np.float32)
+    tw[s >= 0], rw[s >= 0] = np.asarray(tsdf_w, dtype=np.float32).reshape(-1, 2)[s[s >= 0]], np.asarray(rgb_w, dtype=np.float32).reshape(-1, 4)[s[s >= 0]]
+    rows, tris, m, xyz, vq, tq = mesh_host(tw.reshape(nz, ny, nx, 2), rw.reshape(nz, ny, nx, 4), anchor, voxel, min_weight, full=True, first=first, where=True)
+    rows, tris, perm = reorder_to_blocks(rows, tris, vq, tq, blocks, first, dims)
+    return (rows, tris, m, xyz[perm]) if full else (rows, tris, m)
+
+
+def _sparse_counters(integrate, mesh, reserve, n):
+    out = _mesh_counters(integrate, mesh)
+    out.update(blocks=int(n), pairs=int(reserve[2]), volume_bytes=int(n) * BLOCK_BYTES, reserved_pixels=int(reserve[1]), out_of_range=int(reserve[5]))
+    return out
+
+
+def _check_frozen(c, max_blocks, voxel):
+    """The counters of a reservation [views, valid, pairs, blocks, dropped, out of range, ...] before the pool is made."""
+    if int(c[1]) == 0:
+        raise ValueError("mesh export: no view has a valid pixel (mesh.sil_min, mesh.max_depth)")
+    if int(c[4]) > 0 or int(c[3]) > int(max_blocks):
+        raise ValueError(f"mesh export: the views need {int(c[3])} voxel blocks ({int(c[4])} dropped), more than mesh.max_blocks = {int(max_blocks)} "
+                         f"(at most 2^21) hold at mesh.voxel = {voxel} m; raise mesh.max_blocks or mesh.voxel, or set mesh.bounds")
+    if int(c[3]) == 0:
+        raise ValueError(f"mesh export: no voxel block was reserved ({int(c[5])} of {int(c[1])} valid pixels out of range; mesh.bounds, mesh.voxel)")
+
+
+def _sparse_options(voxel, trunc, max_blocks):
+    voxel, trunc = float(voxel), float(trunc)
+    if not (np.isfinite(voxel) and voxel > 0 and np.isfinite(trunc) and trunc > 0):
+        raise ValueError(f"voxel = {voxel}, trunc = {trunc} (both must be finite and positive)")
+    if not trunc <= MAX_TRUNC_VOXELS * voxel:
+        raise ValueError(f"trunc = {trunc} is more than {MAX_TRUNC_VOXELS} voxel = {MAX_TRUNC_VOXELS * voxel}")
+    if not 1 <= int(max_blocks) <= MAX_BLOCKS:
+        raise ValueError(f"max_blocks = {max_blocks} (1 .. 2^21)")
+    return voxel, trunc, int(max_blocks)
+
+
+class HostSparseTsdfVolume:
+    """The voxel-block volume of ``device: cpu``: ``reserve`` every view, ``freeze``, ``add`` every view, ``extract``.  The host statement
+    run over the block set's bounding lattice -- ``integrate_host`` / ``mesh_host`` with the unreserved samples zeroed after every view --
+    and reordered to the block order; it holds that whole lattice (at most 2^30 samples), so it is the yardstick, not the memory saving."""
+
+    def __init__(self, voxel, trunc, H, W, cam, sil_min=0.99, depth_max=0.0, min_weight=1.0, max_blocks=1 << 18, bounds=None, anchor=(0.0, 0.0, 0.0), device=None):
+        self.voxel, self.trunc, self.max_blocks = _sparse_options(voxel, trunc, max_blocks)
+        self.anchor = np.asarray(anchor, dtype=np.float64).reshape(3).copy()
+        self.H, self.W, self.cam = int(H), int(W), cam
+        self.sil_min, self.depth_max, self.min_weight = float(sil_min), float(depth_max), float(min_weight)
+        self.clip = block_clip(bounds, self.anchor, self.voxel)
+        self.keys, self.rc, self.c = np.zeros(0, dtype=np.int64), [0] * 8, [0, 0, 0]
+        self.blocks = None
+
+    def reserve(self, depth, sil, pose):
+        if self.blocks is not None:
+            raise RuntimeError("HostSparseTsdfVolume.reserve after freeze")
+        c = self.cam
+        keys, info = reserve_host(depth, sil, pose, c["fx"], c["fy"], c["cx"], c["cy"], self.voxel, self.trunc, self.anchor, self.sil_min, self.depth_max, self.clip)
+        self.keys = np.union1d(self.keys, keys)
+        self.rc[0] += 1; self.rc[1] += info["valid"]; self.rc[2] += info["pairs"]; self.rc[5] += info["out_of_range"]
+        self.rc[3] = len(self.keys)
+
+    def freeze(self):
+        _check_frozen(self.rc, self.max_blocks, self.voxel)
+        self.blocks, self.first, self.dims, self.origin = _frozen_lattice(self.keys, self.anchor, self.voxel)
+        nx, ny, nz = self.dims
+        if nx * ny * nz > MAX_SAMPLES:
+            raise ValueError(f"mesh export: the host path holds the block set's bounding lattice, {nx} x {ny} x {nz} samples (at most 2^30); raise mesh.voxel or set mesh.bounds")
+        self.tsdf_w, self.rgb_w = empty_volume(nx, ny, nz)
+        self.reserved = (pool_index(self.blocks, self.first, self.dims, np.arange(nx * ny * nz)) >= 0).reshape(nz, ny, nx)
+        return len(self.keys)
+
+    def add(self, color, depth, sil, pose):
+        if self.blocks is None:
+            raise RuntimeError("HostSparseTsdfVolume.add before freeze")
+        c = self.cam
+        _, g = integrate_host(self.tsdf_w, self.rgb_w, color, depth, sil, pose, c["fx"], c["fy"], c["cx"], c["cy"], self.anchor, self.voxel, self.trunc,
+                              self.sil_min, self.depth_max, full=True, first=self.first)
+        self.tsdf_w[~self.reserved] = 0      # a sample outside the frozen set is never touched
+        self.rgb_w[~self.reserved] = 0
+        self.c[0] += 1; self.c[1] += int((g["upd"] & self.reserved).sum()); self.c[2] += int((g["col"] & self.reserved).sum())
+
+    def pool(self):
+        """(tsdf_w [n,512,2], rgb_w [n,512,4]): the reserved blocks' samples in the pool's order."""
+        nx, ny, nz = self.dims
+        s = pool_index(self.blocks, self.first, self.dims, np.arange(nx * ny * nz))
+        at = np.argsort(s, kind="stable")[int((s < 0).sum()):]
+        return self.tsdf_w.reshape(-1, 2)[at].reshape(-1, 512, 2), self.rgb_w.reshape(-1, 4)[at].reshape(-1, 512, 4)
+
+    def extract(self):
+        rows, tris, m, vq, tq = mesh_host(self.tsdf_w, self.rgb_w, self.anchor, self.voxel, self.min_weight, first=self.first, where=True)
+        rows, tris, _ = reorder_to_blocks(rows, tris, vq, tq, self.blocks, self.first, self.dims)
+        return rows, tris, _sparse_counters(self.c, m, self.rc, len(self.keys))
+
+
+class SparseTsdfVolume:
+    """The device voxel-block volume: owns the table, the counters and -- from ``freeze`` on -- the sorted keys, the neighbour table and the
+    pool.  ``reserve`` is one mm3dgs_tsdf_blocks_reserve call on the current stream; ``freeze`` one read-back of the counters, one
+    mm3dgs_tsdf_blocks_list, one torch.sort (once per export: plumbing) and one mm3dgs_tsdf_blocks_index; ``add`` one
+    mm3dgs_tsdf_blocks_integrate; ``extract`` one mm3dgs_tsdf_blocks_mesh_plan, one read-back (the totals, the counters and the block
+    set's bounding box), exact allocations and one mm3dgs_tsdf_blocks_mesh_emit."""
+
+    def __init__(self, voxel, trunc, H, W, cam, sil_min=0.99, depth_max=0.0, min_weight=1.0, max_blocks=1 << 18, bounds=None, anchor=(0.0, 0.0, 0.0), device="cuda:0"):
+        import ctypes as C
+        from . import _lib
+        from .rasterizer import _stream
+        if not str(device).startswith("cuda"):
+            raise ValueError("SparseTsdfVolume needs a CUDA device (the host path is HostSparseTsdfVolume)")
+        self.voxel, self.trunc, self.max_blocks = _sparse_options(voxel, trunc, max_blocks)
+        self.anchor = np.asarray(anchor, dtype=np.float64).reshape(3).copy()
+        self.H, self.W, self.cam, self.device = int(H), int(W), cam, device
+        self.sil_min, self.depth_max, self.min_weight = float(sil_min), float(depth_max), float(min_weight)
+        clip = block_clip(bounds, self.anchor, self.voxel)
+        self.clip = None if clip is None else (C.c_int * 6)(*[int(v) for v in clip])
+        self.lib = _lib.load()
+        self.table_bytes = int(self.lib.mm3dgs_tsdf_blocks_table_bytes(self.max_blocks))
+        self.table = torch.empty(self.table_bytes // 8, dtype=torch.int64, device=device)
+        self.rc = torch.zeros(8, dtype=torch.int64, device=device)          # the reservation's counters
+        self.counters = torch.zeros(8, dtype=torch.int64, device=device)    # the integration's
+        self.n = None
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_reset(_lib.ptr(self.table), self.max_blocks, _lib.ptr(self.rc), _stream()))
+
+    def _anchor(self):
+        import ctypes as C
+        return (C.c_double * 3)(*self.anchor.tolist())
+
+    def _view(self, what, color, depth, sil, pose):
+        tensors = [depth, pose] + ([] if sil is None else [sil]) + ([] if color is None else [color])
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
+            raise RuntimeError(f"SparseTsdfVolume.{what} needs device tensors (the host path is HostSparseTsdfVolume)")
+        H, W = self.H, self.W
+        if (color is not None and tuple(color.shape) != (3, H, W)) or tuple(depth.shape) != (H, W) or (sil is not None and tuple(sil.shape) != (H, W)):
+            raise ValueError(f"SparseTsdfVolume.{what}: color [3,{H},{W}], depth and sil [{H},{W}]; got {None if color is None else tuple(color.shape)}, "
+                             f"{tuple(depth.shape)}, {None if sil is None else tuple(sil.shape)}")
+        prep = lambda t: None if t is None else t.detach().float().contiguous()
+        return prep(color), prep(depth), prep(sil), prep(pose).reshape(7)
+
+    def reserve(self, depth, sil, pose):
+        from . import _lib
+        from .rasterizer import _stream
+        if self.n is not None:
+            raise RuntimeError("SparseTsdfVolume.reserve after freeze")
+        _, depth_c, sil_c, pose_c = self._view("reserve", None, depth, sil, pose)
+        c, P = self.cam, _lib.ptr
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_reserve(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c), P(depth_c), P(sil_c),
+                                                       self.sil_min, self.depth_max, self._anchor(), self.voxel, self.trunc, self.clip, P(self.table), self.max_blocks,
+                                                       P(self.rc), _stream()))
+
+    def freeze(self):
+        """Lists, sorts and indexes the block set and allocates the pool at exactly n blocks; returns n.  ValueError when blocks were
+        dropped (``mesh.max_blocks``) or no view had a valid pixel."""
+        from . import _lib
+        from .rasterizer import _stream
+        P = _lib.ptr
+        c = self.rc.cpu().numpy()      # the one read-back
+        _check_frozen(c, self.max_blocks, self.voxel)
+        n = int(c[3])
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_list(P(self.table), self.max_blocks, P(keys), n, _stream()))
+        self.keys = torch.sort(keys).values.contiguous()
+        self.neighbours = torch.empty(n, 27, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_index(P(self.table), self.max_blocks, P(self.keys), n, P(self.neighbours), P(self.rc), _stream()))
+        self.tsdf_w = torch.zeros(n, 512, 2, dtype=torch.float32, device=self.device)
+        self.rgb_w = torch.zeros(n, 512, 4, dtype=torch.float32, device=self.device)
+        self.n = n
+        return n
+
+    def add(self, color, depth, sil, pose):
+        from . import _lib
+        from .rasterizer import _stream
+        if self.n is None:
+            raise RuntimeError("SparseTsdfVolume.add before freeze")
+        color_c, depth_c, sil_c, pose_c = self._view("add", color, depth, sil, pose)
+        c, P = self.cam, _lib.ptr
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_integrate(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c), P(color_c),
+                                                         P(depth_c), P(sil_c), self.sil_min, self.depth_max, self._anchor(), self.voxel, self.trunc, P(self.keys),
+                                                         self.n, P(self.tsdf_w), P(self.rgb_w), P(self.counters), _stream()))
+
+    def extract(self):
+        """(rows [V,4] int32, triangles [T,3] int32, counters): tensors on the device; sets ``dims`` and ``origin`` of the bounding lattice."""
+        from . import _lib
+        from .rasterizer import _stream
+        P, n = _lib.ptr, self.n
+        nbytes = int(self.lib.mm3dgs_tsdf_blocks_mesh_work_bytes(n))
+        work = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)
+        mc = torch.empty(8, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_mesh_plan(n, P(self.neighbours), P(self.tsdf_w), self.min_weight, P(work), P(mc), _stream()))
+        digits = torch.stack([self.keys & 0x1fffff, (self.keys >> 21) & 0x1fffff, self.keys >> 42], 1)      # bx, by, bz + 2^20
+        totals = torch.cat([mc, self.counters, self.rc, digits.amin(0), digits.amax(0)]).cpu().numpy()      # the one read-back before the allocation
+        V, T, rc = int(totals[0]), int(totals[1]), totals[16:24]
+        if int(rc[6]):
+            raise RuntimeError(f"SparseTsdfVolume: mm3dgs_tsdf_blocks_index rejected {int(rc[6])} of the {n} sorted keys")
+        if V >= 1 << 31:
+            raise ValueError(f"mesh of {V} vertices: more than int32 triangle indices reach; raise mesh.voxel")
+        bmin, bmax = totals[24:27].astype(np.int64) - BLOCK_BIAS, totals[27:30].astype(np.int64) - BLOCK_BIAS
+        self.dims = [int(v) for v in BLOCK * (bmax - bmin + 1)]
+        self.origin = self.anchor + self.voxel * (BLOCK * bmin).astype(np.float64)
+        rows = torch.empty(max(V, 1), 4, dtype=torch.int32, device=self.device)
+        tris = torch.empty(max(T, 1), 3, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_mesh_emit(n, P(self.keys), P(self.neighbours), P(self.tsdf_w), P(self.rgb_w), self._anchor(), self.voxel, P(work), P(rows), V,
+                                                         P(tris), T, P(mc), _stream()))
+        m = np.array([V, T, V, T, 0, 0, 0, 0], dtype=np.int64)     # the allocations are exact: nothing is dropped
+        return rows[:V], tris[:T], _sparse_counters(totals[8:16], m, rc, n)
+
+
 # ---- files ----------------------------------------------------------------------------------------------------------------------
-_FACE = np.dtype([("n", "u1"), ("v", "<i4", 3)])
+_FACE =np.dtype([("n", "u1"), ("v", "<i4", 3)])
 
 
 def mesh_header(n_vertices, n_faces):

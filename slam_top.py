@@ -32,7 +32,8 @@ the same views fused into a truncated signed distance volume and meshed by march
 from the checkpoint.  `--geometry` (or `geometry.eval: true`) adds `geometry/metrics.json`, `accuracy.ply` and `completion.ply`: the exported mesh or cloud scored
 against a reference surface (the same frames' sensor depth at the ground-truth poses, or a PLY file) -- accuracy, completion, completion ratio, F-score, Chamfer
 distance; `--geometry --eval` likewise from the checkpoint.  `--mesh-clean small|largest` (or `mesh.clean`) removes the mesh's small disconnected pieces behind
-the extraction, for `--mesh` and for the meshes `--geometry` scores (`mesh.clean_min_triangles`; mesh_clean.py).
+the extraction, for `--mesh` and for the meshes `--geometry` scores (`mesh.clean_min_triangles`; mesh_clean.py).  `--mesh-volume sparse` (or `mesh.volume`)
+holds the fusion volume in hashed 8 x 8 x 8-sample blocks along the surface instead of one dense lattice (`mesh.max_blocks`).
 
 `--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
 `outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
@@ -158,6 +159,7 @@ def main():
     ap.add_argument("--mesh", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) write the reconstruction as a coloured triangle mesh to outputdir/mesh/mesh.ply (the config's `mesh` block)")
     ap.add_argument("--geometry", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) score the exported geometry against a reference surface into outputdir/geometry (the config's `geometry` block)")
     ap.add_argument("--mesh-clean", choices=("small", "largest"), default=None, help="with --mesh / --geometry: remove the mesh's small disconnected pieces (overrides the `mesh` block's `clean`; small: components below mesh.clean_min_triangles triangles, largest: all but the largest component)")
+    ap.add_argument("--mesh-volume", choices=("dense", "sparse"), default=None, help="with --mesh / --geometry: how the fusion volume is held (overrides the `mesh` block's `volume`; dense: one lattice over the box of the views, sparse: hashed 8 x 8 x 8-sample blocks along the surface, mesh.max_blocks)")
     ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
@@ -179,6 +181,8 @@ def main():
     outdir = cfg["outputdir"]
     if args.mesh_clean:
         cfg["mesh"] = dict(cfg.get("mesh") or {}, clean=args.mesh_clean)
+    if args.mesh_volume:
+        cfg["mesh"] = dict(cfg.get("mesh") or {}, volume=args.mesh_volume)
     if args.eval:
         seq = build_sequence(cfg, args.frames, args.gaussians)
         if args.pointcloud:
