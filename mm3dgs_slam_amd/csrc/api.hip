@@ -795,6 +795,28 @@ static bool tsdf_lattice_ok(int nx, int ny, int nz) {
 }
 static bool tsdf_origin_ok(const double* o) { return o && isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]); }
 
+// the checks every call with a view shares, dense or blocks; `who` names the call, `color` is NULL for a call that reads none, and a
+// block call (max_trunc_voxels > 0) bounds the truncation distance in voxels
+static int tsdf_view(const char* who, int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
+                     const float* sil, float sil_min, float depth_max, const double* origin, double voxel, double trunc, double max_trunc_voxels, TsdfView& v) {
+  if (H <= 0 || W <= 0) return fail(-1, "%s: H = %d, W = %d (both must be positive)", who, H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "%s: %d x %d has more than 2^28 pixels", who, H, W);
+  if (!depth || !pose || !origin) return fail(-1, "%s: NULL argument (depth, pose and the origin or anchor are required)", who);
+  if (!(voxel > 0.0) || !isfinite(voxel) || !(trunc > 0.0) || !isfinite(trunc)) return fail(-1, "%s: voxel = %g, trunc = %g (both must be finite and positive)", who, voxel, trunc);
+  if (max_trunc_voxels > 0.0 && !(trunc <= max_trunc_voxels * voxel))
+    return fail(-1, "%s: trunc = %g is more than %g voxel = %g", who, trunc, max_trunc_voxels, max_trunc_voxels * voxel);
+  if (!tsdf_origin_ok(origin)) return fail(-1, "%s: the origin or anchor must be finite", who);
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "%s: fx = %g, fy = %g (finite, not 0)", who, fx, fy);
+  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "%s: cx = %g, cy = %g (must be finite)", who, cx, cy);
+  if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)sil | (uintptr_t)pose) & 3) return fail(-1, "%s: the images and the pose must be 4-byte aligned", who);
+  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
+  v.pose = pose; v.color = color; v.depth = depth; v.sil = sil;
+  v.sil_min = sil_min; v.depth_max = depth_max;
+  v.o[0] = origin[0]; v.o[1] = origin[1]; v.o[2] = origin[2]; v.voxel = voxel; v.trunc = trunc;
+  v.nx = v.ny = v.nz = 0;
+  return 0;
+}
+
 int mm3dgs_tsdf_reset(int nx, int ny, int nz, void* tsdf_w, void* rgb_w, uint64_t* counters, void* stream) {
   if (!tsdf_lattice_ok(nx, ny, nz)) return fail(-1, "tsdf_reset: lattice %d x %d x %d (every size at least 2, at most 2^30 samples)", nx, ny, nz);
   if (!tsdf_w || !rgb_w || !counters) return fail(-1, "tsdf_reset: NULL argument (tsdf_w, rgb_w and counters are required)");
@@ -810,25 +832,12 @@ int mm3dgs_tsdf_reset(int nx, int ny, int nz, void* tsdf_w, void* rgb_w, uint64_
 int mm3dgs_tsdf_integrate(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
                           const float* silhouette_or_null, float sil_min, float depth_max, const double* origin, double voxel, double trunc, int nx,
                           int ny, int nz, void* tsdf_w, void* rgb_w, uint64_t* counters, void* stream) {
-  if (H <= 0 || W <= 0) return fail(-1, "tsdf_integrate: H = %d, W = %d (both must be positive)", H, W);
-  if (!eval_shape_ok(H, W)) return fail(-1, "tsdf_integrate: %d x %d has more than 2^28 pixels", H, W);
+  TsdfView v;
+  if (int rc = tsdf_view("tsdf_integrate", H, W, fx, fy, cx, cy, pose, color, depth, silhouette_or_null, sil_min, depth_max, origin, voxel, trunc, 0.0, v)) return rc;
   if (!tsdf_lattice_ok(nx, ny, nz)) return fail(-1, "tsdf_integrate: lattice %d x %d x %d (every size at least 2, at most 2^30 samples)", nx, ny, nz);
-  if (!color || !depth || !pose || !origin || !tsdf_w || !rgb_w || !counters)
-    return fail(-1, "tsdf_integrate: NULL argument (color, depth, pose, origin, tsdf_w, rgb_w and counters are required)");
-  if (!(voxel > 0.0) || !isfinite(voxel) || !(trunc > 0.0) || !isfinite(trunc))
-    return fail(-1, "tsdf_integrate: voxel = %g, trunc = %g (both must be finite and positive)", voxel, trunc);
-  if (!tsdf_origin_ok(origin)) return fail(-1, "tsdf_integrate: the origin must be finite");
-  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "tsdf_integrate: fx = %g, fy = %g (finite, not 0)", fx, fy);
-  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "tsdf_integrate: cx = %g, cy = %g (must be finite)", cx, cy);
+  if (!color || !tsdf_w || !rgb_w || !counters) return fail(-1, "tsdf_integrate: NULL argument (color, tsdf_w, rgb_w and counters are required)");
   if ((uintptr_t)rgb_w & 15) return fail(-1, "tsdf_integrate: rgb_w must be 16-byte aligned");
   if (((uintptr_t)tsdf_w | (uintptr_t)counters) & 7) return fail(-1, "tsdf_integrate: tsdf_w and counters must be 8-byte aligned");
-  if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)silhouette_or_null | (uintptr_t)pose) & 3)
-    return fail(-1, "tsdf_integrate: the images and the pose must be 4-byte aligned");
-  TsdfView v;
-  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
-  v.pose = pose; v.color = color; v.depth = depth; v.sil = silhouette_or_null;
-  v.sil_min = sil_min; v.depth_max = depth_max;
-  v.o[0] = origin[0]; v.o[1] = origin[1]; v.o[2] = origin[2]; v.voxel = voxel; v.trunc = trunc;
   v.nx = nx; v.ny = ny; v.nz = nz;
   launch_tsdf_integrate(v, tsdf_w, rgb_w, counters, (hipStream_t)stream);
   return check_launch("tsdf_integrate");
@@ -861,27 +870,8 @@ int mm3dgs_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void
 
 // ---- the same as a voxel-block volume (tsdf_sparse.hip) ----------------------------------------------------------------------------
 #define TSDF_MAX_BLOCKS ((uint64_t)1 << 21)      // 2^30 samples: 32-bit bases, int32 indices
+#define TSDF_BLOCKS_MAX_TRUNC 16.0                // voxels: a pixel's box of blocks stays within BLK_MAX_BOX (tsdf_sparse.hip)
 static bool tsdf_blocks_ok(uint64_t n) { return n >= 1 && n <= TSDF_MAX_BLOCKS; }
-// the checks every call with a view shares; `who` names the call
-static int tsdf_blocks_view(const char* who, int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
-                            const float* sil, float sil_min, float depth_max, const double* anchor, double voxel, double trunc, TsdfView& v) {
-  if (H <= 0 || W <= 0) return fail(-1, "%s: H = %d, W = %d (both must be positive)", who, H, W);
-  if (!eval_shape_ok(H, W)) return fail(-1, "%s: %d x %d has more than 2^28 pixels", who, H, W);
-  if (!depth || !pose || !anchor) return fail(-1, "%s: NULL argument (depth, pose and anchor are required)", who);
-  if (!(voxel > 0.0) || !isfinite(voxel) || !(trunc > 0.0) || !isfinite(trunc)) return fail(-1, "%s: voxel = %g, trunc = %g (both must be finite and positive)", who, voxel, trunc);
-  if (!(trunc <= 16.0 * voxel)) return fail(-1, "%s: trunc = %g is more than 16 voxel = %g", who, trunc, 16.0 * voxel);
-  if (!tsdf_origin_ok(anchor)) return fail(-1, "%s: the anchor must be finite", who);
-  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "%s: fx = %g, fy = %g (finite, not 0)", who, fx, fy);
-  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "%s: cx = %g, cy = %g (must be finite)", who, cx, cy);
-  if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)sil | (uintptr_t)pose) & 3) return fail(-1, "%s: the images and the pose must be 4-byte aligned", who);
-  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
-  v.pose = pose; v.color = color; v.depth = depth; v.sil = sil;
-  v.sil_min = sil_min; v.depth_max = depth_max;
-  v.o[0] = anchor[0]; v.o[1] = anchor[1]; v.o[2] = anchor[2]; v.voxel = voxel; v.trunc = trunc;
-  v.nx = v.ny = v.nz = 0;
-  return 0;
-}
-
 size_t mm3dgs_tsdf_blocks_table_bytes(uint64_t max_blocks) { return tsdf_blocks_ok(max_blocks) ? tsdf_blocks_table_bytes(max_blocks, nullptr) : 0; }
 
 int mm3dgs_tsdf_blocks_reset(void* table, uint64_t max_blocks, uint64_t* counters, void* stream) {
@@ -896,7 +886,7 @@ int mm3dgs_tsdf_blocks_reserve(int H, int W, double fx, double fy, double cx, do
                                float sil_min, float depth_max, const double* anchor, double voxel, double trunc, const int* clip_or_null, void* table,
                                uint64_t max_blocks, uint64_t* counters, void* stream) {
   TsdfView v;
-  if (int rc = tsdf_blocks_view("tsdf_blocks_reserve", H, W, fx, fy, cx, cy, pose, nullptr, depth, silhouette_or_null, sil_min, depth_max, anchor, voxel, trunc, v)) return rc;
+  if (int rc = tsdf_view("tsdf_blocks_reserve", H, W, fx, fy, cx, cy, pose, nullptr, depth, silhouette_or_null, sil_min, depth_max, anchor, voxel, trunc, TSDF_BLOCKS_MAX_TRUNC, v)) return rc;
   if (!tsdf_blocks_ok(max_blocks)) return fail(-1, "tsdf_blocks_reserve: max_blocks = %llu (1 .. 2^21)", (unsigned long long)max_blocks);
   if (!table || !counters) return fail(-1, "tsdf_blocks_reserve: NULL argument (table and counters are required)");
   if (((uintptr_t)table | (uintptr_t)counters) & 7) return fail(-1, "tsdf_blocks_reserve: table and counters must be 8-byte aligned");
@@ -931,7 +921,7 @@ int mm3dgs_tsdf_blocks_integrate(int H, int W, double fx, double fy, double cx, 
                                  const float* silhouette_or_null, float sil_min, float depth_max, const double* anchor, double voxel, double trunc,
                                  const uint64_t* keys, uint64_t n, void* tsdf_w, void* rgb_w, uint64_t* counters, void* stream) {
   TsdfView v;
-  if (int rc = tsdf_blocks_view("tsdf_blocks_integrate", H, W, fx, fy, cx, cy, pose, color, depth, silhouette_or_null, sil_min, depth_max, anchor, voxel, trunc, v)) return rc;
+  if (int rc = tsdf_view("tsdf_blocks_integrate", H, W, fx, fy, cx, cy, pose, color, depth, silhouette_or_null, sil_min, depth_max, anchor, voxel, trunc, TSDF_BLOCKS_MAX_TRUNC, v)) return rc;
   if (!tsdf_blocks_ok(n)) return fail(-1, "tsdf_blocks_integrate: n = %llu blocks (1 .. 2^21)", (unsigned long long)n);
   if (!color || !keys || !tsdf_w || !rgb_w || !counters) return fail(-1, "tsdf_blocks_integrate: NULL argument (color, keys, tsdf_w, rgb_w and counters are required)");
   if ((uintptr_t)rgb_w & 15) return fail(-1, "tsdf_blocks_integrate: rgb_w must be 16-byte aligned");

@@ -16,8 +16,12 @@
 //                           tm_scan (one workgroup: scan_block_counts over both per-256 counts, the totals), tm_base (per-sample vertex base
 //                           and per-cube triangle base).  Emit: tm_vertex (one 16-byte row per vertex at base[q] + popcount(mask[q] below d)),
 //                           tm_triangle (int32[3] per triangle, by tetrahedron then case order).  No atomic decides a position or an index.
+//                           The cube, edge, vertex and triangle kernels are tsdf_march.h's, instantiated here over the dense lattice
+//                           (TmGrid: a stride to a neighbour, none beyond the lattice, 32-bit index arithmetic); state, scan and base
+//                           see only the flat run of samples and are defined here for both volumes.
 #include <math.h>
-#include "tsdf_sample.h"      // the per-sample update, the case tables and the work layout (shared with tsdf_sparse.hip)
+#include "tsdf_sample.h"      // the per-sample update (shared with tsdf_sparse.hip)
+#include "tsdf_march.h"       // the extraction over a lattice (shared with tsdf_sparse.hip)
 
 #define TB TM_TB
 
@@ -61,84 +65,34 @@ void launch_tsdf_integrate(const TsdfView& v, void* tsdf_w, void* rgb_w, uint64_
 // ---- marching tetrahedra --------------------------------------------------------------------------------------------------------
 size_t tsdf_mesh_work_bytes(int nx, int ny, int nz) { size_t b; tm_work(nullptr, (size_t)nx * (size_t)ny * (size_t)nz, &b); return b; }
 
-struct TmGrid { int nx, ny, nz; size_t n; };
-
-__device__ __forceinline__ size_t tm_corner(const TmGrid& g, unsigned c) {
-  return (size_t)(c & 1u) + (size_t)((c >> 1) & 1u) * (size_t)g.nx + (size_t)((c >> 2) & 1u) * (size_t)g.nx * (size_t)g.ny;
-}
-
-__device__ __forceinline__ void tm_coords(const TmGrid& g, size_t i, int& x, int& y, int& z) {
-  x = (int)(i % (size_t)g.nx);
-  y = (int)((i / (size_t)g.nx) % (size_t)g.ny);
-  z = (int)(i / ((size_t)g.nx * (size_t)g.ny));
-}
+// the dense lattice: sample (x, y, z) at flat index (z ny + y) nx + x; beyond 0 .. nx - 1 (ny, nz) there is no sample.  n <= 2^30 (the entry
+// points have checked): a flat index and a step of one row and one slice fit 32 bits, which spares every lane 64-bit divisions
+struct TmGrid {
+  struct Cell { int i, x, y, z; };
+  int nx, ny, nz;
+  size_t n;
+  __device__ __forceinline__ Cell cell(size_t i) const {
+    const unsigned u = (unsigned)i, row = u / (unsigned)nx;
+    return {(int)u, (int)(u % (unsigned)nx), (int)(row % (unsigned)ny), (int)(row / (unsigned)ny)};
+  }
+  __device__ __forceinline__ long long at(const Cell& c, int dx, int dy, int dz) const {
+    if ((unsigned)(c.x + dx) >= (unsigned)nx || (unsigned)(c.y + dy) >= (unsigned)ny || (unsigned)(c.z + dz) >= (unsigned)nz) return -1;
+    return c.i + dx + (dy + dz * ny) * nx;
+  }
+  __device__ __forceinline__ void lattice_index(const Cell& c, int q[3]) const { q[0] = c.x; q[1] = c.y; q[2] = c.z; }
+  __device__ __forceinline__ bool cube(const Cell& c, long long q[8]) const {
+    if (c.x >= nx - 1 || c.y >= ny - 1 || c.z >= nz - 1) return false;
+    for (unsigned e = 0; e < 8; e++) q[e] = c.i + (int)(e & 1u) + ((int)((e >> 1) & 1u) + (int)((e >> 2) & 1u) * ny) * nx;
+    return true;
+  }
+};
+static TmGrid tm_grid(int nx, int ny, int nz) { return {nx, ny, nz, (size_t)nx * (size_t)ny * (size_t)nz}; }
 
 __global__ void __launch_bounds__(TB) tm_state_kernel(size_t n, const float2* __restrict__ tsdf_w, float min_weight, uint8_t* __restrict__ state) {
   const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
   if (i >= n) return;
   const float2 tw = tsdf_w[i];
   state[i] = (uint8_t)((tw.y >= min_weight ? 1 : 0) | (tw.x < 0.f ? 2 : 0));      // (a NaN weight is not known)
-}
-
-// the 8 corner states of the cube with origin i: all known -> valid; the inside bits by corner number
-__device__ __forceinline__ bool tm_cube_corners(const TmGrid& g, const uint8_t* __restrict__ state, size_t i, unsigned& inside) {
-  unsigned known = 1;
-  inside = 0;
-  for (unsigned c = 0; c < 8; c++) {
-    const unsigned s = state[i + tm_corner(g, c)];
-    known &= s;
-    inside |= ((s >> 1) & 1u) << c;
-  }
-  return (known & 1u) != 0;
-}
-
-__global__ void __launch_bounds__(TB) tm_cube_kernel(TmGrid g, const uint8_t* __restrict__ state, uint8_t* __restrict__ cube, uint32_t* __restrict__ tcounts) {
-  __shared__ uint32_t wtot[TB / 64];
-  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-  uint32_t ntri = 0;
-  uint8_t out = 0;
-  if (i < g.n) {
-    int x, y, z;
-    tm_coords(g, i, x, y, z);
-    unsigned inside;
-    if (x < g.nx - 1 && y < g.ny - 1 && z < g.nz - 1 && tm_cube_corners(g, state, i, inside)) {
-      for (int k = 0; k < 6; k++) ntri += TM_CASES[tm_tet_mask(inside, k)] & 3u;
-      out = (uint8_t)(0x80u | ntri);
-    }
-    cube[i] = out;
-  }
-  const uint32_t incl = block_scan_incl(ntri, wtot);
-  if (threadIdx.x == TB - 1) tcounts[blockIdx.x] = incl;
-}
-
-__global__ void __launch_bounds__(TB)
-tm_edge_kernel(TmGrid g, const uint8_t* __restrict__ state, const uint8_t* __restrict__ cube, uint8_t* __restrict__ vmask, uint32_t* __restrict__ vcounts) {
-  __shared__ uint32_t wtot[TB / 64];
-  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-  unsigned mask = 0;
-  if (i < g.n) {
-    int x, y, z;
-    tm_coords(g, i, x, y, z);
-    const unsigned in0 = (state[i] >> 1) & 1u;
-    // valid cubes with origin q - e, e in {0,1}^3 (bit e of `around`); a cube beyond the lattice is not valid
-    unsigned around = 0;
-    for (unsigned e = 0; e < 8; e++) {
-      if (((e & 1u) && x == 0) || ((e & 2u) && y == 0) || ((e & 4u) && z == 0)) continue;
-      around |= (unsigned)(cube[i - tm_corner(g, e)] >> 7) << e;
-    }
-    for (unsigned d = 1; d < 8; d++) {
-      if (((d & 1u) && x == g.nx - 1) || ((d & 2u) && y == g.ny - 1) || ((d & 4u) && z == g.nz - 1)) continue;
-      // the cubes that contain the edge (q, d): origins q - e with e inside the zero bits of d
-      unsigned near = 0;
-      for (unsigned e = 0; e < 8; e++)
-        if (!(e & d)) near |= (around >> e) & 1u;
-      const unsigned in1 = (state[i + tm_corner(g, d)] >> 1) & 1u;
-      if (near && in0 != in1) mask |= 1u << d;
-    }
-    vmask[i] = (uint8_t)mask;
-  }
-  const uint32_t incl = block_scan_incl((uint32_t)__popc(mask), wtot);
-  if (threadIdx.x == TB - 1) vcounts[blockIdx.x] = incl;
 }
 
 __global__ void __launch_bounds__(1024)
@@ -180,104 +134,10 @@ void launch_tm_scan_base(size_t n, const TmWork& w, uint64_t* counters, hipStrea
 }
 
 void launch_tsdf_mesh_plan(int nx, int ny, int nz, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s) {
-  TmGrid g;
-  g.nx = nx; g.ny = ny; g.nz = nz; g.n = (size_t)nx * (size_t)ny * (size_t)nz;
-  const TmWork w = tm_work(work, g.n);
-  const unsigned nb = (unsigned)tm_nb(g.n);
-  launch_tm_state(g.n, tsdf_w, min_weight, w, s);
-  hipLaunchKernelGGL(tm_cube_kernel, dim3(nb), dim3(TB), 0, s, g, w.state, w.cube, w.tcounts);
-  hipLaunchKernelGGL(tm_edge_kernel, dim3(nb), dim3(TB), 0, s, g, w.state, w.cube, w.vmask, w.vcounts);
-  launch_tm_scan_base(g.n, w, counters, s);
-}
-
-__global__ void __launch_bounds__(TB)
-tm_vertex_kernel(TmGrid g, TmEmit e, const float2* __restrict__ tsdf_w, const float4* __restrict__ rgb_w, const uint8_t* __restrict__ vmask,
-                 const uint32_t* __restrict__ vbase, const unsigned long long* __restrict__ hdr, uint4* __restrict__ rows, unsigned long long* __restrict__ counters) {
-#pragma clang fp contract(off)
-  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-  if (i == 0) {      // the counts of this emit: what the caps let through (the triangle kernel adds its two behind the kernel boundary)
-    const unsigned long long V = hdr[0], written = V < e.vcap ? V : e.vcap;
-    counters[2] = written;
-    counters[3] = 0ull;
-    counters[4] = V - written;
-    counters[5] = 0ull;
-  }
-  if (i >= g.n) return;
-  const unsigned mask = vmask[i];
-  if (!mask) return;
-  int q[3];
-  tm_coords(g, i, q[0], q[1], q[2]);
-  const double T0 = (double)tsdf_w[i].x;
-  const float4 c0 = rgb_w[i];
-  unsigned long long r = vbase[i];
-  for (unsigned d = 1; d < 8; d++) {
-    if (!((mask >> d) & 1u)) continue;
-    if (r < e.vcap) {
-      const size_t j = i + tm_corner(g, d);
-      const double T1 = (double)tsdf_w[j].x;
-      const float4 c1 = rgb_w[j];
-      const double t = T0 / (T0 - T1);
-      const float px = (float)(e.o[0] + e.voxel * ((double)q[0] + t * (double)(d & 1u)));
-      const float py = (float)(e.o[1] + e.voxel * ((double)q[1] + t * (double)((d >> 1) & 1u)));
-      const float pz = (float)(e.o[2] + e.voxel * ((double)q[2] + t * (double)((d >> 2) & 1u)));
-      const float cr = (float)((double)c0.x + t * ((double)c1.x - (double)c0.x));
-      const float cg = (float)((double)c0.y + t * ((double)c1.y - (double)c0.y));
-      const float cb = (float)((double)c0.z + t * ((double)c1.z - (double)c0.z));
-      rows[r] = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), pc_quant(cr) | (pc_quant(cg) << 8) | (pc_quant(cb) << 16) | 0xff000000u);
-    }
-    r++;
-  }
-}
-
-__global__ void __launch_bounds__(TB)
-tm_triangle_kernel(TmGrid g, TmEmit e, const uint8_t* __restrict__ state, const uint8_t* __restrict__ cube, const uint8_t* __restrict__ vmask,
-                   const uint32_t* __restrict__ vbase, const uint32_t* __restrict__ tbase, int* __restrict__ tris, unsigned long long* __restrict__ counters) {
-  const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-  uint32_t written = 0, dropped = 0;
-  if (i < g.n && (cube[i] & 0x7fu)) {      // (a cube with triangles is valid and inside the lattice)
-    unsigned inside;
-    tm_cube_corners(g, state, i, inside);
-    unsigned long long r = tbase[i];
-    for (int k = 0; k < 6; k++) {
-      const uint32_t cs = TM_CASES[tm_tet_mask(inside, k)];
-      const unsigned corner[4] = {0u, TM_MID1[k], TM_MID2[k], 7u};
-      for (uint32_t s = 0; s < (cs & 3u); s++) {
-        uint32_t idx[3];
-        for (int a = 0; a < 3; a++) {
-          const unsigned edge = (cs >> (2 + 9 * s + 3 * a)) & 7u;
-          const unsigned lo = corner[TM_EDGE_LO[edge]], hi = corner[TM_EDGE_HI[edge]];
-          const size_t smp = i + tm_corner(g, lo);
-          idx[a] = vbase[smp] + (uint32_t)__popc((unsigned)vmask[smp] & ((1u << (hi ^ lo)) - 1u));
-        }
-        if ((TM_ODD >> k) & 1u) { const uint32_t t = idx[1]; idx[1] = idx[2]; idx[2] = t; }
-        if (r < e.tcap && idx[0] < e.vcap && idx[1] < e.vcap && idx[2] < e.vcap) {
-          tris[3 * r] = (int)idx[0];
-          tris[3 * r + 1] = (int)idx[1];
-          tris[3 * r + 2] = (int)idx[2];
-          written++;
-        } else {
-          dropped++;
-        }
-        r++;
-      }
-    }
-  }
-  const uint32_t sw = wave_scan_incl(written), sd = wave_scan_incl(dropped);
-  if ((threadIdx.x & 63) == 63) {
-    if (sw) atomicAdd(counters + 3, (unsigned long long)sw);
-    if (sd) atomicAdd(counters + 5, (unsigned long long)sd);
-  }
+  tm_launch_plan(tm_grid(nx, ny, nz), tsdf_w, min_weight, work, counters, s);
 }
 
 void launch_tsdf_mesh_emit(int nx, int ny, int nz, const void* tsdf_w, const void* rgb_w, const double* origin, double voxel, const void* work, void* rows,
                            uint64_t vcap, void* tris, uint64_t tcap, uint64_t* counters, hipStream_t s) {
-  TmGrid g;
-  g.nx = nx; g.ny = ny; g.nz = nz; g.n = (size_t)nx * (size_t)ny * (size_t)nz;
-  const TmWork w = tm_work((void*)work, g.n);
-  TmEmit e;
-  e.o[0] = origin[0]; e.o[1] = origin[1]; e.o[2] = origin[2]; e.voxel = voxel; e.vcap = vcap; e.tcap = tcap;
-  const unsigned nb = (unsigned)tm_nb(g.n);
-  hipLaunchKernelGGL(tm_vertex_kernel, dim3(nb), dim3(TB), 0, s, g, e, (const float2*)tsdf_w, (const float4*)rgb_w, w.vmask, w.vbase, w.hdr, (uint4*)rows,
-                     (unsigned long long*)counters);
-  hipLaunchKernelGGL(tm_triangle_kernel, dim3(nb), dim3(TB), 0, s, g, e, w.state, w.cube, w.vmask, w.vbase, w.tbase, (int*)tris, (unsigned long long*)counters);
+  tm_launch_emit(tm_grid(nx, ny, nz), tsdf_w, rgb_w, origin, voxel, work, rows, vcap, tris, tcap, counters, s);
 }

@@ -19,11 +19,13 @@
 //   blk_integrate_kernel   one launch per view, one workgroup of 256 per block, a wave of 64 lanes = one 8 x 8 z slice, two slices per wave;
 //                          the per-sample body is the dense kernel's (tsdf_sample.h).  A block whose bounding sphere is behind the camera
 //                          or projects outside the image (conservatively: a pixel of slack, the sphere 1e-6 larger) leaves early.
-//   blk_cube / blk_edge / blk_vertex / blk_triangle   tsdf.hip's marching tetrahedra over n 512 samples with block-local indexing and the
-//                          neighbour table at the faces (a missing neighbour is unknown); state, scan and base are tsdf.hip's own kernels.
+//   marching tetrahedra    tsdf_march.h's cube, edge, vertex and triangle kernels, instantiated over the block lattice (BlkGrid: n 512
+//                          samples with block-local indexing and the neighbour table at the faces; a missing neighbour is unknown);
+//                          state, scan and base are tsdf.hip's own kernels.
 // Every loop is bounded: probes, a pixel's block box (8^3), the 27 neighbours.  No atomic decides a position or an index.
 #include <math.h>
 #include "tsdf_sample.h"
+#include "tsdf_march.h"
 
 #define SB 256
 #define BLK_MAX_PROBE 128
@@ -311,189 +313,50 @@ void launch_tsdf_blocks_integrate(const TsdfView& v, const uint64_t* keys, uint6
 }
 
 // ---- marching tetrahedra -----------------------------------------------------------------------------------------------------------
-struct BlkGrid { unsigned n; size_t samples; const int* nbr; };
-
-// pool index of the sample (x, y, z), each in -1 .. 8, relative to block r; -1: the block that would hold it is not in the set
-__device__ __forceinline__ long long blk_at(const BlkGrid& g, unsigned r, int x, int y, int z) {
-  const int j = ((z + 8) >> 3) * 9 + ((y + 8) >> 3) * 3 + ((x + 8) >> 3);
-  unsigned rr = r;
-  if (j != 13) {
-    rr = (unsigned)g.nbr[(size_t)r * 27 + j];
-    if (rr >= g.n) return -1;      // (-1, or an index the caller's table should not hold)
+// the block lattice: sample (x, y, z) of block r at pool index 512 r + 64 z + 8 y + x; a step across a face goes through the 27-neighbour
+// table, and there is no sample where the block that would hold it is not in the set
+struct BlkGrid {
+  struct Cell { unsigned r; int x, y, z; };
+  unsigned blocks;
+  size_t n;      // 512 blocks: every workgroup of 256 is full
+  const int* nbr;
+  const unsigned long long* keys;      // (the emit's: only lattice_index reads them)
+  __device__ __forceinline__ Cell cell(size_t i) const { return {(unsigned)(i >> 9), (int)(i & 7), (int)((i >> 3) & 7), (int)((i >> 6) & 7)}; }
+  __device__ __forceinline__ long long at(const Cell& c, int dx, int dy, int dz) const {
+    const int x = c.x + dx, y = c.y + dy, z = c.z + dz;      // each in -1 .. 8
+    const int j = ((z + 8) >> 3) * 9 + ((y + 8) >> 3) * 3 + ((x + 8) >> 3);
+    unsigned rr = c.r;
+    if (j != 13) {
+      rr = (unsigned)nbr[(size_t)c.r * 27 + j];
+      if (rr >= blocks) return -1;      // (-1, or an index the caller's table should not hold)
+    }
+    return (long long)rr * 512 + (z & 7) * 64 + (y & 7) * 8 + (x & 7);
   }
-  return (long long)rr * 512 + (z & 7) * 64 + (y & 7) * 8 + (x & 7);
-}
-
-__device__ __forceinline__ void blk_split(size_t i, unsigned& r, int& x, int& y, int& z) {
-  r = (unsigned)(i >> 9);
-  x = (int)(i & 7); y = (int)((i >> 3) & 7); z = (int)((i >> 6) & 7);
-}
-
-// the 8 corner states of the cube with origin (r; x, y, z): all known (and present) -> valid; the inside bits by corner number
-__device__ __forceinline__ bool blk_cube_corners(const BlkGrid& g, const uint8_t* __restrict__ state, unsigned r, int x, int y, int z, unsigned& inside) {
-  unsigned known = 1;
-  inside = 0;
-  for (unsigned c = 0; c < 8; c++) {
-    const long long q = blk_at(g, r, x + (int)(c & 1u), y + (int)((c >> 1) & 1u), z + (int)((c >> 2) & 1u));
-    const unsigned s = q < 0 ? 0u : state[q];
-    known &= s;
-    inside |= ((s >> 1) & 1u) << c;
+  __device__ __forceinline__ void lattice_index(const Cell& c, int q[3]) const {
+    int b[3];
+    blk_coords(keys[c.r], b[0], b[1], b[2]);
+    q[0] = 8 * b[0] + c.x; q[1] = 8 * b[1] + c.y; q[2] = 8 * b[2] + c.z;
   }
-  return (known & 1u) != 0;
+  __device__ __forceinline__ bool cube(const Cell& c, long long q[8]) const {
+    bool all = true;
+    for (unsigned e = 0; e < 8; e++) {
+      q[e] = at(c, (int)(e & 1u), (int)((e >> 1) & 1u), (int)((e >> 2) & 1u));
+      all = all && q[e] >= 0;
+    }
+    return all;
+  }
+};
+static BlkGrid blk_grid(uint64_t n, const int* neighbours, const uint64_t* keys) {
+  return {(unsigned)n, (size_t)n * 512, neighbours, (const unsigned long long*)keys};
 }
 
-__global__ void __launch_bounds__(SB) blk_cube_kernel(BlkGrid g, const uint8_t* __restrict__ state, uint8_t* __restrict__ cube, uint32_t* __restrict__ tcounts) {
-  __shared__ uint32_t wtot[SB / 64];
-  const size_t i = (size_t)blockIdx.x * SB + threadIdx.x;      // (n 512 samples: every workgroup is full)
-  unsigned r, inside;
-  int x, y, z;
-  blk_split(i, r, x, y, z);
-  uint32_t ntri = 0;
-  uint8_t out = 0;
-  if (blk_cube_corners(g, state, r, x, y, z, inside)) {
-    for (int k = 0; k < 6; k++) ntri += TM_CASES[tm_tet_mask(inside, k)] & 3u;
-    out = (uint8_t)(0x80u | ntri);
-  }
-  cube[i] = out;
-  const uint32_t incl = block_scan_incl(ntri, wtot);
-  if (threadIdx.x == SB - 1) tcounts[blockIdx.x] = incl;
-}
-
-__global__ void __launch_bounds__(SB)
-blk_edge_kernel(BlkGrid g, const uint8_t* __restrict__ state, const uint8_t* __restrict__ cube, uint8_t* __restrict__ vmask, uint32_t* __restrict__ vcounts) {
-  __shared__ uint32_t wtot[SB / 64];
-  const size_t i = (size_t)blockIdx.x * SB + threadIdx.x;
-  unsigned r;
-  int x, y, z;
-  blk_split(i, r, x, y, z);
-  unsigned mask = 0;
-  const unsigned in0 = (state[i] >> 1) & 1u;
-  // valid cubes with origin q - e, e in {0,1}^3 (bit e of `around`); a cube in a block that is not there is not valid
-  unsigned around = 0;
-  for (unsigned e = 0; e < 8; e++) {
-    const long long q = blk_at(g, r, x - (int)(e & 1u), y - (int)((e >> 1) & 1u), z - (int)((e >> 2) & 1u));
-    if (q >= 0) around |= (unsigned)(cube[q] >> 7) << e;
-  }
-  for (unsigned d = 1; d < 8; d++) {
-    const long long q = blk_at(g, r, x + (int)(d & 1u), y + (int)((d >> 1) & 1u), z + (int)((d >> 2) & 1u));
-    if (q < 0) continue;
-    unsigned near = 0;
-    for (unsigned e = 0; e < 8; e++)
-      if (!(e & d)) near |= (around >> e) & 1u;
-    const unsigned in1 = (state[q] >> 1) & 1u;
-    if (near && in0 != in1) mask |= 1u << d;
-  }
-  vmask[i] = (uint8_t)mask;
-  const uint32_t incl = block_scan_incl((uint32_t)__popc(mask), wtot);
-  if (threadIdx.x == SB - 1) vcounts[blockIdx.x] = incl;
-}
-
-void launch_tsdf_blocks_mesh_plan(uint64_t n, const int* neighbours, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s) {
-  BlkGrid g;
-  g.n = (unsigned)n; g.samples = (size_t)n * 512; g.nbr = neighbours;
-  const TmWork w = tm_work(work, g.samples);
-  const unsigned nb = (unsigned)tm_nb(g.samples);      // = 2 n <= 2^22
-  launch_tm_state(g.samples, tsdf_w, min_weight, w, s);
-  hipLaunchKernelGGL(blk_cube_kernel, dim3(nb), dim3(SB), 0, s, g, w.state, w.cube, w.tcounts);
-  hipLaunchKernelGGL(blk_edge_kernel, dim3(nb), dim3(SB), 0, s, g, w.state, w.cube, w.vmask, w.vcounts);
-  launch_tm_scan_base(g.samples, w, counters, s);
-}
 size_t tsdf_blocks_mesh_work_bytes(uint64_t n) { size_t b; tm_work(nullptr, (size_t)n * 512, &b); return b; }
 
-__global__ void __launch_bounds__(SB)
-blk_vertex_kernel(BlkGrid g, TmEmit e, const unsigned long long* __restrict__ keys, const float2* __restrict__ tsdf_w, const float4* __restrict__ rgb_w,
-                  const uint8_t* __restrict__ vmask, const uint32_t* __restrict__ vbase, const unsigned long long* __restrict__ hdr, uint4* __restrict__ rows,
-                  unsigned long long* __restrict__ counters) {
-#pragma clang fp contract(off)
-  const size_t i = (size_t)blockIdx.x * SB + threadIdx.x;
-  if (i == 0) {      // the counts of this emit: what the caps let through (the triangle kernel adds its two behind the kernel boundary)
-    const unsigned long long V = hdr[0], written = V < e.vcap ? V : e.vcap;
-    counters[2] = written;
-    counters[3] = 0ull;
-    counters[4] = V - written;
-    counters[5] = 0ull;
-  }
-  const unsigned mask = vmask[i];
-  if (!mask) return;
-  unsigned r;
-  int x, y, z, b[3];
-  blk_split(i, r, x, y, z);
-  blk_coords(keys[r], b[0], b[1], b[2]);
-  const int q[3] = {8 * b[0] + x, 8 * b[1] + y, 8 * b[2] + z};
-  const double T0 = (double)tsdf_w[i].x;
-  const float4 c0 = rgb_w[i];
-  unsigned long long row = vbase[i];
-  for (unsigned d = 1; d < 8; d++) {
-    if (!((mask >> d) & 1u)) continue;
-    const long long j = blk_at(g, r, x + (int)(d & 1u), y + (int)((d >> 1) & 1u), z + (int)((d >> 2) & 1u));      // (there: the plan found the edge through the same table)
-    if (row < e.vcap && j >= 0) {
-      const double T1 = (double)tsdf_w[j].x;
-      const float4 c1 = rgb_w[j];
-      const double t = T0 / (T0 - T1);
-      const float px = (float)(e.o[0] + e.voxel * ((double)q[0] + t * (double)(d & 1u)));
-      const float py = (float)(e.o[1] + e.voxel * ((double)q[1] + t * (double)((d >> 1) & 1u)));
-      const float pz = (float)(e.o[2] + e.voxel * ((double)q[2] + t * (double)((d >> 2) & 1u)));
-      const float cr = (float)((double)c0.x + t * ((double)c1.x - (double)c0.x));
-      const float cg = (float)((double)c0.y + t * ((double)c1.y - (double)c0.y));
-      const float cb = (float)((double)c0.z + t * ((double)c1.z - (double)c0.z));
-      rows[row] = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), pc_quant(cr) | (pc_quant(cg) << 8) | (pc_quant(cb) << 16) | 0xff000000u);
-    }
-    row++;
-  }
-}
-
-__global__ void __launch_bounds__(SB)
-blk_triangle_kernel(BlkGrid g, TmEmit e, const uint8_t* __restrict__ state, const uint8_t* __restrict__ cube, const uint8_t* __restrict__ vmask,
-                    const uint32_t* __restrict__ vbase, const uint32_t* __restrict__ tbase, int* __restrict__ tris, unsigned long long* __restrict__ counters) {
-  const size_t i = (size_t)blockIdx.x * SB + threadIdx.x;
-  uint32_t written = 0, dropped = 0;
-  if (cube[i] & 0x7fu) {      // (a cube with triangles is valid: its 8 corners are there)
-    unsigned r, inside;
-    int x, y, z;
-    blk_split(i, r, x, y, z);
-    blk_cube_corners(g, state, r, x, y, z, inside);
-    unsigned long long row = tbase[i];
-    for (int k = 0; k < 6; k++) {
-      const uint32_t cs = TM_CASES[tm_tet_mask(inside, k)];
-      const unsigned corner[4] = {0u, TM_MID1[k], TM_MID2[k], 7u};
-      for (uint32_t s = 0; s < (cs & 3u); s++) {
-        uint32_t idx[3];
-        for (int a = 0; a < 3; a++) {
-          const unsigned edge = (cs >> (2 + 9 * s + 3 * a)) & 7u;
-          const unsigned lo = corner[TM_EDGE_LO[edge]], hi = corner[TM_EDGE_HI[edge]];
-          const long long smp = blk_at(g, r, x + (int)(lo & 1u), y + (int)((lo >> 1) & 1u), z + (int)((lo >> 2) & 1u));
-          // (a corner of a valid cube is there; with another neighbour table than the plan's the triangle is dropped, not read out of bounds)
-          idx[a] = smp < 0 ? 0xffffffffu : vbase[smp] + (uint32_t)__popc((unsigned)vmask[smp] & ((1u << (hi ^ lo)) - 1u));
-        }
-        if ((TM_ODD >> k) & 1u) { const uint32_t t = idx[1]; idx[1] = idx[2]; idx[2] = t; }
-        if (row < e.tcap && idx[0] < e.vcap && idx[1] < e.vcap && idx[2] < e.vcap) {
-          tris[3 * row] = (int)idx[0];
-          tris[3 * row + 1] = (int)idx[1];
-          tris[3 * row + 2] = (int)idx[2];
-          written++;
-        } else {
-          dropped++;
-        }
-        row++;
-      }
-    }
-  }
-  const uint32_t sw = wave_scan_incl(written), sd = wave_scan_incl(dropped);
-  if ((threadIdx.x & 63) == 63) {
-    if (sw) atomicAdd(counters + 3, (unsigned long long)sw);
-    if (sd) atomicAdd(counters + 5, (unsigned long long)sd);
-  }
+void launch_tsdf_blocks_mesh_plan(uint64_t n, const int* neighbours, const void* tsdf_w, float min_weight, void* work, uint64_t* counters, hipStream_t s) {
+  tm_launch_plan(blk_grid(n, neighbours, nullptr), tsdf_w, min_weight, work, counters, s);
 }
 
 void launch_tsdf_blocks_mesh_emit(uint64_t n, const uint64_t* keys, const int* neighbours, const void* tsdf_w, const void* rgb_w, const double* anchor, double voxel,
                                   const void* work, void* rows, uint64_t vcap, void* tris, uint64_t tcap, uint64_t* counters, hipStream_t s) {
-  BlkGrid g;
-  g.n = (unsigned)n; g.samples = (size_t)n * 512; g.nbr = neighbours;
-  const TmWork w = tm_work((void*)work, g.samples);
-  TmEmit e;
-  e.o[0] = anchor[0]; e.o[1] = anchor[1]; e.o[2] = anchor[2]; e.voxel = voxel; e.vcap = vcap; e.tcap = tcap;
-  const unsigned nb = (unsigned)tm_nb(g.samples);
-  hipLaunchKernelGGL(blk_vertex_kernel, dim3(nb), dim3(SB), 0, s, g, e, (const unsigned long long*)keys, (const float2*)tsdf_w, (const float4*)rgb_w, w.vmask, w.vbase,
-                     w.hdr, (uint4*)rows, (unsigned long long*)counters);
-  hipLaunchKernelGGL(blk_triangle_kernel, dim3(nb), dim3(SB), 0, s, g, e, w.state, w.cube, w.vmask, w.vbase, w.tbase, (int*)tris, (unsigned long long*)counters);
+  tm_launch_emit(blk_grid(n, neighbours, keys), tsdf_w, rgb_w, anchor, voxel, work, rows, vcap, tris, tcap, counters, s);
 }

@@ -185,6 +185,15 @@ def mesh_bounds(slam, opt, poses=None):
     return box
 
 
+def _extract_clean(volume, opt, device):
+    """(rows, triangles, counters) of a filled volume, with `mesh.clean` small / largest cleaned behind the extraction."""
+    rows, triangles, counters = volume.extract()
+    if opt.get("clean", "none") != "none":
+        rows, triangles, _, info = mc.clean(rows, triangles, opt["clean"], opt["clean_min_triangles"], device=device)
+        counters = dict(counters, clean=dict(info, mode=opt["clean"], min_triangles=opt["clean_min_triangles"], vertices=int(rows.shape[0]), triangles=int(triangles.shape[0])))
+    return rows, triangles, counters
+
+
 def mesh_geometry(slam, opt, poses=None):
     """The views of an export fused and meshed (what `export_mesh` writes and `evaluate_geometry` scores): (rows, triangles, counters,
     lattice sizes, origin); device tensors on a GPU.  `opt`: `options` of the `mesh` block; `poses` as in `views`.  With `mesh.clean`
@@ -206,12 +215,7 @@ def mesh_geometry(slam, opt, poses=None):
                         depth_max=float(opt["max_depth"]), min_weight=float(opt["min_weight"]), device=cfg["device"])
         for view in views(slam, opt["every"], opt["source"], "mesh", poses):
             volume.add(*view)
-        rows, triangles, counters = volume.extract()
-        if opt.get("clean", "none") != "none":
-            rows, triangles, _, info = mc.clean(rows, triangles, opt["clean"], opt["clean_min_triangles"], device=cfg["device"])
-            counters = dict(counters, clean=dict(info, mode=opt["clean"], min_triangles=opt["clean_min_triangles"], vertices=int(rows.shape[0]),
-                                                 triangles=int(triangles.shape[0])))
-    return rows, triangles, counters, dims, origin
+        return _extract_clean(volume, opt, cfg["device"]) + (dims, origin)
 
 
 def sparse_mesh_geometry(slam, opt, poses=None):
@@ -233,12 +237,7 @@ def sparse_mesh_geometry(slam, opt, poses=None):
         volume.freeze()
         for view in views(slam, opt["every"], opt["source"], "mesh", poses):
             volume.add(*view)
-        rows, triangles, counters = volume.extract()
-        if opt.get("clean", "none") != "none":
-            rows, triangles, _, info = mc.clean(rows, triangles, opt["clean"], opt["clean_min_triangles"], device=cfg["device"])
-            counters = dict(counters, clean=dict(info, mode=opt["clean"], min_triangles=opt["clean_min_triangles"], vertices=int(rows.shape[0]),
-                                                 triangles=int(triangles.shape[0])))
-    return rows, triangles, counters, volume.dims, volume.origin
+        return _extract_clean(volume, opt, cfg["device"]) + (volume.dims, volume.origin)
 
 
 def export_pointcloud(slam, path=None, every=None, voxel=None, source=None):

@@ -24,7 +24,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .pointcloud import CLOUD_PROPERTIES, as_np, device_view, pose_rotation, quantise_colour, read_header, read_ply, valid_mask
+from .pointcloud import CLOUD_PROPERTIES, as_np, cam_args, device_view, pose_rotation, quantise_colour, read_header, read_ply, valid_mask
 
 INTEGRATE_COUNTERS = ("views", "dist_updates", "colour_updates")
 MESH_COUNTERS = ("vertices", "triangles", "vertices_written", "triangles_written", "vertices_dropped", "triangles_dropped")
@@ -304,15 +304,40 @@ def _mesh_counters(integrate, mesh):
     return out
 
 
+def _check_voxel_trunc(voxel, trunc, max_trunc_voxels=None):
+    voxel, trunc = float(voxel), float(trunc)
+    if not (np.isfinite(voxel) and voxel > 0 and np.isfinite(trunc) and trunc > 0):
+        raise ValueError(f"voxel = {voxel}, trunc = {trunc} (both must be finite and positive)")
+    if max_trunc_voxels is not None and not trunc <= max_trunc_voxels * voxel:
+        raise ValueError(f"trunc = {trunc} is more than {max_trunc_voxels} voxel = {max_trunc_voxels * voxel}")
+    return voxel, trunc
+
+
+def double3(v):
+    """A numpy origin or anchor as the C ABI's ``const double*`` of three values."""
+    import ctypes as C
+    return (C.c_double * 3)(*v.tolist())
+
+
+def _emit_exact(device, totals, emit):
+    """What both device extractions do behind the read-back of the plan's totals [V, T, ...]: rows and triangles allocated at exactly V and
+    T, `emit(rows, V, triangles, T)`, and the emit's counter row -- the allocations are exact: nothing is dropped."""
+    V, T = int(totals[0]), int(totals[1])
+    if V >= 1 << 31:
+        raise ValueError(f"mesh of {V} vertices: more than int32 triangle indices reach; raise mesh.voxel")
+    rows = torch.empty(max(V, 1), 4, dtype=torch.int32, device=device)
+    tris = torch.empty(max(T, 1), 3, dtype=torch.int32, device=device)
+    emit(rows, V, tris, T)
+    return rows[:V], tris[:T], np.array([V, T, V, T, 0, 0, 0, 0], dtype=np.int64)
+
+
 class HostTsdfVolume:
     """The volume of ``device: cpu``: the host statement, view by view."""
 
     def __init__(self, dims, origin, voxel, trunc, H, W, cam, sil_min=0.99, depth_max=0.0, min_weight=1.0, device=None):
         self.nx, self.ny, self.nz = (int(v) for v in dims)
         check_lattice(self.nx, self.ny, self.nz)
-        self.origin, self.voxel, self.trunc = np.asarray(origin, dtype=np.float64).reshape(3).copy(), float(voxel), float(trunc)
-        if not (np.isfinite(self.voxel) and self.voxel > 0 and np.isfinite(self.trunc) and self.trunc > 0):
-            raise ValueError(f"voxel = {voxel}, trunc = {trunc} (both must be finite and positive)")
+        self.origin, (self.voxel, self.trunc) = np.asarray(origin, dtype=np.float64).reshape(3).copy(), _check_voxel_trunc(voxel, trunc)
         self.H, self.W, self.cam = int(H), int(W), cam
         self.sil_min, self.depth_max, self.min_weight = float(sil_min), float(depth_max), float(min_weight)
         self.tsdf_w, self.rgb_w = empty_volume(self.nx, self.ny, self.nz)
@@ -347,18 +372,13 @@ class TsdfVolume:
         self.rgb_w = torch.zeros(self.nz, self.ny, self.nx, 4, dtype=torch.float32, device=device)
         self.counters = torch.zeros(8, dtype=torch.int64, device=device)
 
-    def _origin(self):
-        import ctypes as C
-        return (C.c_double * 3)(*self.origin.tolist())
-
     def add(self, color, depth, sil, pose):
         from . import _lib
         from .rasterizer import _stream
         color_c, depth_c, sil_c, pose_c = device_view("TsdfVolume", self.H, self.W, color, depth, sil, pose)
-        c, P = self.cam, _lib.ptr
-        _lib.check(self.lib.mm3dgs_tsdf_integrate(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c), P(color_c),
-                                                  P(depth_c), P(sil_c), self.sil_min, self.depth_max, self._origin(), self.voxel, self.trunc,
-                                                  self.nx, self.ny, self.nz, P(self.tsdf_w), P(self.rgb_w), P(self.counters), _stream()))
+        P = _lib.ptr
+        _lib.check(self.lib.mm3dgs_tsdf_integrate(self.H, self.W, *cam_args(self.cam), P(pose_c), P(color_c), P(depth_c), P(sil_c), self.sil_min, self.depth_max,
+                                                  double3(self.origin), self.voxel, self.trunc, self.nx, self.ny, self.nz, P(self.tsdf_w), P(self.rgb_w), P(self.counters), _stream()))
 
     def extract(self):
         """(rows [V,4] int32, triangles [T,3] int32, counters): tensors on the device."""
@@ -370,15 +390,9 @@ class TsdfVolume:
         mc = torch.empty(8, dtype=torch.int64, device=self.device)
         _lib.check(self.lib.mm3dgs_tsdf_mesh_plan(self.nx, self.ny, self.nz, P(self.tsdf_w), self.min_weight, P(work), P(mc), _stream()))
         totals = torch.cat([mc, self.counters]).cpu().numpy()      # the one read-back before the allocation
-        V, T = int(totals[0]), int(totals[1])
-        if V >= 1 << 31:
-            raise ValueError(f"mesh of {V} vertices: more than int32 triangle indices reach; raise mesh.voxel")
-        rows = torch.empty(max(V, 1), 4, dtype=torch.int32, device=self.device)
-        tris = torch.empty(max(T, 1), 3, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.mm3dgs_tsdf_mesh_emit(self.nx, self.ny, self.nz, P(self.tsdf_w), P(self.rgb_w), self._origin(), self.voxel, P(work), P(rows), V,
-                                                  P(tris), T, P(mc), _stream()))
-        m = np.array([V, T, V, T, 0, 0, 0, 0], dtype=np.int64)     # the allocations are exact: nothing is dropped
-        return rows[:V], tris[:T], _mesh_counters(totals[8:], m)
+        rows, tris, m = _emit_exact(self.device, totals, lambda rows, V, tris, T: _lib.check(self.lib.mm3dgs_tsdf_mesh_emit(
+            self.nx, self.ny, self.nz, P(self.tsdf_w), P(self.rgb_w), double3(self.origin), self.voxel, P(work), P(rows), V, P(tris), T, P(mc), _stream())))
+        return rows, tris, _mesh_counters(totals[8:], m)
 
 
 # ---- the volume as voxel blocks (mesh.volume: sparse) ------------------------------------------------------------------------------------
@@ -555,11 +569,7 @@ def _check_frozen(c, max_blocks, voxel):
 
 
 def _sparse_options(voxel, trunc, max_blocks):
-    voxel, trunc = float(voxel), float(trunc)
-    if not (np.isfinite(voxel) and voxel > 0 and np.isfinite(trunc) and trunc > 0):
-        raise ValueError(f"voxel = {voxel}, trunc = {trunc} (both must be finite and positive)")
-    if not trunc <= MAX_TRUNC_VOXELS * voxel:
-        raise ValueError(f"trunc = {trunc} is more than {MAX_TRUNC_VOXELS} voxel = {MAX_TRUNC_VOXELS * voxel}")
+    voxel, trunc = _check_voxel_trunc(voxel, trunc, MAX_TRUNC_VOXELS)
     if not 1 <= int(max_blocks) <= MAX_BLOCKS:
         raise ValueError(f"max_blocks = {max_blocks} (1 .. 2^21)")
     return voxel, trunc, int(max_blocks)
@@ -648,31 +658,15 @@ class SparseTsdfVolume:
         self.n = None
         _lib.check(self.lib.mm3dgs_tsdf_blocks_reset(_lib.ptr(self.table), self.max_blocks, _lib.ptr(self.rc), _stream()))
 
-    def _anchor(self):
-        import ctypes as C
-        return (C.c_double * 3)(*self.anchor.tolist())
-
-    def _view(self, what, color, depth, sil, pose):
-        tensors = [depth, pose] + ([] if sil is None else [sil]) + ([] if color is None else [color])
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
-            raise RuntimeError(f"SparseTsdfVolume.{what} needs device tensors (the host path is HostSparseTsdfVolume)")
-        H, W = self.H, self.W
-        if (color is not None and tuple(color.shape) != (3, H, W)) or tuple(depth.shape) != (H, W) or (sil is not None and tuple(sil.shape) != (H, W)):
-            raise ValueError(f"SparseTsdfVolume.{what}: color [3,{H},{W}], depth and sil [{H},{W}]; got {None if color is None else tuple(color.shape)}, "
-                             f"{tuple(depth.shape)}, {None if sil is None else tuple(sil.shape)}")
-        prep = lambda t: None if t is None else t.detach().float().contiguous()
-        return prep(color), prep(depth), prep(sil), prep(pose).reshape(7)
-
     def reserve(self, depth, sil, pose):
         from . import _lib
         from .rasterizer import _stream
         if self.n is not None:
             raise RuntimeError("SparseTsdfVolume.reserve after freeze")
-        _, depth_c, sil_c, pose_c = self._view("reserve", None, depth, sil, pose)
-        c, P = self.cam, _lib.ptr
-        _lib.check(self.lib.mm3dgs_tsdf_blocks_reserve(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c), P(depth_c), P(sil_c),
-                                                       self.sil_min, self.depth_max, self._anchor(), self.voxel, self.trunc, self.clip, P(self.table), self.max_blocks,
-                                                       P(self.rc), _stream()))
+        _, depth_c, sil_c, pose_c = device_view("SparseTsdfVolume", self.H, self.W, None, depth, sil, pose, "reserve")
+        P = _lib.ptr
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_reserve(self.H, self.W, *cam_args(self.cam), P(pose_c), P(depth_c), P(sil_c), self.sil_min, self.depth_max,
+                                                       double3(self.anchor), self.voxel, self.trunc, self.clip, P(self.table), self.max_blocks, P(self.rc), _stream()))
 
     def freeze(self):
         """Lists, sorts and indexes the block set and allocates the pool at exactly n blocks; returns n.  ValueError when blocks were
@@ -698,11 +692,10 @@ class SparseTsdfVolume:
         from .rasterizer import _stream
         if self.n is None:
             raise RuntimeError("SparseTsdfVolume.add before freeze")
-        color_c, depth_c, sil_c, pose_c = self._view("add", color, depth, sil, pose)
-        c, P = self.cam, _lib.ptr
-        _lib.check(self.lib.mm3dgs_tsdf_blocks_integrate(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c), P(color_c),
-                                                         P(depth_c), P(sil_c), self.sil_min, self.depth_max, self._anchor(), self.voxel, self.trunc, P(self.keys),
-                                                         self.n, P(self.tsdf_w), P(self.rgb_w), P(self.counters), _stream()))
+        color_c, depth_c, sil_c, pose_c = device_view("SparseTsdfVolume", self.H, self.W, color, depth, sil, pose)
+        P = _lib.ptr
+        _lib.check(self.lib.mm3dgs_tsdf_blocks_integrate(self.H, self.W, *cam_args(self.cam), P(pose_c), P(color_c), P(depth_c), P(sil_c), self.sil_min, self.depth_max,
+                                                         double3(self.anchor), self.voxel, self.trunc, P(self.keys), self.n, P(self.tsdf_w), P(self.rgb_w), P(self.counters), _stream()))
 
     def extract(self):
         """(rows [V,4] int32, triangles [T,3] int32, counters): tensors on the device; sets ``dims`` and ``origin`` of the bounding lattice."""
@@ -715,20 +708,15 @@ class SparseTsdfVolume:
         _lib.check(self.lib.mm3dgs_tsdf_blocks_mesh_plan(n, P(self.neighbours), P(self.tsdf_w), self.min_weight, P(work), P(mc), _stream()))
         digits = torch.stack([self.keys & 0x1fffff, (self.keys >> 21) & 0x1fffff, self.keys >> 42], 1)      # bx, by, bz + 2^20
         totals = torch.cat([mc, self.counters, self.rc, digits.amin(0), digits.amax(0)]).cpu().numpy()      # the one read-back before the allocation
-        V, T, rc = int(totals[0]), int(totals[1]), totals[16:24]
+        rc = totals[16:24]
         if int(rc[6]):
             raise RuntimeError(f"SparseTsdfVolume: mm3dgs_tsdf_blocks_index rejected {int(rc[6])} of the {n} sorted keys")
-        if V >= 1 << 31:
-            raise ValueError(f"mesh of {V} vertices: more than int32 triangle indices reach; raise mesh.voxel")
         bmin, bmax = totals[24:27].astype(np.int64) - BLOCK_BIAS, totals[27:30].astype(np.int64) - BLOCK_BIAS
         self.dims = [int(v) for v in BLOCK * (bmax - bmin + 1)]
         self.origin = self.anchor + self.voxel * (BLOCK * bmin).astype(np.float64)
-        rows = torch.empty(max(V, 1), 4, dtype=torch.int32, device=self.device)
-        tris = torch.empty(max(T, 1), 3, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.mm3dgs_tsdf_blocks_mesh_emit(n, P(self.keys), P(self.neighbours), P(self.tsdf_w), P(self.rgb_w), self._anchor(), self.voxel, P(work), P(rows), V,
-                                                         P(tris), T, P(mc), _stream()))
-        m = np.array([V, T, V, T, 0, 0, 0, 0], dtype=np.int64)     # the allocations are exact: nothing is dropped
-        return rows[:V], tris[:T], _sparse_counters(totals[8:16], m, rc, n)
+        rows, tris, m = _emit_exact(self.device, totals, lambda rows, V, tris, T: _lib.check(self.lib.mm3dgs_tsdf_blocks_mesh_emit(
+            n, P(self.keys), P(self.neighbours), P(self.tsdf_w), P(self.rgb_w), double3(self.anchor), self.voxel, P(work), P(rows), V, P(tris), T, P(mc), _stream())))
+        return rows, tris, _sparse_counters(totals[8:16], m, rc, n)
 
 
 # ---- files ----------------------------------------------------------------------------------------------------------------------

@@ -154,17 +154,22 @@ class HostPointCloudBuilder:
         return np.concatenate(self.parts) if self.parts else np.empty((0, 4), dtype=np.int32)
 
 
-def device_view(who, H, W, color, depth, sil, pose):
-    """One view as the device builders (`who`: PointCloudBuilder, TsdfVolume) take it: device tensors color [3,H,W], depth and sil (or None)
-    [H,W], pose 7 values, returned as contiguous float32 (color, depth, sil, pose [7]); such a tensor is not copied."""
-    tensors = [color, depth, pose] + ([] if sil is None else [sil])
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
-        raise RuntimeError(f"{who}.add needs device tensors (the host path is Host{who})")
-    if tuple(color.shape) != (3, H, W) or tuple(depth.shape) != (H, W) or (sil is not None and tuple(sil.shape) != (H, W)):
-        raise ValueError(f"{who}.add: color [3,{H},{W}], depth and sil [{H},{W}]; got {tuple(color.shape)}, "
-                         f"{tuple(depth.shape)}, {None if sil is None else tuple(sil.shape)}")
+def device_view(who, H, W, color, depth, sil, pose, method="add"):
+    """One view as the device builders (`who`: PointCloudBuilder, TsdfVolume, SparseTsdfVolume; `method`: the one that was called) take it:
+    device tensors color [3,H,W] (None where the method reads none), depth and sil (or None) [H,W], pose 7 values, returned as contiguous
+    float32 (color, depth, sil, pose [7]); such a tensor is not copied."""
+    shape = lambda t: None if t is None else tuple(t.shape)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (color, depth, pose, sil) if t is not None):
+        raise RuntimeError(f"{who}.{method} needs device tensors (the host path is Host{who})")
+    if shape(color) not in (None, (3, H, W)) or shape(depth) != (H, W) or shape(sil) not in (None, (H, W)):
+        raise ValueError(f"{who}.{method}: color [3,{H},{W}], depth and sil [{H},{W}]; got {shape(color)}, {shape(depth)}, {shape(sil)}")
     prep = lambda t: None if t is None else t.detach().float().contiguous()
     return prep(color), prep(depth), prep(sil), prep(pose).reshape(7)
+
+
+def cam_args(cam):
+    """(fx, fy, cx, cy) of a camera dict as the C ABI's four doubles."""
+    return tuple(float(cam[k]) for k in ("fx", "fy", "cx", "cy"))
 
 
 class PointCloudBuilder:
@@ -202,10 +207,9 @@ class PointCloudBuilder:
         from . import _lib
         from .rasterizer import _stream
         color_c, depth_c, sil_c, pose_c = device_view("PointCloudBuilder", self.H, self.W, color, depth, sil, pose)
-        c, P = self.cam, _lib.ptr
-        _lib.check(self.lib.mm3dgs_pointcloud_add_view(self.H, self.W, float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"]), P(pose_c),
-                                                       P(color_c), P(depth_c), P(sil_c), self.sil_min, self.depth_max, self.voxel, self.view,
-                                                       P(self.buf), self.cap, P(self.table), self.slots, P(self.counters), P(self.work), _stream()))
+        P = _lib.ptr
+        _lib.check(self.lib.mm3dgs_pointcloud_add_view(self.H, self.W, *cam_args(self.cam), P(pose_c), P(color_c), P(depth_c), P(sil_c), self.sil_min, self.depth_max,
+                                                       self.voxel, self.view, P(self.buf), self.cap, P(self.table), self.slots, P(self.counters), P(self.work), _stream()))
         self.view += 1
         self._read = None
 

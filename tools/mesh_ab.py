@@ -164,7 +164,7 @@ def mesh_times(slam, args, emit, H, W, source, origin, voxel, trunc):
         _lib.check(vol.lib.mm3dgs_tsdf_mesh_plan(SIDE, SIDE, SIDE, P(vol.tsdf_w), 1.0, P(work), P(mc), _stream()))
 
     def emit_():
-        _lib.check(vol.lib.mm3dgs_tsdf_mesh_emit(SIDE, SIDE, SIDE, P(vol.tsdf_w), P(vol.rgb_w), vol._origin(), voxel, P(work), P(rows), V, P(tris), T, P(mc), _stream()))
+        _lib.check(vol.lib.mm3dgs_tsdf_mesh_emit(SIDE, SIDE, SIDE, P(vol.tsdf_w), P(vol.rgb_w), ms.double3(vol.origin), voxel, P(work), P(rows), V, P(tris), T, P(mc), _stream()))
 
     for _ in range(args.untimed):
         plan(); emit_()

@@ -102,12 +102,12 @@ def one_config(slam, args, emit, H, W, source):
 
     def sparse_mesh():
         _lib.check(lib.mm3dgs_tsdf_blocks_mesh_plan(n, P(sparse.neighbours), P(sparse.tsdf_w), 1.0, P(swork), P(mc), _stream()))
-        _lib.check(lib.mm3dgs_tsdf_blocks_mesh_emit(n, P(sparse.keys), P(sparse.neighbours), P(sparse.tsdf_w), P(sparse.rgb_w), sparse._anchor(), voxel, P(swork), P(srows),
+        _lib.check(lib.mm3dgs_tsdf_blocks_mesh_emit(n, P(sparse.keys), P(sparse.neighbours), P(sparse.tsdf_w), P(sparse.rgb_w), ms.double3(sparse.anchor), voxel, P(swork), P(srows),
                                                     sc_["vertices"], P(stris), sc_["triangles"], P(mc), _stream()))
 
     def dense_mesh():
         _lib.check(lib.mm3dgs_tsdf_mesh_plan(SIDE, SIDE, SIDE, P(dense.tsdf_w), 1.0, P(dwork), P(mc), _stream()))
-        _lib.check(lib.mm3dgs_tsdf_mesh_emit(SIDE, SIDE, SIDE, P(dense.tsdf_w), P(dense.rgb_w), dense._origin(), voxel, P(dwork), P(drows), dc_["vertices"], P(dtris),
+        _lib.check(lib.mm3dgs_tsdf_mesh_emit(SIDE, SIDE, SIDE, P(dense.tsdf_w), P(dense.rgb_w), ms.double3(dense.origin), voxel, P(dwork), P(drows), dc_["vertices"], P(dtris),
                                              dc_["triangles"], P(mc), _stream()))
 
     us = timed((("sparse", sparse_mesh), ("dense", dense_mesh)), args.calls, args.untimed)

@@ -125,6 +125,43 @@ def mesh():
             put(f"mesh {dims} {kind}", rows[:V], tris[:T], c)
 
 
+def mesh_sparse():
+    from tests import mesh_sparse_cases as sc, test_gpu_mesh_sparse as t
+    from mm3dgs_slam_amd import mesh as ms
+
+    def frozen(key, blk):
+        put(f"blocks {key} keys", blk.keys.cpu()[:blk.n], blk.neighbours())
+
+    def extract(key, blk, anchor, voxel):
+        m = t.BlockMesher(blk, anchor, voxel, 0, 0)
+        assert m.plan() == 0
+        V, T = (int(x) for x in m.counters.cpu()[:2])
+        m = t.BlockMesher(blk, anchor, voxel, V, T, work_fill=0xFF)
+        assert m.plan() == 0 and m.emit() == 0
+        rows, tris, c = m.read()
+        put(f"blocks {key} mesh", rows[:V], tris[:T], c)
+
+    wall = t._against_dense(sc.sphere_case(0.03, True))      # reserved, frozen and integrated, as the tests' `wall` fixture
+    frozen("wall", wall["blk"])
+    put("blocks wall pool", *wall["blk"].pool())
+    extract("wall", wall["blk"], wall["case"]["anchor"], wall["case"]["voxel"])
+    base = sc.scattered_case((17, 33), "all", 3)             # the anchor in the scene's middle, as the tests' `astride` fixture
+    b0 = ms.key_blocks(sc.reserve_all(base)[0])
+    case = dict(base, anchor=base["voxel"] * 8.0 * 0.5 * (b0.min(0) + b0.max(0) + 1) + np.array([0.0031, -0.0042, 0.0057]))
+    blk, views = t.Blocks(case, 512), [t.to_dev(v) for v in case["views"]]
+    for v in views:
+        assert blk.reserve(v) == 0
+    blk.freeze()
+    for v in views:
+        assert blk.integrate(v) == 0
+    frozen("negative", blk)
+    put("blocks negative pool", *blk.pool())
+    extract("negative", blk, case["anchor"], case["voxel"])
+    for name in ("one block", "2 x 2 x 2", "sphere", "torus", "sphere minus a third", "torus minus a third"):
+        a = t._analytic(name)
+        extract(name, t.GivenBlocks(a["keys"], *sc.to_pool(a["tsdf_w"], a["rgb_w"], a["blocks"], a["first"], a["dims"])), a["origin"], a["voxel"])
+
+
 def geometry():
     from tests import geometry_cases as cases, test_gpu_geometry as t
 
@@ -186,7 +223,7 @@ def pose_prediction():
 
 def main():
     from mm3dgs_slam_amd import _lib
-    for stage in (surgery, pointcloud, mesh, geometry, evaluation, depth_align, pose_prediction):
+    for stage in (surgery, pointcloud, mesh, mesh_sparse, geometry, evaluation, depth_align, pose_prediction):
         t0 = time.time()
         before = len(OUT)
         stage()
