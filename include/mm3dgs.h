@@ -710,6 +710,61 @@ int mm3dgs_mesh_sample_plan(uint64_t n_vertices, const void* vrows /*[n_vertices
 int mm3dgs_mesh_sample_emit(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed,
                             const void* work, void* rows /*[cap] x 16 bytes*/, uint64_t cap, uint64_t* counters /*[8], device*/, void* stream);
 
+/* ---- normals: normal consistency of two sampled meshes, and area-weighted vertex normals ------------------------------------------------
+ * Host statement: mm3dgs_slam_amd/geometry.py (nn_index_host, normal_row, vertex_normals_host).  Meshes as the sampler takes them.
+ *
+ * The face cross product c_t = (b - a) x (c - a) from the float32 corners widened to double, no fused multiply-add, as the sampler's area
+ * forms it (one device function serves all three).  A triangle is rejected when an index is outside [0, n_vertices), a corner is not finite,
+ * or c.c is 0 or not finite.
+ *
+ * mm3dgs_nn_query_index: mm3dgs_nn_query (same arguments, same launches, same bytes in dist_out, row and work) that also writes index_out
+ * uint32 [n_q], 4-byte aligned: the original reference row (the fourth word of the sorted record) of the record with the smallest double
+ * squared distance, the smallest row index on an exact tie -- the stop rule leaves only strictly farther records unsearched, so the
+ * lexicographic minimum over (d2, row) of the searched records is the global one, whatever the order inside a cell -- and 0xffffffff for a
+ * query that is skipped or clamped.
+ *
+ * mm3dgs_mesh_sample_emit_tri: mm3dgs_mesh_sample_emit (same bytes in rows and counters) that also writes tri_out uint32 [cap], 4-byte
+ * aligned: the triangle of every written sample.
+ *
+ * mm3dgs_normal_consistency: one lane per query i with its triangle tq = tri_q[i] (of mesh q), its nearest row j = index[i] and that row's
+ * triangle tr = tri_r[j] (of mesh r; tri_r has n_r entries).  dot = (c_tq . c_tr) / (sqrt(c_tq . c_tq) sqrt(c_tr . c_tr)) in double,
+ * clamped to [-1, 1], rounded once to float32 at the store to dot_out [n_q].  Not counted, dot_out NaN: j == 0xffffffff (no neighbour; this
+ * test comes first), or j >= n_r, tq >= m_q, tr >= m_r or a rejected triangle (bad triangle) -- nothing is read for an id out of range.
+ * row: double[8] on the device: [0] n counted, [1] mean |dot|, [2] mean dot, [3] min |dot|, [4] 0, [5] not counted: no neighbour, [6] not
+ * counted: bad triangle, [7] 0 -- over the stored float32 values widened to double, summed in mm3dgs_nn_query's order (per workgroup one
+ * partial row in a fixed lane order, one workgroup over the partial rows); [1:4] are 0 when n is 0.  No float atomic: the same bytes on
+ * every call.  work: mm3dgs_normal_consistency_work_bytes(n_q) bytes, 8-byte aligned.  Two launches, no host synchronisation.  Nothing
+ * outside dot_out[0:n_q], row[0:8] and work is written.
+ *
+ * mm3dgs_mesh_vertex_normals: normals float [n_vertices][3], area-weighted, in fixed point so that no order of arrival changes a bit.
+ * Every triangle t that is not rejected has E_t, the binary exponent of max(|c_x|, |c_y|, |c_z|) as frexp returns it; E_v = max E_t over
+ * the triangles with corner v (integer atomicMax); every such triangle adds llrint(ldexp(c_k, 40 - E_v)), k = x, y, z, to three int64 sums
+ * S_v (64-bit integer atomicAdd: each term is below 2^40 in magnitude, so the sums are exact up to a valence of 2^22; beyond it they wrap
+ * in two's complement, which is the defined behaviour); n_v = S_v / sqrt(S_v . S_v) in double from the sums converted to double, rounded
+ * once to float32; (0, 0, 0) when v has no such triangle or S_v = 0.  counters uint64[8], device, not cumulative: [0] vertices, [1] vertices
+ * without a normal, [2] rejected triangles, the rest 0.  work: mm3dgs_mesh_vertex_normals_work_bytes(n_vertices) bytes, 8-byte aligned,
+ * contents irrelevant before and after.  Four launches (zero, exponents, sums, normals), no adjacency, no sort, no host synchronisation.
+ * Nothing outside normals[0:3 n_vertices], counters[0:8] and work is written.
+ *
+ * -1 (nothing is launched, nothing is written): the cases of mm3dgs_nn_query / mm3dgs_mesh_sample_emit for the first two, and a NULL
+ * index_out or tri_out (tri_out only with a cap above 0) or one not 4-byte aligned; n_q or n_r of 0 or above 2^30; m of 0 or above 2^30;
+ * n_vertices of 0 or above 2^31 - 1; a NULL pointer; vertex rows not 16-byte aligned, row, work or counters not 8-byte aligned, any other
+ * array not 4-byte aligned.  The *_work_bytes functions return 0 for sizes the calls reject. */
+int mm3dgs_nn_query_index(uint64_t n_q, const void* q_rows /*[n_q] x 16 bytes*/, uint64_t n_ref, double cell, const int64_t* origin_cell /*host [3]*/,
+                          int gx, int gy, int gz, const uint32_t* cell_start, const void* sorted, double max_dist, double threshold,
+                          float* dist_out /*[n_q]*/, uint32_t* index_out /*[n_q]*/, double* row /*[8], device*/, void* work, void* stream);
+int mm3dgs_mesh_sample_emit_tri(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed,
+                                const void* work, void* rows /*[cap] x 16 bytes*/, uint32_t* tri_out /*[cap]*/, uint64_t cap,
+                                uint64_t* counters /*[8], device*/, void* stream);
+size_t mm3dgs_normal_consistency_work_bytes(uint64_t n_q);
+int mm3dgs_normal_consistency(uint64_t n_q, const uint32_t* tri_q /*[n_q]*/, const uint32_t* index /*[n_q]*/, uint64_t n_r, const uint32_t* tri_r /*[n_r]*/,
+                              uint64_t n_vertices_q, const void* vrows_q, uint64_t m_q, const int32_t* triangles_q, uint64_t n_vertices_r,
+                              const void* vrows_r, uint64_t m_r, const int32_t* triangles_r, float* dot_out /*[n_q]*/, double* row /*[8], device*/,
+                              void* work, void* stream);
+size_t mm3dgs_mesh_vertex_normals_work_bytes(uint64_t n_vertices);
+int mm3dgs_mesh_vertex_normals(uint64_t n_vertices, const void* vrows /*[n_vertices] x 16 bytes*/, uint64_t m, const int32_t* triangles /*[m][3]*/,
+                               float* normals /*[n_vertices][3]*/, void* work, uint64_t* counters /*[8], device*/, void* stream);
+
 /* ---- visibility culling: the rows of a point set that the views of a run could have seen ------------------------------------------------
  * Host statement: mm3dgs_slam_amd/cull.py (cull_host).  rows: [n] x 16 bytes {float x, y, z; uint32 rgba} on the device, 16-byte aligned;
  * seen: uint32 [n] and counters: uint64 [8] on the device, both zeroed by the caller before the first view.
@@ -989,7 +1044,10 @@ const char* mm3dgs_last_error(void);
         pieces); mm3dgs_mesh_depth_work_bytes / mm3dgs_mesh_depth_render / mm3dgs_depth_compare_work_bytes / mm3dgs_depth_compare (a
         triangle mesh rendered to a depth image from a camera, and the depth L1 of two such images); mm3dgs_tsdf_blocks_table_bytes /
         mm3dgs_tsdf_blocks_reset / _reserve / _list / _index / _integrate / mm3dgs_tsdf_blocks_mesh_work_bytes / _mesh_plan / _mesh_emit
-        (the mesh export's volume as hashed 8 x 8 x 8 voxel blocks, mesh.volume: sparse); a caller that needs them looks the symbols up */
+        (the mesh export's volume as hashed 8 x 8 x 8 voxel blocks, mesh.volume: sparse); mm3dgs_nn_query_index /
+        mm3dgs_mesh_sample_emit_tri / mm3dgs_normal_consistency_work_bytes / mm3dgs_normal_consistency /
+        mm3dgs_mesh_vertex_normals_work_bytes / mm3dgs_mesh_vertex_normals (normal consistency for the geometry scores, vertex normals
+        for mesh.ply); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

@@ -100,6 +100,14 @@ MESH_CLEAN = {"clean": "none", "clean_min_triangles": 100}
 # placeholder, not a measured default
 MESH_VOLUME = {"volume": "dense", "max_blocks": 1 << 18}
 
+# Normals (geometry.py: the face cross product, mm3dgs_normal_consistency / mm3dgs_mesh_vertex_normals), two more opt-in keys merged the
+# same way and kept apart for the same reason.  `geometry.normals`: the evaluation also scores normal consistency -- the mean |dot| of the
+# face normal under a sample and the face normal under its nearest sample of the other surface, both directions -- into the `normals`
+# block of metrics.json and outputdir/geometry/normals.npz; needs `estimate: mesh` and a mesh as the reference.  `mesh.normals`: mesh.ply
+# carries area-weighted vertex normals of the final (cleaned) mesh, `float nx ny nz` behind the position
+GEOMETRY_NORMALS = {"normals": False}
+MESH_NORMALS = {"normals": False}
+
 # configs/UTMM.yml's hot-path settings that differ from TUM.yml (BASELINE.json configs[2]: RGB-D + IMU): 640x330, intrinsics of the
 # 1280x660 sensor scaled by 1/2 (gradslam_datasets/datautils.py:73-118), isotropic Gaussians, IMU dead-reckoning for the pose
 # prediction, Pearson term in tracking, 0.002 pose learning rates, size threshold 200.

@@ -1053,6 +1053,83 @@ int mm3dgs_mesh_sample_emit(uint64_t n_vertices, const void* vrows, uint64_t m, 
   return check_launch("mesh_sample_emit");
 }
 
+// ---- normals (geometry.hip): the two calls above with an index / a triangle per row, normal consistency, vertex normals ----------------
+int mm3dgs_nn_query_index(uint64_t n_q, const void* q_rows, uint64_t n_ref, double cell, const int64_t* origin_cell, int gx, int gy, int gz,
+                          const uint32_t* cell_start, const void* sorted, double max_dist, double threshold, float* dist_out, uint32_t* index_out,
+                          double* row, void* work, void* stream) {
+  if (n_q < 1 || n_q > NN_MAX_ROWS) return fail(-1, "nn_query_index: n_q = %llu (1 .. 2^30)", (unsigned long long)n_q);
+  if (n_ref < 1 || n_ref > NN_MAX_ROWS) return fail(-1, "nn_query_index: n_ref = %llu (1 .. 2^30)", (unsigned long long)n_ref);
+  if (!nn_grid_ok(gx, gy, gz)) return fail(-1, "nn_query_index: grid %d x %d x %d (every size at least 1, at most 2^26 cells)", gx, gy, gz);
+  if (!(cell > 0.0) || !isfinite(cell)) return fail(-1, "nn_query_index: cell = %g (must be finite and positive)", cell);
+  if (!(max_dist > 0.0) || !isfinite(max_dist)) return fail(-1, "nn_query_index: max_dist = %g (must be finite and positive)", max_dist);
+  if (!(threshold >= 0.0) || !isfinite(threshold)) return fail(-1, "nn_query_index: threshold = %g (must be finite and not negative)", threshold);
+  const double rings = ceil(max_dist / cell);
+  if (!(rings <= NN_MAX_RINGS)) return fail(-1, "nn_query_index: max_dist / cell = %g (at most 2^20 rings)", max_dist / cell);
+  if (!nn_origin_ok(origin_cell)) return fail(-1, "nn_query_index: origin_cell is NULL or beyond +-2^40");
+  if (!q_rows || !cell_start || !sorted || !dist_out || !index_out || !row || !work)
+    return fail(-1, "nn_query_index: NULL argument (q_rows, cell_start, sorted, dist_out, index_out, row and work are required)");
+  if (((uintptr_t)q_rows | (uintptr_t)sorted) & 15) return fail(-1, "nn_query_index: q_rows and sorted must be 16-byte aligned");
+  if (((uintptr_t)row | (uintptr_t)work) & 7) return fail(-1, "nn_query_index: row and work must be 8-byte aligned");
+  if (((uintptr_t)cell_start | (uintptr_t)dist_out | (uintptr_t)index_out) & 3) return fail(-1, "nn_query_index: cell_start, dist_out and index_out must be 4-byte aligned");
+  launch_nn_query_index(nn_grid(cell, origin_cell, gx, gy, gz), n_q, q_rows, n_ref, cell_start, sorted, max_dist, threshold, (int)(rings < 1.0 ? 1.0 : rings),
+                        dist_out, index_out, row, work, (hipStream_t)stream);
+  return check_launch("nn_query_index");
+}
+
+int mm3dgs_mesh_sample_emit_tri(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed, const void* work,
+                                void* rows, uint32_t* tri_out, uint64_t cap, uint64_t* counters, void* stream) {
+  if (mesh_sample_check("mesh_sample_emit_tri", n_vertices, vrows, m, triangles, density, work, counters)) return -1;
+  if (cap > ((uint64_t)1 << 31)) return fail(-1, "mesh_sample_emit_tri: cap = %llu (at most 2^31)", (unsigned long long)cap);
+  if ((!rows || !tri_out) && cap) return fail(-1, "mesh_sample_emit_tri: rows or tri_out is NULL with a cap above 0");
+  if ((uintptr_t)rows & 15) return fail(-1, "mesh_sample_emit_tri: rows must be 16-byte aligned");
+  if ((uintptr_t)tri_out & 3) return fail(-1, "mesh_sample_emit_tri: tri_out must be 4-byte aligned");
+  launch_mesh_sample_emit_tri(mesh_sample(n_vertices, vrows, m, triangles, density, seed), work, rows, tri_out, cap, counters, (hipStream_t)stream);
+  return check_launch("mesh_sample_emit_tri");
+}
+
+// the size and pointer checks of one mesh argument (density and seed are not used by these calls)
+static int normals_mesh_check(const char* who, const char* side, uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* tris) {
+  if (m < 1 || m > MS_MAX_TRIANGLES) return fail(-1, "%s: m%s = %llu triangles (1 .. 2^30)", who, side, (unsigned long long)m);
+  if (n_vertices < 1 || n_vertices > ((uint64_t)1 << 31) - 1) return fail(-1, "%s: n_vertices%s = %llu (1 .. 2^31 - 1)", who, side, (unsigned long long)n_vertices);
+  if (!vrows || !tris) return fail(-1, "%s: NULL argument (vrows%s and triangles%s are required)", who, side, side);
+  if ((uintptr_t)vrows & 15) return fail(-1, "%s: vrows%s must be 16-byte aligned", who, side);
+  if ((uintptr_t)tris & 3) return fail(-1, "%s: triangles%s must be 4-byte aligned", who, side);
+  return 0;
+}
+
+size_t mm3dgs_normal_consistency_work_bytes(uint64_t n_q) { return (n_q >= 1 && n_q <= NN_MAX_ROWS) ? normal_consistency_work_bytes(n_q) : 0; }
+
+int mm3dgs_normal_consistency(uint64_t n_q, const uint32_t* tri_q, const uint32_t* index, uint64_t n_r, const uint32_t* tri_r, uint64_t n_vertices_q,
+                              const void* vrows_q, uint64_t m_q, const int32_t* triangles_q, uint64_t n_vertices_r, const void* vrows_r, uint64_t m_r,
+                              const int32_t* triangles_r, float* dot_out, double* row, void* work, void* stream) {
+  if (n_q < 1 || n_q > NN_MAX_ROWS) return fail(-1, "normal_consistency: n_q = %llu (1 .. 2^30)", (unsigned long long)n_q);
+  if (n_r < 1 || n_r > NN_MAX_ROWS) return fail(-1, "normal_consistency: n_r = %llu (1 .. 2^30)", (unsigned long long)n_r);
+  if (normals_mesh_check("normal_consistency", "_q", n_vertices_q, vrows_q, m_q, triangles_q)) return -1;
+  if (normals_mesh_check("normal_consistency", "_r", n_vertices_r, vrows_r, m_r, triangles_r)) return -1;
+  if (!tri_q || !index || !tri_r || !dot_out || !row || !work)
+    return fail(-1, "normal_consistency: NULL argument (tri_q, index, tri_r, dot_out, row and work are required)");
+  if (((uintptr_t)row | (uintptr_t)work) & 7) return fail(-1, "normal_consistency: row and work must be 8-byte aligned");
+  if (((uintptr_t)tri_q | (uintptr_t)index | (uintptr_t)tri_r | (uintptr_t)dot_out) & 3)
+    return fail(-1, "normal_consistency: tri_q, index, tri_r and dot_out must be 4-byte aligned");
+  launch_normal_consistency(n_q, tri_q, index, n_r, tri_r, mesh_sample(n_vertices_q, vrows_q, m_q, triangles_q, 1.0, 0u),
+                            mesh_sample(n_vertices_r, vrows_r, m_r, triangles_r, 1.0, 0u), dot_out, row, work, (hipStream_t)stream);
+  return check_launch("normal_consistency");
+}
+
+size_t mm3dgs_mesh_vertex_normals_work_bytes(uint64_t n_vertices) {
+  return (n_vertices >= 1 && n_vertices <= ((uint64_t)1 << 31) - 1) ? mesh_vertex_normals_work_bytes(n_vertices) : 0;
+}
+
+int mm3dgs_mesh_vertex_normals(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, float* normals, void* work, uint64_t* counters,
+                               void* stream) {
+  if (normals_mesh_check("mesh_vertex_normals", "", n_vertices, vrows, m, triangles)) return -1;
+  if (!normals || !work || !counters) return fail(-1, "mesh_vertex_normals: NULL argument (normals, work and counters are required)");
+  if (((uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "mesh_vertex_normals: work and counters must be 8-byte aligned");
+  if ((uintptr_t)normals & 3) return fail(-1, "mesh_vertex_normals: normals must be 4-byte aligned");
+  launch_mesh_vertex_normals(mesh_sample(n_vertices, vrows, m, triangles, 1.0, 0u), normals, work, counters, (hipStream_t)stream);
+  return check_launch("mesh_vertex_normals");
+}
+
 // ---- visibility culling (cull.hip) -------------------------------------------------------------------------------------------------
 size_t mm3dgs_cull_work_bytes(uint64_t n) { return n <= NN_MAX_ROWS ? cull_work_bytes(n) : 0; }
 

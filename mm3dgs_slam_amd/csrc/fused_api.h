@@ -183,6 +183,20 @@ void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t 
 size_t mesh_sample_work_bytes(uint64_t m);
 void launch_mesh_sample_plan(const MeshSample& ms, void* work, uint64_t* counters, hipStream_t s);
 void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint64_t cap, uint64_t* counters, hipStream_t s);
+// the same two with what the normal scores need: the original reference row of the nearest record (index_out, 0xffffffff: none), and the
+// triangle of every sample (tri_out); the bytes of dist_out, row and rows are those of the calls above
+void launch_nn_query_index(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
+                           double threshold, int rmax, float* dist_out, uint32_t* index_out, double* row, void* work, hipStream_t s);
+void launch_mesh_sample_emit_tri(const MeshSample& ms, const void* work, void* rows, uint32_t* tri_out, uint64_t cap, uint64_t* counters, hipStream_t s);
+// normal consistency of one direction: per query its triangle tri_q[i] of mesh q, its nearest reference row index[i] (0xffffffff: none) and
+// that row's triangle tri_r[index[i]] of mesh r -> dot_out[i] and one row of eight figures; density and seed of the meshes are unused;
+// work = the buffer of normal_consistency_work_bytes(n_q); n_q, n_r <= 2^30 and the meshes as the entry point has checked them
+size_t normal_consistency_work_bytes(uint64_t n_q);
+void launch_normal_consistency(uint64_t n_q, const uint32_t* tri_q, const uint32_t* index, uint64_t n_r, const uint32_t* tri_r, const MeshSample& mq,
+                               const MeshSample& mr, float* dot_out, double* row, void* work, hipStream_t s);
+// area-weighted vertex normals in fixed point (float [n_vertices][3]); work = the buffer of mesh_vertex_normals_work_bytes(n_vertices)
+size_t mesh_vertex_normals_work_bytes(uint64_t n_vertices);
+void launch_mesh_vertex_normals(const MeshSample& ms, float* normals, void* work, uint64_t* counters, hipStream_t s);
 // visibility culling (cull.hip): one view marks the rows (16 bytes each) it sees in seen (uint32 per row, += 1), select keeps the rows with
 // seen >= min_views in order; depth NULL = frustum only; work = the buffer of cull_work_bytes(n); n <= 2^30, near / far / eps >= 0 and
 // finite, H W <= 2^28, as the entry points have checked

@@ -22,6 +22,10 @@
 //   ms_scan_kernel     one workgroup of 1024: scan_block_counts, the 64-bit total, the degenerate count, the counter block.
 //   ms_base_kernel     prefix[t] += block prefix.
 //   ms_emit_kernel     one lane per SAMPLE: binary search of its triangle in the exclusive prefix, then the sample's row.
+// Normals (mm3dgs_nn_query_index / mm3dgs_mesh_sample_emit_tri / mm3dgs_normal_consistency / mm3dgs_mesh_vertex_normals; host statement:
+//   geometry.nn_index_host / normal_row / vertex_normals_host): ng_query_kernel<true> also keeps the original row of the nearest record,
+//   ms_emit_kernel<true> the triangle of every sample (the <false> instantiations are the calls above, byte for byte); ms_cross / ms_face
+//   state the face cross product once; nc_dot_kernel / nc_finish_kernel and the four vn_* kernels are described where they stand.
 #include <math.h>
 #include "block_ops.h"
 #include "fused_api.h"
@@ -149,9 +153,11 @@ void launch_nn_grid_build(const NnGrid& g, uint64_t n_ref, const void* rows, voi
 // ---- query ------------------------------------------------------------------------------------------------------------------------
 size_t nn_query_work_bytes(uint64_t n_q) { return align_up(ng_nb((size_t)n_q) * NN_ROW * sizeof(double), 256); }
 
-struct NnQuery { double qx, qy, qz, best2; };
+struct NnQuery { double qx, qy, qz, best2; uint32_t besti; };      // besti: the original row of the best record (INDEX only)
 
-// the records [b, e) against the query: squared distance in double (each coordinate widened, then subtracted; three squares, a sum)
+// the records [b, e) against the query: squared distance in double (each coordinate widened, then subtracted; three squares, a sum);
+// INDEX: the minimum is lexicographic over (d2, original row), so neither the order inside a cell nor duplicates decide the row
+template <bool INDEX>
 __device__ __forceinline__ void ng_scan_records(const uint4* __restrict__ sorted, uint32_t b, uint32_t e, uint32_t n_ref, NnQuery& q) {
 #pragma clang fp contract(off)
   e = e < n_ref ? e : n_ref;
@@ -159,6 +165,7 @@ __device__ __forceinline__ void ng_scan_records(const uint4* __restrict__ sorted
     const uint4 v = sorted[p];      // one 16-byte load per candidate
     const double dx = q.qx - (double)__uint_as_float(v.x), dy = q.qy - (double)__uint_as_float(v.y), dz = q.qz - (double)__uint_as_float(v.z);
     const double d2 = dx * dx + dy * dy + dz * dz;
+    if (INDEX && (d2 < q.best2 || (d2 == q.best2 && v.w < q.besti))) q.besti = v.w;
     q.best2 = d2 < q.best2 ? d2 : q.best2;
   }
 }
@@ -167,6 +174,7 @@ __device__ __forceinline__ int ng_lo(int c, int r) { return c - r > 0 ? c - r : 
 __device__ __forceinline__ int ng_hi(int c, int r, int g) { return c + r < g - 1 ? c + r : g - 1; }
 
 // every cell within Chebyshev distance r of (cx, cy, cz), clipped to the grid: one range of records per row of cells
+template <bool INDEX>
 __device__ __forceinline__ void ng_cube(const NnGrid& g, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted, uint32_t n_ref, int cx,
                                         int cy, int cz, int r, NnQuery& q) {
   const int x0 = ng_lo(cx, r), x1 = ng_hi(cx, r, g.gx);
@@ -174,11 +182,12 @@ __device__ __forceinline__ void ng_cube(const NnGrid& g, const uint32_t* __restr
   for (int z = ng_lo(cz, r); z <= ng_hi(cz, r, g.gz); z++)
     for (int y = ng_lo(cy, r); y <= ng_hi(cy, r, g.gy); y++) {
       const size_t row = ((size_t)z * (size_t)g.gy + (size_t)y) * (size_t)g.gx;
-      ng_scan_records(sorted, cell_start[row + x0], cell_start[row + x1 + 1], n_ref, q);
+      ng_scan_records<INDEX>(sorted, cell_start[row + x0], cell_start[row + x1 + 1], n_ref, q);
     }
 }
 
 // the cells at Chebyshev distance exactly r >= 1, clipped to the grid: whole rows on the four faces across y and z, two cells per row elsewhere
+template <bool INDEX>
 __device__ __forceinline__ void ng_ring(const NnGrid& g, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted, uint32_t n_ref, int cx,
                                         int cy, int cz, int r, NnQuery& q) {
   const int x0 = ng_lo(cx, r), x1 = ng_hi(cx, r, g.gx);
@@ -187,19 +196,20 @@ __device__ __forceinline__ void ng_ring(const NnGrid& g, const uint32_t* __restr
     for (int y = ng_lo(cy, r); y <= ng_hi(cy, r, g.gy); y++) {
       const size_t row = ((size_t)z * (size_t)g.gy + (size_t)y) * (size_t)g.gx;
       if (fz || y - cy == r || cy - y == r) {
-        if (x0 <= x1) ng_scan_records(sorted, cell_start[row + x0], cell_start[row + x1 + 1], n_ref, q);
+        if (x0 <= x1) ng_scan_records<INDEX>(sorted, cell_start[row + x0], cell_start[row + x1 + 1], n_ref, q);
       } else {
         const int xa = cx - r, xb = cx + r;
-        if (xa >= 0 && xa < g.gx) ng_scan_records(sorted, cell_start[row + xa], cell_start[row + xa + 1], n_ref, q);
-        if (xb >= 0 && xb < g.gx) ng_scan_records(sorted, cell_start[row + xb], cell_start[row + xb + 1], n_ref, q);
+        if (xa >= 0 && xa < g.gx) ng_scan_records<INDEX>(sorted, cell_start[row + xa], cell_start[row + xa + 1], n_ref, q);
+        if (xb >= 0 && xb < g.gx) ng_scan_records<INDEX>(sorted, cell_start[row + xb], cell_start[row + xb + 1], n_ref, q);
       }
     }
   }
 }
 
+template <bool INDEX>
 __global__ void __launch_bounds__(GB)
 ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted,
-                uint32_t n_ref, double max_dist, float threshold, int rmax, float* __restrict__ dist_out, double* __restrict__ partial) {
+                uint32_t n_ref, double max_dist, float threshold, int rmax, float* __restrict__ dist_out, uint32_t* __restrict__ index_out, double* __restrict__ partial) {
 #pragma clang fp contract(off)
   __shared__ double wsum[GB / 64][2];
   __shared__ uint32_t wcnt[4][GB / 64];
@@ -213,12 +223,13 @@ ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const u
     const uint4 r = qrows[i];
     const float x = __uint_as_float(r.x), y = __uint_as_float(r.y), z = __uint_as_float(r.z);
     float out;
+    uint32_t nearest = NN_NO_CELL;      // (INDEX) 0xffffffff: none
     if (!ng_finite(x, y, z)) {
       skipped = true;
       out = __uint_as_float(0x7fc00000u);
     } else {
       NnQuery q;
-      q.qx = (double)x; q.qy = (double)y; q.qz = (double)z; q.best2 = (double)INFINITY;
+      q.qx = (double)x; q.qy = (double)y; q.qz = (double)z; q.best2 = (double)INFINITY; q.besti = NN_NO_CELL;
       double c[3];
       ng_cell(g, x, y, z, c);
       // the first ring that touches the grid, and the last one that does (as doubles: a far query's cell may not fit an int)
@@ -235,15 +246,16 @@ ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const u
         const int cx = (int)c[0], cy = (int)c[1], cz = (int)c[2];      // |c| <= grid size + rmax here
         const int last = rfar < (double)rmax ? (int)rfar : rmax;
         int rr = r0 <= 1.0 ? 1 : (int)r0;
-        if (rr == 1) ng_cube(g, cell_start, sorted, n_ref, cx, cy, cz, 1, q);      // rings 0 and 1: nine ranges
-        else ng_ring(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
+        if (rr == 1) ng_cube<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, 1, q);      // rings 0 and 1: nine ranges
+        else ng_ring<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
         while (rr < last && !(sqrt(q.best2) <= (double)rr * g.cell)) {      // at most rmax trips
           rr++;
-          ng_ring(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
+          ng_ring<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
         }
       }
       const double d = sqrt(q.best2);
       clamped = !(d <= max_dist);
+      if (INDEX && !clamped) nearest = q.besti;
       out = clamped ? (float)max_dist : (float)d;      // the one rounding
       within = out <= threshold;
       scored = true;
@@ -251,6 +263,7 @@ ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const u
       atomicMax(&smax, __float_as_uint(out));      // LDS, integer: a non-negative float orders as its bits
     }
     dist_out[i] = out;
+    if (INDEX) index_out[i] = nearest;
   }
   double sums[2] = {dd, dd * dd};
   block_sums_f64<2, false>(sums, wsum);
@@ -301,8 +314,16 @@ __global__ void __launch_bounds__(GB) ng_finish_kernel(const double* __restrict_
 void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
                      double threshold, int rmax, float* dist_out, double* row, void* work, hipStream_t s) {
   const unsigned nb = (unsigned)ng_nb((size_t)n_q);
-  hipLaunchKernelGGL(ng_query_kernel, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q, (const uint32_t*)cell_start, (const uint4*)sorted,
-                     (uint32_t)n_ref, max_dist, (float)threshold, rmax, dist_out, (double*)work);
+  hipLaunchKernelGGL(ng_query_kernel<false>, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q, (const uint32_t*)cell_start, (const uint4*)sorted,
+                     (uint32_t)n_ref, max_dist, (float)threshold, rmax, dist_out, (uint32_t*)nullptr, (double*)work);
+  hipLaunchKernelGGL(ng_finish_kernel, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
+}
+
+void launch_nn_query_index(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
+                           double threshold, int rmax, float* dist_out, uint32_t* index_out, double* row, void* work, hipStream_t s) {
+  const unsigned nb = (unsigned)ng_nb((size_t)n_q);
+  hipLaunchKernelGGL(ng_query_kernel<true>, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q, (const uint32_t*)cell_start, (const uint4*)sorted,
+                     (uint32_t)n_ref, max_dist, (float)threshold, rmax, dist_out, index_out, (double*)work);
   hipLaunchKernelGGL(ng_finish_kernel, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
 }
 
@@ -349,6 +370,27 @@ __device__ __forceinline__ bool ms_load(const MeshSample& ms, uint32_t t, MsTri&
   return true;
 }
 
+// the face cross product c = (b - a) x (c - a) of loaded corners: the one statement behind the sampler's area, the normal consistency and
+// the vertex normals
+__device__ __forceinline__ void ms_cross(const MsTri& T, double (&c)[3]) {
+#pragma clang fp contract(off)
+  c[0] = T.e1[1] * T.e2[2] - T.e1[2] * T.e2[1];
+  c[1] = T.e1[2] * T.e2[0] - T.e1[0] * T.e2[2];
+  c[2] = T.e1[0] * T.e2[1] - T.e1[1] * T.e2[0];
+}
+__device__ __forceinline__ double ms_dot(const double (&a)[3], const double (&b)[3]) {
+#pragma clang fp contract(off)
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+// c and c . c of triangle t of the mesh; false: t >= m (nothing is read), ms_load rejects it, or c . c is 0 or not finite
+__device__ __forceinline__ bool ms_face(const MeshSample& ms, uint32_t t, double (&c)[3], double& cc) {
+  MsTri T;
+  if (t >= ms.m || !ms_load(ms, t, T)) return false;
+  ms_cross(T, c);
+  cc = ms_dot(c, c);
+  return cc > 0.0 && cc < (double)INFINITY;
+}
+
 // n_t = min(floor(A density + u_t), MS_TRI_MAX); 0 and `degenerate` for a triangle ms_load rejects or whose area is 0 or not finite
 #define MS_TRI_MAX 8388608.0      // 2^23: a 256-block's total stays below 2^32
 __device__ __forceinline__ uint32_t ms_count(const MeshSample& ms, uint32_t t, bool& degenerate) {
@@ -356,8 +398,9 @@ __device__ __forceinline__ uint32_t ms_count(const MeshSample& ms, uint32_t t, b
   MsTri T;
   degenerate = true;
   if (!ms_load(ms, t, T)) return 0u;
-  const double cx = T.e1[1] * T.e2[2] - T.e1[2] * T.e2[1], cy = T.e1[2] * T.e2[0] - T.e1[0] * T.e2[2], cz = T.e1[0] * T.e2[1] - T.e1[1] * T.e2[0];
-  const double A = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+  double c[3];
+  ms_cross(T, c);
+  const double A = 0.5 * sqrt(ms_dot(c, c));
   if (!(A > 0.0) || !(A < (double)INFINITY)) return 0u;
   degenerate = false;
   const double u = (double)ms_hash(ms.seed, t, 0xffffffffu) * 0x1p-32;
@@ -416,9 +459,10 @@ void launch_mesh_sample_plan(const MeshSample& ms, void* work, uint64_t* counter
   hipLaunchKernelGGL(ms_base_kernel, dim3(nb), dim3(GB), 0, s, ms.m, w.bcounts, w.prefix);
 }
 
+template <bool TRI>
 __global__ void __launch_bounds__(GB)
 ms_emit_kernel(MeshSample ms, const uint32_t* __restrict__ prefix, const unsigned long long* __restrict__ hdr, unsigned long long cap, uint4* __restrict__ rows,
-               unsigned long long* __restrict__ counters) {
+               uint32_t* __restrict__ tri_out, unsigned long long* __restrict__ counters) {
 #pragma clang fp contract(off)
   const unsigned long long total = hdr[0], written = total < cap ? total : cap;
   const unsigned long long i = (unsigned long long)blockIdx.x * GB + threadIdx.x;
@@ -444,11 +488,216 @@ ms_emit_kernel(MeshSample ms, const uint32_t* __restrict__ prefix, const unsigne
   const float pz = (float)(T.a[2] + r1 * T.e1[2] + r2 * T.e2[2]);
   const uint32_t rgba = (w0 >= r1 && w0 >= r2) ? T.rgba[0] : (r1 >= r2 ? T.rgba[1] : T.rgba[2]);      // the largest weight, lowest index on a tie
   rows[i] = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), rgba);      // one 16-byte store
+  if (TRI) tri_out[i] = t;
 }
 
 void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint64_t cap, uint64_t* counters, hipStream_t s) {
   const MsWork w = ms_work((void*)work, (size_t)ms.m);
   size_t nb = ng_nb((size_t)cap);
   nb = nb < 1 ? 1 : nb;
-  hipLaunchKernelGGL(ms_emit_kernel, dim3((unsigned)nb), dim3(GB), 0, s, ms, w.prefix, w.hdr, (unsigned long long)cap, (uint4*)rows, (unsigned long long*)counters);
+  hipLaunchKernelGGL(ms_emit_kernel<false>, dim3((unsigned)nb), dim3(GB), 0, s, ms, w.prefix, w.hdr, (unsigned long long)cap, (uint4*)rows, (uint32_t*)nullptr,
+                     (unsigned long long*)counters);
+}
+
+void launch_mesh_sample_emit_tri(const MeshSample& ms, const void* work, void* rows, uint32_t* tri_out, uint64_t cap, uint64_t* counters, hipStream_t s) {
+  const MsWork w = ms_work((void*)work, (size_t)ms.m);
+  size_t nb = ng_nb((size_t)cap);
+  nb = nb < 1 ? 1 : nb;
+  hipLaunchKernelGGL(ms_emit_kernel<true>, dim3((unsigned)nb), dim3(GB), 0, s, ms, w.prefix, w.hdr, (unsigned long long)cap, (uint4*)rows, tri_out,
+                     (unsigned long long*)counters);
+}
+
+// ---- normal consistency ---------------------------------------------------------------------------------------------------------------
+// nc_dot_kernel, one lane per query: the faces of its own triangle and of its nearest row's triangle, their normalised dot product clamped
+// to [-1, 1] and rounded once at the store; per workgroup one partial row {sum |dot|, sum dot, min |dot|, n, -, no neighbour, bad triangle, -}
+// over the stored values, in ng_query_kernel's order; nc_finish_kernel adds the partial rows as ng_finish_kernel does.
+size_t normal_consistency_work_bytes(uint64_t n_q) { return nn_query_work_bytes(n_q); }
+
+__global__ void __launch_bounds__(GB)
+nc_dot_kernel(uint32_t n_q, const uint32_t* __restrict__ tri_q, const uint32_t* __restrict__ index, uint32_t n_r, const uint32_t* __restrict__ tri_r,
+              MeshSample mq, MeshSample mr, float* __restrict__ dot_out, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  __shared__ double wsum[GB / 64][2];
+  __shared__ uint32_t wcnt[3][GB / 64];
+  __shared__ uint32_t smin;
+  const uint32_t i = blockIdx.x * GB + threadIdx.x;
+  if (threadIdx.x == 0) smin = 0x7f800000u;      // +inf
+  __syncthreads();
+  bool counted = false, none = false, bad = false;
+  double dd = 0.0;
+  if (i < n_q) {
+    const uint32_t j = index[i];
+    float out = __uint_as_float(0x7fc00000u);
+    if (j == NN_NO_CELL) {
+      none = true;
+    } else {
+      double cq[3], cr[3], qq = 0.0, rr = 0.0;
+      bad = true;
+      if (j < n_r && ms_face(mq, tri_q[i], cq, qq) && ms_face(mr, tri_r[j], cr, rr)) {      // (ms_face reads nothing for an id >= m)
+        double d = ms_dot(cq, cr) / (sqrt(qq) * sqrt(rr));
+        d = d < -1.0 ? -1.0 : (d > 1.0 ? 1.0 : d);
+        out = (float)d;      // the one rounding
+        if (out == out) {
+          bad = false;
+          counted = true;
+          dd = (double)out;
+          atomicMin(&smin, __float_as_uint(fabsf(out)));      // LDS, integer: a non-negative float orders as its bits
+        }
+      }
+    }
+    dot_out[i] = out;
+  }
+  double sums[2] = {fabs(dd), dd};
+  block_sums_f64<2, false>(sums, wsum);
+  const bool is[3] = {counted, none, bad};
+  const uint32_t cnt = block_flag_counts(is, wcnt);
+  double* row = partial + (size_t)blockIdx.x * NN_ROW;
+  if (threadIdx.x == 0) row[3] = (double)cnt;
+  if (threadIdx.x == 1 || threadIdx.x == 2) row[4 + threadIdx.x] = (double)cnt;
+  if (threadIdx.x == 0) {
+    row[0] = sums[0];
+    row[1] = sums[1];
+    row[2] = (double)__uint_as_float(smin);
+    row[4] = 0.0;
+    row[7] = 0.0;
+  }
+}
+
+// one workgroup, ng_finish_kernel's order: lane t adds the partial rows t, t + 256, ..., then the lanes are added in index order (column 2: a minimum)
+__global__ void __launch_bounds__(GB) nc_finish_kernel(const double* __restrict__ partial, int nrows, double* __restrict__ row) {
+  __shared__ double sh[GB][NN_ROW];
+  double a[NN_ROW];
+  for (int k = 0; k < NN_ROW; k++) a[k] = k == 2 ? (double)INFINITY : 0.0;
+  for (int r = threadIdx.x; r < nrows; r += GB)
+    for (int k = 0; k < NN_ROW; k++) {
+      const double v = partial[(size_t)r * NN_ROW + k];
+      a[k] = k == 2 ? (v < a[k] ? v : a[k]) : a[k] + v;
+    }
+  for (int k = 0; k < NN_ROW; k++) sh[threadIdx.x][k] = a[k];
+  __syncthreads();
+  if (threadIdx.x < NN_ROW) {
+    const int k = threadIdx.x;
+    double t = k == 2 ? (double)INFINITY : 0.0;
+    for (int l = 0; l < GB; l++) t = k == 2 ? (sh[l][k] < t ? sh[l][k] : t) : t + sh[l][k];
+    sh[0][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double sabs = sh[0][0], sum = sh[0][1], mn = sh[0][2], n = sh[0][3], none = sh[0][5], bad = sh[0][6];
+    row[0] = n;
+    row[1] = n > 0.0 ? sabs / n : 0.0;
+    row[2] = n > 0.0 ? sum / n : 0.0;
+    row[3] = n > 0.0 ? mn : 0.0;
+    row[4] = 0.0;
+    row[5] = none;
+    row[6] = bad;
+    row[7] = 0.0;
+  }
+}
+
+void launch_normal_consistency(uint64_t n_q, const uint32_t* tri_q, const uint32_t* index, uint64_t n_r, const uint32_t* tri_r, const MeshSample& mq,
+                               const MeshSample& mr, float* dot_out, double* row, void* work, hipStream_t s) {
+  const unsigned nb = (unsigned)ng_nb((size_t)n_q);
+  hipLaunchKernelGGL(nc_dot_kernel, dim3(nb), dim3(GB), 0, s, (uint32_t)n_q, tri_q, index, (uint32_t)n_r, tri_r, mq, mr, dot_out, (double*)work);
+  hipLaunchKernelGGL(nc_finish_kernel, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
+}
+
+// ---- vertex normals -------------------------------------------------------------------------------------------------------------------
+// Area-weighted (the face cross product is twice the area times the unit normal), accumulated in fixed point: integer adds commute, so no
+// order of arrival changes a bit.  E_v = the largest frexp exponent among the faces at v, every face adds llrint(c 2^(40 - E_v)) to three
+// int64 sums: a term is below 2^40 in magnitude, so a valence up to 2^22 cannot overflow; beyond it the sums wrap (two's complement).
+//   vn_zero_kernel    E_v = VN_NO_EXP, S_v = 0, the counters to zero.
+//   vn_exp_kernel     one lane per triangle: integer atomicMax on the three E_v; the rejected triangles are counted.
+//   vn_add_kernel     one lane per triangle: three 64-bit integer atomicAdd per corner.
+//   vn_finish_kernel  one lane per vertex: n_v = S_v / sqrt(S_v . S_v) in double, one rounding; the vertices without a normal are counted.
+// work = [int32 E per vertex][int64 S x 3 per vertex]
+#define VN_NO_EXP (-0x7fffffff - 1)
+#define VN_FRAC_BITS 40
+struct VnWork { int* E; unsigned long long* S; };
+static VnWork vn_work(void* base, size_t nv, size_t* bytes = nullptr) {
+  Carve c = {(uintptr_t)base};
+  VnWork w;
+  w.E = c.take<int>(nv);
+  w.S = c.take<unsigned long long>(3 * nv);
+  if (bytes) *bytes = c.at;
+  return w;
+}
+size_t mesh_vertex_normals_work_bytes(uint64_t n_vertices) { size_t b; vn_work(nullptr, (size_t)n_vertices, &b); return b; }
+
+__global__ void __launch_bounds__(GB) vn_zero_kernel(uint32_t nv, int* __restrict__ E, unsigned long long* __restrict__ S, unsigned long long* __restrict__ counters) {
+  const uint32_t v = blockIdx.x * GB + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < 8) counters[threadIdx.x] = threadIdx.x == 0 ? (unsigned long long)nv : 0ull;
+  if (v >= nv) return;
+  E[v] = VN_NO_EXP;
+  S[3 * (size_t)v] = 0ull; S[3 * (size_t)v + 1] = 0ull; S[3 * (size_t)v + 2] = 0ull;
+}
+
+// the corners of triangle t (valid once ms_face has accepted it)
+__device__ __forceinline__ void vn_corners(const MeshSample& ms, uint32_t t, uint32_t (&v)[3]) {
+  for (int k = 0; k < 3; k++) v[k] = (uint32_t)ms.tris[3 * (size_t)t + k];
+}
+
+__global__ void __launch_bounds__(GB) vn_exp_kernel(MeshSample ms, int* __restrict__ E, unsigned long long* __restrict__ counters) {
+  const uint32_t t = blockIdx.x * GB + threadIdx.x;
+  bool rejected = false;
+  if (t < ms.m) {
+    double c[3], cc;
+    if (ms_face(ms, t, c, cc)) {
+      const double ax = fabs(c[0]), ay = fabs(c[1]), az = fabs(c[2]);
+      const double mx = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
+      int e;
+      frexp(mx, &e);
+      uint32_t v[3];
+      vn_corners(ms, t, v);
+      for (int k = 0; k < 3; k++) atomicMax(&E[v[k]], e);      // integer: a maximum does not depend on the order
+    } else {
+      rejected = true;
+    }
+  }
+  const unsigned long long mr = __ballot(rejected);
+  if ((threadIdx.x & 63) == 0 && mr) atomicAdd(counters + 2, (unsigned long long)__popcll(mr));      // integer adds: any order
+}
+
+__global__ void __launch_bounds__(GB) vn_add_kernel(MeshSample ms, const int* __restrict__ E, unsigned long long* __restrict__ S) {
+  const uint32_t t = blockIdx.x * GB + threadIdx.x;
+  if (t >= ms.m) return;
+  double c[3], cc;
+  if (!ms_face(ms, t, c, cc)) return;
+  uint32_t v[3];
+  vn_corners(ms, t, v);
+  for (int k = 0; k < 3; k++) {
+    const int sh = VN_FRAC_BITS - E[v[k]];      // E_v >= this face's exponent: |c 2^sh| < 2^40
+    for (int a = 0; a < 3; a++) atomicAdd(&S[3 * (size_t)v[k] + a], (unsigned long long)llrint(ldexp(c[a], sh)));      // wraps as int64 does
+  }
+}
+
+__global__ void __launch_bounds__(GB)
+vn_finish_kernel(uint32_t nv, const int* __restrict__ E, const unsigned long long* __restrict__ S, float* __restrict__ normals, unsigned long long* __restrict__ counters) {
+#pragma clang fp contract(off)
+  const uint32_t v = blockIdx.x * GB + threadIdx.x;
+  bool without = false;
+  if (v < nv) {
+    const double s[3] = {(double)(long long)S[3 * (size_t)v], (double)(long long)S[3 * (size_t)v + 1], (double)(long long)S[3 * (size_t)v + 2]};
+    const double ss = ms_dot(s, s);
+    float n[3] = {0.f, 0.f, 0.f};
+    if (E[v] != VN_NO_EXP && ss > 0.0) {
+      const double len = sqrt(ss);
+      for (int a = 0; a < 3; a++) n[a] = (float)(s[a] / len);      // the one rounding
+    } else {
+      without = true;
+    }
+    for (int a = 0; a < 3; a++) normals[3 * (size_t)v + a] = n[a];
+  }
+  const unsigned long long mw = __ballot(without);
+  if ((threadIdx.x & 63) == 0 && mw) atomicAdd(counters + 1, (unsigned long long)__popcll(mw));
+}
+
+void launch_mesh_vertex_normals(const MeshSample& ms, float* normals, void* work, uint64_t* counters, hipStream_t s) {
+  const VnWork w = vn_work(work, (size_t)ms.n_vertices);
+  const unsigned nbv = (unsigned)ng_nb((size_t)ms.n_vertices), nbt = (unsigned)ng_nb((size_t)ms.m);
+  unsigned long long* cn = (unsigned long long*)counters;
+  hipLaunchKernelGGL(vn_zero_kernel, dim3(nbv), dim3(GB), 0, s, ms.n_vertices, w.E, w.S, cn);
+  hipLaunchKernelGGL(vn_exp_kernel, dim3(nbt), dim3(GB), 0, s, ms, w.E, cn);
+  hipLaunchKernelGGL(vn_add_kernel, dim3(nbt), dim3(GB), 0, s, ms, (const int*)w.E, w.S);
+  hipLaunchKernelGGL(vn_finish_kernel, dim3(nbv), dim3(GB), 0, s, ms.n_vertices, (const int*)w.E, (const unsigned long long*)w.S, normals, cn);
 }

@@ -8,7 +8,15 @@ import numpy as np
 import torch
 
 from . import cull as cl, geometry as geo, mesh as ms, mesh_clean as mc, mesh_depth as md, pointcloud as pc
-from .config import _TUM, GEOMETRY_CULL, GEOMETRY_DEPTH, MESH_CLEAN, MESH_VOLUME
+from .config import _TUM, GEOMETRY_CULL, GEOMETRY_DEPTH, GEOMETRY_NORMALS, MESH_CLEAN, MESH_NORMALS, MESH_VOLUME
+
+
+def _flag(key, value):
+    if value is None:
+        return False
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{key} = {value!r} (true / false)")
+    return bool(value)
 
 
 def options(cfg, block, **overrides):
@@ -17,7 +25,7 @@ def options(cfg, block, **overrides):
     `clean_min_triangles` of an export; `estimate`, `reference` and `align` of the evaluation."""
     opt = dict(_TUM[block], **(cfg.get(block) or {}))
     if block == "geometry":
-        opt = dict(GEOMETRY_DEPTH, **dict(GEOMETRY_CULL, **opt))
+        opt = dict(GEOMETRY_NORMALS, **dict(GEOMETRY_DEPTH, **dict(GEOMETRY_CULL, **opt)))
         opt.update((k, v) for k, v in overrides.items() if v is not None)
         opt.update(estimate=str(opt["estimate"]), reference=str(opt["reference"]), align=str(opt["align"] or "none").lower(),
                    cull=str(opt["cull"] or "none").lower())
@@ -39,9 +47,10 @@ def options(cfg, block, **overrides):
         if isinstance(pairs, bool) or not isinstance(pairs, (int, np.integer)) or not 1 <= int(pairs) <= md.MAX_PAIRS:
             raise ValueError(f"geometry.depth_max_pairs = {pairs!r} (an integer, 1 .. 2^31)")
         opt["depth_max_pairs"] = int(pairs)
+        opt["normals"] = _flag("geometry.normals", opt["normals"])
         return opt
     if block == "mesh":
-        opt = dict(MESH_VOLUME, **dict(MESH_CLEAN, **opt))
+        opt = dict(MESH_NORMALS, **dict(MESH_VOLUME, **dict(MESH_CLEAN, **opt)))
     opt["every"] = opt["every"] or cfg["mapping"]["kf_every"]
     opt.update((k, v) for k, v in overrides.items() if v is not None)
     every, voxel, source = int(opt["every"]), float(opt["voxel"]), str(opt["source"])
@@ -61,6 +70,7 @@ def options(cfg, block, **overrides):
             opt["clean_min_triangles"] = mc.check_options("small", opt["clean_min_triangles"])[1]
         except (TypeError, ValueError):
             raise ValueError(f"mesh.clean_min_triangles = {opt['clean_min_triangles']!r} (an integer, at least 1)") from None
+        opt["normals"] = _flag("mesh.normals", opt["normals"])
         opt["volume"] = str(opt["volume"] or "dense").lower()
         if opt["volume"] not in ("dense", "sparse"):
             raise ValueError(f"mesh.volume = {opt['volume']!r} (dense / sparse)")
@@ -267,7 +277,8 @@ def export_mesh(slam, path=None, every=None, voxel=None, source=None):
     over the same views takes the box of their lifted valid points, which is grown by trunc + voxel, the origin snapped down to a
     multiple of voxel --, then marching tetrahedra over the samples seen at least `mesh.min_weight` times, and with `mesh.clean` small /
     largest the removal of the small disconnected pieces (mesh_clean.py; the returned dict gains `clean`).  Writes `path/mesh.ply`
-    (default `outputdir/mesh`; the format: `mesh.write_mesh_ply`).  One mm3dgs_tsdf_integrate call per view and one mm3dgs_tsdf_mesh_plan /
+    (default `outputdir/mesh`; the format: `mesh.write_mesh_ply`; with `mesh.normals: true` the file carries the area-weighted vertex
+    normals of the final mesh, `geometry.vertex_normals`, and the returned dict gains `normals`: its counters).  One mm3dgs_tsdf_integrate call per view and one mm3dgs_tsdf_mesh_plan /
     _emit pair on a GPU, the host statement on `device: cpu`.  Returns the path, the counters and the lattice; raises ValueError when the
     lattice exceeds `mesh.max_voxels`.  With `mesh.volume: sparse` the volume is held in 8 x 8 x 8-sample blocks only where a view's
     truncation band reaches (`sparse_mesh_geometry`): neither the bounds pass nor `mesh.max_voxels`; the returned dict gains `volume`,
@@ -276,9 +287,14 @@ def export_mesh(slam, path=None, every=None, voxel=None, source=None):
     path = os.path.join(slam.cfg["outputdir"], "mesh") if path is None else path
     rows, triangles, counters, dims, origin = mesh_geometry(slam, opt)
     os.makedirs(path, exist_ok=True)
-    out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles), "counters": counters, "lattice": tuple(dims),
+    normals = nc = None
+    if opt["normals"]:      # of the final mesh: behind mesh.clean
+        normals, nc = geo.vertex_normals(rows, triangles, slam.cfg["device"])
+    out = {"mesh": ms.write_mesh_ply(os.path.join(path, "mesh.ply"), rows, triangles, normals), "counters": counters, "lattice": tuple(dims),
            "origin": origin.tolist(), "voxel": opt["voxel"], "trunc": opt["trunc"]}
     cleaned = ""
+    if nc is not None:
+        out["normals"] = nc
     if opt["volume"] == "sparse":
         out.update(volume="sparse", blocks=counters["blocks"], pairs=counters["pairs"], volume_bytes=counters["volume_bytes"])
         cleaned = f"; sparse volume: {counters['blocks']} blocks from {counters['pairs']} (pixel, block) pairs, {counters['volume_bytes']} bytes"
@@ -288,6 +304,8 @@ def export_mesh(slam, path=None, every=None, voxel=None, source=None):
     slam.mesh_export = out      # what the last export wrote
     print(f"Mesh: {counters['vertices']} vertices, {counters['triangles']} triangles from {counters['views']} views "
           f"(lattice {dims[0]} x {dims[1]} x {dims[2]}, voxel {opt['voxel']} m){cleaned} in {out['mesh']}")
+    if nc is not None:
+        print(f"Mesh normals: {nc['vertices'] - nc['without_normal']} of {nc['vertices']} vertices ({nc['rejected_triangles']} triangles without an area)")
     return out
 
 
@@ -304,7 +322,8 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     depth L1 as the `depth_l1` block of metrics.json and the per-view table and frame indices to `path/depth_l1.npz`.
     With `mesh.clean` small / largest the estimate mesh and the `reference: sensor` mesh come cleaned from their builder (a reference
     file is left as it is) and metrics.json gains a `mesh_clean` block.  Writes `path/metrics.json`,
-    `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); arguments left None come from the `geometry` config block.  HIP
+    `accuracy.ply` and `completion.ply` (default `outputdir/geometry`); `geometry.normals: true` (the same two needs as `depth_l1`) adds
+    normal consistency: the `normals` block of metrics.json and `path/normals.npz`; arguments left None come from the `geometry` config block.  HIP
     kernels and one read-back of the [2,8] table on a GPU, the host statement on `device: cpu`.  Touches no pose and no other output.
     Returns the comparison with the paths."""
     opt = options(slam.cfg, "geometry", estimate=estimate, reference=reference)
@@ -328,7 +347,11 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     ref = build(dict(block, source="sensor"), gt_poses(slam), "reference") if reference == "sensor" else ms.read_surface_ply(reference)
     if opt["depth_l1"] and not (estimate == "mesh" and geo._is_mesh(ref)):
         raise ValueError("geometry.depth_l1 needs `estimate: mesh` and a mesh as the reference (`reference: sensor`, or a PLY file with faces)")
+    if opt["normals"] and not (estimate == "mesh" and geo._is_mesh(ref)):
+        raise ValueError("geometry.normals needs `estimate: mesh` and a mesh as the reference (`reference: sensor`, or a PLY file with faces)")
     culled = {} if opt["cull"] == "none" else {"cull": cull_views(slam, opt, block, ref)}
+    if opt["normals"]:
+        culled["normals"] = True
     result = geo.compare(est, ref, device=slam.cfg["device"], threshold=float(opt["threshold"]), max_dist=float(opt["max_dist"]),
                          cell=float(opt["cell"] or 0), density=float(opt["density"]), seed=int(opt["seed"]), max_samples=int(opt["max_samples"]), **culled)
     if "cull" in culled and culled["cull"]["mode"] == "occlusion" and opt["cull_depth"] == "reference":
@@ -353,6 +376,10 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
           f"completion ratio {result['completion_ratio'] * 100:.2f} % at {float(opt['threshold']) * 100:g} cm, F-score {result['fscore']:.4f}, Chamfer "
           f"{result['chamfer'] * 100:.3f} cm ({result['n_estimate']} / {result['n_reference']} points, clamped {int(t[0, 5])} / {int(t[1, 5])}) in "
           f"{result['files']['metrics']}")
+    if opt["normals"]:
+        nf = result["normals"]
+        print(f"Normal consistency: {nf['normal_consistency']:.4f} (normal accuracy {nf['normal_accuracy']:.4f}, normal completion {nf['normal_completion']:.4f}; "
+              f"mean |dot| over {int(result['normal_table'][0, 0])} / {int(result['normal_table'][1, 0])} points) in {result['files']['normals']}")
     if opt["depth_l1"]:
         d = result["depth_l1"]
         print(f"Depth L1 ({d['views']} views, {d['empty_views']} empty): {d['mean'] * 100:.3f} cm (pooled {d['pooled'] * 100:.3f} cm, rmse {d['rmse'] * 100:.3f} cm, max "

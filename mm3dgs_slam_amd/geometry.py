@@ -39,7 +39,38 @@ kernel file state the same one).
 **Culling** (``cull=``, off by default; ``cull.py`` states the rule).  A reference file covers the whole scene, a run sees part of it: with
 the run's views given, both point sets are reduced -- after sampling, before the search -- to the rows at least ``min_views`` views could
 have seen (inside a view's frustum; with depth images also not behind the surface the view measured), and every figure, array and file is
-about the kept rows."""
+about the kept rows.
+
+**Normals** (``normals=`` / ``vertex_normals``, both opt-in; the kernels and the numpy statement follow the rules below).
+
+*Face cross product.*  ``c_t = (b - a) x (c - a)`` from the float32 corners widened to double, no contraction, exactly as the sampler's
+area forms it (``ms_cross`` on the device, ``_face_cross`` here: one statement for the area, the consistency and the vertex normals).  A
+triangle is *rejected* when the sampler's load rejects it (an index outside ``[0, n_vertices)``, a corner that is not finite) or when
+``c . c`` is 0 or not finite.
+
+*Nearest row.*  ``nn_index_host`` / mm3dgs_nn_query_index do the search above and also give ``index[i]`` (uint32): the original
+reference row of the record with the smallest double squared distance, the smallest row on an exact tie (so duplicates in the reference
+are decided), ``0xffffffff`` when the query is skipped or clamped.  The ring stop rule leaves only strictly farther records unsearched, so
+the lexicographic minimum over ``(d2, row)`` of the searched records is the global one.  The distances and the row are those of the
+search without the index.  *Sample -> triangle*: the sampler also gives the triangle of every sample (``sample_mesh_host(full=True)``:
+``tri``; mm3dgs_mesh_sample_emit_tri: ``tri_out``).
+
+*One direction's normal row.*  For query i with its triangle ``tq``, its nearest row ``j = index[i]`` and that row's triangle ``tr``:
+``dot = (c_tq . c_tr) / (sqrt(c_tq . c_tq) sqrt(c_tr . c_tr))`` in double, clamped to [-1, 1], rounded once to float32 at the store.  The
+dot is NaN and the query is not counted when j is none (this test comes first), or when j or a triangle id is out of range or a triangle
+is rejected (nothing is read for such ids).  The row is eight float64 values over the stored float32 dots widened to double, summed in
+``kernel_order_sum``'s order on the device: n counted, mean |dot|, mean dot, min |dot|, 0, not counted: no neighbour, not counted:
+bad triangle, 0; the means and the min are 0 when n is 0 (``normal_row``, the twin of ``direction_row``).  ``normal_accuracy =
+row_er[1]``, ``normal_completion = row_re[1]``, ``normal_consistency = (normal_accuracy + normal_completion) / 2``, and the same three
+from field 2 as ``*_signed``.  |dot| is the headline because a dataset's mesh and a TSDF mesh need not share an orientation (what
+Occupancy Networks' evaluator does for meshes that are not watertight).  The normal under a sample is its face's, recomputed from the
+faces: a file's stored normals are never used.
+
+*Vertex normals* are area-weighted, and no order of arrival changes a bit: every triangle t that is not rejected has ``E_t``, the binary
+exponent of ``max(|c_x|, |c_y|, |c_z|)`` as ``frexp`` returns it; ``E_v = max E_t`` over the triangles with corner v; every such triangle
+adds ``llrint(ldexp(c_k, 40 - E_v))``, k = x, y, z, to three int64 sums ``S_v`` (a term is below 2^40, so the sums are exact up to a valence
+of 2^22 and wrap in two's complement beyond); ``n_v = S_v / sqrt(S_v . S_v)`` in double from the sums converted to double, rounded once
+to float32; ``(0, 0, 0)``, and counted, when v has no such triangle or ``S_v = 0``."""
 from __future__ import annotations
 
 import json
@@ -55,6 +86,10 @@ SAMPLE_COUNTERS = ("samples", "degenerate", "written", "dropped", "triangles", "
 MAX_CELLS = 1 << 26
 MAX_RINGS = 1 << 20
 TRI_MAX = 1 << 23      # samples of one triangle
+NO_INDEX = np.uint32(0xffffffff)      # no nearest row: the query is skipped or clamped
+NORMAL_ROW_NAMES = ("n", "mean_abs_dot", "mean_dot", "min_abs_dot", "reserved4", "no_neighbour", "bad_triangle", "reserved7")
+NORMAL_COUNTERS = ("vertices", "without_normal", "rejected_triangles")
+FRAC_BITS = 40         # fixed-point bits of the vertex-normal sums below a vertex's largest face exponent
 
 
 # ---- the mixer ------------------------------------------------------------------------------------------------------------------
@@ -95,6 +130,17 @@ def nn_distances_host(query, reference, cell, max_dist, grid=None):
     """(dist float32 [n_q], info): the truncated nearest-neighbour distance of every query row to the reference rows by the ring search of
     the module docstring, in float64; NaN for a skipped query.  info: clamped (bool [n_q]), ref_skipped, cell (the one used), origin_cell,
     dims.  `grid` (cell, origin_cell, dims) overrides the grid taken from the reference's box."""
+    return _nn_search(query, reference, cell, max_dist, grid, False)[::2]
+
+
+def nn_index_host(query, reference, cell, max_dist, grid=None):
+    """(dist, index uint32 [n_q], info): ``nn_distances_host`` (the same distances and info) with the nearest row of the module docstring:
+    the original reference row of the smallest float64 squared distance, the smallest row on a tie, NO_INDEX for a skipped or clamped
+    query."""
+    return _nn_search(query, reference, cell, max_dist, grid, True)
+
+
+def _nn_search(query, reference, cell, max_dist, grid, want_index):
     qxyz, qfin = _finite_rows(query)
     rxyz, rfin = _finite_rows(reference)
     max_dist = float(max_dist)
@@ -102,13 +148,15 @@ def nn_distances_host(query, reference, cell, max_dist, grid=None):
         raise ValueError(f"max_dist = {max_dist} (must be finite and positive)")
     nq = len(qxyz)
     dist = np.full(nq, np.nan, dtype=np.float32)
+    index = np.full(nq, NO_INDEX, dtype=np.uint32)
     clamped = np.zeros(nq, dtype=bool)
     R = rxyz[rfin].astype(np.float64)
+    orig = np.flatnonzero(rfin)
     info = {"clamped": clamped, "ref_skipped": int((~rfin).sum()), "cell": float(cell), "origin_cell": np.zeros(3, dtype=np.int64), "dims": [1, 1, 1]}
     if len(R) == 0:
         dist[qfin] = np.float32(max_dist)
         clamped[qfin] = True
-        return dist, info
+        return dist, index, info
     cell, o, dims = grid if grid is not None else grid_for(R.min(0), R.max(0), cell)
     info.update(cell=float(cell), origin_cell=np.asarray(o, dtype=np.int64), dims=list(dims))
     g = np.asarray(dims, dtype=np.int64)
@@ -117,10 +165,10 @@ def nn_distances_host(query, reference, cell, max_dist, grid=None):
     rmax = max(int(np.ceil(max_dist / cell)), 1)
     rc = np.floor(R / cell).astype(np.int64) - np.asarray(o, dtype=np.int64)
     inside = ((rc >= 0) & (rc < g)).all(1)      # (with an explicit grid a reference point may lie outside it: left out)
-    R, rc = R[inside], rc[inside]
+    R, rc, orig = R[inside], rc[inside], orig[inside]
     lin = (rc[:, 2] * g[1] + rc[:, 1]) * g[0] + rc[:, 0]
     order = np.argsort(lin, kind="stable")
-    R, lin = R[order], lin[order]
+    R, lin, orig = R[order], lin[order], orig[order]
     qi = np.flatnonzero(qfin)
     Q = qxyz[qi].astype(np.float64)
     with np.errstate(over="ignore"):
@@ -129,6 +177,7 @@ def nn_distances_host(query, reference, cell, max_dist, grid=None):
     rfar = np.maximum(c, (g - 1.0) - c).max(1)                       # the last one that does
     ci = np.clip(c, -float(1 << 41), float(1 << 41)).astype(np.int64)
     best2 = np.full(len(Q), np.inf)
+    besti = np.full(len(Q), int(NO_INDEX), dtype=np.int64)
     active = np.flatnonzero(r0 <= rmax)
     for r in range(0, rmax + 1):
         if not len(active):
@@ -158,14 +207,20 @@ def nn_distances_host(query, reference, cell, max_dist, grid=None):
                         cand = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n) + np.repeat(b, n)
                         d = Q[ids[owner]] - R[cand]
                         d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+                        before = best2[ids]
                         np.minimum.at(best2, ids[owner], d2)
+                        if want_index:      # the lexicographic minimum over (d2, original row)
+                            besti[ids[best2[ids] < before]] = int(NO_INDEX)
+                            hit = d2 == best2[ids[owner]]
+                            np.minimum.at(besti, ids[owner][hit], orig[cand[hit]])
         stop = (np.sqrt(best2[active]) <= r * cell) | (rfar[active] <= r)
         active = active[~stop]
     d = np.sqrt(best2)
     cl = ~(d <= max_dist)
     dist[qi] = np.where(cl, np.float32(max_dist), d.astype(np.float32))
     clamped[qi] = cl
-    return dist, info
+    index[qi] = np.where(cl, int(NO_INDEX), besti).astype(np.uint32)
+    return dist, index, info
 
 
 def nn_brute_host(query, reference, max_dist):
@@ -183,6 +238,25 @@ def nn_brute_host(query, reference, max_dist):
     out[~qfin] = np.nan
     d[~qfin] = np.nan
     return out, cl, d
+
+
+def nn_index_brute_host(query, reference, max_dist):
+    """``nn_index_host`` by float64 brute force (tests): (dist float32 [n_q], index uint32 [n_q])."""
+    qxyz, qfin = _finite_rows(query)
+    rxyz, rfin = _finite_rows(reference)
+    orig = np.flatnonzero(rfin)
+    R = rxyz[rfin].astype(np.float64)
+    dist = np.full(len(qxyz), np.nan, dtype=np.float32)
+    index = np.full(len(qxyz), NO_INDEX, dtype=np.uint32)
+    for k in np.flatnonzero(qfin):
+        d, j = np.inf, int(NO_INDEX)
+        if len(R):
+            e = qxyz[k].astype(np.float64) - R
+            d2 = e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1] + e[:, 2] * e[:, 2]
+            d, j = np.sqrt(d2.min()), int(orig[d2 == d2.min()].min())
+        cl = not d <= float(max_dist)
+        dist[k], index[k] = (np.float32(max_dist), NO_INDEX) if cl else (np.float32(d), j)
+    return dist, index
 
 
 def kernel_order_sum(values):
@@ -235,7 +309,8 @@ def derived_figures(table):
 
 
 # ---- surface sampling ---------------------------------------------------------------------------------------------------------------
-def _triangle_counts(vrows, triangles, density, seed):
+def _face_cross(vrows, triangles):
+    """The face cross product of the module docstring: (c float64 [m,3], c . c, loaded: the triangles ms_load accepts, (a, e1, e2, ti))."""
     xyz = rows_xyz(vrows).astype(np.float64)
     tri = as_np(triangles, np.int32).reshape(-1, 3).astype(np.int64)
     m, nv = len(tri), len(xyz)
@@ -248,7 +323,23 @@ def _triangle_counts(vrows, triangles, density, seed):
         cx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
         cy = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
         cz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
-        A = 0.5 * np.sqrt(cx * cx + cy * cy + cz * cz)
+        cc = cx * cx + cy * cy + cz * cz
+    return np.stack([cx, cy, cz], 1), cc, ok, (a, e1, e2, ti)
+
+
+def face_cross_host(vrows, triangles):
+    """(c float64 [m,3], c . c [m], ok bool [m]) per triangle; ok False: rejected (the values of such a row mean nothing)."""
+    c, cc, ok, _ = _face_cross(vrows, triangles)
+    with np.errstate(invalid="ignore"):
+        ok = ok & (cc > 0) & (cc < np.inf)
+    return c, cc, ok
+
+
+def _triangle_counts(vrows, triangles, density, seed):
+    _, cc, ok, (a, e1, e2, ti) = _face_cross(vrows, triangles)
+    m = len(ti)
+    with np.errstate(invalid="ignore", over="ignore"):
+        A = 0.5 * np.sqrt(cc)
         ok &= (A > 0) & (A < np.inf)
         u = sample_hash(seed, np.arange(m, dtype=np.uint32), np.uint32(0xffffffff)).astype(np.float64) * 2.0 ** -32
         nt = np.where(ok, np.minimum(np.floor(np.where(ok, A, 0.0) * float(density) + u), float(TRI_MAX)), 0.0).astype(np.int64)
@@ -290,9 +381,10 @@ def sample_mesh_host(vrows, triangles, density, seed=0, cap=None, full=False):
     return rows, counters, {"xyz": xyz, "tri": tid, "scale": scale, "counts": nt, "area": area}
 
 
-def sample_mesh_device(vrows, triangles, density, seed=0, max_samples=1 << 24, device="cuda:0"):
+def sample_mesh_device(vrows, triangles, density, seed=0, max_samples=1 << 24, device="cuda:0", want_tri=False):
     """The device sampler: (rows tensor [n,4] int32 on the device, counters dict) -- one mm3dgs_mesh_sample_plan, one read-back of the
-    counter block, the exact allocation, one mm3dgs_mesh_sample_emit.  Raises when the samples exceed `max_samples`."""
+    counter block, the exact allocation, one mm3dgs_mesh_sample_emit.  Raises when the samples exceed `max_samples`.  With `want_tri`
+    (rows, counters, tri int32 [n]: the triangle of every sample) through mm3dgs_mesh_sample_emit_tri."""
     from . import _lib
     from .rasterizer import _stream
     lib, P = _lib.load(), _lib.ptr
@@ -300,7 +392,8 @@ def sample_mesh_device(vrows, triangles, density, seed=0, max_samples=1 << 24, d
     tr = torch.as_tensor(triangles, device=device).to(torch.int32).reshape(-1, 3).contiguous()
     m, nv = int(tr.shape[0]), int(vr.shape[0])
     if m == 0 or nv == 0:
-        return torch.empty(0, 4, dtype=torch.int32, device=device), dict(zip(SAMPLE_COUNTERS[:5], (0, m, 0, 0, m)))
+        out = torch.empty(0, 4, dtype=torch.int32, device=device), dict(zip(SAMPLE_COUNTERS[:5], (0, m, 0, 0, m)))
+        return out + (torch.empty(0, dtype=torch.int32, device=device),) if want_tri else out
     nbytes = int(lib.mm3dgs_mesh_sample_work_bytes(m))
     if nbytes == 0:
         raise ValueError(f"mesh of {m} triangles: at most 2^30")
@@ -313,8 +406,152 @@ def sample_mesh_device(vrows, triangles, density, seed=0, max_samples=1 << 24, d
         raise ValueError(f"{total} surface samples at density {density} per m^2: more than max_samples = {int(max_samples)}; lower geometry.density "
                          f"or raise geometry.max_samples")
     rows = torch.empty(max(total, 1), 4, dtype=torch.int32, device=device)
+    out = {"samples": total, "degenerate": int(c[1]), "written": total, "dropped": 0, "triangles": m}
+    if want_tri:
+        tri = torch.empty(max(total, 1), dtype=torch.int32, device=device)
+        _lib.check(lib.mm3dgs_mesh_sample_emit_tri(nv, P(vr), m, P(tr), float(density), int(seed) & 0xffffffff, P(work), P(rows), P(tri), total, P(counters), _stream()))
+        return rows[:total], out, tri[:total]
     _lib.check(lib.mm3dgs_mesh_sample_emit(nv, P(vr), m, P(tr), float(density), int(seed) & 0xffffffff, P(work), P(rows), total, P(counters), _stream()))
-    return rows[:total], {"samples": total, "degenerate": int(c[1]), "written": total, "dropped": 0, "triangles": m}
+    return rows[:total], out
+
+
+# ---- normals ------------------------------------------------------------------------------------------------------------------------
+def normal_dots_host(tri_q, index, tri_r, mesh_q, mesh_r):
+    """(dot float32 [n_q], no_neighbour bool [n_q]) of one direction by the rules of the module docstring: tri_q [n_q] the triangle of every
+    query sample (of mesh_q = (vertex rows, triangles)), index [n_q] its nearest reference row (NO_INDEX: none), tri_r [n_r] the triangle
+    of every reference row (of mesh_r).  NaN: not counted."""
+    tq, j = as_np(tri_q, np.int64).reshape(-1) & 0xffffffff, as_np(index, np.int64).reshape(-1) & 0xffffffff
+    tr_all = as_np(tri_r, np.int64).reshape(-1) & 0xffffffff
+    cq, qq, okq = face_cross_host(*mesh_q)
+    cr, rr, okr = face_cross_host(*mesh_r)
+    none = j == int(NO_INDEX)
+    good = ~none & (j < len(tr_all))
+    tr = np.where(good, tr_all[np.where(good, j, 0)] if len(tr_all) else 0, 0)
+    good &= (tq < len(okq)) & (tr < len(okr))
+    tq, tr = np.where(good, tq, 0), np.where(good, tr, 0)
+    if len(okq) and len(okr):
+        good &= okq[tq] & okr[tr]
+    else:
+        good &= False
+    dot = np.full(len(tq), np.nan, dtype=np.float32)
+    if good.any():
+        a, b = cq[tq[good]], cr[tr[good]]
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            d = (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]) / (np.sqrt(qq[tq[good]]) * np.sqrt(rr[tr[good]]))
+            d = np.where(d < -1.0, -1.0, np.where(d > 1.0, 1.0, d))
+        dot[good] = d.astype(np.float32)
+    return dot, none
+
+
+def normal_row(dot, no_neighbour, sum_order="numpy"):
+    """The eight figures of one direction's normals (NORMAL_ROW_NAMES) from the stored float32 dots (NaN = not counted) and the mask of the
+    queries without a neighbour; the host twin of ``direction_row`` (`sum_order` as there)."""
+    dot = np.asarray(dot, dtype=np.float32)
+    counted = ~np.isnan(dot)
+    d = dot[counted].astype(np.float64)
+    n = len(d)
+    row = np.zeros(8, dtype=np.float64)
+    row[0] = n
+    if n:
+        row[1], row[2], row[3] = np.abs(d).sum() / n, d.sum() / n, np.abs(d).min()
+        if sum_order == "kernel":
+            z = np.where(counted, dot, np.float32(0)).astype(np.float64)
+            row[1], row[2] = kernel_order_sum(np.abs(z)) / n, kernel_order_sum(z) / n
+    none = np.asarray(no_neighbour, dtype=bool) & ~counted
+    row[5] = float(none.sum())
+    row[6] = float((~counted & ~none).sum())
+    return row
+
+
+def normal_figures(table):
+    """The derived values of a [2,8] normal table (row 0: estimate -> reference, row 1: reference -> estimate)."""
+    t = np.asarray(table, dtype=np.float64).reshape(2, 8)
+    return {"normal_accuracy": float(t[0, 1]), "normal_completion": float(t[1, 1]), "normal_consistency": 0.5 * (float(t[0, 1]) + float(t[1, 1])),
+            "normal_accuracy_signed": float(t[0, 2]), "normal_completion_signed": float(t[1, 2]),
+            "normal_consistency_signed": 0.5 * (float(t[0, 2]) + float(t[1, 2]))}
+
+
+def vertex_normals_host(vrows, triangles):
+    """(normals float32 [n_vertices,3], counters dict) by the fixed-point rule of the module docstring."""
+    nv = len(as_np(vrows, np.int32).reshape(-1, 4))
+    c, _, ok = face_cross_host(vrows, triangles)
+    tri = as_np(triangles, np.int32).reshape(-1, 3).astype(np.int64)[ok]
+    c = c[ok]
+    none = np.iinfo(np.int64).min
+    E = np.full(nv, none, dtype=np.int64)
+    S = np.zeros((nv, 3), dtype=np.int64)
+    if len(tri):
+        _, Et = np.frexp(np.abs(c).max(1))
+        for k in range(3):
+            np.maximum.at(E, tri[:, k], Et.astype(np.int64))
+        for k in range(3):
+            term = np.rint(np.ldexp(c, (FRAC_BITS - E[tri[:, k]])[:, None].astype(np.int64))).astype(np.int64)
+            for a in range(3):
+                np.add.at(S[:, a], tri[:, k], term[:, a])      # (int64 adds wrap as the device's do)
+    s = S.astype(np.float64)
+    ss = s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1] + s[:, 2] * s[:, 2]
+    has = (E != none) & (ss > 0)
+    normals = np.zeros((nv, 3), dtype=np.float32)
+    normals[has] = (s[has] / np.sqrt(ss[has])[:, None]).astype(np.float32)
+    return normals, {"vertices": nv, "without_normal": int((~has).sum()), "rejected_triangles": int((~ok).sum())}
+
+
+def vertex_normals_device(vrows, triangles, device="cuda:0"):
+    """The same on the device: (normals tensor float32 [n_vertices,3], counters tensor int64 [8]) from one mm3dgs_mesh_vertex_normals call,
+    no read-back."""
+    from . import _lib
+    from .rasterizer import _stream
+    lib, P = _lib.load(), _lib.ptr
+    vr = torch.as_tensor(vrows, device=device).to(torch.int32).reshape(-1, 4).contiguous()
+    tr = torch.as_tensor(triangles, device=device).to(torch.int32).reshape(-1, 3).contiguous()
+    m, nv = int(tr.shape[0]), int(vr.shape[0])
+    normals = torch.zeros(nv, 3, dtype=torch.float32, device=device)
+    counters = torch.zeros(8, dtype=torch.int64, device=device)
+    if m == 0 or nv == 0:
+        counters[0], counters[1] = nv, nv
+        return normals, counters
+    nbytes = int(lib.mm3dgs_mesh_vertex_normals_work_bytes(nv))
+    if nbytes == 0 or m > 1 << 30:
+        raise ValueError(f"mesh of {nv} vertices and {m} triangles: at most 2^31 - 1 and 2^30")
+    work = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+    _lib.check(lib.mm3dgs_mesh_vertex_normals(nv, P(vr), m, P(tr), P(normals), P(work), P(counters), _stream()))
+    return normals, counters
+
+
+def vertex_normals(vrows, triangles, device="cpu"):
+    """(normals float32 [n_vertices,3], counters dict): ``vertex_normals_device`` on a CUDA device (numpy after one read-back),
+    ``vertex_normals_host`` otherwise."""
+    if not str(device).startswith("cuda"):
+        return vertex_normals_host(as_np(vrows, np.int32), as_np(triangles, np.int32))
+    normals, counters = vertex_normals_device(vrows, triangles, device)
+    c = counters.cpu().numpy()
+    return normals.cpu().numpy(), dict(zip(NORMAL_COUNTERS, (int(v) for v in c[:3])))
+
+
+def normal_consistency_device(tri_q, index, tri_r, mesh_q, mesh_r, dot=None, row=None, device="cuda:0"):
+    """(dot [n_q] float32, row [8] float64) on the device: one mm3dgs_normal_consistency call, no read-back; the arguments of
+    ``normal_dots_host`` as int32 / uint32-valued tensors and (vertex rows, triangles) tensors."""
+    from . import _lib
+    from .rasterizer import _stream
+    lib, P = _lib.load(), _lib.ptr
+    as32 = lambda t, w: torch.as_tensor(t, device=device).to(torch.int32).reshape(-1, w).contiguous()
+    tq, ix, tr = as32(tri_q, 1), as32(index, 1), as32(tri_r, 1)
+    vq, fq, vr, fr = as32(mesh_q[0], 4), as32(mesh_q[1], 3), as32(mesh_r[0], 4), as32(mesh_r[1], 3)
+    nq = int(tq.shape[0])
+    dot = torch.empty(nq, dtype=torch.float32, device=device) if dot is None else dot
+    row = torch.zeros(8, dtype=torch.float64, device=device) if row is None else row
+    if nq == 0:
+        row.zero_()
+        return dot, row
+    if min(int(tr.shape[0]), int(vq.shape[0]), int(fq.shape[0]), int(vr.shape[0]), int(fr.shape[0])) == 0:      # nothing to look up: no kernel has anything to read
+        dot.fill_(float("nan"))
+        none = (ix.reshape(-1) == -1).sum().double()
+        row.copy_(torch.stack([none * 0, none * 0, none * 0, none * 0, none * 0, none, nq - none, none * 0]))
+        return dot, row
+    work = torch.empty(int(lib.mm3dgs_normal_consistency_work_bytes(nq)) // 8, dtype=torch.int64, device=device)
+    _lib.check(lib.mm3dgs_normal_consistency(nq, P(tq), P(ix), int(tr.shape[0]), P(tr), int(vq.shape[0]), P(vq), int(fq.shape[0]), P(fq), int(vr.shape[0]), P(vr),
+                                             int(fr.shape[0]), P(fr), P(dot), P(row), P(work), _stream()))
+    return dot, row
 
 
 # ---- the device path ------------------------------------------------------------------------------------------------------------------
@@ -363,8 +600,9 @@ class GeometryScorer:
                                                  P(self.counters), P(work), _stream()))
         self.grid = True
 
-    def query(self, rows, dist=None, row=None):
-        """(dist [n_q] float32, row [8] float64) on the device for the query rows [n_q,4] int32."""
+    def query(self, rows, dist=None, row=None, index=None):
+        """(dist [n_q] float32, row [8] float64) on the device for the query rows [n_q,4] int32.  With `index` (int32 [n_q], holding the
+        uint32 values) mm3dgs_nn_query_index also writes the nearest reference row of every query into it (-1 = 0xffffffff: none)."""
         from . import _lib
         from .rasterizer import _stream
         q = torch.as_tensor(rows, device=self.device).to(torch.int32).reshape(-1, 4).contiguous()
@@ -374,6 +612,8 @@ class GeometryScorer:
         if nq == 0:
             row.zero_()
             return dist, row
+        if index is not None and self.grid is None:
+            index.fill_(-1)
         if self.grid is None:      # no finite reference point: every finite query is clamped (no kernel has anything to search)
             fin = torch.isfinite(q[:, :3].view(torch.float32)).all(1)
             dist.copy_(torch.where(fin, torch.full_like(dist, self.max_dist), torch.full_like(dist, float("nan"))))
@@ -385,6 +625,10 @@ class GeometryScorer:
         P = _lib.ptr
         gx, gy, gz = self.dims
         work = torch.empty(int(self.lib.mm3dgs_nn_query_work_bytes(nq)) // 8, dtype=torch.int64, device=self.device)
+        if index is not None:
+            _lib.check(self.lib.mm3dgs_nn_query_index(nq, P(q), self.n_ref, self.cell, self._origin, gx, gy, gz, P(self.cell_start), P(self.sorted), self.max_dist,
+                                                      self.threshold, P(dist), P(index), P(row), P(work), _stream()))
+            return dist, row
         _lib.check(self.lib.mm3dgs_nn_query(nq, P(q), self.n_ref, self.cell, self._origin, gx, gy, gz, P(self.cell_start), P(self.sorted), self.max_dist,
                                             self.threshold, P(dist), P(row), P(work), _stream()))
         return dist, row
@@ -395,17 +639,28 @@ def _is_mesh(side):
     return isinstance(side, (tuple, list)) and len(side) == 2
 
 
-def compare_host(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24, cull=None, sum_order="numpy"):
+def _need_meshes(estimate, reference):
+    if not (_is_mesh(estimate) and _is_mesh(reference)):
+        raise ValueError("normals need a mesh on both sides (a point cloud has no faces)")
+
+
+def compare_host(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24, cull=None, sum_order="numpy",
+                 normals=False):
     """The comparison of the module docstring on the host (`sum_order`: ``direction_row``).  Each side is rows [n,4] int32 or (vertex rows, triangles).  Returns a dict:
     the derived figures, table [2,8], cells (the cell each grid used), counters, n_estimate, n_reference, and the arrays estimate_rows,
     reference_rows, dist_estimate, dist_reference.  `cull` (``cull.spec``: the run's views plus the options; None: off) removes from both
     point sets, after sampling and before the search, what no view could have seen: everything returned is then about the kept points,
-    and the result gains `cull` (``cull.summary``) and estimate_index / reference_index (the original row of every kept row)."""
+    and the result gains `cull` (``cull.summary``) and estimate_index / reference_index (the original row of every kept row).  `normals`
+    (both sides must be meshes, ValueError otherwise) adds the normal scores of the module docstring: `normals` (``normal_figures``),
+    normal_table [2,8], dot_estimate, dot_reference and nearest_estimate / nearest_reference (the nearest row of the other set, uint32)."""
     cell = float(cell) if cell and float(cell) > 0 else float(threshold)
-    sets, counters = [], {}
+    if normals:
+        _need_meshes(estimate, reference)
+    sets, counters, tris = [], {}, []
     for name, side in (("estimate", estimate), ("reference", reference)):
         if _is_mesh(side):
-            rows, c = sample_mesh_host(side[0], side[1], density, seed)
+            rows, c, *full = sample_mesh_host(side[0], side[1], density, seed, full=bool(normals))
+            tris += [f["tri"] for f in full]
             if c["samples"] > int(max_samples):
                 raise ValueError(f"{c['samples']} surface samples at density {density} per m^2: more than max_samples = {int(max_samples)}")
             counters[name + "_sampler"] = c
@@ -417,21 +672,35 @@ def compare_host(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, dens
         from . import cull as cl
         (sets[0], ie, ce), (sets[1], ir, cr) = cl.apply_host(sets[0], cull), cl.apply_host(sets[1], cull)
         culled = (cl.summary(cull, ce, cr), ie, ir)
-    d_er, i_er = nn_distances_host(sets[0], sets[1], cell, max_dist)
-    d_re, i_re = nn_distances_host(sets[1], sets[0], cell, max_dist)
+    d_er, n_er, i_er = _nn_search(sets[0], sets[1], cell, max_dist, None, bool(normals))
+    d_re, n_re, i_re = _nn_search(sets[1], sets[0], cell, max_dist, None, bool(normals))
     table = np.stack([direction_row(d_er, i_er["clamped"], threshold, sum_order), direction_row(d_re, i_re["clamped"], threshold, sum_order)])
     counters.update(reference_skipped=i_er["ref_skipped"], estimate_skipped=i_re["ref_skipped"])
-    return _result(table, (i_er["cell"], i_re["cell"]), counters, sets, (d_er, d_re), threshold, max_dist, culled)
+    out = _result(table, (i_er["cell"], i_re["cell"]), counters, sets, (d_er, d_re), threshold, max_dist, culled)
+    if normals:
+        te, tr = (t if culled is None else t[as_np(i, np.int64)] for t, i in zip(tris, (culled or (None, None, None))[1:]))
+        dot_e, none_e = normal_dots_host(te, n_er, tr, estimate, reference)
+        dot_r, none_r = normal_dots_host(tr, n_re, te, reference, estimate)
+        _normal_result(out, np.stack([normal_row(dot_e, none_e, sum_order), normal_row(dot_r, none_r, sum_order)]), (dot_e, dot_r), (n_er, n_re))
+    return out
 
 
-def compare_device(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24, device="cuda:0", cull=None):
+def compare_device(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, density=10000.0, seed=0, max_samples=1 << 24, device="cuda:0", cull=None,
+                   normals=False):
     """The same comparison on the device: meshes sampled by the kernels, one GeometryScorer per direction, the [2,8] table read back once;
     the rows and distances stay device tensors.  `cull` as in ``compare_host``: one ``cull.Culler`` per side (one mm3dgs_cull_mark_view
-    per view, one mm3dgs_cull_select and one read-back of its counters)."""
+    per view, one mm3dgs_cull_select and one read-back of its counters).  `normals` as in ``compare_host``: the samplers also give the
+    triangle of every sample, the two queries the nearest row, one mm3dgs_normal_consistency per direction fills a second [2,8] table, and
+    both tables are read back together; the dots and nearest rows stay device tensors (the rows as int32 holding the uint32 values)."""
     cell = float(cell) if cell and float(cell) > 0 else float(threshold)
-    sets, counters = [], {}
+    if normals:
+        _need_meshes(estimate, reference)
+    sets, counters, tris = [], {}, []
     for name, side in (("estimate", estimate), ("reference", reference)):
-        if _is_mesh(side):
+        if _is_mesh(side) and normals:
+            rows, counters[name + "_sampler"], tri = sample_mesh_device(side[0], side[1], density, seed, max_samples, device, want_tri=True)
+            tris.append(tri)
+        elif _is_mesh(side):
             rows, counters[name + "_sampler"] = sample_mesh_device(side[0], side[1], density, seed, max_samples, device)
         else:
             rows = torch.as_tensor(side, device=device).to(torch.int32).reshape(-1, 4).contiguous()
@@ -444,11 +713,21 @@ def compare_device(estimate, reference, threshold=0.05, max_dist=1.0, cell=0, de
         culled = (cl.summary(cull, ce, cr), ie, ir)
     on_ref = GeometryScorer(sets[1], cell, max_dist, threshold, device)
     on_est = GeometryScorer(sets[0], cell, max_dist, threshold, device)
-    table = torch.zeros(2, 8, dtype=torch.float64, device=device)
-    d_er, _ = on_ref.query(sets[0], row=table[0])
-    d_re, _ = on_est.query(sets[1], row=table[1])
+    table = torch.zeros(4 if normals else 2, 8, dtype=torch.float64, device=device)
+    n_er = torch.empty(sets[0].shape[0], dtype=torch.int32, device=device) if normals else None
+    n_re = torch.empty(sets[1].shape[0], dtype=torch.int32, device=device) if normals else None
+    d_er, _ = on_ref.query(sets[0], row=table[0], index=n_er)
+    d_re, _ = on_est.query(sets[1], row=table[1], index=n_re)
     counters.update(reference_skipped=on_ref.ref_skipped, estimate_skipped=on_est.ref_skipped)
-    return _result(table.cpu().numpy(), (on_ref.cell, on_est.cell), counters, sets, (d_er, d_re), threshold, max_dist, culled)      # the one read-back
+    if normals:
+        te, tr = (t if culled is None else t[torch.as_tensor(i, device=device).long()] for t, i in zip(tris, (culled or (None, None, None))[1:]))
+        dot_e, _ = normal_consistency_device(te, n_er, tr, estimate, reference, row=table[2], device=device)
+        dot_r, _ = normal_consistency_device(tr, n_re, te, reference, estimate, row=table[3], device=device)
+    both = table.cpu().numpy()      # the one read-back
+    out = _result(both[:2], (on_ref.cell, on_est.cell), counters, sets, (d_er, d_re), threshold, max_dist, culled)
+    if normals:
+        _normal_result(out, both[2:], (dot_e, dot_r), (n_er, n_re))
+    return out
 
 
 def _result(table, cells, counters, sets, dists, threshold, max_dist, culled=None):
@@ -459,6 +738,11 @@ def _result(table, cells, counters, sets, dists, threshold, max_dist, culled=Non
                max_dist=float(max_dist), n_estimate=int(sets[0].shape[0]), n_reference=int(sets[1].shape[0]),
                estimate_rows=sets[0], reference_rows=sets[1], dist_estimate=dists[0], dist_reference=dists[1])
     return out
+
+
+def _normal_result(out, table, dots, nearest):
+    out.update(normals=normal_figures(table), normal_table=np.asarray(table, dtype=np.float64), dot_estimate=dots[0], dot_reference=dots[1],
+               nearest_estimate=nearest[0], nearest_reference=nearest[1])
 
 
 def compare(estimate, reference, device="cpu", **kw):
@@ -514,13 +798,19 @@ def metrics_dict(result, extra=None):
     out["reference_to_estimate"] = {name: float(t[1, k]) for k, name in enumerate(ROW_NAMES[:7])}
     if result.get("cull") is not None:
         out["cull"] = result["cull"]
+    if result.get("normals") is not None:
+        nt = result["normal_table"]
+        out["normals"] = dict(result["normals"], estimate_to_reference={name: float(nt[0, k]) for k, name in enumerate(NORMAL_ROW_NAMES[:7]) if k != 4},
+                              reference_to_estimate={name: float(nt[1, k]) for k, name in enumerate(NORMAL_ROW_NAMES[:7]) if k != 4})
     out.update(extra or {})
     return out
 
 
 def write_outputs(path, result, extra=None):
     """path/metrics.json, path/accuracy.ply (the estimate's points coloured by distance over [0, 2 threshold]) and path/completion.ply (the
-    reference's points likewise).  Returns the three paths."""
+    reference's points likewise); with normal scores also path/normals.npz (dot_estimate, dot_reference float32 and nearest_estimate,
+    nearest_reference uint32: per point of either set the dot product and the nearest row of the other set, 0xffffffff: none).  Returns the
+    paths."""
     from .pointcloud import write_ply
     os.makedirs(path, exist_ok=True)
     files = {"metrics": os.path.join(path, "metrics.json")}
@@ -529,4 +819,8 @@ def write_outputs(path, result, extra=None):
         fh.write("\n")
     files["accuracy"] = write_ply(os.path.join(path, "accuracy.ply"), colour_by_distance(result["estimate_rows"], result["dist_estimate"], result["threshold"]))
     files["completion"] = write_ply(os.path.join(path, "completion.ply"), colour_by_distance(result["reference_rows"], result["dist_reference"], result["threshold"]))
+    if result.get("normals") is not None:
+        files["normals"] = os.path.join(path, "normals.npz")
+        np.savez(files["normals"], dot_estimate=as_np(result["dot_estimate"], np.float32), dot_reference=as_np(result["dot_reference"], np.float32),
+                 nearest_estimate=as_np(result["nearest_estimate"], np.int64).astype(np.uint32), nearest_reference=as_np(result["nearest_reference"], np.int64).astype(np.uint32))
     return files

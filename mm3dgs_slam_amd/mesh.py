@@ -721,43 +721,62 @@ class SparseTsdfVolume:
 
 # ---- files ----------------------------------------------------------------------------------------------------------------------
 _FACE =np.dtype([("n", "u1"), ("v", "<i4", 3)])
+NORMAL_PROPERTIES = "property float nx\nproperty float ny\nproperty float nz\n"
 
 
-def mesh_header(n_vertices, n_faces):
-    return ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {int(n_vertices)}\n" + CLOUD_PROPERTIES
+def mesh_header(n_vertices, n_faces, normals=False):
+    props = CLOUD_PROPERTIES.replace("property uchar red\n", NORMAL_PROPERTIES + "property uchar red\n") if normals else CLOUD_PROPERTIES
+    return ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {int(n_vertices)}\n" + props
             + f"element face {int(n_faces)}\nproperty list uchar int vertex_indices\nend_header\n")
 
 
-def write_mesh_ply(path, rows, triangles):
+def write_mesh_ply(path, rows, triangles, normals=None):
     """Binary little-endian PLY: ``float x y z; uchar red green blue alpha`` per vertex (the row bytes as they are), ``list uchar int
-    vertex_indices`` per face (the byte 3, then three int32)."""
+    vertex_indices`` per face (the byte 3, then three int32).  With `normals` (float32 [V,3], ``geometry.vertex_normals``) a vertex is
+    ``float x y z; float nx ny nz; uchar red green blue alpha`` (28 bytes); without them the file is what it has always been."""
     rows = as_np(rows, np.int32).reshape(-1, 4)
     tri = as_np(triangles, np.int32).reshape(-1, 3)
     faces = np.empty(len(tri), dtype=_FACE)
     faces["n"] = 3
     faces["v"] = tri
+    body = rows.astype("<i4", copy=False)
+    if normals is not None:
+        nrm = as_np(normals, np.float32).reshape(-1, 3)
+        if len(nrm) != len(rows):
+            raise ValueError(f"{len(nrm)} normals for {len(rows)} vertices")
+        body = np.concatenate([body[:, :3], nrm.astype("<f4", copy=False).view("<i4"), body[:, 3:]], 1)
     with open(path, "wb") as fh:
-        fh.write(mesh_header(len(rows), len(tri)).encode("ascii"))
-        fh.write(rows.astype("<i4", copy=False).tobytes())
+        fh.write(mesh_header(len(rows), len(tri), normals is not None).encode("ascii"))
+        fh.write(np.ascontiguousarray(body).tobytes())
         fh.write(faces.tobytes())
     return path
 
 
-def read_mesh_ply(path):
-    """(rows [V,4] int32, triangles [T,3] int32) of a file written by ``write_mesh_ply``."""
+def read_mesh_ply_normals(path):
+    """(rows [V,4] int32, triangles [T,3] int32, normals float32 [V,3] or None) of a file written by ``write_mesh_ply``."""
+    plain = ["x", "y", "z", "red", "green", "blue", "alpha"]
     with open(path, "rb") as fh:
         elements = read_header(fh)
-        if ([e[0] for e in elements] != ["vertex", "face"] or [p for _, p in elements[0][2]] != ["x", "y", "z", "red", "green", "blue", "alpha"]
+        names = [p for _, p in elements[0][2]] if elements else []
+        if ([e[0] for e in elements] != ["vertex", "face"] or names not in (plain, plain[:3] + ["nx", "ny", "nz"] + plain[3:])
                 or elements[1][2] != [("list", "uchar")]):
             raise ValueError(f"{path}: not a mesh of write_mesh_ply")
-        nv, nf = elements[0][1], elements[1][1]
-        body, faces = fh.read(16 * nv), fh.read(_FACE.itemsize * nf)
-    if len(body) != 16 * nv or len(faces) != _FACE.itemsize * nf:
+        nv, nf, words = elements[0][1], elements[1][1], 4 if names == plain else 7
+        body, faces = fh.read(4 * words * nv), fh.read(_FACE.itemsize * nf)
+    if len(body) != 4 * words * nv or len(faces) != _FACE.itemsize * nf:
         raise ValueError(f"{path}: {len(body)} + {len(faces)} body bytes for {nv} vertices and {nf} faces")
     f = np.frombuffer(faces, dtype=_FACE)
     if not bool((f["n"] == 3).all()):
         raise ValueError(f"{path}: a face that is not a triangle")
-    return np.frombuffer(body, dtype="<i4").reshape(nv, 4).copy(), f["v"].astype(np.int32).copy()
+    body = np.frombuffer(body, dtype="<i4").reshape(nv, words)
+    if words == 4:
+        return body.copy(), f["v"].astype(np.int32).copy(), None
+    return np.ascontiguousarray(body[:, [0, 1, 2, 6]]), f["v"].astype(np.int32).copy(), np.ascontiguousarray(body[:, 3:6]).view(np.float32)
+
+
+def read_mesh_ply(path):
+    """(rows [V,4] int32, triangles [T,3] int32) of a file written by ``write_mesh_ply`` (with or without normals, which are dropped)."""
+    return read_mesh_ply_normals(path)[:2]
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2", "int": "<i4",

@@ -33,7 +33,9 @@ from the checkpoint.  `--geometry` (or `geometry.eval: true`) adds `geometry/met
 against a reference surface (the same frames' sensor depth at the ground-truth poses, or a PLY file) -- accuracy, completion, completion ratio, F-score, Chamfer
 distance; `--geometry --eval` likewise from the checkpoint.  `--mesh-clean small|largest` (or `mesh.clean`) removes the mesh's small disconnected pieces behind
 the extraction, for `--mesh` and for the meshes `--geometry` scores (`mesh.clean_min_triangles`; mesh_clean.py).  `--mesh-volume sparse` (or `mesh.volume`)
-holds the fusion volume in hashed 8 x 8 x 8-sample blocks along the surface instead of one dense lattice (`mesh.max_blocks`).
+holds the fusion volume in hashed 8 x 8 x 8-sample blocks along the surface instead of one dense lattice (`mesh.max_blocks`).  `--mesh-normals` (or
+`mesh.normals: true`) writes area-weighted vertex normals into `mesh.ply`; `--geometry-normals` (or `geometry.normals: true`) adds normal consistency to
+the geometry scores (`estimate: mesh` against a mesh).
 
 `--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
 `outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
@@ -160,6 +162,8 @@ def main():
     ap.add_argument("--geometry", action="store_true", help="after the run (or, with --eval, from the checkpoint without running a frame) score the exported geometry against a reference surface into outputdir/geometry (the config's `geometry` block)")
     ap.add_argument("--mesh-clean", choices=("small", "largest"), default=None, help="with --mesh / --geometry: remove the mesh's small disconnected pieces (overrides the `mesh` block's `clean`; small: components below mesh.clean_min_triangles triangles, largest: all but the largest component)")
     ap.add_argument("--mesh-volume", choices=("dense", "sparse"), default=None, help="with --mesh / --geometry: how the fusion volume is held (overrides the `mesh` block's `volume`; dense: one lattice over the box of the views, sparse: hashed 8 x 8 x 8-sample blocks along the surface, mesh.max_blocks)")
+    ap.add_argument("--mesh-normals", action="store_true", help="with --mesh: write area-weighted vertex normals into mesh.ply (`float nx ny nz` behind the position; sets the `mesh` block's `normals`)")
+    ap.add_argument("--geometry-normals", action="store_true", help="with --geometry: also score normal consistency (needs `estimate: mesh` and a mesh as the reference; sets the `geometry` block's `normals`)")
     ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
@@ -183,6 +187,10 @@ def main():
         cfg["mesh"] = dict(cfg.get("mesh") or {}, clean=args.mesh_clean)
     if args.mesh_volume:
         cfg["mesh"] = dict(cfg.get("mesh") or {}, volume=args.mesh_volume)
+    if args.mesh_normals:
+        cfg["mesh"] = dict(cfg.get("mesh") or {}, normals=True)
+    if args.geometry_normals:
+        cfg["geometry"] = dict(cfg.get("geometry") or {}, normals=True)
     if args.eval:
         seq = build_sequence(cfg, args.frames, args.gaussians)
         if args.pointcloud:
