@@ -760,26 +760,33 @@ int mm3dgs_pointcloud_reset(void* table_or_null, uint64_t slots, uint64_t* count
   return check_launch("pointcloud_reset");
 }
 
+// the checks of one posed pinhole camera, shared by every call that takes one (`who` names the call), and its struct; the NULL and alignment
+// tests of the pose stay with each call, whose messages name its other pointers
+static int view_check(const char* who, int H, int W, double fx, double fy, double cx, double cy, const float* pose, PinholeView& out) {
+  if (H <= 0 || W <= 0) return fail(-1, "%s: H = %d, W = %d (both must be positive)", who, H, W);
+  if (!eval_shape_ok(H, W)) return fail(-1, "%s: %d x %d has more than 2^28 pixels", who, H, W);
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "%s: fx = %g, fy = %g (finite, not 0)", who, fx, fy);
+  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "%s: cx = %g, cy = %g (must be finite)", who, cx, cy);
+  out.H = H; out.W = W; out.fx = fx; out.fy = fy; out.cx = cx; out.cy = cy; out.pose = pose;
+  return 0;
+}
+
 int mm3dgs_pointcloud_add_view(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
                                const float* silhouette_or_null, float sil_min, float depth_max, double voxel, uint32_t view, void* rows,
                                uint64_t cap, void* table_or_null, uint64_t slots, uint64_t* counters, void* work, void* stream) {
-  if (H <= 0 || W <= 0) return fail(-1, "pointcloud_add_view: H = %d, W = %d (both must be positive)", H, W);
-  if (!eval_shape_ok(H, W)) return fail(-1, "pointcloud_add_view: %d x %d has more than 2^28 pixels", H, W);
+  PointCloudView v;
+  if (int rc = view_check("pointcloud_add_view", H, W, fx, fy, cx, cy, pose, v)) return rc;
   if (!color || !depth || !pose || !rows || !counters || !work)
     return fail(-1, "pointcloud_add_view: NULL argument (color, depth, pose, rows, counters and work are required)");
   if (!(voxel >= 0.0) || !isfinite(voxel)) return fail(-1, "pointcloud_add_view: voxel = %g (must be finite and not negative)", voxel);
   if (voxel > 0.0 && !table_or_null) return fail(-1, "pointcloud_add_view: voxel = %g needs a table", voxel);
   if (voxel > 0.0 && !pointcloud_slots_ok(slots))
     return fail(-1, "pointcloud_add_view: slots = %llu (a power of two, at least 64, at most 2^40)", (unsigned long long)slots);
-  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "pointcloud_add_view: fx = %g, fy = %g (finite, not 0)", fx, fy);
-  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "pointcloud_add_view: cx = %g, cy = %g (must be finite)", cx, cy);
   if (((uintptr_t)rows | (uintptr_t)table_or_null) & 15) return fail(-1, "pointcloud_add_view: rows and table must be 16-byte aligned");
   if (((uintptr_t)counters | (uintptr_t)work) & 7) return fail(-1, "pointcloud_add_view: counters and work must be 8-byte aligned");
   if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)silhouette_or_null | (uintptr_t)pose) & 3)
     return fail(-1, "pointcloud_add_view: the images and the pose must be 4-byte aligned");
-  PointCloudView v;
-  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
-  v.pose = pose; v.color = color; v.depth = depth; v.sil = silhouette_or_null;
+  v.color = color; v.depth = depth; v.sil = silhouette_or_null;
   v.sil_min = sil_min; v.depth_max = depth_max; v.voxel = voxel; v.view = view;
   v.table = voxel > 0.0 ? (unsigned long long*)table_or_null : nullptr;      // voxel == 0: no thinning, a table is ignored
   v.slots = v.table ? slots : 0;
@@ -795,22 +802,18 @@ static bool tsdf_lattice_ok(int nx, int ny, int nz) {
 }
 static bool tsdf_origin_ok(const double* o) { return o && isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]); }
 
-// the checks every call with a view shares, dense or blocks; `who` names the call, `color` is NULL for a call that reads none, and a
-// block call (max_trunc_voxels > 0) bounds the truncation distance in voxels
+// the checks every TSDF call with a view shares beyond view_check, dense or blocks; `who` names the call, `color` is NULL for a call that
+// reads none, and a block call (max_trunc_voxels > 0) bounds the truncation distance in voxels
 static int tsdf_view(const char* who, int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* color, const float* depth,
                      const float* sil, float sil_min, float depth_max, const double* origin, double voxel, double trunc, double max_trunc_voxels, TsdfView& v) {
-  if (H <= 0 || W <= 0) return fail(-1, "%s: H = %d, W = %d (both must be positive)", who, H, W);
-  if (!eval_shape_ok(H, W)) return fail(-1, "%s: %d x %d has more than 2^28 pixels", who, H, W);
+  if (int rc = view_check(who, H, W, fx, fy, cx, cy, pose, v)) return rc;
   if (!depth || !pose || !origin) return fail(-1, "%s: NULL argument (depth, pose and the origin or anchor are required)", who);
   if (!(voxel > 0.0) || !isfinite(voxel) || !(trunc > 0.0) || !isfinite(trunc)) return fail(-1, "%s: voxel = %g, trunc = %g (both must be finite and positive)", who, voxel, trunc);
   if (max_trunc_voxels > 0.0 && !(trunc <= max_trunc_voxels * voxel))
     return fail(-1, "%s: trunc = %g is more than %g voxel = %g", who, trunc, max_trunc_voxels, max_trunc_voxels * voxel);
   if (!tsdf_origin_ok(origin)) return fail(-1, "%s: the origin or anchor must be finite", who);
-  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "%s: fx = %g, fy = %g (finite, not 0)", who, fx, fy);
-  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "%s: cx = %g, cy = %g (must be finite)", who, cx, cy);
   if (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)sil | (uintptr_t)pose) & 3) return fail(-1, "%s: the images and the pose must be 4-byte aligned", who);
-  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
-  v.pose = pose; v.color = color; v.depth = depth; v.sil = sil;
+  v.color = color; v.depth = depth; v.sil = sil;
   v.sil_min = sil_min; v.depth_max = depth_max;
   v.o[0] = origin[0]; v.o[1] = origin[1]; v.o[2] = origin[2]; v.voxel = voxel; v.trunc = trunc;
   v.nx = v.ny = v.nz = 0;
@@ -994,26 +997,37 @@ int mm3dgs_nn_grid_build(uint64_t n_ref, const void* rows, double cell, const in
 
 size_t mm3dgs_nn_query_work_bytes(uint64_t n_q) { return (n_q >= 1 && n_q <= NN_MAX_ROWS) ? nn_query_work_bytes(n_q) : 0; }
 
+// mm3dgs_nn_query and mm3dgs_nn_query_index: one body; want_index adds index_out to the required and to the 4-byte aligned pointers.
+// want_index only words the checks: behind them index_out is non-NULL exactly when it is set (mm3dgs_nn_query passes NULL), and the
+// launcher goes by the pointer alone
+static int nn_query_call(const char* who, uint64_t n_q, const void* q_rows, uint64_t n_ref, double cell, const int64_t* origin_cell, int gx, int gy, int gz,
+                         const uint32_t* cell_start, const void* sorted, double max_dist, double threshold, float* dist_out, double* row, void* work,
+                         void* stream, uint32_t* index_out, bool want_index) {
+  if (n_q < 1 || n_q > NN_MAX_ROWS) return fail(-1, "%s: n_q = %llu (1 .. 2^30)", who, (unsigned long long)n_q);
+  if (n_ref < 1 || n_ref > NN_MAX_ROWS) return fail(-1, "%s: n_ref = %llu (1 .. 2^30)", who, (unsigned long long)n_ref);
+  if (!nn_grid_ok(gx, gy, gz)) return fail(-1, "%s: grid %d x %d x %d (every size at least 1, at most 2^26 cells)", who, gx, gy, gz);
+  if (!(cell > 0.0) || !isfinite(cell)) return fail(-1, "%s: cell = %g (must be finite and positive)", who, cell);
+  if (!(max_dist > 0.0) || !isfinite(max_dist)) return fail(-1, "%s: max_dist = %g (must be finite and positive)", who, max_dist);
+  if (!(threshold >= 0.0) || !isfinite(threshold)) return fail(-1, "%s: threshold = %g (must be finite and not negative)", who, threshold);
+  const double rings = ceil(max_dist / cell);
+  if (!(rings <= NN_MAX_RINGS)) return fail(-1, "%s: max_dist / cell = %g (at most 2^20 rings)", who, max_dist / cell);
+  if (!nn_origin_ok(origin_cell)) return fail(-1, "%s: origin_cell is NULL or beyond +-2^40", who);
+  if (!q_rows || !cell_start || !sorted || !dist_out || (want_index && !index_out) || !row || !work)
+    return fail(-1, "%s: NULL argument (q_rows, cell_start, sorted, dist_out, %srow and work are required)", who, want_index ? "index_out, " : "");
+  if (((uintptr_t)q_rows | (uintptr_t)sorted) & 15) return fail(-1, "%s: q_rows and sorted must be 16-byte aligned", who);
+  if (((uintptr_t)row | (uintptr_t)work) & 7) return fail(-1, "%s: row and work must be 8-byte aligned", who);
+  if (((uintptr_t)cell_start | (uintptr_t)dist_out | (uintptr_t)index_out) & 3)
+    return fail(-1, "%s: cell_start%s must be 4-byte aligned", who, want_index ? ", dist_out and index_out" : " and dist_out");
+  launch_nn_query(nn_grid(cell, origin_cell, gx, gy, gz), n_q, q_rows, n_ref, cell_start, sorted, max_dist, threshold, (int)(rings < 1.0 ? 1.0 : rings),
+                  dist_out, index_out, row, work, (hipStream_t)stream);
+  return check_launch(who);
+}
+
 int mm3dgs_nn_query(uint64_t n_q, const void* q_rows, uint64_t n_ref, double cell, const int64_t* origin_cell, int gx, int gy, int gz,
                     const uint32_t* cell_start, const void* sorted, double max_dist, double threshold, float* dist_out, double* row, void* work,
                     void* stream) {
-  if (n_q < 1 || n_q > NN_MAX_ROWS) return fail(-1, "nn_query: n_q = %llu (1 .. 2^30)", (unsigned long long)n_q);
-  if (n_ref < 1 || n_ref > NN_MAX_ROWS) return fail(-1, "nn_query: n_ref = %llu (1 .. 2^30)", (unsigned long long)n_ref);
-  if (!nn_grid_ok(gx, gy, gz)) return fail(-1, "nn_query: grid %d x %d x %d (every size at least 1, at most 2^26 cells)", gx, gy, gz);
-  if (!(cell > 0.0) || !isfinite(cell)) return fail(-1, "nn_query: cell = %g (must be finite and positive)", cell);
-  if (!(max_dist > 0.0) || !isfinite(max_dist)) return fail(-1, "nn_query: max_dist = %g (must be finite and positive)", max_dist);
-  if (!(threshold >= 0.0) || !isfinite(threshold)) return fail(-1, "nn_query: threshold = %g (must be finite and not negative)", threshold);
-  const double rings = ceil(max_dist / cell);
-  if (!(rings <= NN_MAX_RINGS)) return fail(-1, "nn_query: max_dist / cell = %g (at most 2^20 rings)", max_dist / cell);
-  if (!nn_origin_ok(origin_cell)) return fail(-1, "nn_query: origin_cell is NULL or beyond +-2^40");
-  if (!q_rows || !cell_start || !sorted || !dist_out || !row || !work)
-    return fail(-1, "nn_query: NULL argument (q_rows, cell_start, sorted, dist_out, row and work are required)");
-  if (((uintptr_t)q_rows | (uintptr_t)sorted) & 15) return fail(-1, "nn_query: q_rows and sorted must be 16-byte aligned");
-  if (((uintptr_t)row | (uintptr_t)work) & 7) return fail(-1, "nn_query: row and work must be 8-byte aligned");
-  if (((uintptr_t)cell_start | (uintptr_t)dist_out) & 3) return fail(-1, "nn_query: cell_start and dist_out must be 4-byte aligned");
-  launch_nn_query(nn_grid(cell, origin_cell, gx, gy, gz), n_q, q_rows, n_ref, cell_start, sorted, max_dist, threshold, (int)(rings < 1.0 ? 1.0 : rings),
-                  dist_out, row, work, (hipStream_t)stream);
-  return check_launch("nn_query");
+  return nn_query_call("nn_query", n_q, q_rows, n_ref, cell, origin_cell, gx, gy, gz, cell_start, sorted, max_dist, threshold, dist_out, row, work, stream,
+                       nullptr, false);
 }
 
 #define MS_MAX_TRIANGLES ((uint64_t)1 << 30)
@@ -1043,48 +1057,36 @@ int mm3dgs_mesh_sample_plan(uint64_t n_vertices, const void* vrows, uint64_t m, 
   return check_launch("mesh_sample_plan");
 }
 
+// mm3dgs_mesh_sample_emit and mm3dgs_mesh_sample_emit_tri: one body; want_tri adds tri_out to the pointers a cap above 0 needs and only
+// words the checks: the launcher goes by the pointer alone.  _emit_tri with a cap of 0 may pass a NULL tri_out and then runs the kernel
+// without triangle ids: with no sample to write, the two instantiations write the same two counters
+static int mesh_sample_emit_call(const char* who, uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed,
+                                 const void* work, void* rows, uint64_t cap, uint64_t* counters, void* stream, uint32_t* tri_out, bool want_tri) {
+  if (mesh_sample_check(who, n_vertices, vrows, m, triangles, density, work, counters)) return -1;
+  if (cap > ((uint64_t)1 << 31)) return fail(-1, "%s: cap = %llu (at most 2^31)", who, (unsigned long long)cap);
+  if ((!rows || (want_tri && !tri_out)) && cap) return fail(-1, "%s: rows %sis NULL with a cap above 0", who, want_tri ? "or tri_out " : "");
+  if ((uintptr_t)rows & 15) return fail(-1, "%s: rows must be 16-byte aligned", who);
+  if ((uintptr_t)tri_out & 3) return fail(-1, "%s: tri_out must be 4-byte aligned", who);
+  launch_mesh_sample_emit(mesh_sample(n_vertices, vrows, m, triangles, density, seed), work, rows, tri_out, cap, counters, (hipStream_t)stream);
+  return check_launch(who);
+}
+
 int mm3dgs_mesh_sample_emit(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed, const void* work,
                             void* rows, uint64_t cap, uint64_t* counters, void* stream) {
-  if (mesh_sample_check("mesh_sample_emit", n_vertices, vrows, m, triangles, density, work, counters)) return -1;
-  if (cap > ((uint64_t)1 << 31)) return fail(-1, "mesh_sample_emit: cap = %llu (at most 2^31)", (unsigned long long)cap);
-  if (!rows && cap) return fail(-1, "mesh_sample_emit: rows is NULL with a cap above 0");
-  if ((uintptr_t)rows & 15) return fail(-1, "mesh_sample_emit: rows must be 16-byte aligned");
-  launch_mesh_sample_emit(mesh_sample(n_vertices, vrows, m, triangles, density, seed), work, rows, cap, counters, (hipStream_t)stream);
-  return check_launch("mesh_sample_emit");
+  return mesh_sample_emit_call("mesh_sample_emit", n_vertices, vrows, m, triangles, density, seed, work, rows, cap, counters, stream, nullptr, false);
 }
 
 // ---- normals (geometry.hip): the two calls above with an index / a triangle per row, normal consistency, vertex normals ----------------
 int mm3dgs_nn_query_index(uint64_t n_q, const void* q_rows, uint64_t n_ref, double cell, const int64_t* origin_cell, int gx, int gy, int gz,
                           const uint32_t* cell_start, const void* sorted, double max_dist, double threshold, float* dist_out, uint32_t* index_out,
                           double* row, void* work, void* stream) {
-  if (n_q < 1 || n_q > NN_MAX_ROWS) return fail(-1, "nn_query_index: n_q = %llu (1 .. 2^30)", (unsigned long long)n_q);
-  if (n_ref < 1 || n_ref > NN_MAX_ROWS) return fail(-1, "nn_query_index: n_ref = %llu (1 .. 2^30)", (unsigned long long)n_ref);
-  if (!nn_grid_ok(gx, gy, gz)) return fail(-1, "nn_query_index: grid %d x %d x %d (every size at least 1, at most 2^26 cells)", gx, gy, gz);
-  if (!(cell > 0.0) || !isfinite(cell)) return fail(-1, "nn_query_index: cell = %g (must be finite and positive)", cell);
-  if (!(max_dist > 0.0) || !isfinite(max_dist)) return fail(-1, "nn_query_index: max_dist = %g (must be finite and positive)", max_dist);
-  if (!(threshold >= 0.0) || !isfinite(threshold)) return fail(-1, "nn_query_index: threshold = %g (must be finite and not negative)", threshold);
-  const double rings = ceil(max_dist / cell);
-  if (!(rings <= NN_MAX_RINGS)) return fail(-1, "nn_query_index: max_dist / cell = %g (at most 2^20 rings)", max_dist / cell);
-  if (!nn_origin_ok(origin_cell)) return fail(-1, "nn_query_index: origin_cell is NULL or beyond +-2^40");
-  if (!q_rows || !cell_start || !sorted || !dist_out || !index_out || !row || !work)
-    return fail(-1, "nn_query_index: NULL argument (q_rows, cell_start, sorted, dist_out, index_out, row and work are required)");
-  if (((uintptr_t)q_rows | (uintptr_t)sorted) & 15) return fail(-1, "nn_query_index: q_rows and sorted must be 16-byte aligned");
-  if (((uintptr_t)row | (uintptr_t)work) & 7) return fail(-1, "nn_query_index: row and work must be 8-byte aligned");
-  if (((uintptr_t)cell_start | (uintptr_t)dist_out | (uintptr_t)index_out) & 3) return fail(-1, "nn_query_index: cell_start, dist_out and index_out must be 4-byte aligned");
-  launch_nn_query_index(nn_grid(cell, origin_cell, gx, gy, gz), n_q, q_rows, n_ref, cell_start, sorted, max_dist, threshold, (int)(rings < 1.0 ? 1.0 : rings),
-                        dist_out, index_out, row, work, (hipStream_t)stream);
-  return check_launch("nn_query_index");
+  return nn_query_call("nn_query_index", n_q, q_rows, n_ref, cell, origin_cell, gx, gy, gz, cell_start, sorted, max_dist, threshold, dist_out, row, work,
+                       stream, index_out, true);
 }
 
 int mm3dgs_mesh_sample_emit_tri(uint64_t n_vertices, const void* vrows, uint64_t m, const int32_t* triangles, double density, uint32_t seed, const void* work,
                                 void* rows, uint32_t* tri_out, uint64_t cap, uint64_t* counters, void* stream) {
-  if (mesh_sample_check("mesh_sample_emit_tri", n_vertices, vrows, m, triangles, density, work, counters)) return -1;
-  if (cap > ((uint64_t)1 << 31)) return fail(-1, "mesh_sample_emit_tri: cap = %llu (at most 2^31)", (unsigned long long)cap);
-  if ((!rows || !tri_out) && cap) return fail(-1, "mesh_sample_emit_tri: rows or tri_out is NULL with a cap above 0");
-  if ((uintptr_t)rows & 15) return fail(-1, "mesh_sample_emit_tri: rows must be 16-byte aligned");
-  if ((uintptr_t)tri_out & 3) return fail(-1, "mesh_sample_emit_tri: tri_out must be 4-byte aligned");
-  launch_mesh_sample_emit_tri(mesh_sample(n_vertices, vrows, m, triangles, density, seed), work, rows, tri_out, cap, counters, (hipStream_t)stream);
-  return check_launch("mesh_sample_emit_tri");
+  return mesh_sample_emit_call("mesh_sample_emit_tri", n_vertices, vrows, m, triangles, density, seed, work, rows, cap, counters, stream, tri_out, true);
 }
 
 // the size and pointer checks of one mesh argument (density and seed are not used by these calls)
@@ -1135,21 +1137,17 @@ size_t mm3dgs_cull_work_bytes(uint64_t n) { return n <= NN_MAX_ROWS ? cull_work_
 
 int mm3dgs_cull_mark_view(int H, int W, double fx, double fy, double cx, double cy, const float* pose, const float* depth_or_null, float depth_max,
                           double z_near, double z_far, double eps, uint64_t n, const void* rows, uint32_t* seen, uint64_t* counters, void* stream) {
-  if (H <= 0 || W <= 0) return fail(-1, "cull_mark_view: H = %d, W = %d (both must be positive)", H, W);
-  if (!eval_shape_ok(H, W)) return fail(-1, "cull_mark_view: %d x %d has more than 2^28 pixels", H, W);
+  CullView v;
+  if (int rc = view_check("cull_mark_view", H, W, fx, fy, cx, cy, pose, v)) return rc;
   if (n > NN_MAX_ROWS) return fail(-1, "cull_mark_view: n = %llu (at most 2^30)", (unsigned long long)n);
   if (!pose || !counters || (n && (!rows || !seen))) return fail(-1, "cull_mark_view: NULL argument (pose and counters are required; rows and seen unless n is 0)");
-  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "cull_mark_view: fx = %g, fy = %g (finite, not 0)", fx, fy);
-  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "cull_mark_view: cx = %g, cy = %g (must be finite)", cx, cy);
   if (!(z_near >= 0.0) || !isfinite(z_near) || !(z_far >= 0.0) || !isfinite(z_far) || !(eps >= 0.0) || !isfinite(eps))
     return fail(-1, "cull_mark_view: near = %g, far = %g, eps = %g (each must be finite and not negative)", z_near, z_far, eps);
   if (!(depth_max == depth_max)) return fail(-1, "cull_mark_view: depth_max is not a number");
   if ((uintptr_t)rows & 15) return fail(-1, "cull_mark_view: rows must be 16-byte aligned");
   if ((uintptr_t)counters & 7) return fail(-1, "cull_mark_view: counters must be 8-byte aligned");
   if (((uintptr_t)seen | (uintptr_t)depth_or_null | (uintptr_t)pose) & 3) return fail(-1, "cull_mark_view: seen, the depth image and the pose must be 4-byte aligned");
-  CullView v;
-  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy;
-  v.pose = pose; v.depth = depth_or_null; v.depth_max = depth_max;
+  v.depth = depth_or_null; v.depth_max = depth_max;
   v.z_near = z_near; v.z_far = z_far; v.eps = eps;
   launch_cull_mark_view(v, n, rows, seen, counters, (hipStream_t)stream);
   return check_launch("cull_mark_view");
@@ -1224,22 +1222,19 @@ size_t mm3dgs_mesh_depth_work_bytes(uint64_t V, uint64_t T, int H, int W, uint64
 int mm3dgs_mesh_depth_render(int H, int W, double fx, double fy, double cx, double cy, const float* pose, double z_near, double z_far, uint64_t V,
                              const void* vrows, uint64_t T, const int32_t* triangles, uint64_t max_pairs, float* depth_out, int32_t* tri_out_or_null, void* work,
                              uint64_t* counters, void* stream) {
-  if (H <= 0 || W <= 0) return fail(-1, "mesh_depth_render: H = %d, W = %d (both must be positive)", H, W);
-  if (!eval_shape_ok(H, W)) return fail(-1, "mesh_depth_render: %d x %d has more than 2^28 pixels", H, W);
+  MeshDepthView v;
+  if (int rc = view_check("mesh_depth_render", H, W, fx, fy, cx, cy, pose, v)) return rc;
   if (V > NN_MAX_ROWS || T > NN_MAX_ROWS) return fail(-1, "mesh_depth_render: V = %llu, T = %llu (each at most 2^30)", (unsigned long long)V, (unsigned long long)T);
   if (max_pairs > MD_MAX_PAIRS) return fail(-1, "mesh_depth_render: max_pairs = %llu (at most 2^31)", (unsigned long long)max_pairs);
   if (!pose || !depth_out || !work || !counters || (V && !vrows) || (T && !triangles))
     return fail(-1, "mesh_depth_render: NULL argument (pose, depth_out, work and counters are required; vrows unless V is 0; triangles unless T is 0)");
-  if (!isfinite(fx) || !isfinite(fy) || fx == 0.0 || fy == 0.0) return fail(-1, "mesh_depth_render: fx = %g, fy = %g (finite, not 0)", fx, fy);
-  if (!isfinite(cx) || !isfinite(cy)) return fail(-1, "mesh_depth_render: cx = %g, cy = %g (must be finite)", cx, cy);
   if (!(z_near >= 0.0) || !isfinite(z_near) || !(z_far >= 0.0) || !isfinite(z_far))
     return fail(-1, "mesh_depth_render: near = %g, far = %g (each must be finite and not negative)", z_near, z_far);
   if ((uintptr_t)vrows & 15) return fail(-1, "mesh_depth_render: vrows must be 16-byte aligned");
   if (((uintptr_t)work | (uintptr_t)counters) & 7) return fail(-1, "mesh_depth_render: work and counters must be 8-byte aligned");
   if (((uintptr_t)triangles | (uintptr_t)depth_out | (uintptr_t)tri_out_or_null | (uintptr_t)pose) & 3)
     return fail(-1, "mesh_depth_render: triangles, depth_out, tri_out and the pose must be 4-byte aligned");
-  MeshDepthView v;
-  v.H = H; v.W = W; v.fx = fx; v.fy = fy; v.cx = cx; v.cy = cy; v.pose = pose; v.z_near = z_near; v.z_far = z_far;
+  v.z_near = z_near; v.z_far = z_far;
   launch_mesh_depth_render(v, V, vrows, T, triangles, max_pairs, depth_out, tri_out_or_null, work, counters, (hipStream_t)stream);
   return check_launch("mesh_depth_render");
 }

@@ -2,9 +2,9 @@
 // statement: cull.cull_host).  Rows are the cloud's 16-byte rows {float x, y, z; uint32 rgba}; seen is one uint32 per row, zeroed by the caller.
 //
 //   cull_mark_kernel     one launch per view, one lane per row and step, a workgroup walking 8 steps of 256 consecutive rows.  One lane per
-//                        workgroup builds the Rigid into LDS (as in tsdf.hip).  A lane loads its row once and walks the rule in double, no contraction, in tsdf_integrate_kernel's summation order: finite,
-//                        z_c > near, z_c <= far (far > 0), the pixel floor(fx x_c / z_c + cx + 0.5) inside the image, and with a depth image
-//                        the pixel's validity (view_pixel.h, no silhouette) and z_c <= (double)d + eps.  Only a row that is seen touches the
+//                        workgroup builds the Rigid into LDS.  A lane loads its row once and walks the rule in double through view_pixel.h's
+//                        statements (the ones tsdf_sample.h calls): finite, z_c > near, z_c <= far (far > 0), the pixel inside the image, and with
+//                        a depth image the pixel's validity (no silhouette) and z_c <= (double)d + eps.  Only a row that is seen touches the
 //                        depth image (one scattered 4-byte load) and seen[i] (plain load, add, store: the row belongs to this lane and views are
 //                        ordered on the stream).  Counters: [0] views, [1] sightings -- one integer add per workgroup (tsdf.hip's header: one
 //                        per wave on one word is what a view cost there).  The adds all land on one word and are what bounds the launch: with
@@ -37,31 +37,25 @@ static CullWork cull_work(void* base, size_t n, size_t* bytes = nullptr) {
 }
 size_t cull_work_bytes(uint64_t n) { size_t b; cull_work(nullptr, (size_t)n, &b); return b; }
 
-__device__ __forceinline__ bool cull_finite(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }
-
 __global__ void __launch_bounds__(CB)
 cull_mark_kernel(CullView v, const uint4* __restrict__ rows, uint32_t n, uint32_t* __restrict__ seen, unsigned long long* __restrict__ counters) {
 #pragma clang fp contract(off)
-  __shared__ Rigid g;      // the pose is the same for every row: one lane normalises the quaternion for its workgroup
+  __shared__ Rigid g;
   __shared__ uint32_t wcnt[1][CB / 64];
-  if (threadIdx.x == 0) g = rigid_from_pose(v.pose);
-  __syncthreads();
+  view_rigid_shared(v.pose, g);
   uint32_t nhit = 0;
   for (int k = 0; k < CULL_CHUNKS; k++) {      // 256 consecutive rows per step: every load of a wave is one contiguous KiB
     const size_t i = ((size_t)blockIdx.x * CULL_CHUNKS + k) * CB + threadIdx.x;
     if (i >= n) break;
     const uint4 r = rows[i];      // one 16-byte load
     const float xf = __uint_as_float(r.x), yf = __uint_as_float(r.y), zf = __uint_as_float(r.z);
-    if (!cull_finite(xf, yf, zf)) continue;
-    const double pw0 = (double)xf, pw1 = (double)yf, pw2 = (double)zf;
-    const double z = g.R[2][0] * pw0 + g.R[2][1] * pw1 + g.R[2][2] * pw2 + g.t[2];
+    if (!view_finite(xf, yf, zf)) continue;
+    double x, y, z;
+    size_t pix;
+    view_to_camera(g, (double)xf, (double)yf, (double)zf, x, y, z);      // (x and y are needed only behind the test of z)
     if (!(z > v.z_near) || (v.z_far > 0.0 && !(z <= v.z_far))) continue;      // (a NaN fails the first test)
-    const double x = g.R[0][0] * pw0 + g.R[0][1] * pw1 + g.R[0][2] * pw2 + g.t[0];
-    const double y = g.R[1][0] * pw0 + g.R[1][1] * pw1 + g.R[1][2] * pw2 + g.t[1];
-    const double fu = floor(v.fx * x / z + v.cx + 0.5), fv = floor(v.fy * y / z + v.cy + 0.5);
-    if (!(fu >= 0.0 && fu < (double)v.W && fv >= 0.0 && fv < (double)v.H)) continue;      // (a NaN fails)
+    if (!view_pixel_index(v, x, y, z, pix)) continue;
     if (v.depth) {      // occlusion: a hole in the depth image sees nothing
-      const size_t pix = (size_t)(int)fv * (size_t)v.W + (size_t)(int)fu;
       float d;
       if (!view_pixel_valid(v.depth, nullptr, 0.f, v.depth_max, pix, d) || !(z <= (double)d + v.eps)) continue;
     }
@@ -83,7 +77,7 @@ void launch_cull_mark_view(const CullView& v, uint64_t n, const void* rows, uint
 // kept / skipped of row i (i < n)
 __device__ __forceinline__ bool cull_kept(const uint4* __restrict__ rows, const uint32_t* __restrict__ seen, uint32_t min_views, uint32_t i, uint4& r, bool& skipped) {
   r = rows[i];
-  skipped = !cull_finite(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z));
+  skipped = !view_finite(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z));
   return !skipped && seen[i] >= min_views;
 }
 

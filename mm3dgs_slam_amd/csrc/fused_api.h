@@ -124,13 +124,14 @@ void launch_align_depth(int H, int W, const float* est, const float* depth, cons
 size_t eval_image_work_bytes(int H, int W);
 void launch_eval_image(int H, int W, const float* image, const float* gt, const float* depth, const float* gt_depth, const float* window,
                        double* rows, double* row, hipStream_t s);
+// one posed pinhole camera: the image size, the intrinsics and the world->camera 7-vector (qw,qx,qy,qz,tx,ty,tz; device).  Every view struct
+// below begins with it, api.hip's view_check fills and checks it, view_pixel.h states what the kernels do with it
+struct PinholeView { int H, W; double fx, fy, cx, cy; const float* pose; };
 // fused point cloud (pointcloud.hip): one view's valid pixels lifted to world points and appended to rows (16 B each) from counters[0],
 // thinned to the first point per voxel through the caller's table when voxel > 0 (table NULL otherwise); work = the buffer of
 // pointcloud_work_bytes(H, W); H W <= 2^28, slots a power of two >= 64 and hash_shift = 64 - log2(slots), as the entry point has checked
-struct PointCloudView {
-  int H, W;
-  double fx, fy, cx, cy;
-  const float* pose; const float* color; const float* depth; const float* sil;
+struct PointCloudView : PinholeView {
+  const float* color; const float* depth; const float* sil;
   float sil_min, depth_max;
   double voxel;
   uint32_t view;
@@ -142,10 +143,8 @@ void launch_pointcloud_add_view(const PointCloudView& v, void* rows, uint64_t ca
 // coloured triangle mesh (tsdf.hip): one view fused into the caller's dense volume (tsdf_w float2, rgb_w float4 over nx x ny x nz samples at
 // o + voxel (i, j, k), x fastest), and marching tetrahedra over it in two calls (plan: counts and bases into work = the buffer of
 // tsdf_mesh_work_bytes; emit: rows and triangles); every size >= 2 and nx ny nz <= 2^30, as the entry points have checked
-struct TsdfView {
-  int H, W;
-  double fx, fy, cx, cy;
-  const float* pose; const float* color; const float* depth; const float* sil;
+struct TsdfView : PinholeView {
+  const float* color; const float* depth; const float* sil;
   float sil_min, depth_max;
   double o[3], voxel, trunc;
   int nx, ny, nz;
@@ -178,16 +177,14 @@ struct MeshSample { const uint4* vrows; uint32_t n_vertices; const int* tris; ui
 size_t nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz);
 void launch_nn_grid_build(const NnGrid& g, uint64_t n_ref, const void* rows, void* cell_start, void* sorted, uint64_t* counters, void* work, hipStream_t s);
 size_t nn_query_work_bytes(uint64_t n_q);
+// index_out_or_null: what the normal scores need, the original reference row of the nearest record per query (0xffffffff: none); the bytes
+// of dist_out and row do not depend on it
 void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
-                     double threshold, int rmax, float* dist_out, double* row, void* work, hipStream_t s);
+                     double threshold, int rmax, float* dist_out, uint32_t* index_out_or_null, double* row, void* work, hipStream_t s);
 size_t mesh_sample_work_bytes(uint64_t m);
 void launch_mesh_sample_plan(const MeshSample& ms, void* work, uint64_t* counters, hipStream_t s);
-void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint64_t cap, uint64_t* counters, hipStream_t s);
-// the same two with what the normal scores need: the original reference row of the nearest record (index_out, 0xffffffff: none), and the
-// triangle of every sample (tri_out); the bytes of dist_out, row and rows are those of the calls above
-void launch_nn_query_index(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
-                           double threshold, int rmax, float* dist_out, uint32_t* index_out, double* row, void* work, hipStream_t s);
-void launch_mesh_sample_emit_tri(const MeshSample& ms, const void* work, void* rows, uint32_t* tri_out, uint64_t cap, uint64_t* counters, hipStream_t s);
+// tri_out_or_null: the triangle of every sample (the normal scores'); the bytes of rows do not depend on it
+void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint32_t* tri_out_or_null, uint64_t cap, uint64_t* counters, hipStream_t s);
 // normal consistency of one direction: per query its triangle tri_q[i] of mesh q, its nearest reference row index[i] (0xffffffff: none) and
 // that row's triangle tri_r[index[i]] of mesh r -> dot_out[i] and one row of eight figures; density and seed of the meshes are unused;
 // work = the buffer of normal_consistency_work_bytes(n_q); n_q, n_r <= 2^30 and the meshes as the entry point has checked them
@@ -200,10 +197,8 @@ void launch_mesh_vertex_normals(const MeshSample& ms, float* normals, void* work
 // visibility culling (cull.hip): one view marks the rows (16 bytes each) it sees in seen (uint32 per row, += 1), select keeps the rows with
 // seen >= min_views in order; depth NULL = frustum only; work = the buffer of cull_work_bytes(n); n <= 2^30, near / far / eps >= 0 and
 // finite, H W <= 2^28, as the entry points have checked
-struct CullView {
-  int H, W;
-  double fx, fy, cx, cy;
-  const float* pose; const float* depth;
+struct CullView : PinholeView {
+  const float* depth;
   float depth_max;
   double z_near, z_far, eps;
 };
@@ -225,12 +220,7 @@ void launch_mesh_clean_emit(uint64_t V, uint64_t T, const void* rows, const int*
 // winning triangle [H,W] int32 (tri NULL: not written) from one posed camera, through per-tile lists of at most max_pairs (tile, triangle)
 // pairs in work = the buffer of mesh_depth_work_bytes; and one row [8] of the comparison of two depth images, work = the buffer of
 // depth_compare_work_bytes; V, T <= 2^30, max_pairs <= 2^31, H W <= 2^28, near / far >= 0 and finite, as the entry points have checked
-struct MeshDepthView {
-  int H, W;
-  double fx, fy, cx, cy;
-  const float* pose;
-  double z_near, z_far;
-};
+struct MeshDepthView : PinholeView { double z_near, z_far; };
 size_t mesh_depth_work_bytes(uint64_t V, uint64_t T, int H, int W, uint64_t max_pairs);
 void launch_mesh_depth_render(const MeshDepthView& v, uint64_t V, const void* vrows, uint64_t T, const int* tris, uint64_t max_pairs, float* depth, int* tri,
                               void* work, uint64_t* counters, hipStream_t s);

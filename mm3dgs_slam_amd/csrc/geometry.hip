@@ -25,10 +25,11 @@
 // Normals (mm3dgs_nn_query_index / mm3dgs_mesh_sample_emit_tri / mm3dgs_normal_consistency / mm3dgs_mesh_vertex_normals; host statement:
 //   geometry.nn_index_host / normal_row / vertex_normals_host): ng_query_kernel<true> also keeps the original row of the nearest record,
 //   ms_emit_kernel<true> the triangle of every sample (the <false> instantiations are the calls above, byte for byte); ms_cross / ms_face
-//   state the face cross product once; nc_dot_kernel / nc_finish_kernel and the four vn_* kernels are described where they stand.
+//   state the face cross product once; nc_dot_kernel and the four vn_* kernels are described where they stand.
 #include <math.h>
 #include "block_ops.h"
 #include "fused_api.h"
+#include "view_pixel.h"      // view_finite
 
 #define GB 256
 #define NN_NO_CELL 0xffffffffu
@@ -49,8 +50,6 @@ static NgWork ng_work(void* base, size_t n_ref, size_t nc, size_t* bytes = nullp
   return w;
 }
 size_t nn_grid_work_bytes(uint64_t n_ref, int gx, int gy, int gz) { size_t b; ng_work(nullptr, (size_t)n_ref, (size_t)gx * (size_t)gy * (size_t)gz, &b); return b; }
-
-__device__ __forceinline__ bool ng_finite(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }
 
 // the cell coordinates of a finite position, relative to the grid's origin cell, as doubles (they may lie outside the grid, or beyond an int)
 __device__ __forceinline__ void ng_cell(const NnGrid& g, float x, float y, float z, double (&c)[3]) {
@@ -75,7 +74,7 @@ ng_count_kernel(NnGrid g, const uint4* __restrict__ rows, uint32_t n, uint32_t* 
     const uint4 r = rows[i];
     const float x = __uint_as_float(r.x), y = __uint_as_float(r.y), z = __uint_as_float(r.z);
     uint32_t cell = NN_NO_CELL;
-    if (!ng_finite(x, y, z)) {
+    if (!view_finite(x, y, z)) {
       bad = true;
     } else {
       double c[3];
@@ -224,7 +223,7 @@ ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const u
     const float x = __uint_as_float(r.x), y = __uint_as_float(r.y), z = __uint_as_float(r.z);
     float out;
     uint32_t nearest = NN_NO_CELL;      // (INDEX) 0xffffffff: none
-    if (!ng_finite(x, y, z)) {
+    if (!view_finite(x, y, z)) {
       skipped = true;
       out = __uint_as_float(0x7fc00000u);
     } else {
@@ -279,52 +278,66 @@ ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const u
   }
 }
 
-// one workgroup: lane t adds the partial rows t, t + 256, ... in index order, then the lanes are added in index order
+// the eight figures of one direction from the finished sums: distances, and normal consistency
+__device__ __forceinline__ void ng_figures(const double* t, double* row) {
+  const double sum = t[0], sq = t[1], mx = t[2], n = t[3], within = t[4], clamped = t[5], skipped = t[6];
+  row[0] = n;
+  row[1] = n > 0.0 ? sum / n : 0.0;
+  row[2] = n > 0.0 ? sqrt(sq / n) : 0.0;
+  row[3] = mx;
+  row[4] = n > 0.0 ? within / n : 0.0;
+  row[5] = clamped;
+  row[6] = skipped;
+  row[7] = 0.0;
+}
+__device__ __forceinline__ void nc_figures(const double* t, double* row) {
+  const double sabs = t[0], sum = t[1], mn = t[2], n = t[3], none = t[5], bad = t[6];
+  row[0] = n;
+  row[1] = n > 0.0 ? sabs / n : 0.0;
+  row[2] = n > 0.0 ? sum / n : 0.0;
+  row[3] = n > 0.0 ? mn : 0.0;
+  row[4] = 0.0;
+  row[5] = none;
+  row[6] = bad;
+  row[7] = 0.0;
+}
+
+// one workgroup: lane t adds the partial rows t, t + 256, ... in index order, then the lanes are added in index order (geometry.kernel_order_sum
+// states this order).  Column 2 is a maximum from 0 and the figures ng_figures' (NORMALS false: the distances), or a minimum from +inf and
+// the figures nc_figures' (NORMALS true: nc_dot_kernel's rows)
+template <bool NORMALS>
 __global__ void __launch_bounds__(GB) ng_finish_kernel(const double* __restrict__ partial, int nrows, double* __restrict__ row) {
   __shared__ double sh[GB][NN_ROW];
+  const double start = NORMALS ? (double)INFINITY : 0.0;
   double a[NN_ROW];
-  for (int k = 0; k < NN_ROW; k++) a[k] = 0.0;
+  for (int k = 0; k < NN_ROW; k++) a[k] = k == 2 ? start : 0.0;
   for (int r = threadIdx.x; r < nrows; r += GB)
     for (int k = 0; k < NN_ROW; k++) {
       const double v = partial[(size_t)r * NN_ROW + k];
-      a[k] = k == 2 ? (v > a[k] ? v : a[k]) : a[k] + v;
+      a[k] = k == 2 ? ((NORMALS ? v < a[k] : v > a[k]) ? v : a[k]) : a[k] + v;
     }
   for (int k = 0; k < NN_ROW; k++) sh[threadIdx.x][k] = a[k];
   __syncthreads();
   if (threadIdx.x < NN_ROW) {
     const int k = threadIdx.x;
-    double t = 0.0;
-    for (int l = 0; l < GB; l++) t = k == 2 ? (sh[l][k] > t ? sh[l][k] : t) : t + sh[l][k];
+    double t = k == 2 ? start : 0.0;
+    for (int l = 0; l < GB; l++) t = k == 2 ? ((NORMALS ? sh[l][k] < t : sh[l][k] > t) ? sh[l][k] : t) : t + sh[l][k];
     sh[0][k] = t;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double sum = sh[0][0], sq = sh[0][1], mx = sh[0][2], n = sh[0][3], within = sh[0][4], clamped = sh[0][5], skipped = sh[0][6];
-    row[0] = n;
-    row[1] = n > 0.0 ? sum / n : 0.0;
-    row[2] = n > 0.0 ? sqrt(sq / n) : 0.0;
-    row[3] = mx;
-    row[4] = n > 0.0 ? within / n : 0.0;
-    row[5] = clamped;
-    row[6] = skipped;
-    row[7] = 0.0;
+    if (NORMALS) nc_figures(sh[0], row);
+    else ng_figures(sh[0], row);
   }
 }
 
+// index_out_or_null selects ng_query_kernel<true>: the kernel is the same, byte for byte of dist_out and row
 void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
-                     double threshold, int rmax, float* dist_out, double* row, void* work, hipStream_t s) {
+                     double threshold, int rmax, float* dist_out, uint32_t* index_out_or_null, double* row, void* work, hipStream_t s) {
   const unsigned nb = (unsigned)ng_nb((size_t)n_q);
-  hipLaunchKernelGGL(ng_query_kernel<false>, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q, (const uint32_t*)cell_start, (const uint4*)sorted,
-                     (uint32_t)n_ref, max_dist, (float)threshold, rmax, dist_out, (uint32_t*)nullptr, (double*)work);
-  hipLaunchKernelGGL(ng_finish_kernel, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
-}
-
-void launch_nn_query_index(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
-                           double threshold, int rmax, float* dist_out, uint32_t* index_out, double* row, void* work, hipStream_t s) {
-  const unsigned nb = (unsigned)ng_nb((size_t)n_q);
-  hipLaunchKernelGGL(ng_query_kernel<true>, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q, (const uint32_t*)cell_start, (const uint4*)sorted,
-                     (uint32_t)n_ref, max_dist, (float)threshold, rmax, dist_out, index_out, (double*)work);
-  hipLaunchKernelGGL(ng_finish_kernel, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
+  hipLaunchKernelGGL(index_out_or_null ? ng_query_kernel<true> : ng_query_kernel<false>, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q,
+                     (const uint32_t*)cell_start, (const uint4*)sorted, (uint32_t)n_ref, max_dist, (float)threshold, rmax, dist_out, index_out_or_null, (double*)work);
+  hipLaunchKernelGGL(ng_finish_kernel<false>, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
 }
 
 // ---- surface sampler --------------------------------------------------------------------------------------------------------------
@@ -360,7 +373,7 @@ __device__ __forceinline__ bool ms_load(const MeshSample& ms, uint32_t t, MsTri&
   const float af[3] = {__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z)};
   const float bf[3] = {__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)};
   const float cf[3] = {__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)};
-  if (!ng_finite(af[0], af[1], af[2]) || !ng_finite(bf[0], bf[1], bf[2]) || !ng_finite(cf[0], cf[1], cf[2])) return false;
+  if (!view_finite(af[0], af[1], af[2]) || !view_finite(bf[0], bf[1], bf[2]) || !view_finite(cf[0], cf[1], cf[2])) return false;
   for (int k = 0; k < 3; k++) {
     T.a[k] = (double)af[k];
     T.e1[k] = (double)bf[k] - (double)af[k];
@@ -491,26 +504,19 @@ ms_emit_kernel(MeshSample ms, const uint32_t* __restrict__ prefix, const unsigne
   if (TRI) tri_out[i] = t;
 }
 
-void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint64_t cap, uint64_t* counters, hipStream_t s) {
+// tri_out_or_null selects ms_emit_kernel<true>
+void launch_mesh_sample_emit(const MeshSample& ms, const void* work, void* rows, uint32_t* tri_out_or_null, uint64_t cap, uint64_t* counters, hipStream_t s) {
   const MsWork w = ms_work((void*)work, (size_t)ms.m);
   size_t nb = ng_nb((size_t)cap);
   nb = nb < 1 ? 1 : nb;
-  hipLaunchKernelGGL(ms_emit_kernel<false>, dim3((unsigned)nb), dim3(GB), 0, s, ms, w.prefix, w.hdr, (unsigned long long)cap, (uint4*)rows, (uint32_t*)nullptr,
-                     (unsigned long long*)counters);
-}
-
-void launch_mesh_sample_emit_tri(const MeshSample& ms, const void* work, void* rows, uint32_t* tri_out, uint64_t cap, uint64_t* counters, hipStream_t s) {
-  const MsWork w = ms_work((void*)work, (size_t)ms.m);
-  size_t nb = ng_nb((size_t)cap);
-  nb = nb < 1 ? 1 : nb;
-  hipLaunchKernelGGL(ms_emit_kernel<true>, dim3((unsigned)nb), dim3(GB), 0, s, ms, w.prefix, w.hdr, (unsigned long long)cap, (uint4*)rows, tri_out,
-                     (unsigned long long*)counters);
+  hipLaunchKernelGGL(tri_out_or_null ? ms_emit_kernel<true> : ms_emit_kernel<false>, dim3((unsigned)nb), dim3(GB), 0, s, ms, w.prefix, w.hdr, (unsigned long long)cap,
+                     (uint4*)rows, tri_out_or_null, (unsigned long long*)counters);
 }
 
 // ---- normal consistency ---------------------------------------------------------------------------------------------------------------
 // nc_dot_kernel, one lane per query: the faces of its own triangle and of its nearest row's triangle, their normalised dot product clamped
 // to [-1, 1] and rounded once at the store; per workgroup one partial row {sum |dot|, sum dot, min |dot|, n, -, no neighbour, bad triangle, -}
-// over the stored values, in ng_query_kernel's order; nc_finish_kernel adds the partial rows as ng_finish_kernel does.
+// over the stored values, in ng_query_kernel's order; ng_finish_kernel<true> adds the partial rows.
 size_t normal_consistency_work_bytes(uint64_t n_q) { return nn_query_work_bytes(n_q); }
 
 __global__ void __launch_bounds__(GB)
@@ -563,43 +569,11 @@ nc_dot_kernel(uint32_t n_q, const uint32_t* __restrict__ tri_q, const uint32_t* 
   }
 }
 
-// one workgroup, ng_finish_kernel's order: lane t adds the partial rows t, t + 256, ..., then the lanes are added in index order (column 2: a minimum)
-__global__ void __launch_bounds__(GB) nc_finish_kernel(const double* __restrict__ partial, int nrows, double* __restrict__ row) {
-  __shared__ double sh[GB][NN_ROW];
-  double a[NN_ROW];
-  for (int k = 0; k < NN_ROW; k++) a[k] = k == 2 ? (double)INFINITY : 0.0;
-  for (int r = threadIdx.x; r < nrows; r += GB)
-    for (int k = 0; k < NN_ROW; k++) {
-      const double v = partial[(size_t)r * NN_ROW + k];
-      a[k] = k == 2 ? (v < a[k] ? v : a[k]) : a[k] + v;
-    }
-  for (int k = 0; k < NN_ROW; k++) sh[threadIdx.x][k] = a[k];
-  __syncthreads();
-  if (threadIdx.x < NN_ROW) {
-    const int k = threadIdx.x;
-    double t = k == 2 ? (double)INFINITY : 0.0;
-    for (int l = 0; l < GB; l++) t = k == 2 ? (sh[l][k] < t ? sh[l][k] : t) : t + sh[l][k];
-    sh[0][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double sabs = sh[0][0], sum = sh[0][1], mn = sh[0][2], n = sh[0][3], none = sh[0][5], bad = sh[0][6];
-    row[0] = n;
-    row[1] = n > 0.0 ? sabs / n : 0.0;
-    row[2] = n > 0.0 ? sum / n : 0.0;
-    row[3] = n > 0.0 ? mn : 0.0;
-    row[4] = 0.0;
-    row[5] = none;
-    row[6] = bad;
-    row[7] = 0.0;
-  }
-}
-
 void launch_normal_consistency(uint64_t n_q, const uint32_t* tri_q, const uint32_t* index, uint64_t n_r, const uint32_t* tri_r, const MeshSample& mq,
                                const MeshSample& mr, float* dot_out, double* row, void* work, hipStream_t s) {
   const unsigned nb = (unsigned)ng_nb((size_t)n_q);
   hipLaunchKernelGGL(nc_dot_kernel, dim3(nb), dim3(GB), 0, s, (uint32_t)n_q, tri_q, index, (uint32_t)n_r, tri_r, mq, mr, dot_out, (double*)work);
-  hipLaunchKernelGGL(nc_finish_kernel, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
+  hipLaunchKernelGGL(ng_finish_kernel<true>, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
 }
 
 // ---- vertex normals -------------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,7 @@
 // pixel E_i = n_i . (dx, dy, 1), S = E0 + E1 + E2, inside when the three E_i share S's sign, z = det / S -- no clipping at the camera plane.
 //
 // One view is five launches on the caller's stream:
-//   md_vertex_kernel    one lane per vertex: p_c (3 doubles) to the work buffer; the same lanes zero the tile counts and cursors.
+//   md_vertex_kernel    one lane per vertex: p_c (3 doubles, view_to_camera) to the work buffer; the same lanes zero the tile counts, cursors.
 //   md_setup_kernel     one lane per triangle: invalid / behind / drawn (block_flag_counts, one add per workgroup and class), the setup
 //                       record (n0, n1, n2, det: 80 B) and the pixel rectangle -- floor(min) - 1 .. ceil(max) + 1 of the projections when
 //                       all three corners lie in front and project finitely, else the whole image: only ever a superset of the hits --,
@@ -61,16 +61,16 @@ __global__ void __launch_bounds__(MB)
 md_vertex_kernel(MeshDepthView v, const uint4* __restrict__ vrows, uint32_t V, double* __restrict__ pc, uint32_t ntiles, uint32_t* __restrict__ counts,
                  uint32_t* __restrict__ cursor) {
 #pragma clang fp contract(off)
-  __shared__ Rigid g;      // the pose is the same for every vertex: one lane normalises the quaternion for its workgroup
-  if (threadIdx.x == 0) g = rigid_from_pose(v.pose);
-  __syncthreads();
+  __shared__ Rigid g;
+  view_rigid_shared(v.pose, g);
   const size_t i = (size_t)blockIdx.x * MB + threadIdx.x;
   if (i <= ntiles) counts[i] = 0u;
   if (i < ntiles) cursor[i] = 0u;
   if (i >= V) return;
   const uint4 r = vrows[i];      // one 16-byte load
-  const double x = (double)__uint_as_float(r.x), y = (double)__uint_as_float(r.y), z = (double)__uint_as_float(r.z);
-  for (int k = 0; k < 3; k++) pc[3 * i + k] = g.R[k][0] * x + g.R[k][1] * y + g.R[k][2] * z + g.t[k];
+  double c[3];
+  view_to_camera(g, (double)__uint_as_float(r.x), (double)__uint_as_float(r.y), (double)__uint_as_float(r.z), c[0], c[1], c[2]);
+  for (int k = 0; k < 3; k++) pc[3 * i + k] = c[k];
 }
 
 __device__ __forceinline__ void md_cross(const double* u, const double* w, double* o) {
@@ -143,7 +143,7 @@ md_setup_kernel(MeshDepthView v, const double* __restrict__ pc, uint32_t V, cons
       for (int k = 0; k < 3; k++) { o[k] = n0[k]; o[3 + k] = n1[k]; o[6 + k] = n2[k]; }
       o[9] = det;
       int x0 = 0, y0 = 0, x1 = v.W - 1, y1 = v.H - 1;      // the whole image unless all three corners project
-      if (a[2] > 0.0 && b[2] > 0.0 && c[2] > 0.0) {
+      if (a[2] > 0.0 && b[2] > 0.0 && c[2] > 0.0) {      // the unrounded projection bounds a rectangle: not view_pixel_index's nearest pixel (no + 0.5, no floor)
         const double pxa = v.fx * a[0] / a[2] + v.cx, pxb = v.fx * b[0] / b[2] + v.cx, pxc = v.fx * c[0] / c[2] + v.cx;
         const double pya = v.fy * a[1] / a[2] + v.cy, pyb = v.fy * b[1] / b[2] + v.cy, pyc = v.fy * c[1] / c[2] + v.cy;
         if (md_finite(pxa) && md_finite(pxb) && md_finite(pxc) && md_finite(pya) && md_finite(pyb) && md_finite(pyc)) {

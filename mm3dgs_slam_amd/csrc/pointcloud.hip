@@ -19,7 +19,7 @@
 #include <math.h>
 #include "block_ops.h"
 #include "fused_api.h"
-#include "view_pixel.h"      // Rigid / rigid_from_pose, view_pixel_valid, pc_quant (shared with tsdf.hip)
+#include "view_pixel.h"      // Rigid / rigid_from_pose, view_lift, view_pixel_valid, pc_quant
 
 #define PB 256
 #define PC_MAX_PROBE 128                 // slots a point may inspect; the table is sized for a load of at most 1/2
@@ -42,18 +42,11 @@ size_t pointcloud_work_bytes(int H, int W) { size_t b; pc_work(nullptr, (size_t)
 
 struct PcPoint { float x, y, z; };
 
-// the world point of pixel i at depth z: p_c = ((u - cx) / fx z, (v - cy) / fy z, z), p_w = R^T (p_c - t); no half-pixel offset
+// the world point of pixel i at depth z (view_lift), rounded once to float32
 __device__ __forceinline__ PcPoint pc_backproject(const PointCloudView& v, const Rigid& g, int i, float zf) {
-#pragma clang fp contract(off)
-  const double z = (double)zf;
-  const double c0 = ((double)(i % v.W) - v.cx) / v.fx * z - g.t[0];
-  const double c1 = ((double)(i / v.W) - v.cy) / v.fy * z - g.t[1];
-  const double c2 = z - g.t[2];
-  PcPoint p;
-  p.x = (float)(g.R[0][0] * c0 + g.R[1][0] * c1 + g.R[2][0] * c2);
-  p.y = (float)(g.R[0][1] * c0 + g.R[1][1] * c1 + g.R[2][1] * c2);
-  p.z = (float)(g.R[0][2] * c0 + g.R[1][2] * c1 + g.R[2][2] * c2);
-  return p;
+  double P[3];
+  view_lift(v, g, (double)(i % v.W), (double)(i / v.W), (double)zf, P);
+  return {(float)P[0], (float)P[1], (float)P[2]};
 }
 
 // the pixel test of view_pixel.h on this view's images

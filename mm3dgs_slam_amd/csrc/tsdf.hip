@@ -32,14 +32,13 @@ __global__ void __launch_bounds__(TB)
 tsdf_integrate_kernel(TsdfView v, float2* __restrict__ tsdf_w, float4* __restrict__ rgb_w, unsigned long long* __restrict__ counters, unsigned xb,
                       unsigned yb) {
 #pragma clang fp contract(off)
-  __shared__ Rigid g;      // the pose is the same for every sample: one lane normalises the quaternion for its workgroup
+  __shared__ Rigid g;
   __shared__ uint32_t wsum[2][TB / 64];
   const unsigned b = blockIdx.x;
   const int i = (int)(b % xb) * 64 + (int)(threadIdx.x & 63);
   const int j = (int)((b / xb) % yb) * 4 + (int)(threadIdx.x >> 6);
   const int k0 = (int)(b / (xb * yb)) * TZ;
-  if (threadIdx.x == 0) g = rigid_from_pose(v.pose);
-  __syncthreads();
+  view_rigid_shared(v.pose, g);
   uint32_t nupd = 0, ncup = 0;
   if (i < v.nx && j < v.ny) {
     const size_t hw = (size_t)v.H * (size_t)v.W;

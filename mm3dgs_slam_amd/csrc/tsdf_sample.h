@@ -8,18 +8,16 @@
 
 // ---- one sample, one view ----------------------------------------------------------------------------------------------------------
 // The sample at the world point (pw0, pw1, pw2) with its two volume words at tw / rw.  In double from the float32 inputs, no contraction
-// (the host statement rounds alike); z <= 0, a pixel outside the image or one that fails the point cloud's validity test, or sdf < -trunc
-// end the sample before anything is loaded from the volume.  Running means, rounded to float32 once at the 8- and 16-byte stores.
+// (the host statement rounds alike), the projection through view_pixel.h's statements (culling's too); z <= 0, a pixel outside the image or
+// one that fails the point cloud's validity test, or sdf < -trunc end the sample before anything is loaded from the volume.  Running means,
+// rounded to float32 once at the 8- and 16-byte stores.
 __device__ __forceinline__ void tsdf_sample_update(const TsdfView& v, const Rigid& g, size_t hw, double pw0, double pw1, double pw2, float2* __restrict__ tw,
                                                    float4* __restrict__ rw, uint32_t& nupd, uint32_t& ncup) {
 #pragma clang fp contract(off)
-  const double z = g.R[2][0] * pw0 + g.R[2][1] * pw1 + g.R[2][2] * pw2 + g.t[2];
-  if (!(z > 0.0)) return;
-  const double x = g.R[0][0] * pw0 + g.R[0][1] * pw1 + g.R[0][2] * pw2 + g.t[0];
-  const double y = g.R[1][0] * pw0 + g.R[1][1] * pw1 + g.R[1][2] * pw2 + g.t[1];
-  const double fu = floor(v.fx * x / z + v.cx + 0.5), fv = floor(v.fy * y / z + v.cy + 0.5);
-  if (!(fu >= 0.0 && fu < (double)v.W && fv >= 0.0 && fv < (double)v.H)) return;      // (a NaN fails)
-  const size_t pix = (size_t)(int)fv * (size_t)v.W + (size_t)(int)fu;
+  double x, y, z;
+  size_t pix;
+  view_to_camera(g, pw0, pw1, pw2, x, y, z);      // (x and y are needed only behind the test of z)
+  if (!(z > 0.0) || !view_pixel_index(v, x, y, z, pix)) return;
   float d;
   if (!view_pixel_valid(v.depth, v.sil, v.sil_min, v.depth_max, pix, d)) return;
   const double sdf = (double)d - z;

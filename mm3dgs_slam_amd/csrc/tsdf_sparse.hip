@@ -4,7 +4,7 @@
 // blocks in z-major raster order; all ones = empty.  The export reserves all its views, freezes the block set (list, sort, index), then
 // integrates all views; a sample outside the frozen set is never touched.
 //
-//   blk_reserve_kernel     one launch per view, one lane per pixel.  A valid pixel (view_pixel.h) is lifted to its world point P in double;
+//   blk_reserve_kernel     one launch per view, one lane per pixel.  A valid pixel is lifted to its world point P (view_lift);
 //                          with ax = (|u - cx| trunc + (d + trunc) / 2) / |fx|, ay likewise and R = sqrt(ax^2 + ay^2 + trunc^2) every sample
 //                          the integration can update through this pixel with |sdf| <= trunc lies within R of P (|z - d| <= trunc, the
 //                          nearest-pixel projection at most half a pixel off, the ray's slope).  Per axis the blocks from
@@ -106,24 +106,21 @@ blk_reserve_kernel(TsdfView v, TsdfBlockClip clip, BlkTable t, unsigned long lon
   __shared__ uint32_t wsum[4][SB / 64];
   const int n = v.H * v.W;
   const int i = blockIdx.x * SB + threadIdx.x;
-  if (threadIdx.x == 0) g = rigid_from_pose(v.pose);
-  __syncthreads();
+  view_rigid_shared(v.pose, g);
   uint32_t valid = 0, pairs = 0, dropped = 0, oor = 0;
   float df;
   if (i < n && view_pixel_valid(v.depth, v.sil, v.sil_min, v.depth_max, (size_t)i, df)) {
     valid = 1;
     const double z = (double)df, u = (double)(i % v.W), w = (double)(i / v.W);
-    const double c0 = (u - v.cx) / v.fx * z - g.t[0];
-    const double c1 = (w - v.cy) / v.fy * z - g.t[1];
-    const double c2 = z - g.t[2];
+    double P[3];
+    view_lift(v, g, u, w, z, P);
     const double ax = (fabs(u - v.cx) * v.trunc + 0.5 * (z + v.trunc)) / fabs(v.fx);
     const double ay = (fabs(w - v.cy) * v.trunc + 0.5 * (z + v.trunc)) / fabs(v.fy);
     const double R = sqrt(ax * ax + ay * ay + v.trunc * v.trunc);
     int lo[3], hi[3];
     bool in = true;
     for (int a = 0; a < 3; a++) {
-      const double P = g.R[0][a] * c0 + g.R[1][a] * c1 + g.R[2][a] * c2;
-      const double bl = floor(floor((P - R - v.o[a]) / v.voxel) / 8.0), bh = floor(ceil((P + R - v.o[a]) / v.voxel) / 8.0);
+      const double bl = floor(floor((P[a] - R - v.o[a]) / v.voxel) / 8.0), bh = floor(ceil((P[a] + R - v.o[a]) / v.voxel) / 8.0);
       if (!(fabs(bl) < (double)BLK_BIAS && fabs(bh) < (double)BLK_BIAS && bh - bl < (double)BLK_MAX_BOX)) { in = false; break; }      // (a NaN fails)
       lo[a] = (int)bl;
       hi[a] = (int)bh;
@@ -274,18 +271,17 @@ blk_integrate_kernel(TsdfView v, const unsigned long long* __restrict__ keys, fl
   __shared__ Rigid g;
   __shared__ uint32_t wsum[2][SB / 64];
   const unsigned r = blockIdx.x;
-  if (threadIdx.x == 0) g = rigid_from_pose(v.pose);
-  __syncthreads();
+  view_rigid_shared(v.pose, g);
   if (threadIdx.x == 0 && r == 0) atomicAdd(counters, 1ull);
   int b[3];
   blk_coords(keys[r], b[0], b[1], b[2]);
   // the block's bounding sphere in the camera frame: the same for every lane, so the whole workgroup leaves or stays
   const double rad = v.voxel * 3.5 * 1.7320508075688773 * (1.0 + 1e-6);
   const double m0 = v.o[0] + v.voxel * ((double)(8 * b[0]) + 3.5), m1 = v.o[1] + v.voxel * ((double)(8 * b[1]) + 3.5), m2 = v.o[2] + v.voxel * ((double)(8 * b[2]) + 3.5);
-  const double zc = g.R[2][0] * m0 + g.R[2][1] * m1 + g.R[2][2] * m2 + g.t[2];
+  double xc, yc, zc;
+  view_to_camera(g, m0, m1, m2, xc, yc, zc);
   if (zc + rad <= 0.0) return;      // every sample has z <= 0
-  if (zc - rad > 0.0 && v.fx > 0.0 && v.fy > 0.0) {
-    const double xc = g.R[0][0] * m0 + g.R[0][1] * m1 + g.R[0][2] * m2 + g.t[0], yc = g.R[1][0] * m0 + g.R[1][1] * m1 + g.R[1][2] * m2 + g.t[1];
+  if (zc - rad > 0.0 && v.fx > 0.0 && v.fy > 0.0) {      // (a bound on the sphere's pixels with slack, not view_pixel_index's nearest pixel)
     const double zn = zc - rad, zf = zc + rad;
     // x / z over the sphere lies in [(xc - rad) / (its sign < 0 ? zn : zf), (xc + rad) / (its sign > 0 ? zn : zf)]
     const double uhi = v.fx * ((xc + rad) / (xc + rad >= 0.0 ? zn : zf)) + v.cx + 0.5, ulo = v.fx * ((xc - rad) / (xc - rad <= 0.0 ? zn : zf)) + v.cx + 0.5;

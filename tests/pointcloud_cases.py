@@ -14,6 +14,27 @@ def camera(H, W):
     return {"fx": f + 0.37, "fy": f - 0.21, "cx": 0.5 * W - 0.85, "cy": 0.5 * H + 0.4}
 
 
+def view_faults(pose_ptr):
+    """The faults of the posed pinhole view itself -- H, W, fx, fy, cx, cy, pose -- as overrides of a driver's arguments: the one list every
+    call that takes a view must reject (pointcloud_add_view, the three tsdf calls, cull_mark_view, mesh_depth_render).  pose_ptr: the
+    device address of the good pose."""
+    nan, inf = float("nan"), float("inf")
+    return {"H = 0": dict(H=0), "W < 0": dict(W=-3), "more than 2^28 pixels": dict(H=1 << 14, W=(1 << 14) + 1), "fx NaN": dict(fx=nan), "fx = 0": dict(fx=0.0),
+            "fy = 0": dict(fy=0.0), "fy inf": dict(fy=inf), "cx NaN": dict(cx=nan), "cy inf": dict(cy=inf), "NULL pose": dict(pose=None),
+            "misaligned pose": dict(pose=pose_ptr + 2)}
+
+
+def view_fault_texts(who, H, W, pose_ptr, misaligned):
+    """(overrides, mm3dgs_last_error() text) of five single faults of a view for the call named `who`: both size faults, both intrinsics
+    faults and the misaligned pose, whose text (`misaligned`) names the call's other pointers.  The texts are the ones api.hip had before its
+    view checks were stated once: they are part of the C ABI's behaviour."""
+    return [(dict(H=0, W=W), f"{who}: H = 0, W = {W} (both must be positive)"),
+            (dict(H=1 << 14, W=(1 << 14) + 1), f"{who}: 16384 x 16385 has more than 2^28 pixels"),
+            (dict(fx=0.0, fy=2.5), f"{who}: fx = 0, fy = 2.5 (finite, not 0)"),
+            (dict(cx=1.5, cy=float("inf")), f"{who}: cx = 1.5, cy = inf (must be finite)"),
+            (dict(pose=pose_ptr + 2), f"{who}: {misaligned}")]
+
+
 def pose(k=0, shift=(0.0, 0.0, 0.0)):
     """A world->camera pose with a non-unit quaternion (the kernel normalises) whose world points all have positive coordinates for depths
     below ~4 m (t = -5 on every axis puts the camera centre near (+5, +5, +5) R)."""

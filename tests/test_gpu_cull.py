@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from mm3dgs_slam_amd import cull as cl, geometry as geo, pointcloud as pc
-from tests import cull_cases as cases
+from tests import cull_cases as cases, pointcloud_cases as pcases
 from tests.test_gpu_geometry import _dev, _guarded, _guards_ok, _lib, _ptr, _stream
 
 pytestmark = pytest.mark.gpu
@@ -162,10 +162,10 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
     c = Cull(scene).run()
     before = c.snapshot()
     nan, inf = float("nan"), float("inf")
-    bad_mark = {"NULL rows": dict(rows=None), "NULL seen": dict(seen=None), "NULL pose": dict(pose=None), "NULL counters": dict(counters=None), "H = 0": dict(H=0),
-                "H < 0": dict(H=-12), "W = 0": dict(W=0), "more than 2^28 pixels": dict(H=1 << 15, W=1 << 14), "near < 0": dict(near=-0.25), "near NaN": dict(near=nan),
-                "far < 0": dict(far=-1.0), "far inf": dict(far=inf), "eps < 0": dict(eps=-0.01), "eps NaN": dict(eps=nan), "fx NaN": dict(fx=nan), "fy = 0": dict(fy=0.0),
-                "cx NaN": dict(cx=nan), "cy inf": dict(cy=inf), "depth_max NaN": dict(depth_max=nan), "n > 2^30": dict(n=(1 << 30) + 1),
+    bad_mark = {**pcases.view_faults(c.views[0][1].data_ptr()), "NULL rows": dict(rows=None), "NULL seen": dict(seen=None), "NULL counters": dict(counters=None),
+                "H < 0": dict(H=-12), "W = 0": dict(W=0), "2^29 pixels": dict(H=1 << 15, W=1 << 14), "near < 0": dict(near=-0.25), "near NaN": dict(near=nan),
+                "far < 0": dict(far=-1.0), "far inf": dict(far=inf), "eps < 0": dict(eps=-0.01), "eps NaN": dict(eps=nan),
+                "depth_max NaN": dict(depth_max=nan), "n > 2^30": dict(n=(1 << 30) + 1),
                 "misaligned rows": dict(rows=c.rows.data_ptr() + 8), "misaligned seen": dict(seen=c.seen.data_ptr() + 2),
                 "misaligned counters": dict(counters=c.counters.data_ptr() + 4), "misaligned depth": dict(depth=c.views[0][0].data_ptr() + 2)}
     for what, over in bad_mark.items():
@@ -184,6 +184,13 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
     for k, a in before.items():
         assert now[k].tobytes() == a.tobytes(), k
     assert int(lib.mm3dgs_cull_work_bytes((1 << 30) + 1)) == 0
+
+
+def test_view_fault_texts():
+    scene = cases.random_scene(257, n_views=1, seed=8)
+    c = Cull(scene)
+    for over, text in pcases.view_fault_texts("cull_mark_view", scene["H"], scene["W"], c.views[0][1].data_ptr(), "seen, the depth image and the pose must be 4-byte aligned"):
+        assert c.mark(**over) == -1 and _lib().mm3dgs_last_error().decode() == text, over
 
 
 def test_compare_device_equals_compare_host_with_culling():

@@ -335,6 +335,33 @@ def test_rejected_calls_return_minus_one_and_write_nothing(nn_cases):
     assert nn.build() == 0 and nn.query() == 0 and s.plan() == 0 and s.emit() == 0
 
 
+def pair_fault_texts(who, index=False, tri=False):
+    """(overrides, mm3dgs_last_error() text) of single faults of mm3dgs_nn_query / _index (`who` names the call, index: the longer pointer
+    lists) or of mm3dgs_mesh_sample_emit / _tri, for the drivers here and in tests/test_gpu_normals.py.  The texts are the ones api.hip had
+    while each member of a pair had a body of its own: they are part of the C ABI's behaviour."""
+    if who.startswith("nn_query"):
+        return [(dict(n_q=0), f"{who}: n_q = 0 (1 .. 2^30)"), (dict(max_dist=0.0), f"{who}: max_dist = 0 (must be finite and positive)"),
+                (dict(gx=512, gy=512, gz=257), f"{who}: grid 512 x 512 x 257 (every size at least 1, at most 2^26 cells)"),
+                (dict(dist=None), f"{who}: NULL argument (q_rows, cell_start, sorted, dist_out, {'index_out, ' if index else ''}row and work are required)"),
+                ("misaligned dist", f"{who}: cell_start{', dist_out and index_out' if index else ' and dist_out'} must be 4-byte aligned")]
+    return [(dict(cap=(1 << 31) + 1), f"{who}: cap = 2147483649 (at most 2^31)"), (dict(density=0.0), f"{who}: density = 0 (must be finite and positive)"),
+            (dict(m=0), f"{who}: m = 0 triangles (1 .. 2^30)"), (dict(rows=None), f"{who}: rows {'or tri_out ' if tri else ''}is NULL with a cap above 0"),
+            ("misaligned rows", f"{who}: rows must be 16-byte aligned")]
+
+
+def test_pair_fault_texts(nn_cases):
+    nn = NN(nn_cases["one reference per cell of 5 x 4 x 3"])
+    assert nn.build() == 0
+    for over, text in pair_fault_texts("nn_query"):
+        over = dict(dist=nn.dist.data_ptr() + 2) if over == "misaligned dist" else over
+        assert nn.query(**over) == -1 and _lib().mm3dgs_last_error().decode() == text, over
+    s = Sampler(*cases.random_mesh(257, seed=1), 150.0, 11, 4096)
+    assert s.plan() == 0
+    for over, text in pair_fault_texts("mesh_sample_emit"):
+        over = dict(rows=s.rows.data_ptr() + 8) if over == "misaligned rows" else over
+        assert s.emit(**over) == -1 and _lib().mm3dgs_last_error().decode() == text, over
+
+
 def test_python_surface_matches_the_host_path():
     """GeometryScorer / sample_mesh_device / compare_device against compare_host: the same counts, and figures that differ by the float32
     roundings of individual stored distances only (the sets are the same bytes: the device's samples are compared against the host's)."""

@@ -278,17 +278,15 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
     nan, inf = float("nan"), float("inf")
     lib = _lib()
     bad = {
-        "H = 0": dict(H=0), "W < 0": dict(W=-3), "more than 2^28 pixels": dict(H=1 << 14, W=(1 << 14) + 1),
+        **pcases.view_faults(vd["pose"].data_ptr()),
         "nx = 1": dict(nx=1), "ny = 0": dict(ny=0), "nz < 0": dict(nz=-4), "more than 2^30 samples": dict(nx=1025, ny=1024, nz=1024), "a product that wraps": dict(nx=1 << 16, ny=1 << 16, nz=1 << 16),
-        "NULL color": dict(color=None), "NULL depth": dict(depth=None), "NULL pose": dict(pose=None), "NULL origin": dict(origin=None), "NULL tsdf_w": dict(tsdf_w=None),
+        "NULL color": dict(color=None), "NULL depth": dict(depth=None), "NULL origin": dict(origin=None), "NULL tsdf_w": dict(tsdf_w=None),
         "NULL rgb_w": dict(rgb_w=None), "NULL counters": dict(counters=None),
         "voxel = 0": dict(voxel=0.0), "voxel < 0": dict(voxel=-0.01), "voxel NaN": dict(voxel=nan), "voxel inf": dict(voxel=inf),
         "trunc = 0": dict(trunc=0.0), "trunc < 0": dict(trunc=-0.1), "trunc NaN": dict(trunc=nan), "trunc inf": dict(trunc=inf),
         "origin NaN": dict(origin=[0.0, nan, 0.0]), "origin inf": dict(origin=[inf, 0.0, 0.0]),
-        "fx = 0": dict(fx=0.0), "fy = 0": dict(fy=0.0), "fx NaN": dict(fx=nan), "fy inf": dict(fy=inf), "cx NaN": dict(cx=nan), "cy inf": dict(cy=inf),
         "misaligned tsdf_w": dict(tsdf_w=dv.tw.data_ptr() + 4), "misaligned rgb_w": dict(rgb_w=dv.rw.data_ptr() + 8), "misaligned counters": dict(counters=dv.counters.data_ptr() + 4),
         "misaligned color": dict(color=vd["color"].data_ptr() + 2), "misaligned depth": dict(depth=vd["depth"].data_ptr() + 1), "misaligned sil": dict(sil=vd["sil"].data_ptr() + 3),
-        "misaligned pose": dict(pose=vd["pose"].data_ptr() + 2),
     }
     for what, over in bad.items():
         assert dv.integrate(vd, case, **over) == -1, what
@@ -320,6 +318,14 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
         assert int(lib.mm3dgs_tsdf_mesh_work_bytes(*shape)) == 0, shape
     assert dv.integrate(vd, case) == 0 and dv.integrate(vd, case, sil=None) == 0      # the silhouette is optional
     assert m.plan() == 0 and m.emit() == 0
+
+
+def test_view_fault_texts():
+    dims, (H, W) = (17, 9, 6), (17, 33)
+    case = cases.integrate_case(dims, H, W, "all")
+    vd, vol = to_dev(case["views"][0]), Volume(dims)
+    for over, text in pcases.view_fault_texts("tsdf_integrate", H, W, vd["pose"].data_ptr(), "the images and the pose must be 4-byte aligned"):
+        assert vol.integrate(vd, case, **over) == -1 and _lib().mm3dgs_last_error().decode() == text, over
 
 
 PARENT_KEYS = ["pose_est", "pose_gt", "keyframes", "ate_rmse", "psnr_list", "ssim_list", "lpips_list"]

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from mm3dgs_slam_amd import cull as cl, export as ex, mesh_depth as md
-from tests import mesh_depth_cases as cases
+from tests import mesh_depth_cases as cases, pointcloud_cases as pcases
 from tests.test_gpu_geometry import _dev, _guarded, _guards_ok, _lib, _ptr, _stream
 
 pytestmark = pytest.mark.gpu
@@ -173,11 +173,11 @@ def test_rejected_calls_return_non_zero_and_write_nothing():
     assert r.call() == 0
     before = r.snapshot()
     nan, inf = float("nan"), float("inf")
-    bad = {"NULL rows": dict(rows=None), "NULL triangles": dict(tris=None), "NULL pose": dict(pose=None), "NULL depth": dict(depth=None), "NULL work": dict(work=None),
-           "NULL counters": dict(counters=None), "H = 0": dict(H=0), "W < 0": dict(W=-3), "more than 2^28 pixels": dict(H=1 << 15, W=1 << 14), "fx = 0": dict(fx=0.0),
+    bad = {**pcases.view_faults(r.pose.data_ptr()), "NULL rows": dict(rows=None), "NULL triangles": dict(tris=None), "NULL depth": dict(depth=None), "NULL work": dict(work=None),
+           "NULL counters": dict(counters=None), "2^29 pixels": dict(H=1 << 15, W=1 << 14),
            "fy NaN": dict(fy=nan), "cx inf": dict(cx=inf), "cy NaN": dict(cy=nan), "near < 0": dict(near=-0.5), "near NaN": dict(near=nan), "far < 0": dict(far=-1.0),
            "far inf": dict(far=inf), "V > 2^30": dict(V=(1 << 30) + 1), "T > 2^30": dict(T=(1 << 30) + 1), "max_pairs > 2^31": dict(max_pairs=(1 << 31) + 1),
-           "misaligned rows": dict(rows=r.rows.data_ptr() + 8), "misaligned triangles": dict(tris=r.tris.data_ptr() + 2), "misaligned pose": dict(pose=r.pose.data_ptr() + 2),
+           "misaligned rows": dict(rows=r.rows.data_ptr() + 8), "misaligned triangles": dict(tris=r.tris.data_ptr() + 2),
            "misaligned depth": dict(depth=r.depth + 2), "misaligned tri": dict(tri=r.tri + 1), "misaligned work": dict(work=r.work + 4),
            "misaligned counters": dict(counters=r.counters.data_ptr() + 4)}
     for what, over in bad.items():
@@ -199,6 +199,12 @@ def test_rejected_calls_return_non_zero_and_write_nothing():
     assert int(lib.mm3dgs_mesh_depth_work_bytes((1 << 30) + 1, 1, 4, 4, 1)) == 0 and int(lib.mm3dgs_mesh_depth_work_bytes(1, (1 << 30) + 1, 4, 4, 1)) == 0
     assert int(lib.mm3dgs_mesh_depth_work_bytes(1, 1, 0, 4, 1)) == 0 and int(lib.mm3dgs_mesh_depth_work_bytes(1, 1, 1 << 15, 1 << 14, 1)) == 0
     assert int(lib.mm3dgs_mesh_depth_work_bytes(1, 1, 4, 4, (1 << 31) + 1)) == 0 and int(lib.mm3dgs_depth_compare_work_bytes(0, 4)) == 0
+
+
+def test_view_fault_texts():
+    r = Render(cases.random_scene(60, seed=2))
+    for over, text in pcases.view_fault_texts("mesh_depth_render", r.H, r.W, r.pose.data_ptr(), "triangles, depth_out, tri_out and the pose must be 4-byte aligned"):
+        assert r.call(**over) == -1 and _lib().mm3dgs_last_error().decode() == text, over
 
 
 @pytest.mark.parametrize("hw", ((1, 1), (17, 33), (48, 64), (480, 640)))

@@ -623,11 +623,11 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
     nan, inf = float("nan"), float("inf")
     lib = _lib()
     big = (1 << 21) + 1
-    common = {"H = 0": dict(H=0), "W < 0": dict(W=-3), "more than 2^28 pixels": dict(H=1 << 14, W=(1 << 14) + 1), "NULL depth": dict(depth=None), "NULL pose": dict(pose=None),
+    common = {**pcases.view_faults(vd["pose"].data_ptr()), "NULL depth": dict(depth=None),
               "NULL anchor": dict(anchor=None), "voxel = 0": dict(voxel=0.0), "voxel NaN": dict(voxel=nan), "voxel inf": dict(voxel=inf), "trunc = 0": dict(trunc=0.0),
               "trunc NaN": dict(trunc=nan), "trunc inf": dict(trunc=inf), "trunc > 16 voxel": dict(trunc=16.5 * case["voxel"]), "anchor NaN": dict(anchor=[0.0, nan, 0.0]),
-              "anchor inf": dict(anchor=[inf, 0.0, 0.0]), "fx = 0": dict(fx=0.0), "fy NaN": dict(fy=nan), "cx NaN": dict(cx=nan), "cy inf": dict(cy=inf),
-              "misaligned depth": dict(depth=vd["depth"].data_ptr() + 1), "misaligned sil": dict(sil=vd["depth"].data_ptr() + 2), "misaligned pose": dict(pose=vd["pose"].data_ptr() + 2)}
+              "anchor inf": dict(anchor=[inf, 0.0, 0.0]), "fy NaN": dict(fy=nan),
+              "misaligned depth": dict(depth=vd["depth"].data_ptr() + 1), "misaligned sil": dict(sil=vd["depth"].data_ptr() + 2)}
     bad_reserve = dict(common, **{"max_blocks = 0": dict(max_blocks=0), "max_blocks above 2^21": dict(max_blocks=big), "NULL table": dict(table=None), "NULL counters": dict(rc=None),
                                   "misaligned table": dict(table=blk.table + 4), "misaligned counters": dict(rc=blk.rc.data_ptr() + 4)})
     for what, over in bad_reserve.items():
@@ -677,6 +677,19 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
         assert torch.equal(now[name], t), name
     assert int(lib.mm3dgs_tsdf_blocks_table_bytes(0)) == 0 and int(lib.mm3dgs_tsdf_blocks_table_bytes(big)) == 0 and int(lib.mm3dgs_tsdf_blocks_mesh_work_bytes(0)) == 0
     assert blk.reserve(vd) == 0 and blk.reserve(vd, sil=None) == 0 and blk.integrate(vd) == 0 and m.plan() == 0 and m.emit() == 0      # the same calls, unharmed
+
+
+@pytest.mark.parametrize("who", ("tsdf_blocks_reserve", "tsdf_blocks_integrate"))
+def test_view_fault_texts(who):
+    case = sc.sphere_case(0.04, False, n_views=1)
+    vd = to_dev(case["views"][0])
+    blk = Blocks(case, 64)
+    assert blk.reserve(vd) == 0
+    blk.freeze()
+    call = blk.reserve if who == "tsdf_blocks_reserve" else blk.integrate
+    H, W = vd["depth"].shape
+    for over, text in pcases.view_fault_texts(who, H, W, vd["pose"].data_ptr(), "the images and the pose must be 4-byte aligned"):
+        assert call(vd, **over) == -1 and _lib().mm3dgs_last_error().decode() == text, over
 
 
 # ---- 7. the export of a native-loop run ------------------------------------------------------------------------------------------------------

@@ -257,6 +257,23 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
     assert int(lib.mm3dgs_mesh_vertex_normals_work_bytes(0)) == 0 and int(lib.mm3dgs_normal_consistency_work_bytes(0)) == 0
 
 
+def test_pair_fault_texts():
+    nn = g.NN(nc.index_case(500, 257))
+    assert nn.build() == 0
+    faults = g.pair_fault_texts("nn_query_index", index=True) + [(dict(index=None), "nn_query_index: NULL argument (q_rows, cell_start, sorted, dist_out, index_out, row and work are required)"),
+                                                                  (dict(index=nn.dist.data_ptr() + 2), "nn_query_index: cell_start, dist_out and index_out must be 4-byte aligned")]
+    for over, text in faults:
+        over = dict(dist=nn.dist.data_ptr() + 2) if over == "misaligned dist" else over
+        assert _query_index(nn, **over)[0] == -1 and _lib().mm3dgs_last_error().decode() == text, over
+    s = g.Sampler(*gc.random_mesh(257, seed=1), 150.0, 11, 4096)
+    assert s.plan() == 0
+    faults = g.pair_fault_texts("mesh_sample_emit_tri", tri=True) + [(dict(tri=None), "mesh_sample_emit_tri: rows or tri_out is NULL with a cap above 0"),
+                                                                     (dict(tri=s.rows.data_ptr() + 2), "mesh_sample_emit_tri: tri_out must be 4-byte aligned")]
+    for over, text in faults:
+        over = dict(rows=s.rows.data_ptr() + 8) if over == "misaligned rows" else over
+        assert _emit_tri(s, **over)[0] == -1 and _lib().mm3dgs_last_error().decode() == text, over
+
+
 # ---- end to end -------------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def sphere_scene():

@@ -286,12 +286,11 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
     before = {"rows": cloud.rows.cpu(), "table": cloud.table.cpu(), "counters": cloud.counters.cpu(), "buf": cloud.buf.cpu()}
     nan, inf = float("nan"), float("inf")
     bad = {
-        "H = 0": dict(H=0), "W < 0": dict(W=-3), "more than 2^28 pixels": dict(H=1 << 14, W=(1 << 14) + 1),
-        "NULL color": dict(color=None), "NULL depth": dict(depth=None), "NULL pose": dict(pose=None), "NULL rows": dict(rows=None),
+        **cases.view_faults(vd["pose"].data_ptr()),
+        "NULL color": dict(color=None), "NULL depth": dict(depth=None), "NULL rows": dict(rows=None),
         "NULL counters": dict(counters=None), "NULL work": dict(work=None),
         "voxel < 0": dict(voxel=-0.01), "voxel NaN": dict(voxel=nan), "voxel inf": dict(voxel=inf),
         "voxel > 0 without a table": dict(table=None), "slots not a power of two": dict(slots=96), "slots below 64": dict(slots=32), "slots 0": dict(slots=0),
-        "fx = 0": dict(fx=0.0), "fy = 0": dict(fy=0.0), "fx NaN": dict(fx=nan), "fy inf": dict(fy=inf),
         "misaligned rows": dict(rows=cloud.rows.data_ptr() + 8), "misaligned table": dict(table=cloud.table.data_ptr() + 8),
         "misaligned counters": dict(counters=cloud.counters.data_ptr() + 4), "misaligned work": dict(work=cloud.work + 4),
         "misaligned color": dict(color=vd["color"].data_ptr() + 2), "misaligned depth": dict(depth=vd["depth"].data_ptr() + 1),
@@ -311,6 +310,14 @@ def test_rejected_calls_return_minus_one_and_write_nothing():
     for shape in ((0, W), (H, 0), (-1, W), (H, -1), (1 << 14, (1 << 14) + 1)):
         assert int(lib.mm3dgs_pointcloud_work_bytes(*shape)) == 0, shape
     assert cloud.call(vd) == 0 and cloud.call(vd, sil=None, view=1) == 0      # the silhouette is optional
+
+
+def test_view_fault_texts():
+    H, W = 17, 33
+    vd = to_dev(cases.view(H, W, "all"))
+    cloud = Cloud(H, W, H * W)
+    for over, text in cases.view_fault_texts("pointcloud_add_view", H, W, vd["pose"].data_ptr(), "the images and the pose must be 4-byte aligned"):
+        assert cloud.call(vd, **over) == -1 and _lib().mm3dgs_last_error().decode() == text, over
 
 
 PARENT_KEYS = ["pose_est", "pose_gt", "keyframes", "ate_rmse", "psnr_list", "ssim_list", "lpips_list"]

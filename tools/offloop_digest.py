@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""sha256 of every output the kernels outside the tracking and mapping loops write (compact, align, eval, pointcloud, tsdf, geometry),
+"""sha256 of every output the kernels outside the tracking and mapping loops write (compact, align, eval, pointcloud, tsdf, geometry, cull, mesh depth),
 over the case lists the GPU tests define, as one JSON file -- to compare two builds of the library bit for bit:
 
     MM3DGS_LIB=$PWD/mm3dgs_slam_amd/csrc/variants/libmm3dgs_hip_parent.so python tools/offloop_digest.py parent.json
@@ -162,8 +162,26 @@ def mesh_sparse():
         extract(name, t.GivenBlocks(a["keys"], *sc.to_pool(a["tsdf_w"], a["rgb_w"], a["blocks"], a["first"], a["dims"])), a["origin"], a["voxel"])
 
 
+def cull():
+    from tests import cull_cases as cases, test_gpu_cull as t
+    scenes = [cases.random_scene(n, H=H, W=W, n_views=3, seed=n + 3) for n in cases.SIZES for H, W in ((12, 16), (48, 64))] + cases.analytic_scenes()
+    scenes += [cases.frustum_only(s) for s in scenes] + cases.shape_scenes()      # (as the tests run them)
+    for k, scene in enumerate(scenes):
+        snap = t.Cull(scene, fill=0xFF).run().snapshot()
+        put(f"cull {k} {scene['name']} {scene['H']}x{scene['W']}", *[snap[name] for name in sorted(snap)])
+
+
+def mesh_depth():
+    from tests import mesh_depth_cases as cases, test_gpu_mesh_depth as t
+    for k, scene in enumerate(cases.host_scenes() + [cases.random_scene(48, seed=7, **cases.WIDE)]):
+        r = t.Render(scene, fill=0xFF)
+        assert r.call() == 0
+        put(f"mesh depth {k} {scene['name']}", *r.read())      # (not the work buffer: the order inside a tile's list is the atomics')
+
+
 def geometry():
-    from tests import geometry_cases as cases, test_gpu_geometry as t
+    from mm3dgs_slam_amd import geometry as geo
+    from tests import geometry_cases as cases, normals_cases as nc, test_gpu_geometry as t, test_gpu_normals as tn
 
     def nn(key, case):
         g = t.NN(case, 0xFF)
@@ -171,6 +189,9 @@ def geometry():
         dist, row, counters, cell_start, srt = g.read()
         cell = np.searchsorted(cell_start, np.arange(len(srt)), "right")      # the within-cell order is the atomics': by row index instead
         put(key, dist, row, counters, cell_start, srt[np.lexsort((srt[:, 3], cell))])
+        rc, *out = tn._query_index(g)
+        assert rc == 0
+        put(key + " index", *out)
 
     for n_ref in cases.SIZES:
         for n_q in cases.SIZES:
@@ -184,6 +205,25 @@ def geometry():
         s = t.Sampler(v, tris, density, seed, int(s.counters.cpu()[0]), 0xFF)
         assert s.plan() == 0 and s.emit() == 0
         put(key, *s.read())
+        rc, rows, tri = tn._emit_tri(s)
+        assert rc == 0
+        put(key + " tri", rows, tri, s.counters)
+
+    def consistency(key, est, ref, density, max_dist=0.2):      # one direction on host-made inputs, as test_gpu_normals._direction
+        fe, (rows_r, _, fr) = geo.sample_mesh_host(*est, density, 0, full=True), geo.sample_mesh_host(*ref, density, 0, full=True)
+        index = geo.nn_index_host(fe[0], rows_r, 0.05, max_dist)[1]
+        put(key, *tn._consistency(fe[2]["tri"], index, fr["tri"], est, ref))
+
+    sphere, flat = nc.icosphere(2), cases.square_mesh()
+    consistency("normals sphere on itself", sphere, sphere, 2000.0)
+    consistency("normals flat, flipped winding", flat, nc.flipped(flat), 2000.0)
+    consistency("normals floor / wall", *nc.floor_and_wall(), 500.0, max_dist=0.25)
+    consistency("normals sphere shifted by 1 cm", sphere, nc.shifted(sphere, (0.01, 0, 0)), 2000.0)
+    mesh, rng = nc.rejecting_mesh(), np.random.default_rng(5)      # ids out of range, as test_consistency_ids_out_of_range
+    m = len(mesh[1])
+    tri_q = rng.choice(np.array([0, 7, 1, 5, m, m + 1, 0x7fffffff, 0xfffffffe], dtype=np.uint32), 700)
+    index = rng.choice(np.array([0, 1, 2, 3, 4, 5, 6, 7, 1 << 20, 0xfffffffe, 0xffffffff], dtype=np.uint32), 700)
+    put("normals ids out of range", *tn._consistency(tri_q, index, np.array([0, 7, 6, m + 3, 0xffffffff, 7, 0], dtype=np.uint32), mesh, mesh))
 
     for m in (1, 255, 256, 257):
         sample(f"sampler random {m}", *cases.random_mesh(m, seed=m), 150.0, m)
@@ -191,6 +231,52 @@ def geometry():
     for where in ("first", "last"):
         sample(f"sampler wall {where}", *cases.wall_mesh(where), 100.0, 6)
     sample("sampler degenerate", *cases.degenerate_mesh()[:2], 100.0, 2)
+
+
+def error_texts():
+    """Return code and mm3dgs_last_error() text of single-fault calls of the six entry points that take a posed view and of the nn_query /
+    mesh_sample_emit pairs.  Host checks only: every call is rejected before a pointer is looked at, so the pointers are made-up addresses."""
+    import ctypes as C
+    from mm3dgs_slam_amd import _lib
+    lib, nan, inf, A = _lib.load(), float("nan"), float("inf"), 0x10000      # A: 16-byte aligned, never dereferenced
+    vec3, org3 = (C.c_double * 3)(0.0, 0.0, 0.0), (C.c_int64 * 3)(0, 0, 0)
+
+    def run(stem, call, good, faults):
+        for what, over in faults.items():
+            rc = call(dict(good, **over))
+            put(f"error text {stem} {what}", str(rc).encode(), lib.mm3dgs_last_error())
+
+    view = dict(H=12, W=16, fx=20.0, fy=21.0, cx=8.0, cy=6.0, pose=A)
+    view_faults = {"H = 0": dict(H=0), "W < 0": dict(W=-3), "2^28": dict(H=1 << 14, W=(1 << 14) + 1), "fx NaN": dict(fx=nan), "fx = 0": dict(fx=0.0), "fy = 0": dict(fy=0.0),
+                   "fy inf": dict(fy=inf), "cx NaN": dict(cx=nan), "cy inf": dict(cy=inf), "NULL pose": dict(pose=None), "misaligned pose": dict(pose=A + 2)}
+    head = lambda a: (a["H"], a["W"], a["fx"], a["fy"], a["cx"], a["cy"], a["pose"])
+    run("pointcloud_add_view", lambda a: lib.mm3dgs_pointcloud_add_view(*head(a), A, A, A, 0.5, 0.0, 0.0, 0, A, 100, None, 0, A, A, None), view, view_faults)
+    run("tsdf_integrate", lambda a: lib.mm3dgs_tsdf_integrate(*head(a), A, A, A, 0.5, 0.0, vec3, 0.1, 0.3, 8, 8, 8, A, A, A, None), view, view_faults)
+    run("tsdf_blocks_reserve", lambda a: lib.mm3dgs_tsdf_blocks_reserve(*head(a), A, A, 0.5, 0.0, vec3, 0.1, 0.3, None, A, 64, A, None), view, view_faults)
+    run("tsdf_blocks_integrate", lambda a: lib.mm3dgs_tsdf_blocks_integrate(*head(a), A, A, A, 0.5, 0.0, vec3, 0.1, 0.3, A, 4, A, A, A, None), view, view_faults)
+    run("cull_mark_view", lambda a: lib.mm3dgs_cull_mark_view(*head(a), A, 0.0, 0.1, 10.0, 0.01, 100, A, A, A, None), view, view_faults)
+    run("mesh_depth_render", lambda a: lib.mm3dgs_mesh_depth_render(*head(a), 0.1, 10.0, 10, A, 10, A, 100, A, A, A, A, None), view, view_faults)
+
+    nnq = dict(n_q=10, q=A, n_ref=10, cell=0.1, origin=org3, gx=4, gy=4, gz=4, cell_start=A, sorted=A, max_dist=0.5, threshold=0.1, dist=A, index=A, row=A, work=A)
+    nnq_faults = {"n_q = 0": dict(n_q=0), "n_q > 2^30": dict(n_q=(1 << 30) + 1), "n_ref = 0": dict(n_ref=0), "gz = 0": dict(gz=0), "2^26 cells": dict(gx=512, gy=512, gz=257),
+                  "cell NaN": dict(cell=nan), "max_dist = 0": dict(max_dist=0.0), "max_dist inf": dict(max_dist=inf), "2^20 rings": dict(cell=1e-9), "threshold < 0": dict(threshold=-0.5),
+                  "NULL origin": dict(origin=None), "NULL q": dict(q=None), "NULL cell_start": dict(cell_start=None), "NULL sorted": dict(sorted=None), "NULL dist": dict(dist=None),
+                  "NULL row": dict(row=None), "NULL work": dict(work=None), "misaligned q": dict(q=A + 8), "misaligned work": dict(work=A + 4), "misaligned dist": dict(dist=A + 2),
+                  "misaligned cell_start": dict(cell_start=A + 1), "misaligned row": dict(row=A + 4)}
+    pre = lambda a: (a["n_q"], a["q"], a["n_ref"], a["cell"], a["origin"], a["gx"], a["gy"], a["gz"], a["cell_start"], a["sorted"], a["max_dist"], a["threshold"], a["dist"])
+    run("nn_query", lambda a: lib.mm3dgs_nn_query(*pre(a), a["row"], a["work"], None), nnq, nnq_faults)
+    run("nn_query_index", lambda a: lib.mm3dgs_nn_query_index(*pre(a), a["index"], a["row"], a["work"], None), nnq,
+        dict(nnq_faults, **{"NULL index": dict(index=None), "misaligned index": dict(index=A + 2)}))
+
+    ms = dict(nv=10, v=A, m=10, tris=A, density=100.0, seed=1, work=A, rows=A, tri=A, cap=100, counters=A)
+    ms_faults = {"m = 0": dict(m=0), "m > 2^30": dict(m=(1 << 30) + 1), "n_vertices = 0": dict(nv=0), "density = 0": dict(density=0.0), "density NaN": dict(density=nan),
+                 "NULL vrows": dict(v=None), "NULL triangles": dict(tris=None), "NULL work": dict(work=None), "NULL counters": dict(counters=None), "NULL rows": dict(rows=None),
+                 "cap > 2^31": dict(cap=(1 << 31) + 1), "misaligned rows": dict(rows=A + 8), "misaligned vrows": dict(v=A + 8), "misaligned work": dict(work=A + 4),
+                 "misaligned triangles": dict(tris=A + 2)}
+    pre_ms = lambda a: (a["nv"], a["v"], a["m"], a["tris"], a["density"], a["seed"], a["work"], a["rows"])
+    run("mesh_sample_emit", lambda a: lib.mm3dgs_mesh_sample_emit(*pre_ms(a), a["cap"], a["counters"], None), ms, ms_faults)
+    run("mesh_sample_emit_tri", lambda a: lib.mm3dgs_mesh_sample_emit_tri(*pre_ms(a), a["tri"], a["cap"], a["counters"], None), ms,
+        dict(ms_faults, **{"NULL tri_out": dict(tri=None), "misaligned tri_out": dict(tri=A + 2)}))
 
 
 def evaluation():
@@ -223,7 +309,7 @@ def pose_prediction():
 
 def main():
     from mm3dgs_slam_amd import _lib
-    for stage in (surgery, pointcloud, mesh, mesh_sparse, geometry, evaluation, depth_align, pose_prediction):
+    for stage in (surgery, pointcloud, mesh, mesh_sparse, geometry, cull, mesh_depth, error_texts, evaluation, depth_align, pose_prediction):
         t0 = time.time()
         before = len(OUT)
         stage()
