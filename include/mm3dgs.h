@@ -765,6 +765,49 @@ size_t mm3dgs_mesh_vertex_normals_work_bytes(uint64_t n_vertices);
 int mm3dgs_mesh_vertex_normals(uint64_t n_vertices, const void* vrows /*[n_vertices] x 16 bytes*/, uint64_t m, const int32_t* triangles /*[m][3]*/,
                                float* normals /*[n_vertices][3]*/, void* work, uint64_t* counters /*[8], device*/, void* stream);
 
+/* ---- point-to-point ICP: the estimate registered to the reference before it is scored ------------------------------------------------------
+ * Host statement: mm3dgs_slam_amd/geometry.py (icp_host, move_rows_host, _horn_solve).  Source rows q_rows and the reference set behind
+ * the grid (cell_start, sorted: as mm3dgs_nn_grid_build wrote them, grid arguments as they were given to it) are 16-byte rows as above.
+ *
+ * mm3dgs_icp_point.  state: double[16] on the device; in: [0:12] the start T = (R | t), row-major [3][4]; out: [0:12] T, [12] passes run,
+ * [13] status (0 converged, 1 iters reached, 2 fewer than 3 correspondences), [14:16] 0.  Pass k = 0 .. iters, everything in double, no
+ * fused multiply-add:
+ *   move    every finite source row p (widened) gives p' = ((R0 p.x + R1 p.y) + R2 p.z) + t per component, rounded once to float32; its
+ *           correspondence q is what mm3dgs_nn_query_index finds for the row p' with this max_dist (the same grid, rings, stop rule and
+ *           lexicographic minimum over (d2, original row)); none for a clamped row or one that is not finite.
+ *   sums    over the rows with a correspondence, p the ORIGINAL coordinates (a solve gives the absolute transform, nothing is composed):
+ *           n, sum p [3], sum q [3], sum p_a q_b [9] (each product rounded, then added), sum d2 (the double squared distance of the
+ *           search); one lane per row, per 256-lane workgroup one partial row in a fixed lane order, one workgroup over the partial rows
+ *           in a fixed order (mm3dgs_nn_query's order); no float atomic: the same inputs give the same bytes on every call.
+ *   figures fitness = n / finite source rows, rmse = sqrt(sum d2 / n), both 0 with n = 0: those of the T the pass started with.
+ *   stop    status 0 when k > 0 and |fitness_k - fitness_{k-1}| < rel_fitness and |rmse_k - rmse_{k-1}| < rel_rmse; else status 2 when
+ *           n < 3; else status 1 when k == iters.  T stays as it was: the figures of the last pass belong to the returned T.
+ *   solve   otherwise Horn's closed form: S = sum p q^T - sum p sum q^T / n, the dominant eigenvector of the symmetric 4 x 4 matrix N(S)
+ *           by cyclic Jacobi rotations (+ - x / sqrt only), w >= 0, normalised; R from the quaternion, t = sum q / n - R sum p / n.
+ * log: double [iters + 1][16] on the device, row k: [0] 1 when pass k ran, [1] n, [2] finite source rows, [3] fitness, [4] rmse, [5:9] the
+ * quaternion (w, x, y, z) of the latest solve of this call (0 before the first), [9:12] t behind this pass, [12] the status on the row of
+ * the pass that stopped, the rest 0; the rows behind the stop are 0.  dist_out float [n_q] / index_out uint32 [n_q], each optional: what
+ * mm3dgs_nn_query_index stores for the moved rows of the last pass that ran (they belong to the returned T).
+ * work: mm3dgs_icp_work_bytes(n_q) bytes, 8-byte aligned, contents irrelevant before and after.  One zeroing launch and 2 (iters + 1)
+ * launches on `stream`, no host synchronisation: the stop is a word on the device, and the launches behind it return at entry.  Nothing
+ * outside state[0:16], log, dist_out[0:n_q], index_out[0:n_q] and work is written.
+ *
+ * mm3dgs_rows_move: rows_out [n] = rows_in [n] with every finite position moved by T (double[12] on the device, row-major [3][4]) by the
+ * component rule above, rounded once; the rgba and a row that is not finite are copied.  rows_out may be rows_in.  One launch.
+ *
+ * -1 (nothing is launched, nothing is written): n_q, n_ref or n of 0 or above 2^30; a grid size below 1 or more than 2^26 cells; cell or
+ * max_dist not finite or not positive; max_dist / cell above 2^20; iters outside 1 .. 1000; a tolerance that is negative or not a number;
+ * an origin_cell that is NULL or beyond +-2^40; a NULL pointer (dist_out and index_out may be NULL); rows or sorted not 16-byte aligned;
+ * state, log, work or T not 8-byte aligned; cell_start, dist_out or index_out not 4-byte aligned.  mm3dgs_icp_work_bytes returns 0 for
+ * sizes the call rejects. */
+size_t mm3dgs_icp_work_bytes(uint64_t n_q);
+int mm3dgs_icp_point(uint64_t n_q, const void* q_rows /*[n_q] x 16 bytes*/, uint64_t n_ref, double cell, const int64_t* origin_cell /*host [3]*/, int gx,
+                     int gy, int gz, const uint32_t* cell_start, const void* sorted, double max_dist, int iters, double rel_fitness, double rel_rmse,
+                     double* state /*[16], device*/, double* log /*[iters + 1][16], device*/, float* dist_out /*[n_q] or NULL*/,
+                     uint32_t* index_out /*[n_q] or NULL*/, void* work, void* stream);
+int mm3dgs_rows_move(uint64_t n, const void* rows_in /*[n] x 16 bytes*/, const double* T /*[12], device*/, void* rows_out /*[n] x 16 bytes*/,
+                     void* stream);
+
 /* ---- visibility culling: the rows of a point set that the views of a run could have seen ------------------------------------------------
  * Host statement: mm3dgs_slam_amd/cull.py (cull_host).  rows: [n] x 16 bytes {float x, y, z; uint32 rgba} on the device, 16-byte aligned;
  * seen: uint32 [n] and counters: uint64 [8] on the device, both zeroed by the caller before the first view.
@@ -1047,7 +1090,8 @@ const char* mm3dgs_last_error(void);
         (the mesh export's volume as hashed 8 x 8 x 8 voxel blocks, mesh.volume: sparse); mm3dgs_nn_query_index /
         mm3dgs_mesh_sample_emit_tri / mm3dgs_normal_consistency_work_bytes / mm3dgs_normal_consistency /
         mm3dgs_mesh_vertex_normals_work_bytes / mm3dgs_mesh_vertex_normals (normal consistency for the geometry scores, vertex normals
-        for mesh.ply); a caller that needs them looks the symbols up */
+        for mesh.ply); mm3dgs_icp_work_bytes / mm3dgs_icp_point / mm3dgs_rows_move (point-to-point ICP of the estimate onto the reference
+        for the geometry scores); a caller that needs them looks the symbols up */
 #define MM3DGS_ABI_VERSION 213
 int mm3dgs_version(void);
 

@@ -134,6 +134,10 @@ _SIGS = {
     "mm3dgs_normal_consistency": (C.c_int, [C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     "mm3dgs_mesh_vertex_normals_work_bytes": (C.c_size_t, [C.c_uint64]),
     "mm3dgs_mesh_vertex_normals": (C.c_int, [C.c_uint64, _P, C.c_uint64, _P, _P, _P, _P, _P]),
+    "mm3dgs_icp_work_bytes": (C.c_size_t, [C.c_uint64]),
+    "mm3dgs_icp_point": (C.c_int, [C.c_uint64, _P, C.c_uint64, C.c_double, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_int,
+                                   C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "mm3dgs_rows_move": (C.c_int, [C.c_uint64, _P, _P, _P, _P]),
     "mm3dgs_cull_mark_view": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, C.c_float, C.c_double, C.c_double, C.c_double,
                                         C.c_uint64, _P, _P, _P, _P]),
     "mm3dgs_cull_work_bytes": (C.c_size_t, [C.c_uint64]),

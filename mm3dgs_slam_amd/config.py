@@ -108,6 +108,14 @@ MESH_VOLUME = {"volume": "dense", "max_blocks": 1 << 18}
 GEOMETRY_NORMALS = {"normals": False}
 MESH_NORMALS = {"normals": False}
 
+# Registration (geometry.py: icp_host / register, mm3dgs_icp_point / mm3dgs_rows_move), five more opt-in keys of the `geometry` block merged
+# the same way and kept apart for the same reason.  `icp` none / point: after `align` and before culling and scoring, the estimate is
+# registered to the reference by point-to-point ICP, as NICE-SLAM's eval_recon does before it measures (metrics.json gains an `icp` block,
+# outputdir/geometry/icp.npz the transform and the per-pass log).  icp_max_dist: the correspondence distance in metres; icp_iters: at most
+# this many solves; icp_rel_fitness / icp_rel_rmse: the loop stops when both figures change by less between two passes.  The four numbers
+# are Open3D's registration_icp defaults (30, 1e-6, 1e-6) and NICE-SLAM's 0.1 m threshold, not measured defaults of ours
+GEOMETRY_ICP = {"icp": "none", "icp_max_dist": 0.1, "icp_iters": 30, "icp_rel_fitness": 1e-6, "icp_rel_rmse": 1e-6}
+
 # configs/UTMM.yml's hot-path settings that differ from TUM.yml (BASELINE.json configs[2]: RGB-D + IMU): 640x330, intrinsics of the
 # 1280x660 sensor scaled by 1/2 (gradslam_datasets/datautils.py:73-118), isotropic Gaussians, IMU dead-reckoning for the pose
 # prediction, Pearson term in tracking, 0.002 pose learning rates, size threshold 200.

@@ -1132,6 +1132,41 @@ int mm3dgs_mesh_vertex_normals(uint64_t n_vertices, const void* vrows, uint64_t 
   return check_launch("mesh_vertex_normals");
 }
 
+// ---- point-to-point ICP (geometry.hip) -----------------------------------------------------------------------------------------------
+size_t mm3dgs_icp_work_bytes(uint64_t n_q) { return (n_q >= 1 && n_q <= NN_MAX_ROWS) ? icp_work_bytes(n_q) : 0; }
+
+int mm3dgs_icp_point(uint64_t n_q, const void* q_rows, uint64_t n_ref, double cell, const int64_t* origin_cell, int gx, int gy, int gz,
+                     const uint32_t* cell_start, const void* sorted, double max_dist, int iters, double rel_fitness, double rel_rmse, double* state, double* log,
+                     float* dist_out, uint32_t* index_out, void* work, void* stream) {
+  if (n_q < 1 || n_q > NN_MAX_ROWS) return fail(-1, "icp_point: n_q = %llu (1 .. 2^30)", (unsigned long long)n_q);
+  if (n_ref < 1 || n_ref > NN_MAX_ROWS) return fail(-1, "icp_point: n_ref = %llu (1 .. 2^30)", (unsigned long long)n_ref);
+  if (!nn_grid_ok(gx, gy, gz)) return fail(-1, "icp_point: grid %d x %d x %d (every size at least 1, at most 2^26 cells)", gx, gy, gz);
+  if (!(cell > 0.0) || !isfinite(cell)) return fail(-1, "icp_point: cell = %g (must be finite and positive)", cell);
+  if (!(max_dist > 0.0) || !isfinite(max_dist)) return fail(-1, "icp_point: max_dist = %g (must be finite and positive)", max_dist);
+  const double rings = ceil(max_dist / cell);
+  if (!(rings <= NN_MAX_RINGS)) return fail(-1, "icp_point: max_dist / cell = %g (at most 2^20 rings)", max_dist / cell);
+  if (iters < 1 || iters > 1000) return fail(-1, "icp_point: iters = %d (1 .. 1000)", iters);
+  if (!(rel_fitness >= 0.0) || !(rel_rmse >= 0.0)) return fail(-1, "icp_point: rel_fitness = %g, rel_rmse = %g (neither may be negative or not a number)", rel_fitness, rel_rmse);
+  if (!nn_origin_ok(origin_cell)) return fail(-1, "icp_point: origin_cell is NULL or beyond +-2^40");
+  if (!q_rows || !cell_start || !sorted || !state || !log || !work)
+    return fail(-1, "icp_point: NULL argument (q_rows, cell_start, sorted, state, log and work are required)");
+  if (((uintptr_t)q_rows | (uintptr_t)sorted) & 15) return fail(-1, "icp_point: q_rows and sorted must be 16-byte aligned");
+  if (((uintptr_t)state | (uintptr_t)log | (uintptr_t)work) & 7) return fail(-1, "icp_point: state, log and work must be 8-byte aligned");
+  if (((uintptr_t)cell_start | (uintptr_t)dist_out | (uintptr_t)index_out) & 3) return fail(-1, "icp_point: cell_start, dist_out and index_out must be 4-byte aligned");
+  launch_icp_point(nn_grid(cell, origin_cell, gx, gy, gz), n_q, q_rows, n_ref, cell_start, sorted, max_dist, (int)(rings < 1.0 ? 1.0 : rings), iters, rel_fitness,
+                   rel_rmse, state, log, dist_out, index_out, work, (hipStream_t)stream);
+  return check_launch("icp_point");
+}
+
+int mm3dgs_rows_move(uint64_t n, const void* rows_in, const double* T, void* rows_out, void* stream) {
+  if (n < 1 || n > NN_MAX_ROWS) return fail(-1, "rows_move: n = %llu (1 .. 2^30)", (unsigned long long)n);
+  if (!rows_in || !T || !rows_out) return fail(-1, "rows_move: NULL argument (rows_in, T and rows_out are required)");
+  if (((uintptr_t)rows_in | (uintptr_t)rows_out) & 15) return fail(-1, "rows_move: rows_in and rows_out must be 16-byte aligned");
+  if ((uintptr_t)T & 7) return fail(-1, "rows_move: T must be 8-byte aligned");
+  launch_rows_move(n, rows_in, T, rows_out, (hipStream_t)stream);
+  return check_launch("rows_move");
+}
+
 // ---- visibility culling (cull.hip) -------------------------------------------------------------------------------------------------
 size_t mm3dgs_cull_work_bytes(uint64_t n) { return n <= NN_MAX_ROWS ? cull_work_bytes(n) : 0; }
 

@@ -181,6 +181,14 @@ size_t nn_query_work_bytes(uint64_t n_q);
 // of dist_out and row do not depend on it
 void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist,
                      double threshold, int rmax, float* dist_out, uint32_t* index_out_or_null, double* row, void* work, hipStream_t s);
+// point-to-point ICP of the query rows onto the grid's reference set: a zeroing launch and 2 (iters + 1) launches, the stop decided on the
+// device (state [16], log [iters + 1][16] doubles; dist_out / index_out may be NULL); work = the buffer of icp_work_bytes(n_q); sizes,
+// max_dist, rmax, 1 <= iters <= 1000 and the tolerances as the entry point has checked them.  rows_move: rows_out = rows_in moved by T
+// (12 doubles on the device, row-major [3][4]); the two arrays may be one
+size_t icp_work_bytes(uint64_t n_q);
+void launch_icp_point(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist, int rmax,
+                      int iters, double rel_fitness, double rel_rmse, double* state, double* log, float* dist_out, uint32_t* index_out, void* work, hipStream_t s);
+void launch_rows_move(uint64_t n, const void* rows_in, const double* T, void* rows_out, hipStream_t s);
 size_t mesh_sample_work_bytes(uint64_t m);
 void launch_mesh_sample_plan(const MeshSample& ms, void* work, uint64_t* counters, hipStream_t s);
 // tri_out_or_null: the triangle of every sample (the normal scores'); the bytes of rows do not depend on it

@@ -26,6 +26,8 @@
 //   geometry.nn_index_host / normal_row / vertex_normals_host): ng_query_kernel<true> also keeps the original row of the nearest record,
 //   ms_emit_kernel<true> the triangle of every sample (the <false> instantiations are the calls above, byte for byte); ms_cross / ms_face
 //   state the face cross product once; nc_dot_kernel and the four vn_* kernels are described where they stand.
+// Registration (mm3dgs_icp_point / mm3dgs_rows_move; host statement: geometry.icp_host / move_rows_host): ng_search is the one per-query search
+//   behind ng_query_kernel and icp_pass_kernel; the icp_* kernels and rows_move_kernel are described where they stand.
 #include <math.h>
 #include "block_ops.h"
 #include "fused_api.h"
@@ -152,7 +154,7 @@ void launch_nn_grid_build(const NnGrid& g, uint64_t n_ref, const void* rows, voi
 // ---- query ------------------------------------------------------------------------------------------------------------------------
 size_t nn_query_work_bytes(uint64_t n_q) { return align_up(ng_nb((size_t)n_q) * NN_ROW * sizeof(double), 256); }
 
-struct NnQuery { double qx, qy, qz, best2; uint32_t besti; };      // besti: the original row of the best record (INDEX only)
+struct NnQuery { double qx, qy, qz, best2; uint32_t besti, bestp; };      // besti: the original row of the best record, bestp: where it lies in `sorted` (INDEX only)
 
 // the records [b, e) against the query: squared distance in double (each coordinate widened, then subtracted; three squares, a sum);
 // INDEX: the minimum is lexicographic over (d2, original row), so neither the order inside a cell nor duplicates decide the row
@@ -164,7 +166,7 @@ __device__ __forceinline__ void ng_scan_records(const uint4* __restrict__ sorted
     const uint4 v = sorted[p];      // one 16-byte load per candidate
     const double dx = q.qx - (double)__uint_as_float(v.x), dy = q.qy - (double)__uint_as_float(v.y), dz = q.qz - (double)__uint_as_float(v.z);
     const double d2 = dx * dx + dy * dy + dz * dz;
-    if (INDEX && (d2 < q.best2 || (d2 == q.best2 && v.w < q.besti))) q.besti = v.w;
+    if (INDEX && (d2 < q.best2 || (d2 == q.best2 && v.w < q.besti))) { q.besti = v.w; q.bestp = p; }
     q.best2 = d2 < q.best2 ? d2 : q.best2;
   }
 }
@@ -205,6 +207,38 @@ __device__ __forceinline__ void ng_ring(const NnGrid& g, const uint32_t* __restr
   }
 }
 
+// the search of one finite query (x, y, z): from its cell to the final q.best2 / q.besti (q.best2 +inf: nothing within rmax rings).  The one
+// statement behind ng_query_kernel and icp_pass_kernel
+template <bool INDEX>
+__device__ __forceinline__ void ng_search(const NnGrid& g, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted, uint32_t n_ref, int rmax,
+                                          float x, float y, float z, NnQuery& q) {
+#pragma clang fp contract(off)
+  q.qx = (double)x; q.qy = (double)y; q.qz = (double)z; q.best2 = (double)INFINITY; q.besti = NN_NO_CELL; q.bestp = 0u;
+  double c[3];
+  ng_cell(g, x, y, z, c);
+  // the first ring that touches the grid, and the last one that does (as doubles: a far query's cell may not fit an int)
+  const double gs[3] = {(double)g.gx, (double)g.gy, (double)g.gz};
+  double r0 = 0.0, rfar = 0.0;
+  for (int a = 0; a < 3; a++) {
+    const double below = -c[a], above = c[a] - (gs[a] - 1.0);
+    const double o = below > above ? below : above;      // > 0: cells outside the grid along this axis
+    r0 = o > r0 ? o : r0;
+    const double f = c[a] > (gs[a] - 1.0) - c[a] ? c[a] : (gs[a] - 1.0) - c[a];
+    rfar = f > rfar ? f : rfar;
+  }
+  if (r0 <= (double)rmax) {      // (else: nothing within max_dist)
+    const int cx = (int)c[0], cy = (int)c[1], cz = (int)c[2];      // |c| <= grid size + rmax here
+    const int last = rfar < (double)rmax ? (int)rfar : rmax;
+    int rr = r0 <= 1.0 ? 1 : (int)r0;
+    if (rr == 1) ng_cube<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, 1, q);      // rings 0 and 1: nine ranges
+    else ng_ring<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
+    while (rr < last && !(sqrt(q.best2) <= (double)rr * g.cell)) {      // at most rmax trips
+      rr++;
+      ng_ring<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
+    }
+  }
+}
+
 template <bool INDEX>
 __global__ void __launch_bounds__(GB)
 ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted,
@@ -228,30 +262,7 @@ ng_query_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const u
       out = __uint_as_float(0x7fc00000u);
     } else {
       NnQuery q;
-      q.qx = (double)x; q.qy = (double)y; q.qz = (double)z; q.best2 = (double)INFINITY; q.besti = NN_NO_CELL;
-      double c[3];
-      ng_cell(g, x, y, z, c);
-      // the first ring that touches the grid, and the last one that does (as doubles: a far query's cell may not fit an int)
-      const double gs[3] = {(double)g.gx, (double)g.gy, (double)g.gz};
-      double r0 = 0.0, rfar = 0.0;
-      for (int a = 0; a < 3; a++) {
-        const double below = -c[a], above = c[a] - (gs[a] - 1.0);
-        const double o = below > above ? below : above;      // > 0: cells outside the grid along this axis
-        r0 = o > r0 ? o : r0;
-        const double f = c[a] > (gs[a] - 1.0) - c[a] ? c[a] : (gs[a] - 1.0) - c[a];
-        rfar = f > rfar ? f : rfar;
-      }
-      if (r0 <= (double)rmax) {      // (else: nothing within max_dist)
-        const int cx = (int)c[0], cy = (int)c[1], cz = (int)c[2];      // |c| <= grid size + rmax here
-        const int last = rfar < (double)rmax ? (int)rfar : rmax;
-        int rr = r0 <= 1.0 ? 1 : (int)r0;
-        if (rr == 1) ng_cube<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, 1, q);      // rings 0 and 1: nine ranges
-        else ng_ring<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
-        while (rr < last && !(sqrt(q.best2) <= (double)rr * g.cell)) {      // at most rmax trips
-          rr++;
-          ng_ring<INDEX>(g, cell_start, sorted, n_ref, cx, cy, cz, rr, q);
-        }
-      }
+      ng_search<INDEX>(g, cell_start, sorted, n_ref, rmax, x, y, z, q);
       const double d = sqrt(q.best2);
       clamped = !(d <= max_dist);
       if (INDEX && !clamped) nearest = q.besti;
@@ -340,8 +351,277 @@ void launch_nn_query(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t 
   hipLaunchKernelGGL(ng_finish_kernel<false>, dim3(1), dim3(GB), 0, s, (const double*)work, (int)nb, row);
 }
 
+// ---- point-to-point ICP -----------------------------------------------------------------------------------------------------------
+// mm3dgs_icp_point / mm3dgs_rows_move; host statement: geometry.icp_host / move_rows_host / _horn_solve.  Pass k = 0 .. iters is two
+// launches, and no launch waits for the host: the stop is a word on the device that every later launch reads at entry.
+//   icp_zero_kernel   the log, the header and state[12:16] to zero.
+//   icp_pass_kernel   one lane per source row: the row moved by T (state[0:12]) and rounded once, ng_search<true> for the moved row, the 17
+//                     terms {1, p, q, p_a q_b, d2} of a row with a correspondence (p: the ORIGINAL coordinates, so a solve gives the absolute
+//                     transform); per workgroup one partial row of ICP_ROW doubles in block_sums_f64's order.  No float atomic.
+//   icp_step_kernel   one workgroup adds the partial rows in ng_finish_kernel's order; lane 0: the figures of T, the stop rule, else Horn's
+//                     closed form on the sums (icp_horn: the dominant eigenvector of N(S) by cyclic Jacobi rotations, + - x / sqrt only).
+//   rows_move_kernel  one lane per row: the position moved by T from device memory, rounded once; rgba and a row that is not finite as they are.
+// work = [ICP_HDR doubles: [0] done, [1] fitness and [2] rmse of the pass before, [3:7] the quaternion of the latest solve][one partial row
+// per workgroup: the 17 sums, finite rows, rows with a correspondence, 0 x 5]
+#define ICP_SUMS 17
+#define ICP_COLS 19     // the columns of a partial row that are added
+#define ICP_ROW 24      // doubles per partial row
+#define ICP_HDR 32
+#define ICP_LOG 16      // doubles per log row
+#define ICP_SWEEPS 50   // icp_horn's cap (see there)
+
+size_t icp_work_bytes(uint64_t n_q) { return ICP_HDR * sizeof(double) + align_up(ng_nb((size_t)n_q) * ICP_ROW * sizeof(double), 256); }
+
+__global__ void __launch_bounds__(GB) icp_zero_kernel(double* __restrict__ state, double* __restrict__ log, size_t nlog, double* __restrict__ hdr) {
+  const size_t step = (size_t)gridDim.x * GB;
+  for (size_t i = (size_t)blockIdx.x * GB + threadIdx.x; i < nlog; i += step) log[i] = 0.0;
+  if (blockIdx.x == 0 && threadIdx.x < ICP_HDR) hdr[threadIdx.x] = 0.0;
+  if (blockIdx.x == 0 && threadIdx.x < 4) state[12 + threadIdx.x] = 0.0;
+}
+
+// one component of a moved position: ((R0 x + R1 y) + R2 z) + t in double, rounded once (T row-major [3][4], no contraction)
+__device__ __forceinline__ float icp_move_axis(const double (&T)[12], int a, double x, double y, double z) {
+#pragma clang fp contract(off)
+  return (float)(((T[4 * a] * x + T[4 * a + 1] * y) + T[4 * a + 2] * z) + T[4 * a + 3]);
+}
+
+// OUT: dist_out / index_out (either may be NULL) also get what mm3dgs_nn_query_index stores for the moved rows
+template <bool OUT>
+__global__ void __launch_bounds__(GB)
+icp_pass_kernel(NnGrid g, const uint4* __restrict__ qrows, uint32_t n_q, const uint32_t* __restrict__ cell_start, const uint4* __restrict__ sorted,
+                uint32_t n_ref, double max_dist, int rmax, const double* __restrict__ state, const double* __restrict__ hdr, float* __restrict__ dist_out,
+                uint32_t* __restrict__ index_out, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  __shared__ double wsum[GB / 64][ICP_SUMS];
+  __shared__ uint32_t wcnt[2][GB / 64];
+  if (hdr[0] != 0.0) return;      // the loop has stopped (uniform: before any barrier)
+  double T[12];
+  for (int k = 0; k < 12; k++) T[k] = state[k];      // uniform loads
+  const uint32_t i = blockIdx.x * GB + threadIdx.x;
+  bool finite = false, paired = false;
+  double v[ICP_SUMS];
+  for (int k = 0; k < ICP_SUMS; k++) v[k] = 0.0;
+  if (i < n_q) {
+    const uint4 r = qrows[i];
+    const float x = __uint_as_float(r.x), y = __uint_as_float(r.y), z = __uint_as_float(r.z);
+    float out = __uint_as_float(0x7fc00000u);
+    uint32_t nearest = NN_NO_CELL;
+    if (view_finite(x, y, z)) {
+      finite = true;
+      const double p[3] = {(double)x, (double)y, (double)z};
+      const float mx = icp_move_axis(T, 0, p[0], p[1], p[2]), my = icp_move_axis(T, 1, p[0], p[1], p[2]), mz = icp_move_axis(T, 2, p[0], p[1], p[2]);
+      if (view_finite(mx, my, mz)) {      // (a moved row beyond float32 is a row that is not finite: skipped)
+        NnQuery q;
+        ng_search<true>(g, cell_start, sorted, n_ref, rmax, mx, my, mz, q);
+        const double d = sqrt(q.best2);
+        const bool clamped = !(d <= max_dist);
+        out = clamped ? (float)max_dist : (float)d;
+        if (!clamped && q.bestp < n_ref) {      // (bestp < n_ref always holds here: the record was read)
+          paired = true;
+          nearest = q.besti;
+          const uint4 b = sorted[q.bestp];
+          const double t[3] = {(double)__uint_as_float(b.x), (double)__uint_as_float(b.y), (double)__uint_as_float(b.z)};
+          v[0] = 1.0;
+          for (int a = 0; a < 3; a++) {
+            v[1 + a] = p[a];
+            v[4 + a] = t[a];
+            for (int c = 0; c < 3; c++) v[7 + 3 * a + c] = p[a] * t[c];
+          }
+          v[16] = q.best2;
+        }
+      }
+    }
+    if (OUT && dist_out) dist_out[i] = out;
+    if (OUT && index_out) index_out[i] = nearest;
+  }
+  block_sums_f64<ICP_SUMS, false>(v, wsum);
+  const bool is[2] = {finite, paired};
+  const uint32_t cnt = block_flag_counts(is, wcnt);
+  double* row = partial + (size_t)blockIdx.x * ICP_ROW;
+  if (threadIdx.x < 2) row[ICP_SUMS + threadIdx.x] = (double)cnt;
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < ICP_SUMS; k++) row[k] = v[k];
+    for (int k = ICP_COLS; k < ICP_ROW; k++) row[k] = 0.0;
+  }
+}
+
+// Horn's closed form on the 17 sums s = {n, sum p, sum q, sum p_a q_b, -}: T (row-major [3][4]) with q ~ R p + t, and the unit quaternion
+// (w >= 0) of R.  S = sum p q^T - sum p sum q^T / n, N(S) the symmetric 4 x 4 matrix of Horn 1987, its dominant eigenvector by cyclic Jacobi
+// rotations in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  + - x / sqrt and comparisons only, no contraction: geometry._horn_solve is
+// the same sequence of operations on the host, so the two agree bit for bit.  A sweep starts only while an off-diagonal element is not
+// exactly zero; an element below the rounding of both its diagonal neighbours is set to zero from the fifth sweep on, so the sum reaches
+// zero: quadratic convergence takes a 4 x 4 matrix there in well under ten sweeps (tests/test_icp.py counts them on random and on
+// degenerate matrices), and ICP_SWEEPS = 50 is the classical cap that only bounds the loop
+__device__ void icp_horn(const double* s, double (&T)[12], double (&quat)[4]) {
+#pragma clang fp contract(off)
+  const double n = s[0];
+  double S[3][3];
+  for (int a = 0; a < 3; a++)
+    for (int b = 0; b < 3; b++) S[a][b] = s[7 + 3 * a + b] - (s[1 + a] * s[4 + b]) / n;
+  double A[4][4], V[4][4];
+  A[0][0] = (S[0][0] + S[1][1]) + S[2][2];
+  A[0][1] = S[1][2] - S[2][1];
+  A[0][2] = S[2][0] - S[0][2];
+  A[0][3] = S[0][1] - S[1][0];
+  A[1][1] = (S[0][0] - S[1][1]) - S[2][2];
+  A[1][2] = S[0][1] + S[1][0];
+  A[1][3] = S[2][0] + S[0][2];
+  A[2][2] = (S[1][1] - S[0][0]) - S[2][2];
+  A[2][3] = S[1][2] + S[2][1];
+  A[3][3] = (S[2][2] - S[0][0]) - S[1][1];
+  for (int a = 0; a < 4; a++)
+    for (int b = 0; b < 4; b++) {
+      if (b < a) A[a][b] = A[b][a];
+      V[a][b] = a == b ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < ICP_SWEEPS; sweep++) {
+    const double off = ((((fabs(A[0][1]) + fabs(A[0][2])) + fabs(A[0][3])) + fabs(A[1][2])) + fabs(A[1][3])) + fabs(A[2][3]);
+    if (off == 0.0) break;
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+#pragma unroll
+      for (int q = p + 1; q < 4; q++) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double gg = 100.0 * fabs(apq);
+        if (sweep > 3 && fabs(A[p][p]) + gg == fabs(A[p][p]) && fabs(A[q][q]) + gg == fabs(A[q][q])) {
+          A[p][q] = 0.0; A[q][p] = 0.0;
+          continue;
+        }
+        const double h = A[q][q] - A[p][p];
+        double t;
+        if (fabs(h) + gg == fabs(h)) {
+          t = apq / h;
+        } else {
+          const double theta = (0.5 * h) / apq;
+          t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
+          if (theta < 0.0) t = -t;
+        }
+        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+        A[p][p] = A[p][p] - t * apq;
+        A[q][q] = A[q][q] + t * apq;
+        A[p][q] = 0.0; A[q][p] = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          if (r != p && r != q) {
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = c * arp - sn * arq; A[p][r] = A[r][p];
+            A[r][q] = sn * arp + c * arq; A[q][r] = A[r][q];
+          }
+          const double vrp = V[r][p], vrq = V[r][q];
+          V[r][p] = c * vrp - sn * vrq;
+          V[r][q] = sn * vrp + c * vrq;
+        }
+      }
+  }
+  double top = A[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];      // the largest eigenvalue, the first one on a tie
+#pragma unroll
+  for (int k = 1; k < 4; k++)
+    if (A[k][k] > top) { top = A[k][k]; w = V[0][k]; x = V[1][k]; y = V[2][k]; z = V[3][k]; }
+  if (w < 0.0) { w = -w; x = -x; y = -y; z = -z; }
+  const double len = sqrt(((w * w + x * x) + y * y) + z * z);
+  w = w / len; x = x / len; y = y / len; z = z / len;
+  quat[0] = w; quat[1] = x; quat[2] = y; quat[3] = z;
+  const double ww = w * w, xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+  double R[3][3];
+  R[0][0] = ((ww + xx) - yy) - zz; R[0][1] = 2.0 * (xy - wz);       R[0][2] = 2.0 * (xz + wy);
+  R[1][0] = 2.0 * (xy + wz);       R[1][1] = ((ww - xx) + yy) - zz; R[1][2] = 2.0 * (yz - wx);
+  R[2][0] = 2.0 * (xz - wy);       R[2][1] = 2.0 * (yz + wx);       R[2][2] = ((ww - xx) - yy) + zz;
+  const double mp[3] = {s[1] / n, s[2] / n, s[3] / n};
+  for (int a = 0; a < 3; a++) {
+    T[4 * a] = R[a][0]; T[4 * a + 1] = R[a][1]; T[4 * a + 2] = R[a][2];
+    T[4 * a + 3] = s[4 + a] / n - ((R[a][0] * mp[0] + R[a][1] * mp[1]) + R[a][2] * mp[2]);
+  }
+}
+
+__global__ void __launch_bounds__(GB)
+icp_step_kernel(const double* __restrict__ partial, int nrows, int k, int iters, double rel_fitness, double rel_rmse, double* __restrict__ state,
+                double* __restrict__ hdr, double* __restrict__ log) {
+#pragma clang fp contract(off)
+  __shared__ double sh[GB][ICP_COLS];
+  if (hdr[0] != 0.0) return;      // (uniform: before any barrier; lane 0 writes the word behind two of them)
+  double a[ICP_COLS];
+#pragma unroll
+  for (int c = 0; c < ICP_COLS; c++) a[c] = 0.0;
+  for (int r = threadIdx.x; r < nrows; r += GB)
+#pragma unroll
+    for (int c = 0; c < ICP_COLS; c++) a[c] = a[c] + partial[(size_t)r * ICP_ROW + c];
+#pragma unroll
+  for (int c = 0; c < ICP_COLS; c++) sh[threadIdx.x][c] = a[c];
+  __syncthreads();
+  if (threadIdx.x < ICP_COLS) {
+    const int c = threadIdx.x;
+    double t = 0.0;
+    for (int l = 0; l < GB; l++) t = t + sh[l][c];
+    sh[0][c] = t;      // (column c of row 0: no other lane reads or writes it)
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double* s = sh[0];
+  const double n = s[0], fin = s[ICP_SUMS];
+  const double fitness = n > 0.0 ? n / fin : 0.0, rmse = n > 0.0 ? sqrt(s[16] / n) : 0.0;      // of the T this pass started with
+  int status = -1;      // -1: go on
+  if (k > 0 && fabs(fitness - hdr[1]) < rel_fitness && fabs(rmse - hdr[2]) < rel_rmse) status = 0;
+  else if (n < 3.0) status = 2;
+  else if (k == iters) status = 1;
+  if (status < 0) {
+    double T[12], quat[4];
+    icp_horn(s, T, quat);
+    for (int c = 0; c < 12; c++) state[c] = T[c];
+    for (int c = 0; c < 4; c++) hdr[3 + c] = quat[c];
+  }
+  hdr[1] = fitness;
+  hdr[2] = rmse;
+  double* row = log + (size_t)k * ICP_LOG;
+  row[0] = 1.0; row[1] = n; row[2] = fin; row[3] = fitness; row[4] = rmse;
+  for (int c = 0; c < 4; c++) row[5 + c] = hdr[3 + c];
+  for (int c = 0; c < 3; c++) row[9 + c] = state[4 * c + 3];
+  row[12] = status > 0 ? (double)status : 0.0;
+  row[13] = 0.0; row[14] = 0.0; row[15] = 0.0;
+  if (status >= 0) {
+    state[12] = (double)(k + 1);
+    state[13] = (double)status;
+    hdr[0] = 1.0;
+  }
+}
+
+void launch_icp_point(const NnGrid& g, uint64_t n_q, const void* qrows, uint64_t n_ref, const void* cell_start, const void* sorted, double max_dist, int rmax,
+                      int iters, double rel_fitness, double rel_rmse, double* state, double* log, float* dist_out, uint32_t* index_out, void* work, hipStream_t s) {
+  const unsigned nb = (unsigned)ng_nb((size_t)n_q);
+  double* hdr = (double*)work;
+  double* partial = hdr + ICP_HDR;
+  const size_t nlog = (size_t)(iters + 1) * ICP_LOG;
+  hipLaunchKernelGGL(icp_zero_kernel, dim3((unsigned)ng_nb(nlog)), dim3(GB), 0, s, state, log, nlog, hdr);
+  for (int k = 0; k <= iters; k++) {
+    hipLaunchKernelGGL((dist_out || index_out) ? icp_pass_kernel<true> : icp_pass_kernel<false>, dim3(nb), dim3(GB), 0, s, g, (const uint4*)qrows, (uint32_t)n_q,
+                       (const uint32_t*)cell_start, (const uint4*)sorted, (uint32_t)n_ref, max_dist, rmax, (const double*)state, (const double*)hdr, dist_out,
+                       index_out, partial);
+    hipLaunchKernelGGL(icp_step_kernel, dim3(1), dim3(GB), 0, s, (const double*)partial, (int)nb, k, iters, rel_fitness, rel_rmse, state, hdr, log);
+  }
+}
+
+// (rows_in and rows_out may be the same array: a lane reads its row before it writes it)
+__global__ void __launch_bounds__(GB) rows_move_kernel(uint32_t n, const uint4* rows_in, const double* __restrict__ Tdev, uint4* rows_out) {
+  double T[12];
+  for (int k = 0; k < 12; k++) T[k] = Tdev[k];      // uniform loads
+  const uint32_t i = blockIdx.x * GB + threadIdx.x;
+  if (i >= n) return;
+  uint4 r = rows_in[i];
+  const float x = __uint_as_float(r.x), y = __uint_as_float(r.y), z = __uint_as_float(r.z);
+  if (view_finite(x, y, z)) {
+    r.x = __float_as_uint(icp_move_axis(T, 0, (double)x, (double)y, (double)z));
+    r.y = __float_as_uint(icp_move_axis(T, 1, (double)x, (double)y, (double)z));
+    r.z = __float_as_uint(icp_move_axis(T, 2, (double)x, (double)y, (double)z));
+  }
+  rows_out[i] = r;      // one 16-byte store
+}
+
+void launch_rows_move(uint64_t n, const void* rows_in, const double* T, void* rows_out, hipStream_t s) {
+  hipLaunchKernelGGL(rows_move_kernel, dim3((unsigned)ng_nb((size_t)n)), dim3(GB), 0, s, (uint32_t)n, (const uint4*)rows_in, T, (uint4*)rows_out);
+}
+
 // ---- surface sampler --------------------------------------------------------------------------------------------------------------
-// work = [256 B header: uint64 samples (0 when they exceed 32 bits)][uint32 exclusive prefix per triangle][2 x uint32 per 256 triangles: samples, degenerate]
+// work =[256 B header: uint64 samples (0 when they exceed 32 bits)][uint32 exclusive prefix per triangle][2 x uint32 per 256 triangles: samples, degenerate]
 struct MsWork { unsigned long long* hdr; uint32_t* prefix; uint32_t* bcounts; uint32_t* dcounts; };
 static MsWork ms_work(void* base, size_t m, size_t* bytes = nullptr) {
   Carve c = {(uintptr_t)base};

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import cull as cl, geometry as geo, mesh as ms, mesh_clean as mc, mesh_depth as md, pointcloud as pc
-from .config import _TUM, GEOMETRY_CULL, GEOMETRY_DEPTH, GEOMETRY_NORMALS, MESH_CLEAN, MESH_NORMALS, MESH_VOLUME
+from .config import _TUM, GEOMETRY_CULL, GEOMETRY_DEPTH, GEOMETRY_ICP, GEOMETRY_NORMALS, MESH_CLEAN, MESH_NORMALS, MESH_VOLUME
 
 
 def _flag(key, value):
@@ -22,10 +22,10 @@ def _flag(key, value):
 def options(cfg, block, **overrides):
     """The `pointcloud`, `mesh` or `geometry` block of `cfg` merged over the defaults, an override that is not None over both, resolved
     and validated: `every` (None: `mapping.kf_every`), `voxel`, `source` and the mesh's `trunc` (0: 4 voxel), `clean` and
-    `clean_min_triangles` of an export; `estimate`, `reference` and `align` of the evaluation."""
+    `clean_min_triangles` of an export; `estimate`, `reference`, `align` and the `icp` keys of the evaluation."""
     opt = dict(_TUM[block], **(cfg.get(block) or {}))
     if block == "geometry":
-        opt = dict(GEOMETRY_NORMALS, **dict(GEOMETRY_DEPTH, **dict(GEOMETRY_CULL, **opt)))
+        opt = dict(GEOMETRY_ICP, **dict(GEOMETRY_NORMALS, **dict(GEOMETRY_DEPTH, **dict(GEOMETRY_CULL, **opt))))
         opt.update((k, v) for k, v in overrides.items() if v is not None)
         opt.update(estimate=str(opt["estimate"]), reference=str(opt["reference"]), align=str(opt["align"] or "none").lower(),
                    cull=str(opt["cull"] or "none").lower())
@@ -48,6 +48,20 @@ def options(cfg, block, **overrides):
             raise ValueError(f"geometry.depth_max_pairs = {pairs!r} (an integer, 1 .. 2^31)")
         opt["depth_max_pairs"] = int(pairs)
         opt["normals"] = _flag("geometry.normals", opt["normals"])
+        opt["icp"] = str(opt["icp"] or "none").lower()
+        if opt["icp"] not in ("none", "point"):
+            raise ValueError(f"geometry.icp = {opt['icp']!r} (none / point)")
+        for key in ("icp_max_dist", "icp_iters", "icp_rel_fitness", "icp_rel_rmse"):
+            if isinstance(opt[key], bool) or not isinstance(opt[key], (int, float, np.integer, np.floating)):
+                raise ValueError(f"geometry.{key} = {opt[key]!r} (a number)")
+        try:
+            opt["icp_max_dist"], opt["icp_iters"], opt["icp_rel_fitness"], opt["icp_rel_rmse"] = geo._check_icp(opt["icp_max_dist"], opt["icp_iters"],
+                                                                                                             opt["icp_rel_fitness"], opt["icp_rel_rmse"])
+        except ValueError as e:
+            raise ValueError(f"geometry.{e}") from None
+        cell = float(opt["cell"]) if opt["cell"] and float(opt["cell"]) > 0 else float(opt["threshold"])
+        if not float(np.ceil(opt["icp_max_dist"] / cell)) <= geo.MAX_RINGS:
+            raise ValueError(f"geometry.icp_max_dist = {opt['icp_max_dist']} over a cell of {cell} (at most 2^20 rings)")
         return opt
     if block == "mesh":
         opt = dict(MESH_NORMALS, **dict(MESH_VOLUME, **dict(MESH_CLEAN, **opt)))
@@ -314,7 +328,9 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     `reference` "sensor": the same frames' own colour and sensor depth fused by the same builder at the GROUND-TRUTH poses -- what a
     perfect tracker and map would have exported (ValueError without sensor depth) --, or the path of a PLY file: a point cloud or, with a
     face element, a mesh (`mesh.read_surface_ply`).  Meshes on either side are sampled at `geometry.density` samples per m^2;
-    `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first; `geometry.cull` frustum / occlusion then
+    `geometry.align` none / horn / umeyama moves the estimate by the trajectory alignment first; `geometry.icp: point` then registers it to
+    the reference by point-to-point ICP (`geometry.register`; metrics.json gains an `icp` block, `path/icp.npz` holds T, log and status;
+    fewer than 3 correspondences leave the estimate where it was, and the block says so); `geometry.cull` frustum / occlusion then
     removes from both point sets what no camera of the run could have seen (`cull_views`, cull.py; metrics.json gains a `cull` block;
     `geometry.cull_depth: reference` tests occlusion against the reference mesh rendered at each view instead of the sensor depth).
     `geometry.depth_l1: true` (needs `estimate: mesh` and a mesh as the reference) also renders both meshes -- the unculled ones, the
@@ -349,6 +365,11 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
         raise ValueError("geometry.depth_l1 needs `estimate: mesh` and a mesh as the reference (`reference: sensor`, or a PLY file with faces)")
     if opt["normals"] and not (estimate == "mesh" and geo._is_mesh(ref)):
         raise ValueError("geometry.normals needs `estimate: mesh` and a mesh as the reference (`reference: sensor`, or a PLY file with faces)")
+    icp = None
+    if opt["icp"] == "point":      # behind `align`, in front of everything that looks at the estimate
+        est, icp = geo.register(est, ref, device=slam.cfg["device"], threshold=float(opt["threshold"]), cell=float(opt["cell"] or 0), density=float(opt["density"]),
+                                seed=int(opt["seed"]), max_samples=int(opt["max_samples"]), max_dist=opt["icp_max_dist"], iters=opt["icp_iters"],
+                                rel_fitness=opt["icp_rel_fitness"], rel_rmse=opt["icp_rel_rmse"])
     culled = {} if opt["cull"] == "none" else {"cull": cull_views(slam, opt, block, ref)}
     if opt["normals"]:
         culled["normals"] = True
@@ -360,6 +381,10 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     extra = {"estimate": estimate, "reference": reference, "align": align, "density": float(opt["density"]), "seed": int(opt["seed"])}
     if cleaned:
         result["mesh_clean"] = extra["mesh_clean"] = dict(cleaned, mode=block["clean"], min_triangles=block["clean_min_triangles"])
+    if icp is not None:
+        result["icp"] = extra["icp"] = dict({k: v for k, v in icp.items() if k not in ("T", "log")}, T=np.asarray(icp["T"]).tolist(), status_name=geo.ICP_STATUS[icp["status"]],
+                                            moved=icp["status"] != 2, max_dist=opt["icp_max_dist"], iters=opt["icp_iters"], rel_fitness=opt["icp_rel_fitness"],
+                                            rel_rmse=opt["icp_rel_rmse"])
     if opt["depth_l1"]:
         frames, poses = scored_frames(slam, block), gt_poses(slam)
         table, summary = md.depth_l1(est, ref, [poses[i].detach() for i in frames], int(slam.cfg["desired_height"]), int(slam.cfg["desired_width"]), slam.cfg["cam"],
@@ -370,12 +395,19 @@ def evaluate_geometry(slam, path=None, estimate=None, reference=None):
     if opt["depth_l1"]:
         result["files"]["depth_l1"] = os.path.join(path, "depth_l1.npz")
         np.savez(result["files"]["depth_l1"], table=table, frames=np.asarray(frames, dtype=np.int64))
+    if icp is not None:
+        result["files"]["icp"] = os.path.join(path, "icp.npz")
+        np.savez(result["files"]["icp"], T=np.asarray(icp["T"], dtype=np.float64), log=np.asarray(icp["log"], dtype=np.float64), status=np.int64(icp["status"]))
     slam.geometry_eval = result      # what the last evaluation found
     t = result["table"]
     print(f"Geometry ({estimate} against {reference}): accuracy {result['accuracy'] * 100:.3f} cm, completion {result['completion'] * 100:.3f} cm, "
           f"completion ratio {result['completion_ratio'] * 100:.2f} % at {float(opt['threshold']) * 100:g} cm, F-score {result['fscore']:.4f}, Chamfer "
           f"{result['chamfer'] * 100:.3f} cm ({result['n_estimate']} / {result['n_reference']} points, clamped {int(t[0, 5])} / {int(t[1, 5])}) in "
           f"{result['files']['metrics']}")
+    if icp is not None:
+        print(f"ICP ({geo.ICP_STATUS[icp['status']]} after {icp['passes']} passes{'' if icp['status'] != 2 else '; the estimate is left where it was'}): fitness "
+              f"{icp['fitness_start']:.4f} -> {icp['fitness']:.4f}, rmse {icp['rmse_start'] * 100:.3f} -> {icp['rmse'] * 100:.3f} cm over {icp['n_source']} / "
+              f"{icp['n_reference']} points within {opt['icp_max_dist']} m in {result['files']['icp']}")
     if opt["normals"]:
         nf = result["normals"]
         print(f"Normal consistency: {nf['normal_consistency']:.4f} (normal accuracy {nf['normal_accuracy']:.4f}, normal completion {nf['normal_completion']:.4f}; "

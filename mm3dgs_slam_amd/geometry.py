@@ -70,7 +70,27 @@ faces: a file's stored normals are never used.
 exponent of ``max(|c_x|, |c_y|, |c_z|)`` as ``frexp`` returns it; ``E_v = max E_t`` over the triangles with corner v; every such triangle
 adds ``llrint(ldexp(c_k, 40 - E_v))``, k = x, y, z, to three int64 sums ``S_v`` (a term is below 2^40, so the sums are exact up to a valence
 of 2^22 and wrap in two's complement beyond); ``n_v = S_v / sqrt(S_v . S_v)`` in double from the sums converted to double, rounded once
-to float32; ``(0, 0, 0)``, and counted, when v has no such triangle or ``S_v = 0``."""
+to float32; ``(0, 0, 0)``, and counted, when v has no such triangle or ``S_v = 0``.
+
+**Registration** (``icp_host`` / mm3dgs_icp_point, ``register``; opt-in, `geometry.icp: point`).  NICE-SLAM's ``eval_recon`` registers the
+reconstruction to the ground truth by point-to-point ICP (Open3D ``registration_icp``: correspondence distance 0.1 m, identity start, 30
+iterations, 1e-6 / 1e-6) before it measures a distance.  The rule here: source rows are the estimate, the target set is the reference,
+the state is ``T = (R, t)`` (twelve doubles, row-major [3,4]) and pass k = 0, 1, ... is
+
+1. *move and search*: every finite source row p (widened) gives ``p' = ((R0 p.x + R1 p.y) + R2 p.z) + t`` per component, no contraction,
+   rounded once to float32 (``move_rows_host``); the correspondence of p is what ``nn_index_host`` returns for the row p' with
+   ``max_dist = icp_max_dist`` -- the same grid, rings, stop rule and lexicographic minimum over ``(d2, original row)``; none for a
+   clamped row or one that is not finite;
+2. *sum*, over the rows with a correspondence q and with p the ORIGINAL coordinates (so a solve gives the absolute transform and nothing
+   is composed): n, sum p, sum q, the nine sums ``p_a q_b`` (each product rounded, then added) and sum d2 (the double squared distance of
+   the search), 17 in all, in ``kernel_order_sum``'s order on the device; with them the finite source rows;
+3. *figures*: ``fitness = n / finite rows``, ``rmse = sqrt(sum d2 / n)``, 0 with n = 0 -- those of the T the pass started with;
+4. *stop*: status 0 when k > 0 and ``|fitness_k - fitness_{k-1}| < rel_fitness`` and ``|rmse_k - rmse_{k-1}| < rel_rmse`` (Open3D's
+   absolute differences); else status 2 when n < 3; else status 1 when k == iters.  T stays: the last pass only evaluates, and the
+   reported figures belong to the returned T;
+5. *solve* otherwise (``_horn_solve``, ``icp_horn`` on the device: one sequence of ``+ - x / sqrt``, so the two agree bit for bit):
+   ``S = sum p q^T - sum p sum q^T / n``, Horn's symmetric 4 x 4 matrix N(S), its dominant eigenvector by cyclic Jacobi rotations,
+   ``w >= 0``, normalised; R from the quaternion, ``t = sum q / n - R sum p / n``."""
 from __future__ import annotations
 
 import json
@@ -633,6 +653,41 @@ class GeometryScorer:
                                             self.threshold, P(dist), P(row), P(work), _stream()))
         return dist, row
 
+    def icp(self, rows, max_dist=0.1, iters=30, rel_fitness=1e-6, rel_rmse=1e-6, start=None, want_index=False):
+        """Point-to-point ICP of the source rows [n,4] int32 onto this reference (``icp_host`` states the rule): one mm3dgs_icp_point call on
+        the current stream -- a zeroing launch and 2 (iters + 1) launches, the stop decided on the device -- and no read-back.  Returns
+        device tensors: state float64 [16] ([0:12] T, [12] passes run, [13] status), log float64 [iters + 1, 16], and with `want_index`
+        dist float32 [n] / index int32 [n] (holding the uint32 values) of the last pass that ran.  `start`: a [3,4] T other than the
+        identity.  A reference without finite rows, or no source row, gives status 2 without a launch."""
+        from . import _lib
+        from .rasterizer import _stream
+        max_dist, iters, rel_fitness, rel_rmse = _check_icp(max_dist, iters, rel_fitness, rel_rmse)
+        if float(np.ceil(max_dist / self.cell)) > MAX_RINGS:
+            raise ValueError(f"icp_max_dist / cell = {max_dist / self.cell} (at most 2^20 rings)")
+        q = torch.as_tensor(rows, device=self.device).to(torch.int32).reshape(-1, 4).contiguous()
+        nq = int(q.shape[0])
+        state = torch.zeros(16, dtype=torch.float64, device=self.device)
+        state[:12] = torch.as_tensor(_IDENTITY if start is None else np.asarray(as_np(start, np.float64)).reshape(12), dtype=torch.float64, device=self.device)
+        log = torch.zeros(iters + 1, 16, dtype=torch.float64, device=self.device)
+        out = {"state": state, "log": log}
+        if want_index:
+            out.update(dist=torch.empty(nq, dtype=torch.float32, device=self.device), index=torch.empty(nq, dtype=torch.int32, device=self.device))
+        if nq == 0 or self.grid is None:      # nothing to search: pass 0 finds no correspondence and stops (no kernel has anything to read)
+            fin = torch.isfinite(q[:, :3].view(torch.float32)).all(1)
+            state[12], state[13] = 1.0, 2.0
+            log[0, 0], log[0, 2], log[0, 12] = 1.0, fin.sum().double(), 2.0
+            log[0, 9:12] = state[3:12:4]
+            if want_index:
+                out["dist"].copy_(torch.where(fin, torch.full_like(out["dist"], max_dist), torch.full_like(out["dist"], float("nan"))))
+                out["index"].fill_(-1)
+            return out
+        P = _lib.ptr
+        gx, gy, gz = self.dims
+        work = torch.empty(int(self.lib.mm3dgs_icp_work_bytes(nq)) // 8, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.mm3dgs_icp_point(nq, P(q), self.n_ref, self.cell, self._origin, gx, gy, gz, P(self.cell_start), P(self.sorted), max_dist, iters,
+                                             rel_fitness, rel_rmse, P(state), P(log), P(out.get("dist")), P(out.get("index")), P(work), _stream()))
+        return out
+
 
 # ---- comparisons ----------------------------------------------------------------------------------------------------------------------
 def _is_mesh(side):
@@ -770,6 +825,259 @@ def align_rows(rows, est_poses, gt_poses, method):
     b = torch.tensor(np.asarray(t).reshape(3), dtype=torch.float64, device=rows.device)
     xyz = rows[:, :3].contiguous().view(torch.float32).double() @ A.T + b
     return torch.cat([xyz.float().view(torch.int32), rows[:, 3:]], 1).contiguous()
+
+
+# ---- registration ---------------------------------------------------------------------------------------------------------------------
+ICP_STATUS = ("converged", "iterations", "too_few_correspondences")
+ICP_SWEEPS = 50        # the Jacobi solver's cap (see ``_horn_solve``)
+ICP_MAX_ITERS = 1000
+_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def move_rows_host(rows, T):
+    """The rows with every finite position moved by T ([3,4] float64, (R | t)) by the component rule of the module docstring, rounded once
+    to float32; the rgba, and a row that is not finite, as they are.  (The identity returns the input bytes except for a coordinate of -0.0,
+    which the sum with 0 x y turns into 0.0.)"""
+    rows = as_np(rows, np.int32).reshape(-1, 4)
+    T = np.asarray(T, dtype=np.float64).reshape(3, 4)
+    xyz, fin = _finite_rows(rows)
+    p = xyz.astype(np.float64)
+    out = rows.copy()
+    with np.errstate(over="ignore", invalid="ignore"):
+        moved = np.stack([((T[a, 0] * p[:, 0] + T[a, 1] * p[:, 1]) + T[a, 2] * p[:, 2]) + T[a, 3] for a in range(3)], 1).astype(np.float32)
+    out[fin, :3] = moved[fin].view(np.int32)
+    return out
+
+
+def _horn_solve(s):
+    """(T [3,4] float64, quaternion [w, x, y, z], sweeps) from the 17 sums ``n, sum p [3], sum q [3], sum p_a q_b [9], -``: Horn's closed
+    form with ``q ~ R p + t``.  Python floats (IEEE doubles) and ``+ - x / sqrt`` only, written operation by operation as ``icp_horn`` in
+    csrc/geometry.hip is, so the device agrees bit for bit.  Cyclic Jacobi rotations in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a
+    sweep starts only while an off-diagonal element is not exactly zero, and from the fifth sweep on an element below the rounding of
+    both its diagonal neighbours is set to zero, so the sum reaches zero: a 4 x 4 matrix gets there in well under ten sweeps
+    (tests/test_icp.py counts them), and ICP_SWEEPS = 50 is the classical cap that only bounds the loop."""
+    from math import sqrt
+    s = [float(v) for v in s]
+    n = s[0]
+    S = [[s[7 + 3 * a + b] - (s[1 + a] * s[4 + b]) / n for b in range(3)] for a in range(3)]
+    A = [[0.0] * 4 for _ in range(4)]
+    A[0][0] = (S[0][0] + S[1][1]) + S[2][2]
+    A[0][1] = S[1][2] - S[2][1]
+    A[0][2] = S[2][0] - S[0][2]
+    A[0][3] = S[0][1] - S[1][0]
+    A[1][1] = (S[0][0] - S[1][1]) - S[2][2]
+    A[1][2] = S[0][1] + S[1][0]
+    A[1][3] = S[2][0] + S[0][2]
+    A[2][2] = (S[1][1] - S[0][0]) - S[2][2]
+    A[2][3] = S[1][2] + S[2][1]
+    A[3][3] = (S[2][2] - S[0][0]) - S[1][1]
+    for a in range(4):
+        for b in range(a):
+            A[a][b] = A[b][a]
+    V = [[1.0 if a == b else 0.0 for b in range(4)] for a in range(4)]
+    sweeps = 0
+    for sweep in range(ICP_SWEEPS):
+        off = ((((abs(A[0][1]) + abs(A[0][2])) + abs(A[0][3])) + abs(A[1][2])) + abs(A[1][3])) + abs(A[2][3])
+        if off == 0.0:
+            break
+        sweeps += 1
+        for p in range(3):
+            for q in range(p + 1, 4):
+                apq = A[p][q]
+                if apq == 0.0:
+                    continue
+                g = 100.0 * abs(apq)
+                if sweep > 3 and abs(A[p][p]) + g == abs(A[p][p]) and abs(A[q][q]) + g == abs(A[q][q]):
+                    A[p][q] = A[q][p] = 0.0
+                    continue
+                h = A[q][q] - A[p][p]
+                if abs(h) + g == abs(h):
+                    t = apq / h
+                else:
+                    theta = (0.5 * h) / apq
+                    t = 1.0 / (abs(theta) + sqrt(1.0 + theta * theta))
+                    if theta < 0.0:
+                        t = -t
+                c = 1.0 / sqrt(t * t + 1.0)
+                sn = t * c
+                A[p][p] = A[p][p] - t * apq
+                A[q][q] = A[q][q] + t * apq
+                A[p][q] = A[q][p] = 0.0
+                for r in range(4):
+                    if r != p and r != q:
+                        arp, arq = A[r][p], A[r][q]
+                        A[r][p] = A[p][r] = c * arp - sn * arq
+                        A[r][q] = A[q][r] = sn * arp + c * arq
+                    vrp, vrq = V[r][p], V[r][q]
+                    V[r][p] = c * vrp - sn * vrq
+                    V[r][q] = sn * vrp + c * vrq
+    top, w, x, y, z = A[0][0], V[0][0], V[1][0], V[2][0], V[3][0]      # the largest eigenvalue, the first one on a tie
+    for k in range(1, 4):
+        if A[k][k] > top:
+            top, w, x, y, z = A[k][k], V[0][k], V[1][k], V[2][k], V[3][k]
+    if w < 0.0:
+        w, x, y, z = -w, -x, -y, -z
+    ln = sqrt(((w * w + x * x) + y * y) + z * z)
+    w, x, y, z = w / ln, x / ln, y / ln, z / ln
+    ww, xx, yy, zz, xy, xz, yz, wx, wy, wz = w * w, x * x, y * y, z * z, x * y, x * z, y * z, w * x, w * y, w * z
+    R = [[((ww + xx) - yy) - zz, 2.0 * (xy - wz), 2.0 * (xz + wy)],
+         [2.0 * (xy + wz), ((ww - xx) + yy) - zz, 2.0 * (yz - wx)],
+         [2.0 * (xz - wy), 2.0 * (yz + wx), ((ww - xx) - yy) + zz]]
+    mp = [s[1] / n, s[2] / n, s[3] / n]
+    T = np.zeros((3, 4), dtype=np.float64)
+    for a in range(3):
+        T[a, :3] = R[a]
+        T[a, 3] = s[4 + a] / n - ((R[a][0] * mp[0] + R[a][1] * mp[1]) + R[a][2] * mp[2])
+    return T, [w, x, y, z], sweeps
+
+
+def _check_icp(max_dist, iters, rel_fitness, rel_rmse):
+    max_dist, rel_fitness, rel_rmse = float(max_dist), float(rel_fitness), float(rel_rmse)
+    if not (np.isfinite(max_dist) and max_dist > 0):
+        raise ValueError(f"icp_max_dist = {max_dist} (must be finite and positive)")
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= ICP_MAX_ITERS:
+        raise ValueError(f"icp_iters = {iters!r} (an integer, 1 .. {ICP_MAX_ITERS})")
+    if not rel_fitness >= 0:
+        raise ValueError(f"icp_rel_fitness = {rel_fitness} (must not be negative)")
+    if not rel_rmse >= 0:
+        raise ValueError(f"icp_rel_rmse = {rel_rmse} (must not be negative)")
+    return max_dist, int(iters), rel_fitness, rel_rmse
+
+
+def icp_pairs_host(source_rows, reference_rows, cell, max_dist, T, grid=None):
+    """One pass's move and search: (dist, index, has bool [n], p float64 [n,3]: the original coordinates, q [n,3]: the correspondence, d2
+    [n]: the double squared distance; p, q, d2 are 0 where `has` is False)."""
+    src = as_np(source_rows, np.int32).reshape(-1, 4)
+    ref = as_np(reference_rows, np.int32).reshape(-1, 4)
+    moved = move_rows_host(src, T)
+    dist, index, _ = _nn_search(moved, ref, cell, max_dist, grid, True)
+    has = index != NO_INDEX
+    j = np.where(has, index, 0).astype(np.int64)
+    Rf = rows_xyz(ref).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.where(has[:, None], Rf[j] if len(Rf) else 0.0, 0.0)
+        p = np.where(has[:, None], rows_xyz(src).astype(np.float64), 0.0)
+        d = rows_xyz(moved).astype(np.float64) - (Rf[j] if len(Rf) else 0.0)
+        d2 = np.where(has, d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2], 0.0)
+    return dist, index, has, p, q, d2
+
+
+def icp_sums(has, p, q, d2, sum_order="numpy"):
+    """The 17 sums of a pass as Python floats, each column added by numpy or in ``kernel_order_sum``'s order."""
+    add = kernel_order_sum if sum_order == "kernel" else (lambda v: float(np.sum(v)))
+    cols = [has.astype(np.float64)] + [p[:, a] for a in range(3)] + [q[:, a] for a in range(3)] + [p[:, a] * q[:, b] for a in range(3) for b in range(3)] + [d2]
+    return [add(c) for c in cols]
+
+
+def icp_host(source_rows, reference_rows, cell, max_dist=0.1, iters=30, rel_fitness=1e-6, rel_rmse=1e-6, sum_order="numpy", start=None):
+    """Point-to-point ICP of the source rows onto the reference rows by the rule of the module docstring, in float64 numpy: the statement
+    mm3dgs_icp_point is held to (bit for bit with `sum_order` "kernel") and the path of ``device: cpu``.  Returns a dict: T [3,4] float64,
+    status (0 converged, 1 `iters` reached, 2 fewer than 3 correspondences), passes, log [iters + 1, 16] float64 -- per pass [0] 1 when it
+    ran, [1] n, [2] finite source rows, [3] fitness, [4] rmse, [5:9] the quaternion of the latest solve (0 before the first), [9:12] t behind
+    the pass, [12] the status on the row of the pass that stopped, the rest 0 --, the index / dist of the last pass (what ``nn_index_host``
+    gives for the source moved by the returned T), fitness, rmse and sweeps (the Jacobi sweeps of every solve).  `start`: a [3,4] T other
+    than the identity."""
+    max_dist, iters, rel_fitness, rel_rmse = _check_icp(max_dist, iters, rel_fitness, rel_rmse)
+    src = as_np(source_rows, np.int32).reshape(-1, 4)
+    ref = as_np(reference_rows, np.int32).reshape(-1, 4)
+    rxyz, rfin = _finite_rows(ref)
+    grid = grid_for(rxyz[rfin].astype(np.float64).min(0), rxyz[rfin].astype(np.float64).max(0), cell) if rfin.any() else None
+    finite = float(_finite_rows(src)[1].sum())
+    T = np.asarray(_IDENTITY if start is None else start, dtype=np.float64).reshape(3, 4).copy()
+    quat, log, sweeps = [0.0] * 4, np.zeros((iters + 1, 16), dtype=np.float64), []
+    before = None
+    for k in range(iters + 1):
+        dist, index, has, p, q, d2 = icp_pairs_host(src, ref, cell, max_dist, T, grid)
+        s = icp_sums(has, p, q, d2, sum_order)
+        n = s[0]
+        fitness = n / finite if n > 0 else 0.0
+        rmse = float(np.sqrt(s[16] / n)) if n > 0 else 0.0
+        status = -1
+        if before is not None and abs(fitness - before[0]) < rel_fitness and abs(rmse - before[1]) < rel_rmse:
+            status = 0
+        elif n < 3:
+            status = 2
+        elif k == iters:
+            status = 1
+        if status < 0:
+            T, quat, sw = _horn_solve(s)
+            sweeps.append(sw)
+        before = (fitness, rmse)
+        log[k, :5] = (1.0, n, finite, fitness, rmse)
+        log[k, 5:9], log[k, 9:12], log[k, 12] = quat, T[:, 3], max(status, 0)
+        if status >= 0:
+            break
+    return {"T": T, "status": status, "passes": k + 1, "log": log, "index": index, "dist": dist, "fitness": fitness, "rmse": rmse, "sweeps": sweeps}
+
+
+def icp_state(result):
+    """The 16 doubles mm3dgs_icp_point leaves in `state` for a result of ``icp_host``."""
+    return np.concatenate([np.asarray(result["T"], dtype=np.float64).reshape(12), [float(result["passes"]), float(result["status"]), 0.0, 0.0]])
+
+
+def icp_record(state, log, n_source, n_reference):
+    """The record of a registration from `state` [16] and `log`: T, status, passes, fitness and rmse of the returned T, those of the start,
+    and the sizes of the two point sets."""
+    state, log = np.asarray(state, dtype=np.float64).reshape(16), np.asarray(log, dtype=np.float64).reshape(-1, 16)
+    passes = int(state[12])
+    last = log[max(passes - 1, 0)]
+    return {"T": state[:12].reshape(3, 4).copy(), "status": int(state[13]), "passes": passes, "fitness": float(last[3]), "rmse": float(last[4]),
+            "fitness_start": float(log[0, 3]), "rmse_start": float(log[0, 4]), "n_source": int(n_source), "n_reference": int(n_reference)}
+
+
+def move_rows(rows, T, device="cpu"):
+    """The rows moved by T: one mm3dgs_rows_move call on a CUDA device (rows and T -- 12 doubles -- may be device tensors; a device tensor
+    comes back, nothing is read back), ``move_rows_host`` otherwise."""
+    if not str(device).startswith("cuda"):
+        return move_rows_host(as_np(rows, np.int32), as_np(T, np.float64))
+    from . import _lib
+    from .rasterizer import _stream
+    r = torch.as_tensor(rows, device=device).to(torch.int32).reshape(-1, 4).contiguous()
+    t = torch.as_tensor(T, device=device).to(torch.float64).reshape(-1)[:12].contiguous()
+    out = torch.empty_like(r)
+    if int(r.shape[0]):
+        _lib.check(_lib.load().mm3dgs_rows_move(int(r.shape[0]), _lib.ptr(r), _lib.ptr(t), _lib.ptr(out), _stream()))
+    return out
+
+
+def _point_set(side, device, density, seed, max_samples):
+    """The point set of one side as ``compare_host`` / ``compare_device`` take it: a mesh sampled, a cloud as it is."""
+    on_device = str(device).startswith("cuda")
+    if _is_mesh(side):
+        if on_device:
+            return sample_mesh_device(side[0], side[1], density, seed, max_samples, device)[0]
+        rows, c = sample_mesh_host(side[0], side[1], density, seed)
+        if c["samples"] > int(max_samples):
+            raise ValueError(f"{c['samples']} surface samples at density {density} per m^2: more than max_samples = {int(max_samples)}")
+        return rows
+    return torch.as_tensor(side, device=device).to(torch.int32).reshape(-1, 4).contiguous() if on_device else as_np(side, np.int32).reshape(-1, 4)
+
+
+def register(estimate, reference, device="cpu", threshold=0.05, cell=0, density=10000.0, seed=0, max_samples=1 << 24, max_dist=0.1, iters=30,
+             rel_fitness=1e-6, rel_rmse=1e-6, sum_order="numpy"):
+    """The estimate registered to the reference by point-to-point ICP (the rule of the module docstring): (the moved estimate, the
+    record).  Each side is rows [n,4] int32 or (vertex rows, triangles); a mesh side is sampled exactly as ``compare`` samples it (the
+    same `density`, `seed`, `max_samples`), a cloud side is taken as it is, and the reference grid has the scoring cell (`cell`, 0:
+    `threshold`).  Of a mesh estimate the vertex rows are moved and the triangles are left; a later ``compare`` samples the moved mesh
+    again -- the second sampling is accepted: the samples of a moved mesh are not the moved samples in the last bit, and the scores are
+    about the mesh that is written.  On a CUDA device: one grid build, one mm3dgs_icp_point, one mm3dgs_rows_move and one read-back of
+    state + log; the moved rows stay on the device.  The record: T [3,4] (reference ~ R estimate + t), status (``ICP_STATUS``), passes,
+    fitness / rmse of the returned T and fitness_start / rmse_start of the start, n_source, n_reference, log.  With status 2 (fewer than 3
+    correspondences) the estimate is returned as it was."""
+    cell = float(cell) if cell and float(cell) > 0 else float(threshold)
+    src, ref = _point_set(estimate, device, density, seed, max_samples), _point_set(reference, device, density, seed, max_samples)
+    rows = estimate[0] if _is_mesh(estimate) else estimate
+    if str(device).startswith("cuda"):
+        out = GeometryScorer(ref, cell, max_dist, threshold, device).icp(src, max_dist, iters, rel_fitness, rel_rmse)
+        both = torch.cat([out["state"], out["log"].reshape(-1)]).cpu().numpy()      # the one read-back
+        state, log = both[:16], both[16:].reshape(-1, 16)
+        moved = move_rows(rows, out["state"], device) if int(state[13]) != 2 else rows
+    else:
+        result = icp_host(src, ref, cell, max_dist, iters, rel_fitness, rel_rmse, sum_order)
+        state, log = icp_state(result), result["log"]
+        moved = move_rows_host(rows, result["T"]) if result["status"] != 2 else rows
+    record = dict(icp_record(state, log, src.shape[0], ref.shape[0]), log=log)
+    return ((moved, estimate[1]) if _is_mesh(estimate) else moved), record
 
 
 # ---- outputs --------------------------------------------------------------------------------------------------------------------------

@@ -35,7 +35,8 @@ distance; `--geometry --eval` likewise from the checkpoint.  `--mesh-clean small
 the extraction, for `--mesh` and for the meshes `--geometry` scores (`mesh.clean_min_triangles`; mesh_clean.py).  `--mesh-volume sparse` (or `mesh.volume`)
 holds the fusion volume in hashed 8 x 8 x 8-sample blocks along the surface instead of one dense lattice (`mesh.max_blocks`).  `--mesh-normals` (or
 `mesh.normals: true`) writes area-weighted vertex normals into `mesh.ply`; `--geometry-normals` (or `geometry.normals: true`) adds normal consistency to
-the geometry scores (`estimate: mesh` against a mesh).
+the geometry scores (`estimate: mesh` against a mesh); `--geometry-icp` (or `geometry.icp: point`) registers the estimate to the reference by
+point-to-point ICP before it is scored (NICE-SLAM's protocol; `icp` block of `metrics.json`, `geometry/icp.npz`).
 
 `--eval [--iteration N]` runs no frame: it builds the same sequence (give the run's `--frames` / `--gaussians`), resumes the checkpoint
 `outputdir/point_cloud/iteration_<N>` (default: the config's `iteration`, else the largest on disk) with the poses of `results.npz`, and
@@ -164,6 +165,7 @@ def main():
     ap.add_argument("--mesh-volume", choices=("dense", "sparse"), default=None, help="with --mesh / --geometry: how the fusion volume is held (overrides the `mesh` block's `volume`; dense: one lattice over the box of the views, sparse: hashed 8 x 8 x 8-sample blocks along the surface, mesh.max_blocks)")
     ap.add_argument("--mesh-normals", action="store_true", help="with --mesh: write area-weighted vertex normals into mesh.ply (`float nx ny nz` behind the position; sets the `mesh` block's `normals`)")
     ap.add_argument("--geometry-normals", action="store_true", help="with --geometry: also score normal consistency (needs `estimate: mesh` and a mesh as the reference; sets the `geometry` block's `normals`)")
+    ap.add_argument("--geometry-icp", action="store_true", help="with --geometry: register the estimate to the reference by point-to-point ICP before it is scored, as NICE-SLAM's eval_recon does (sets the `geometry` block's `icp` to point; icp_max_dist, icp_iters, icp_rel_fitness, icp_rel_rmse)")
     ap.add_argument("--iteration", type=int, default=None, help="with --eval: the checkpoint to score (default: the config's `iteration`, else the largest one in outputdir/point_cloud)")
     args = ap.parse_args()
     from mm3dgs_slam_amd.config import default_config, load_config
@@ -191,6 +193,8 @@ def main():
         cfg["mesh"] = dict(cfg.get("mesh") or {}, normals=True)
     if args.geometry_normals:
         cfg["geometry"] = dict(cfg.get("geometry") or {}, normals=True)
+    if args.geometry_icp:
+        cfg["geometry"] = dict(cfg.get("geometry") or {}, icp="point")
     if args.eval:
         seq = build_sequence(cfg, args.frames, args.gaussians)
         if args.pointcloud:
